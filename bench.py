@@ -14,6 +14,11 @@ Launch: python bench.py [--gpus N --steps K --warmup W].  For N > 1 the ranks ar
 starts them (torch.distributed.run --nproc-per-node N ... bench.py --gpus N, the driver's form), or -- invoked plainly --
 bench.py starts that same torch.distributed.run itself on 127.0.0.1 and a free port and relays rank 0's JSON line
 (`config.launcher` says which).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes work of its own behind the timed
+region: the CPU legs (hoisted oracle port at full size, the as-written call structure extrapolated) with the parity of the HIP path
+against the oracle, and the two rocprofv3 --pmc passes behind roofline.traffic (--no-cpu-baseline / --no-traffic drop either).
+--dump-outputs DIR writes what the last timed step computed as float64 .npy files (see dump_outputs).
 """
 import argparse
 import importlib
@@ -47,6 +52,10 @@ def parse():
     p.add_argument("--kernel", choices=["matern52", "se"], default="matern52")
     p.add_argument("--chunk", type=int, default=65536,
                    help="candidates per device pass (K*, C*, P workspaces: 3 x chunk x N x 8 B = 12.9 GB at the default)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the CPU legs + parity against the oracle and the rocprofv3 traffic passes (after the timed region)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed to DIR/<name>.npy (float64)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                    help="collective backend; gloo + --same-device exercises the N>1 path on a 1-GPU box (tests only)")
@@ -54,7 +63,10 @@ def parse():
     p.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc passes behind roofline.traffic")
     p.add_argument("--traffic-child", action="store_true",
                    help="internal: what measure_traffic() runs under rocprofv3 (one fit + a few full-shape rounds of the maximiser)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def synth(D, N, S):
@@ -259,6 +271,21 @@ def stage_rooflines(prof, N, D, Np, cand, matern):
     return out
 
 
+def dump_outputs(out_dir, sls, gp, res, evals_issued):
+    """--dump-outputs: what a caller of the timed path holds after its LAST step, as float64 arrays in out_dir/<name>.npy --
+    the merged maximiser (best_x, best_value, best_index), the evaluations it issued (whole job), and the fit it ran on (alpha =
+    K_y^-1 y, the posterior mean at the data points, [best_index, mu_best, logdet] of the summary).  N + N + D + 6 values: 128 KB
+    at N = 8192.  Read back after the timed region; the inputs are seeded (synth), so two builds can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    s = gp.summary()
+    arrays = {"best_x": np.asarray(res["x"], dtype=np.float64), "best_value": np.array([res["value"]], dtype=np.float64),
+              "best_index": np.array([res["index"]], dtype=np.float64), "evals_issued": np.array([evals_issued], dtype=np.float64),
+              "fit_alpha": gp.matrix(sls.GP_ALPHA), "fit_mu_data": gp.matrix(sls.GP_MU_DATA),
+              "fit_summary": np.array([s["best_index"], s["mu_best"], s["logdet"]], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def canonical_argv(args):
     """The parsed arguments under their long names (torch.distributed.run's own parser prefix-matches a script argument
     such as `--n` against its options even behind the script path)."""
@@ -266,7 +293,8 @@ def canonical_argv(args):
            "--dims", str(args.d), "--starts", str(args.starts), "--n-local", str(args.n_local), "--kernel", args.kernel,
            "--chunk", str(args.chunk), "--backend", args.backend]
     return (out + (["--no-cpu-baseline"] if args.no_cpu_baseline else []) + (["--same-device"] if args.same_device else []) +
-            (["--no-traffic"] if args.no_traffic else []))
+            (["--no-traffic"] if args.no_traffic else []) + (["--full"] if args.full else []) +
+            (["--dump-outputs", args.dump_outputs] if args.dump_outputs is not None else []))
 
 
 def self_spawn(args):
@@ -385,7 +413,8 @@ def main():
         t_a = time.perf_counter()
         gp.refit_dev(X_dev.data_ptr(), y_dev.data_ptr())
         r = gp.acq_maximize_dev(starts_dev.data_ptr(), S_loc, args.n_local, sls.ACQ_EI, 1.0, offset=lo)   # returns the winner: synchronous
-        issued[0] += gp.last_stats()["evals_issued"]
+        issued_last[0] = gp.last_stats()["evals_issued"]
+        issued[0] += issued_last[0]
         t_b = time.perf_counter()
         t_local[0] += t_b - t_a
         if world > 1:                                   # the single exchange of the step
@@ -394,7 +423,7 @@ def main():
             return dict(value=v, index=i, x=x)
         return r
 
-    issued, t_local, t_xchg = [0], [0.0], [0.0]
+    issued, issued_last, t_local, t_xchg = [0], [0], [0.0], [0.0]
 
     def fence():
         torch.cuda.synchronize()
@@ -420,11 +449,16 @@ def main():
         ti = torch.tensor([float(issued[0])], dtype=torch.float64, device=xdev if xdev is not None else "cpu")
         dist.all_reduce(ti, op=dist.ReduceOp.SUM)
         issued_total = int(ti.item())
+        tl = torch.tensor([float(issued_last[0])], dtype=torch.float64, device=xdev if xdev is not None else "cpu")
+        dist.all_reduce(tl, op=dist.ReduceOp.SUM)
+        issued_last_total = int(tl.item())
     else:
-        issued_total = issued[0]
+        issued_total, issued_last_total = issued[0], issued_last[0]
     names = ["gram", "potri", "potrf", "trtri", "lauum", "cross_gram", "acq_gemm", "grad_gemm", "finalize", "lbfgs"]
     prof = {n: ctx.prof_get(n) for n in names}
     ctx.prof_enable(False)
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, sls, gp, res, issued_last_total)
     per_rank = None
     if world > 1:
         # What makes a scaling curve diagnosable from ONE line: every rank's own numbers, all-gathered over the rendezvous group
@@ -462,10 +496,15 @@ def main():
         flops_total = 2.0 * N * N * issued_rank0
         achieved = flops_total / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
         avg_ms = gemm_ms / max(gemm_launches, 1)
-        # roofline.traffic: measured by THIS run, behind the timed region: two rocprofv3 --pmc passes over a child that runs the same
+        # roofline.traffic (--full): measured by THIS run, behind the timed region: two rocprofv3 --pmc passes over a child that runs the same
         # library at the same shapes (measure_traffic); bytes per full-shape launch (achieved is per launch of the timed region,
         # whose launches shrink with the active set: traffic_detail.candidates_per_launch says what the figure belongs to)
-        traffic, traffic_detail = (None, {"skipped": "--no-traffic / multi-GPU run"}) if (args.no_traffic or world > 1) else measure_traffic(args)
+        if not args.full:
+            traffic, traffic_detail = None, {"skipped": "measured by bench.py --full only"}
+        elif args.no_traffic or world > 1:
+            traffic, traffic_detail = None, {"skipped": "--no-traffic / multi-GPU run"}
+        else:
+            traffic, traffic_detail = measure_traffic(args)
         out = {
             "metric": baseline_metric(),
             "value": evals_issued / (ms_per_step * 1e-3), "unit": "candidate-evals/s", "n_gpus": world, "steps": args.steps,
@@ -503,7 +542,7 @@ def main():
                 assert exchange.startswith("ncclAllGather inside libsls_hip"), exchange
         if args.same_device or args.backend != "nccl":
             out["config"]["test_mode"] = "ranks share GPU 0 over gloo: not a bench line"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             oracle_out, out["cpu_baseline"] = cpu_baseline(args, kernel_id)
             out["cpu_baseline"]["as_written"] = cpu_as_written(args, kernel_id, os.cpu_count() or 1)
             # the oracle run is not thrown away: the same inputs go through the HIP path and the two are diffed

@@ -56,6 +56,37 @@ def test_bench_line_contract_and_two_rank_merge():
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_steps_results(tmp_path):
+    """--dump-outputs DIR: what the last timed step computed, as float64 .npy files -- the same from run to run (seeded inputs)
+    and whatever the number of steps, the maximiser equal to the line's result.  A plain run (no --full) carries neither CPU leg
+    nor a traffic measurement."""
+    plain = [a for a in SMALL if a not in ("--no-cpu-baseline", "--no-traffic")]
+    a, b = tmp_path / "a", tmp_path / "b"
+    ja = run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(a)] + plain)
+    jb = run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(b)] + plain + ["--steps", "2"])
+    assert ja["steps"] == 1 and jb["steps"] == 2
+    for j in (ja, jb):
+        assert "cpu_baseline" not in j and "parity" not in j
+        assert j["roofline"]["traffic"] is None and "--full" in j["roofline"]["traffic_detail"]["skipped"]
+    names = {"best_x", "best_value", "best_index", "evals_issued", "fit_alpha", "fit_mu_data", "fit_summary"}
+    assert {p.stem for p in a.glob("*.npy")} == names and {p.stem for p in b.glob("*.npy")} == names
+    da = {n: np.load(a / f"{n}.npy") for n in names}
+    db = {n: np.load(b / f"{n}.npy") for n in names}
+    assert all(v.dtype == np.float64 for v in list(da.values()) + list(db.values()))
+    assert da["best_x"].shape == (8,) and da["fit_alpha"].shape == (640,) and da["fit_mu_data"].shape == (640,)
+    np.testing.assert_array_equal(da["best_x"], ja["result"]["best_x"])
+    assert da["best_value"][0] == ja["result"]["best_value"] and da["best_index"][0] == ja["result"]["best_index"]
+    assert da["evals_issued"][0] == ja["config"]["evals_issued_per_step"]
+    assert np.all(np.isfinite(da["fit_alpha"])) and np.all(np.isfinite(da["fit_mu_data"]))
+    if ja["potrf_fallbacks"] == 0 and jb["potrf_fallbacks"] == 0:
+        for n in names:
+            np.testing.assert_array_equal(db[n], da[n], err_msg=n)
+    else:
+        for n in names:
+            np.testing.assert_allclose(db[n], da[n], rtol=1e-11, atol=1e-12, err_msg=n)
+
+
+@pytest.mark.gpu
 def test_bench_gpus_n_without_a_launcher_spawns_its_own_ranks():
     """`python bench.py --gpus 2 ...` invoked PLAINLY (no torch.distributed.run around it, short option names and all) must
     not die: it starts the two ranks itself and prints the one JSON line, with the single-rank winner bit for bit
@@ -122,7 +153,7 @@ def test_bench_line_carries_measured_traffic():
     if not (os.path.exists("/opt/rocm/bin/rocprofv3")):
         pytest.skip("rocprofv3 not installed")
     small = [a for a in SMALL if a != "--no-traffic"]
-    j = run([sys.executable, "bench.py", "--gpus", "1"] + small)
+    j = run([sys.executable, "bench.py", "--gpus", "1", "--full"] + small)
     r = j["roofline"]
     assert isinstance(r["traffic"], float) and r["traffic"] > 0, r["traffic_detail"]
     d = r["traffic_detail"]
@@ -138,6 +169,23 @@ def test_bench_self_spawn_arguments_round_trip(monkeypatch):
     a = bench.parse()
     monkeypatch.setattr(sys, "argv", ["bench.py"] + bench.canonical_argv(a))
     assert vars(bench.parse()) == vars(a)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--full", "--dump-outputs", "out dir", "--steps", "5", "--warmup", "0"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out dir" and a.steps == 5 and a.warmup == 0
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + bench.canonical_argv(a))
+    assert vars(bench.parse()) == vars(a)
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None
+
+
+def test_bench_rejects_a_run_without_timed_steps(monkeypatch):
+    """--steps sets the number of timed steps: zero of them would leave ms_per_step undefined (CPU)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
 
 
 @pytest.mark.gpu

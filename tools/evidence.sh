@@ -1,6 +1,6 @@
 #!/bin/bash
 # Evidence of one round for profiles/ (run on the GPU box: gpurun -- 'bash tools/evidence.sh r05'):
-#   <tag>_bench_line_1gpu.json            the DEFAULT bench.py line (cpu_baseline, parity and the run's own traffic measurement included)
+#   <tag>_bench_line_1gpu.json            the bench.py --full line (cpu_baseline, parity and the run's own traffic measurement included)
 #   <tag>_kernel_stats_default_cmd.csv    rocprofv3 --kernel-trace --stats of the same command (without the CPU leg / the PMC children)
 #   <tag>_pmc_acq_gemm.json               MFMA-pipe counters of the full-shape acq_gemm launch (own pass, --kernel-trace only beside --pmc)
 #   <tag>_kernel_stats_c5.csv             kernel stats of the C5 MAP evaluation (objective + gradient; batched value-only evaluations)
@@ -12,7 +12,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-timeout 900 python bench.py > $O/${TAG}_bench_line_1gpu.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/${TAG}_bench_line_1gpu.json 2> $O/bench.err
 python - "$O/${TAG}_bench_line_1gpu.json" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
