@@ -46,6 +46,16 @@ namespace sequential_line_search
         // Batched forms (not in the reference; D x M input, one query point per column).
         void PredictBatch(const Eigen::MatrixXd& Xs, Eigen::VectorXd& mu, Eigen::VectorXd& sigma) const;
 
+        /// Joint posterior of the latent function at the M query points (D x M): the M x M covariance
+        /// K(Xs, Xs) - K*^T K_y^-1 K*, exactly symmetric, diagonal not clamped (sls_gp_predict_cov).  M <= 8192.
+        /// Both calls below need the device handle: a user subclass without one gets a 0 x 0 matrix.
+        Eigen::MatrixXd PredictCovariance(const Eigen::MatrixXd& Xs) const;
+        /// num_samples draws f ~ N(mu, cov + j I) at the M query points, one draw per column (M x num_samples); the same seed gives
+        /// the same bits, and the first k columns do not depend on num_samples (sls_gp_sample_posterior).  jitter_used (may be
+        /// nullptr) receives j.
+        Eigen::MatrixXd SamplePosterior(const Eigen::MatrixXd& Xs, int num_samples, unsigned long long seed,
+                                        double* jitter_used = nullptr) const;
+
     protected:
         KernelType               m_kernel_type;
         Kernel                   m_kernel;

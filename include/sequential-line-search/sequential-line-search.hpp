@@ -57,6 +57,12 @@ namespace sequential_line_search
         Eigen::VectorXd GetPreferenceValueStdevs(const Eigen::MatrixXd& points) const;
         Eigen::VectorXd GetAcquisitionFuncValues(const Eigen::MatrixXd& points) const;
 
+        /// Joint posterior of the preference values at the points (D x M): their M x M covariance (Regressor::PredictCovariance),
+        /// and num_samples draws of them, one per column (M x num_samples, Regressor::SamplePosterior; same seed, same bits).
+        /// Zeros while there is no data, like the accessors above.
+        Eigen::MatrixXd GetPreferenceValueCovariance(const Eigen::MatrixXd& points) const;
+        Eigen::MatrixXd SamplePreferenceValues(const Eigen::MatrixXd& points, const int num_samples, const unsigned long long seed) const;
+
         const Eigen::MatrixXd& GetRawDataPoints() const;
 
         void DampData(const std::string& directory_path) const;

@@ -138,6 +138,36 @@ int sls_gp_predict_grad(sls_gp* gp, const double* Xs, int M, double* dmu, double
  * for M points; grad (D x M) may be NULL. */
 int sls_acq_eval(sls_gp* gp, int acq_type, double ucb_h, const double* Xs, int M, double* val, double* grad);
 
+/* ---- joint posterior at a set of query points (not in the reference) --------------------------------------------------
+ * sklearn's GaussianProcessRegressor.predict(return_cov=True) / sample_y for the latent function of a fitted handle.  For the
+ * handle's data X (D x N), theta = (a, l), and M query points Xs (D x M):
+ *   mu_m  = the posterior mean (the quantity of sls_gp_predict);
+ *   cov   = K(Xs, Xs) - V^T V with V = L^-1 K*, K* = k(X, Xs), L = chol(K_y): the LATENT covariance (no b on the diagonal; its
+ *           diagonal is the sigma^2 of PredictSigma), always in this triangular form whatever the handle's sigma mode (the
+ *           form of PreferenceRegressor, SLS_SIGMA_CHOLESKY_SOLVE).  Full M x M column-major, EXACTLY symmetric (lower tiles
+ *           computed, mirrored).  The diagonal is NOT clamped at 0 (sls_gp_predict clamps sigma^2): rounding may leave it at
+ *           -O(eps a) where the posterior variance vanishes.
+ * 1 <= M <= 8192 (the largest factorisation measured in this library); larger M returns SLS_ERR_UNSUPPORTED, M = 0 is a no-op.
+ * Both GP calls hold the context's lock and the handle's state lock (shared) for the whole call, as the other evaluations of
+ * more than a few points do. */
+/* Joint posterior of the latent function at M query points (D x M): mu (M, may be NULL), cov (M x M column-major, full). */
+int sls_gp_predict_cov(sls_gp* gp, const double* Xs, int M, double* mu, double* cov);
+/* n_samples draws of f ~ N(mu, cov + j I) at the M points: samples M x n_samples column-major, one draw per column;
+   jitter_used (may be NULL) = j.
+ * F = mu 1^T + L_S Z with L_S = chol(cov + j I): j = 0 first; on a non-positive pivot j = 1e-12 a, then ten times that up to
+ * 1e-6 a (the factorisation restarts from a kept copy of cov each time); SLS_ERR_NOT_SPD if 1e-6 a fails too.  A pivot
+ * L_ii^2 <= M 2^-52 a counts as non-positive: duplicate query points make cov exactly singular, and the sign of the pivot that
+ * rounding leaves there is an accident; with this rule such a cov always takes the jitter.  Z[j, s] = normal number s M + j of stream `seed`
+ * (sls_random_normal): the bits depend on neither launch geometry nor the internal chunking over samples, the first k columns of an
+ * n-sample call equal a k-sample call, and equal inputs give equal bits.  Any n_samples >= 1. */
+int sls_gp_sample_posterior(sls_gp* gp, const double* Xs, int M, int n_samples, unsigned long long seed,
+                            double* samples, double* jitter_used);
+/* out[i] = standard normal number offset + i of stream `seed` (the generator behind sls_gp_sample_posterior).
+ * Number t: Philox4x64-10 keyed by (seed, 0) on the block counter (t / 4, 0, 0, 0); each 64-bit output x becomes
+ * u = ((x >> 11) + 0.5) 2^-53; Box-Muller on the outputs (0, 1) and (2, 3) gives r01 cos, r01 sin, r23 cos, r23 sin for
+ * t mod 4 = 0, 1, 2, 3 (r = sqrt(-2 log u_even), angle 2 pi u_odd).  offset >= 0, n >= 0. */
+int sls_random_normal(sls_ctx* ctx, unsigned long long seed, long offset, long n, double* out);
+
 /* ---- multi-start maximiser ------------------------------------------------ */
 /* FindGlobalSolution, parallelised multi-start branch (src/acquisition-function.cpp:121-153): S bounded L-BFGS runs
  * on [0,1]^D from the explicit starts (D x S), n_local objective evaluations each, all S advanced in lock step on the
@@ -308,7 +338,9 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
 /* Per-kernel accumulated device time (ms, HIP events on the context's stream) and launch counts since the last reset.
  * Names: "gram", "potri" (N <= 4096: factor + L^-1 + K^-1 in one launch) or "potrf", "trtri", "lauum" (larger N, or
  * SLS_POTRI_FUSED=0), "fit_small" (N <= 128: the whole fit in one launch), "cross_gram", "acq_gemm", "grad_gemm", "finalize",
- * "lbfgs"; "potrf_fallbacks": launches = how often a single-launch factorisation gave up and was recomputed. */
+ * "lbfgs"; the posterior calls: "post_v" (V = K* L^-T), "post_cov" (the covariance tiles), "post_potrf" (chol(cov + j I), one launch
+ * per jitter tried), "post_sample" (normals + the sample product); "potrf_fallbacks": launches = how often a single-launch
+ * factorisation gave up and was recomputed. */
 int sls_prof_enable(sls_ctx* ctx, int on);
 int sls_prof_reset(sls_ctx* ctx);
 int sls_prof_get(sls_ctx* ctx, const char* name, double* total_ms, long* launches);

@@ -133,6 +133,8 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
         .def("get_acquisition_func_value", &SequentialLineSearchOptimizer::GetAcquisitionFuncValue, "point"_a)
         .def("get_preference_value_means", &SequentialLineSearchOptimizer::GetPreferenceValueMeans, "points"_a)
         .def("get_preference_value_stdevs", &SequentialLineSearchOptimizer::GetPreferenceValueStdevs, "points"_a)
+        .def("get_preference_value_covariance", &SequentialLineSearchOptimizer::GetPreferenceValueCovariance, "points"_a)
+        .def("sample_preference_values", &SequentialLineSearchOptimizer::SamplePreferenceValues, "points"_a, "num_samples"_a, "seed"_a)
         .def("get_acquisition_func_values", &SequentialLineSearchOptimizer::GetAcquisitionFuncValues, "points"_a)
         .def("get_raw_data_points", &SequentialLineSearchOptimizer::GetRawDataPoints)
         .def("damp_data", &SequentialLineSearchOptimizer::DampData, "directory_path"_a)
@@ -160,6 +162,8 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
         .def("get_acquisition_func_value", &PreferentialBayesianOptimizer::GetAcquisitionFuncValue, "point"_a)
         .def("get_preference_value_means", &PreferentialBayesianOptimizer::GetPreferenceValueMeans, "points"_a)
         .def("get_preference_value_stdevs", &PreferentialBayesianOptimizer::GetPreferenceValueStdevs, "points"_a)
+        .def("get_preference_value_covariance", &PreferentialBayesianOptimizer::GetPreferenceValueCovariance, "points"_a)
+        .def("sample_preference_values", &PreferentialBayesianOptimizer::SamplePreferenceValues, "points"_a, "num_samples"_a, "seed"_a)
         .def("get_acquisition_func_values", &PreferentialBayesianOptimizer::GetAcquisitionFuncValues, "points"_a)
         .def("get_raw_data_points", &PreferentialBayesianOptimizer::GetRawDataPoints)
         .def("damp_data", &PreferentialBayesianOptimizer::DampData, "directory_path"_a)

@@ -60,6 +60,7 @@ EXPORTS = [
     "sls_multi_create", "sls_multi_destroy", "sls_multi_size", "sls_multi_exchange", "sls_multi_ctx", "sls_multi_gp_create", "sls_multi_gp_create_from",
     "sls_multi_gp_destroy", "sls_multi_gp_shard", "sls_multi_acq_maximize", "sls_multi_gp_predict", "sls_comm_unique_id", "sls_comm_create",
     "sls_comm_destroy", "sls_comm_allgather_best", "sls_device_trim_cache", "sls_tuning_reload", "sls_gp_generation",
+    "sls_gp_predict_cov", "sls_gp_sample_posterior", "sls_random_normal",
 ]
 
 
@@ -130,6 +131,13 @@ class Context:
         ms, n = C.c_double(), C.c_long()
         _ck(lib().sls_prof_get(self.h, name.encode(), C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+    def random_normal(self, seed, offset, n):
+        """Standard normal numbers offset .. offset + n - 1 of stream `seed` (Philox4x64-10 + Box-Muller, sls_random_normal)."""
+        out = np.empty(int(n))
+        _ck(lib().sls_random_normal(self.h, C.c_ulonglong(int(seed)), C.c_long(int(offset)), C.c_long(int(n)),
+                                    _p(out) if n > 0 else None))
+        return out
 
     # ---- free functions (src/regressor.cpp) ----
     def gram(self, X, theta, b, kernel):
@@ -221,6 +229,23 @@ class GP:
         mu, sg = np.empty(M), np.empty(M)
         _ck(lib().sls_gp_predict(self.h, _p(Xs), M, _p(mu), _p(sg)))
         return mu, sg
+
+    def predict_cov(self, Xs):
+        """Joint posterior of the latent function at the columns of Xs (D x M): (mu (M,), cov (M, M)), sls_gp_predict_cov."""
+        Xs = _f(Xs)
+        M = Xs.shape[1]
+        mu, cov = np.empty(M), np.empty((M, M), order="F")
+        _ck(lib().sls_gp_predict_cov(self.h, _p(Xs), M, _p(mu), _p(cov)))
+        return mu, cov
+
+    def sample_posterior(self, Xs, n_samples, seed):
+        """n_samples draws of the latent function at the columns of Xs: (F (M, n_samples), jitter), sls_gp_sample_posterior."""
+        Xs = _f(Xs)
+        M = Xs.shape[1]
+        F = np.empty((M, int(n_samples)), order="F")
+        jit = C.c_double(0.0)
+        _ck(lib().sls_gp_sample_posterior(self.h, _p(Xs), M, int(n_samples), C.c_ulonglong(int(seed)), _p(F), C.byref(jit)))
+        return F, jit.value
 
     def predict_grad(self, Xs):
         Xs = _f(Xs)

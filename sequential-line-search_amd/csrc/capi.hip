@@ -652,6 +652,18 @@ extern "C" int sls_gp_destroy(sls_gp* gp) {
     return SLS_OK;
 }
 
+namespace slsk {
+GpView gp_view(sls_gp* g) {
+    GpView v;
+    v.ctx = g->ctx;
+    v.D = g->D; v.N = g->N; v.Np = g->Np; v.Dp = g->Dp; v.Dcols = g->Dcols; v.kernel = g->kernel;
+    v.a = g->a; v.b = g->b;
+    v.XT = g->XT.p; v.nx = g->nx.p; v.inv_ell = g->inv_ell.p; v.alpha = g->alpha.p; v.Linv = g->Linv.p;
+    v.state = &g->state_mtx;
+    return v;
+}
+}  // namespace slsk
+
 extern "C" int sls_gp_generation(sls_gp* g, long* generation) {
     if (!g || !generation) return SLS_ERR_INVALID;
     std::unique_lock<std::recursive_mutex> lock_(g->ctx->mtx);

@@ -8,6 +8,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <shared_mutex>
 #include <string>
 #include <vector>
 
@@ -24,6 +25,17 @@ bool potrf_gave_up(sls_ctx* c, int abort_flag, int attempt);
 // what a fitted handle was created from (capi_multi.hip: replicas of an existing handle)
 int gp_export_inputs(sls_gp* g, int* D, int* N, int* kernel, int* sigma_mode, int* device, double* b, std::vector<double>* X,
                      std::vector<double>* y, std::vector<double>* theta);
+
+// The fitted state of a GP handle as the posterior entry points (capi_post.hip) read it: device pointers in the layout of
+// kernels.hpp, and the handle's state lock (shared while reading).
+struct GpView {
+    sls_ctx* ctx;
+    int D, N, Np, Dp, Dcols, kernel;
+    double a, b;
+    const double *XT, *nx, *inv_ell, *alpha, *Linv;
+    std::shared_mutex* state;
+};
+GpView gp_view(sls_gp* g);
 
 struct HipFail {
     int code;

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tuning.hpp"
+#include "../../include/sls_hip.h"
 
 #include <mutex>
 #include <map>
@@ -56,6 +57,20 @@ inline ChipGeometry chip_geometry() {
     g.n_xcd = (g.n_cu % 32 == 0) ? g.n_cu / 32 : 1;
     table[dev] = g;
     return g;
+}
+
+// k and the first-argument-derivative weight c (dk/dx_d = -c (x_d - x'_d) / l_d^2) of the scaled squared distance q
+// (kernels_gram.hip, kernels_post.hip)
+__device__ __forceinline__ void kernel_kc(int kernel, double a, double q, double& k, double& c) {
+    if (kernel == SLS_KERNEL_ARD_SQUARED_EXPONENTIAL) {
+        k = a * exp(-0.5 * q);
+        c = k;
+    } else {
+        const double s = sqrt(5.0 * q);
+        const double e = exp(-s);
+        k = a * (1.0 + s + (5.0 / 3.0) * q) * e;
+        c = a * (5.0 / 3.0) * (1.0 + s) * e;
+    }
 }
 
 struct KernelSpec {
@@ -351,6 +366,35 @@ void launch_append_update(hipStream_t s, double* Kinv, double* L, double* Linv, 
 // generic C = alpha * opA opB^T + beta * C on full 128-tiles (mt x nt tiles, K multiple of 16)
 void launch_gemm_plain(hipStream_t s, const double* A, long lda, bool a_kc, const double* B, long ldb, bool b_kc, double* C,
                        long ldc, int mt, int nt, int K, double alpha, double beta);
+
+// C = A L^T, L lower triangular (k < 128 (tn + 1) per output tile column); C = alpha L B^T + beta C (k < 128 (tm + 1) per tile row).
+// All operands M-contiguous, full 128-tiles (kernels_tri.hip).
+void launch_gemm_rhs_lower(hipStream_t s, const double* A, long lda, const double* L, long ldl, double* C, long ldc, int mt, int nt);
+void launch_gemm_lhs_lower(hipStream_t s, const double* L, long ldl, const double* B, long ldb, double* C, long ldc, int mt, int nt,
+                           double alpha, double beta);
+
+// ---- kernels_post.hip: joint posterior at M query points ---------------------------------------------------------
+// C[i + j*Mp] = k(xs_i, xs_j) - sum_{k < Kv} V[i + k*ldv] V[j + k*ldv] for i, j < M, identity in the padding (i or j >= M), for
+// the full Mp x Mp matrix: one workgroup per LOWER 128 x 128 tile, the tile and its mirror written from the same registers, so C
+// is exactly symmetric.  XsT [n + d*ldx] / ns: the query points' scaled coordinates and norms (launch_prep_points); Dp, Kv
+// multiples of 16.
+void launch_post_cov(hipStream_t s, const double* XsT, long ldx, int Dp, const double* ns, const double* V, long ldv, int Kv, int Mp,
+                     int M, KernelSpec ks, double* C);
+// Standard normal number t of stream `seed`: Philox4x64-10 with key (seed, 0) on block counter (t / 4, 0, 0, 0); each 64-bit
+// output x becomes u = ((x >> 11) + 0.5) 2^-53; Box-Muller on the output pairs (0, 1) and (2, 3) gives r01 cos, r01 sin, r23 cos,
+// r23 sin for t mod 4 = 0 .. 3.
+// Zt[sl + j*ldz] = normal number (s0 + sl) M + j for sl < sc, j < M; 0 for sl in [sc, Scp) or j in [M, Mp) (sample-major).
+void launch_normal_fill(hipStream_t s, unsigned long long seed, long s0, int sc, int Scp, int M, int Mp, double* Zt, long ldz);
+// out[i] = normal number offset + i of stream `seed`, i < n
+void launch_random_normal(hipStream_t s, unsigned long long seed, long offset, long n, double* out);
+// A[i + i*Mp] += v for i < M
+void launch_add_diag(hipStream_t s, double* A, int Mp, int M, double v);
+// flag[0] (device int) = 1 + the first i < M whose pivot L_ii^2 is <= thr (or not a number), 0 if none
+void launch_pivot_check(hipStream_t s, const double* L, int Mp, int M, double thr, int* flag);
+// zero the strictly upper triangle of every 128 x 128 diagonal block of A (Mp x Mp)
+void launch_zero_diag_upper(hipStream_t s, double* A, int Mp);
+// C[m + n*ldc] = mu[m] for m < Mp, n < ncols
+void launch_bcast_cols(hipStream_t s, const double* mu, int Mp, double* C, long ldc, int ncols);
 
 // ---- kernels_map.hip -----------------------------------------------------------
 // MAP-gradient weights (replaces the (D+1) x N x N tensor of CalcLargeKYThetaDerivative, src/regressor.cpp:110-134):

@@ -10,19 +10,6 @@
 
 namespace slsk {
 
-// k and the first-argument-derivative weight c (dk/dx_d = -c (x_d - x'_d) / l_d^2)
-__device__ __forceinline__ void kernel_kc(int kernel, double a, double q, double& k, double& c) {
-    if (kernel == SLS_KERNEL_ARD_SQUARED_EXPONENTIAL) {
-        k = a * exp(-0.5 * q);
-        c = k;
-    } else {
-        const double s = sqrt(5.0 * q);
-        const double e = exp(-s);
-        k = a * (1.0 + s + (5.0 / 3.0) * q) * e;
-        c = a * (5.0 / 3.0) * (1.0 + s) * e;
-    }
-}
-
 // 64 points per workgroup.  Pass 1 (all 256 threads, 64 dimensions at a time): scaled coordinates out (64 consecutive doubles per
 // dimension) and into LDS; pass 2 (one thread per point): the squared norm, summed over the dimensions in index order -- the order,
 // and therefore the bits, of the one-thread-per-point loop this replaces (16 workgroups and 128 dependent strided loads per thread at

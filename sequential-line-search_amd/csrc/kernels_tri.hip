@@ -25,8 +25,9 @@ struct GemmDesc {
     int tri;           // 1: only tiles tm >= tn + tri_off
     int tri_off;
     int order;         // tile issue order (longest k range first): 0 blockIdx = tm + tn*mt; 1 lower triangle row by row from
-                       // tm = 0 (grid = mt (mt + 1) / 2, kmode 3); 2 rows from tm = mt - 1 down (kmode 2); 3 rows from tm = 0 (kmode 4)
-    int kmode;         // 0: [0,K)  1: [128 tn, K)  2: [0, 128 (tm+1))  3: [128 max(tm,tn), K)  4: [128 tm, K)
+                       // tm = 0 (grid = mt (mt + 1) / 2, kmode 3); 2 rows from tm = mt - 1 down (kmode 2); 3 rows from tm = 0 (kmode 4);
+                       // 4 columns from tn = nt - 1 down (kmode 5)
+    int kmode;         // 0: [0,K)  1: [128 tn, K)  2: [0, 128 (tm+1))  3: [128 max(tm,tn), K)  4: [128 tm, K)  5: [0, 128 (tn+1))
     int vb_stride, vb_off, vb_limit;   // tile row (vb_on_n: tile column) valid iff batch*vb_stride + vb_off + tm (tn) < vb_limit
     int vb_on_n;
     int mirror;        // 1 (square lower-triangular outputs): tile (tm, tn), tm > tn, is also written transposed at (tn, tm)
@@ -54,6 +55,9 @@ __global__ __launch_bounds__(256, 2) void tri_gemm_kernel(GemmDesc g) {
     } else if (g.order == 3) {
         tm = unit / g.nt;
         tn = unit % g.nt;
+    } else if (g.order == 4) {
+        tn = g.nt - 1 - unit / g.mt;
+        tm = unit % g.mt;
     }
     const int batch = blockIdx.y;
     if (g.tri && tn + g.tri_off > tm) return;
@@ -64,6 +68,7 @@ __global__ __launch_bounds__(256, 2) void tri_gemm_kernel(GemmDesc g) {
     else if (g.kmode == 2) ke = min(g.K, NB * (tm + 1));
     else if (g.kmode == 3) kb = NB * max(tm, tn);
     else if (g.kmode == 4) kb = NB * tm;
+    else if (g.kmode == 5) ke = min(g.K, NB * (tn + 1));
     const double* A = g.A + batch * g.strideA;
     const double* B = g.B + batch * g.strideB;
     double* C = g.C + batch * g.strideC;
@@ -133,6 +138,23 @@ void launch_gemm_plain(hipStream_t s, const double* A, long lda, bool a_kc, cons
     else if (!a_kc && b_kc) launch_tri_gemm<false, true>(s, g, 1);
     else if (a_kc && b_kc) launch_tri_gemm<true, true>(s, g, 1);
     else launch_tri_gemm<true, false>(s, g, 1);
+}
+
+// C = A L^T with L lower triangular (both M-contiguous): output tile column tn contracts k < 128 (tn + 1) only -- the blocks of L
+// above its diagonal are never read (V = K* L^-T of the joint posterior: half the flops of the plain product).  Longest k range first.
+void launch_gemm_rhs_lower(hipStream_t s, const double* A, long lda, const double* L, long ldl, double* C, long ldc, int mt, int nt) {
+    GemmDesc g = mkdesc(A, lda, L, ldl, C, ldc, mt, nt, nt * NB, 1.0, 0.0);
+    g.kmode = 5;
+    g.order = 4;
+    launch_tri_gemm<false, false>(s, g, 1);
+}
+// C = alpha L B^T + beta C with L lower triangular (both M-contiguous): output tile row tm contracts k < 128 (tm + 1) only.
+void launch_gemm_lhs_lower(hipStream_t s, const double* L, long ldl, const double* B, long ldb, double* C, long ldc, int mt, int nt,
+                           double alpha, double beta) {
+    GemmDesc g = mkdesc(L, ldl, B, ldb, C, ldc, mt, nt, mt * NB, alpha, beta);
+    g.kmode = 2;
+    g.order = 2;
+    launch_tri_gemm<false, false>(s, g, 1);
 }
 
 // C_part[c] = A[:, K_c] * B[:, K_c]^T for `chunks` equal ranges K_c of the contraction (A M-contiguous, B K-contiguous): a tall

@@ -146,6 +146,27 @@ namespace sequential_line_search
         }
     }
 
+    MatrixXd Regressor::PredictCovariance(const MatrixXd& Xs) const
+    {
+        sls_gp* h = GetDeviceHandle();
+        if (!h) return MatrixXd();
+        const long M   = Xs.cols();
+        MatrixXd   cov(M, M);
+        device::Check(sls_gp_predict_cov(h, Xs.data(), static_cast<int>(M), nullptr, cov.data()), "sls_gp_predict_cov");
+        return cov;
+    }
+
+    MatrixXd Regressor::SamplePosterior(const MatrixXd& Xs, int num_samples, unsigned long long seed, double* jitter_used) const
+    {
+        sls_gp* h = GetDeviceHandle();
+        if (!h) return MatrixXd();
+        const long M = Xs.cols();
+        MatrixXd   F(M, num_samples);
+        device::Check(sls_gp_sample_posterior(h, Xs.data(), static_cast<int>(M), num_samples, seed, F.data(), jitter_used),
+                      "sls_gp_sample_posterior");
+        return F;
+    }
+
     // reference: src/regressor.cpp:45-59
     VectorXd CalcSmallK(const VectorXd& x, const MatrixXd& X, const VectorXd& theta, const Kernel kernel)
     {

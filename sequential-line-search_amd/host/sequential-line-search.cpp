@@ -139,6 +139,17 @@ namespace sequential_line_search
         if (m_regressor) m_regressor->PredictBatch(points, mu, sigma);
         return sigma;
     }
+    Eigen::MatrixXd SequentialLineSearchOptimizer::GetPreferenceValueCovariance(const Eigen::MatrixXd& points) const
+    {
+        if (!m_regressor) return Eigen::MatrixXd::Zero(points.cols(), points.cols());
+        return m_regressor->PredictCovariance(points);
+    }
+    Eigen::MatrixXd SequentialLineSearchOptimizer::SamplePreferenceValues(const Eigen::MatrixXd& points, const int num_samples,
+                                                  const unsigned long long seed) const
+    {
+        if (!m_regressor) return Eigen::MatrixXd::Zero(points.cols(), num_samples);
+        return m_regressor->SamplePosterior(points, num_samples, seed);
+    }
     Eigen::VectorXd SequentialLineSearchOptimizer::GetAcquisitionFuncValues(const Eigen::MatrixXd& points) const
     {
         if (!m_regressor) return Eigen::VectorXd::Zero(points.cols());
