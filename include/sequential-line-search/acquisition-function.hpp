@@ -91,6 +91,22 @@ namespace sequential_line_search
                                                     const unsigned            num_local_search_iters  = 50,
                                                     const AcquisitionFuncType func_type = AcquisitionFuncType::ExpectedImprovement,
                                                     const double gaussian_process_upper_confidence_bound_hyperparam = 1.0);
+
+        /// Batch by Thompson sampling (not in the reference): num_points pathwise posterior draws of the latent function
+        /// (Regressor::SamplePosteriorFunctions, stream `seed`, num_frequencies random features), each maximised over [0,1]^D from
+        /// num_global_search_iters uniform random starts with num_local_search_iters L-BFGS evaluations each, all draws in one
+        /// lock-step run on the device.  One maximiser per draw; the starts come from a generator seeded with `seed`, so the same
+        /// seed gives the same points.
+        std::vector<Eigen::VectorXd> FindNextPointsByThompsonSampling(const Regressor& regressor, const unsigned num_points,
+                                                                      const unsigned num_global_search_iters = 100,
+                                                                      const unsigned num_local_search_iters  = 50,
+                                                                      const unsigned long long seed = 0, const int num_frequencies = 2048);
+        /// The same from an explicit start set: starts is D x (num_points S), columns [s S, (s + 1) S) start draw s.
+        std::vector<Eigen::VectorXd> FindNextPointsByThompsonSamplingFromStarts(const Regressor& regressor, const unsigned num_points,
+                                                                                const Eigen::MatrixXd& starts,
+                                                                                const unsigned         num_local_search_iters,
+                                                                                const unsigned long long seed = 0,
+                                                                                const int num_frequencies = 2048);
     } // namespace acquisition_func
 } // namespace sequential_line_search
 

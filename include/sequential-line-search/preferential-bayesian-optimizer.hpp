@@ -48,6 +48,11 @@ namespace sequential_line_search
         /// Builds the next query: option 0 = current best, the others from FindNextPoints.  Non-positive arguments select
         /// the reference's multi-start heuristic (500 D starts, 10 D local evaluations).
         void DetermineNextQuery(const int num_global_search_iters = 0, const int num_local_search_iters = 0);
+        /// Opt-in alternative: option 0 as in DetermineNextQuery, the other options the maximisers of m_num_options - 1 pathwise
+        /// posterior draws (acquisition_func::FindNextPointsByThompsonSampling with stream `seed`).  Non-positive arguments select
+        /// the same heuristic as DetermineNextQuery.
+        void DetermineNextQueryByThompsonSampling(const unsigned long long seed, const int num_global_search_iters = 0,
+                                                  const int num_local_search_iters = 0);
 
         const std::vector<Eigen::VectorXd>& GetCurrentOptions() const { return m_current_options; }
         Eigen::VectorXd                     GetMaximizer() const;
@@ -78,6 +83,10 @@ namespace sequential_line_search
         }
 
     private:
+        /// q options from (q, n_global, n_local): the part in which the two query builders differ
+        using OptionGenerator = std::function<std::vector<Eigen::VectorXd>(int, int, int)>;
+        void BuildNextQuery(const char* caller, int num_global_search_iters, int num_local_search_iters, const OptionGenerator& generate);
+
         const bool m_use_map_hyperparams;
         const int  m_num_options;
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 struct sls_gp;
+struct sls_path;
 
 namespace sequential_line_search
 {
@@ -55,12 +56,47 @@ namespace sequential_line_search
         /// nullptr) receives j.
         Eigen::MatrixXd SamplePosterior(const Eigen::MatrixXd& Xs, int num_samples, unsigned long long seed,
                                         double* jitter_used = nullptr) const;
+        /// num_draws pathwise posterior function draws (sls_path_create): closed-form functions that can be evaluated -- and
+        /// maximised -- anywhere in [0,1]^D, from num_frequencies random features shared by all draws.  Needs the device handle
+        /// (std::invalid_argument otherwise).  The object holds a snapshot of this regressor's fit and must not outlive it.
+        class PosteriorFunctionSamples SamplePosteriorFunctions(int num_draws, unsigned long long seed, int num_frequencies = 2048) const;
 
     protected:
         KernelType               m_kernel_type;
         Kernel                   m_kernel;
         KernelThetaDerivative    m_kernel_theta_derivative;
         KernelFirstArgDerivative m_kernel_first_arg_derivative;
+    };
+
+    /// Posterior function draws of a fitted regressor (Regressor::SamplePosteriorFunctions; include/sls_hip.h sls_path_*).  The
+    /// draws share one set of random frequencies: each is an exact draw from the random-feature-approximate posterior, and the
+    /// O(a / sqrt(F)) error of that prior is common to all of them.  Move-only.
+    class PosteriorFunctionSamples
+    {
+    public:
+        /// handle: a fitted device handle of num_dims dimensions (Regressor::GetDeviceHandle).
+        PosteriorFunctionSamples(sls_gp* handle, int num_dims, int num_draws, unsigned long long seed, int num_frequencies);
+        PosteriorFunctionSamples(PosteriorFunctionSamples&& other) noexcept;
+        PosteriorFunctionSamples& operator=(PosteriorFunctionSamples&& other) noexcept;
+        PosteriorFunctionSamples(const PosteriorFunctionSamples&) = delete;
+        PosteriorFunctionSamples& operator=(const PosteriorFunctionSamples&) = delete;
+        ~PosteriorFunctionSamples();
+
+        int GetNumDraws() const { return m_num_draws; }
+        /// Every draw at every column of Xs (D x M): M x num_draws.
+        Eigen::MatrixXd Evaluate(const Eigen::MatrixXd& Xs) const;
+        /// Gradient of draw `draw` at x (D).
+        Eigen::VectorXd EvaluateDerivative(const Eigen::VectorXd& x, int draw) const;
+        /// One maximiser per draw: starts is D x (num_draws S), columns [s S, (s + 1) S) start draw s; one lock-step bounded L-BFGS
+        /// of num_local_search_iters evaluations per start (the acquisition maximiser's local search tolerances); per draw the
+        /// best end point.  values (may be nullptr) receives the draws' maxima.
+        std::vector<Eigen::VectorXd> Maximize(const Eigen::MatrixXd& starts, unsigned num_local_search_iters,
+                                              Eigen::VectorXd* values = nullptr) const;
+
+    private:
+        sls_path* m_path      = nullptr;
+        int       m_num_draws = 0;
+        int       m_num_dims  = 0;
     };
 
     // k

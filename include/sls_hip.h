@@ -220,6 +220,44 @@ int sls_acq_maximize_pair(sls_gp* gp_mean, sls_gp* gp_sigma, int acq_type, doubl
 /* Re-fit an existing handle in place from device-resident X (D x N), y (N): the timed "GP fit" of bench.py. */
 int sls_gp_refit_dev(sls_gp* gp, const double* X_dev, const double* y_dev);
 
+/* ---- pathwise posterior function draws (not in the reference) ---------------------------------------------------------
+ * Thompson sampling needs a draw of the latent function that can be evaluated -- and maximised -- anywhere in [0,1]^D.  Pathwise
+ * conditioning (Wilson et al. 2020) gives each draw s in closed form:
+ *   f_s(x) = sqrt(a/F) sum_l [ w_{s,l} cos(om_l . x~) + w'_{s,l} sin(om_l . x~) ]  +  sum_i v_{s,i} k(x, x_i)
+ *   v_s    = K_y^-1 ( y - f_prior,s(X) - sqrt(b) eps_s )
+ * with x~ = (x - 0.5) o inv_ell, F random frequencies om_l, w, w' ~ N(0, I), eps_s ~ N(0, I_N).  SE: om ~ N(0, I);
+ * Matern 5/2: om = z sqrt(5 / u), z ~ N(0, I), u ~ chi^2_5.  A PreferenceRegressor handle works unchanged (y = MAP latent, b its
+ * noise).
+ * ONE frequency set is shared by all draws of an object: each draw is an exact draw from the random-feature-approximate posterior,
+ * but the approximation error of the prior (O(a / sqrt(F))) is common to all draws, not independent between them.
+ * Generator (sls_random_normal of stream `seed`; part of the contract):
+ *   frequency l uses numbers l D .. l D + D - 1 (z);  Matern only: u_l = sum_{j<5} z^2 over numbers F D + 5 l + j;
+ *   B0 = F D (SE) or F D + 5 F (Matern) is the length of this draw-independent block;
+ *   draw s starts at B0 + s (2F + N): w_s (F numbers), then w'_s (F), then eps_s (N).
+ * So the first k draws of an n-draw object equal a k-draw object bit for bit, and equal inputs give equal bits.
+ * The object keeps v (N x n_draws), W (2F x n_draws) and om (F x D) on the device and records sls_gp_generation: a call after the
+ * handle was refitted, grown (sls_gp_append_point) or switched in sigma mode returns SLS_ERR_INVALID and uses no stale state.
+ * Locks as the handle's other large calls: the context's lock and the handle's state lock (shared) for the whole call.  The
+ * object must not outlive its handle.
+ * Limits: 1 <= n_draws <= 4096, 1 <= n_freq <= 16384 (padding is internal); anything else is SLS_ERR_INVALID.
+ * Memory: the object keeps om, W and v only (about 8 (F D + 2 F n_draws + N n_draws) bytes, padded).  Each eval / maximize call takes
+ * its workspace from the device pool and returns it at the end: per candidate chunk about 3 chunk N + 2 chunk F doubles (chunk <=
+ * min(16384, 2^26 / max(N, 2F))), i.e. up to 2 GB at N = 8192; sls_device_trim_cache gives the pool's blocks back to the driver. */
+typedef struct sls_path sls_path;
+/* n_draws posterior function draws of the fitted handle gp, F = n_freq random frequencies (2F features), stream `seed`. */
+int sls_path_create(sls_gp* gp, int n_draws, int n_freq, unsigned long long seed, sls_path** out);
+int sls_path_destroy(sls_path* p);
+/* draw_of_point == NULL: val is M x n_draws (every draw at every point, column-major), grad must be NULL.
+   otherwise: val[m] = f_{draw_of_point[m]}(Xs[:,m]), grad D x M (may be NULL).  Xs is D x M.  A point's bits depend neither on its
+   column nor on the other points of the call. */
+int sls_path_eval(sls_path* p, const double* Xs, int M, const int* draw_of_point, double* val, double* grad);
+/* starts D x (n_draws * S): columns [s*S, (s+1)*S) belong to draw s.  One lock-step bounded L-BFGS over all of them (n_local
+   evaluations per start, the maximiser of sls_acq_maximize with f_s as the objective); per draw the first maximum over its own
+   end points: x_out D x n_draws, val_out n_draws, idx_out n_draws (start index within the draw).  Any out pointer may be NULL.
+   A draw's result does not depend on the other draws or their starts. */
+int sls_path_maximize(sls_path* p, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts, double* x_out,
+                      double* val_out, long* idx_out);
+
 /* ---- multi-GPU maximisation ------------------------------------------------------------------------------
  * FindGlobalSolution's multi-start loop (src/acquisition-function.cpp:121-153) shards over its starts: the iterations share
  * only the const regressor (:125-141).  Every GPU holds a replica of the fitted state, runs a contiguous slice of the starts
@@ -339,7 +377,9 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
  * Names: "gram", "potri" (N <= 4096: factor + L^-1 + K^-1 in one launch) or "potrf", "trtri", "lauum" (larger N, or
  * SLS_POTRI_FUSED=0), "fit_small" (N <= 128: the whole fit in one launch), "cross_gram", "acq_gemm", "grad_gemm", "finalize",
  * "lbfgs"; the posterior calls: "post_v" (V = K* L^-T), "post_cov" (the covariance tiles), "post_potrf" (chol(cov + j I), one launch
- * per jitter tried), "post_sample" (normals + the sample product); "potrf_fallbacks": launches = how often a single-launch
+ * per jitter tried), "post_sample" (normals + the sample product); the path draws: "path_setup" (normals, frequencies, weights,
+ * f_prior(X)), "path_solve" (v = K_y^-1 r), "path_prior" (the random-feature prior of an evaluation), "path_data" (the data term
+ * on cross_gram's K*; cross_gram and grad_gemm count under their own names); "potrf_fallbacks": launches = how often a single-launch
  * factorisation gave up and was recomputed. */
 int sls_prof_enable(sls_ctx* ctx, int on);
 int sls_prof_reset(sls_ctx* ctx);

@@ -155,6 +155,8 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
              "other_options"_a, "num_map_estimation_iters"_a = 0)
         .def("determine_next_query", &PreferentialBayesianOptimizer::DetermineNextQuery, "num_global_search_iters"_a = 0,
              "num_local_search_iters"_a = 0)
+        .def("determine_next_query_by_thompson_sampling", &PreferentialBayesianOptimizer::DetermineNextQueryByThompsonSampling,
+             "seed"_a, "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0)
         .def("get_current_options", &PreferentialBayesianOptimizer::GetCurrentOptions)
         .def("get_maximizer", &PreferentialBayesianOptimizer::GetMaximizer)
         .def("get_preference_value_mean", &PreferentialBayesianOptimizer::GetPreferenceValueMean, "point"_a)

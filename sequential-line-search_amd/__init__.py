@@ -61,6 +61,7 @@ EXPORTS = [
     "sls_multi_gp_destroy", "sls_multi_gp_shard", "sls_multi_acq_maximize", "sls_multi_gp_predict", "sls_comm_unique_id", "sls_comm_create",
     "sls_comm_destroy", "sls_comm_allgather_best", "sls_device_trim_cache", "sls_tuning_reload", "sls_gp_generation",
     "sls_gp_predict_cov", "sls_gp_sample_posterior", "sls_random_normal",
+    "sls_path_create", "sls_path_destroy", "sls_path_eval", "sls_path_maximize",
 ]
 
 
@@ -305,6 +306,60 @@ class GP:
 
     def refit_dev(self, X_dev_ptr, y_dev_ptr):
         _ck(lib().sls_gp_refit_dev(self.h, C.c_void_p(X_dev_ptr), C.c_void_p(y_dev_ptr)))
+
+
+class PathSamples:
+    """n_draws pathwise posterior function draws of a fitted GP handle (sls_path_*): F = n_freq shared random frequencies, normal
+    stream `seed`.  A draw can be evaluated anywhere and maximised over [0,1]^D (Thompson sampling)."""
+
+    def __init__(self, gp, n_draws, n_freq=2048, seed=0):
+        self.gp, self.D, self.n_draws, self.n_freq = gp, gp.D, int(n_draws), int(n_freq)
+        self.h = C.c_void_p()
+        _ck(lib().sls_path_create(gp.h, self.n_draws, self.n_freq, C.c_ulonglong(int(seed)), C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().sls_path_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def eval(self, Xs, draw_of_point, want_grad=True):
+        """f_{draw_of_point[m]}(Xs[:, m]): values (M,) and, with want_grad, gradients (D, M)."""
+        Xs = _f(Xs)
+        M = Xs.shape[1]
+        dr = np.ascontiguousarray(np.asarray(draw_of_point, dtype=np.int32))
+        assert dr.shape == (M,)
+        val = np.empty(M)
+        grad = np.empty((self.D, M), order="F") if want_grad else None
+        _ck(lib().sls_path_eval(self.h, _p(Xs), M, dr.ctypes.data_as(C.POINTER(C.c_int)), _p(val), _p(grad) if want_grad else None))
+        return (val, grad) if want_grad else val
+
+    def eval_all(self, Xs):
+        """Every draw at every column of Xs: (M, n_draws)."""
+        Xs = _f(Xs)
+        M = Xs.shape[1]
+        val = np.empty((M, self.n_draws), order="F")
+        _ck(lib().sls_path_eval(self.h, _p(Xs), M, None, _p(val), None))
+        return val
+
+    def maximize(self, starts, n_local, opts=None):
+        """starts (D, n_draws * S), columns [s S, (s + 1) S) for draw s: per draw (x (D, n_draws), value (n_draws,), start index
+        within the draw (n_draws,))."""
+        starts = _f(starts)
+        T = starts.shape[1]
+        assert T % self.n_draws == 0
+        S = T // self.n_draws
+        x = np.empty((self.D, self.n_draws), order="F")
+        val = np.empty(self.n_draws)
+        idx = np.empty(self.n_draws, dtype=np.int64)
+        _ck(lib().sls_path_maximize(self.h, _p(starts), S, int(n_local), C.byref(opts) if opts is not None else None, _p(x), _p(val),
+                                    idx.ctypes.data_as(C.POINTER(C.c_long))))
+        return dict(x=x, value=val, index=idx)
 
 
 class PrefCfg(C.Structure):

@@ -659,6 +659,8 @@ GpView gp_view(sls_gp* g) {
     v.D = g->D; v.N = g->N; v.Np = g->Np; v.Dp = g->Dp; v.Dcols = g->Dcols; v.kernel = g->kernel;
     v.a = g->a; v.b = g->b;
     v.XT = g->XT.p; v.nx = g->nx.p; v.inv_ell = g->inv_ell.p; v.alpha = g->alpha.p; v.Linv = g->Linv.p;
+    v.y = g->y.p; v.L = g->L.p;
+    v.generation = g->generation;
     v.state = &g->state_mtx;
     return v;
 }
@@ -1181,7 +1183,7 @@ extern "C" void sls_lbfgs_default_opts(sls_lbfgs_opts* o) {
     o->history = 6; o->c1 = 1e-4; o->shrink = 0.5; o->gtol = 0.0; o->max_backtracks = 20; o->ftol_rel = 0.0; o->xtol_rel = 0.0;
 }
 // the caller's struct may be shorter than this library's (an older header): its struct_size bytes over the defaults
-static sls_lbfgs_opts read_lbfgs_opts(const sls_lbfgs_opts* in) {
+sls_lbfgs_opts slsk::read_lbfgs_opts(const sls_lbfgs_opts* in) {
     sls_lbfgs_opts o;
     sls_lbfgs_default_opts(&o);
     if (!in) return o;

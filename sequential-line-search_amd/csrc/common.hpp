@@ -33,9 +33,13 @@ struct GpView {
     int D, N, Np, Dp, Dcols, kernel;
     double a, b;
     const double *XT, *nx, *inv_ell, *alpha, *Linv;
+    const double *y, *L;   // the data's targets (N, padded to Np) and the Cholesky factor of K_y (Np x Np)
+    long generation;       // sls_gp_generation
     std::shared_mutex* state;
 };
 GpView gp_view(sls_gp* g);
+// sls_lbfgs_opts as the caller's struct_size declares it, over the library's defaults (capi.hip)
+sls_lbfgs_opts read_lbfgs_opts(const sls_lbfgs_opts* in);
 
 struct HipFail {
     int code;

@@ -201,7 +201,8 @@ void launch_var_gemm(hipStream_t s, const double* Ks, long ldk, int Sp, const do
 // t tiles (0: never) -- the tests run both forms against each other.
 inline bool grad_gemm_wants_split(int Sp) { return !tune_set(TUNE_GRAD_SPLIT_TILES) || 2 * (Sp / 128) < tune(TUNE_GRAD_SPLIT_TILES, 0); }
 void launch_grad_gemm(hipStream_t s, const double* P, const double* Cs, long ldk, int Sp, const double* XT, const double* XaT,
-                      long ld, int Np, int Dcols, double* Gs, double* Gm, double* part = nullptr);
+                      long ld, int Np, int Dcols, double* Gs, double* Gm, double* part = nullptr, int passes = 2);
+// passes = 1: the Gs product only (Cs, XaT, Gm are not read or written)
 struct FinalizeArgs {
     int S, D, nbt;            // candidates in this chunk, dims, number of 128-row tiles of i
     int ntm, split_first;     // candidate tiles of the chunk; first half-split tile of launch_acq_gemm (INT_MAX: none)
@@ -395,6 +396,35 @@ void launch_pivot_check(hipStream_t s, const double* L, int Mp, int M, double th
 void launch_zero_diag_upper(hipStream_t s, double* A, int Mp);
 // C[m + n*ldc] = mu[m] for m < Mp, n < ncols
 void launch_bcast_cols(hipStream_t s, const double* mu, int Mp, double* C, long ldc, int ncols);
+
+// ---- kernels_path.hip: pathwise posterior function draws (sls_path_*) ----------------------------------------------------
+// Om[l + d*Fp] = frequency l (l < F, d < D; 0 in the padding up to Fp x Dc) from the B0 normals Z of the draw-independent block
+void launch_path_omega(hipStream_t s, const double* Z, int F, int Fp, int D, int Dc, int matern, double* Om);
+// W (2Fp x Rp, ld 2Fp): cos weights in rows [0, F), sin weights in rows [Fp, Fp + F), times `scale`, from the draw block E; 0 elsewhere
+void launch_path_weights(hipStream_t s, const double* E, int F, int Fp, int N, int n_draws, int Rp, double scale, double* W);
+// R[i + s*Np] <- y_i - sqrt_b eps_{s,i} - R[i + s*Np] (i < N, s < n_draws), 0 in the padding (Np x Rp)
+void launch_path_rhs(hipStream_t s, const double* y, const double* E, int F, int N, int Np, int n_draws, int Rp, double sqrt_b,
+                     double* R);
+// Random-feature contraction of Mp points (XsT [m + d*ldx], Dp columns) with the frequencies (Om [l + d*Fp], Fp a multiple of 128) on
+// the matrix cores, sincos epilogue.  draw != nullptr (gathered form, rows m < nvalid under draw[m]): G[m + l*ldg] = W_s cos - W_c
+// sin and the value partials vpart[chunk*ldv + m] of the 128-frequency chunks; draw == nullptr: G[m + l*ldg] = cos, G[m + (Fp+l)*ldg]
+// = sin (the features Phi, Mp x 2Fp).
+void launch_path_feat(hipStream_t s, const double* XsT, long ldx, int Dp, int Mp, const double* Om, int Fp, const double* W, long ldw,
+                      const int* draw, int nvalid, double* G, long ldg, double* vpart, long ldv);
+// val[n] = sum over the chunks (in order) of vpart[c*ldv + n]
+void launch_path_vsum(hipStream_t s, const double* vpart, long ldv, int nchunk, int S, double* val);
+// Data term of P (point, draw) pairs on K* / C* ([pt + i*ldk], cross_gram): val[o] += K*[pt, :] . V[:, dr].  Gathered form (draw !=
+// nullptr): point p under draw[p], o = p; every-draw form: point p % npts under draw p / npts, o = pt + dr*ldo.  Pm != nullptr
+// (gathered form only): Pm[pt + i*ldk] = C*[pt, i] V[i, dr] (0 for N <= i < Np) and csum[pt] = sum_i Pm[pt, i]
+void launch_path_data(hipStream_t s, const double* Ks, const double* Cs, long ldk, int N, int Np, const double* V, long ldv, const int* draw,
+                      int npts, long ldo, int P, double* val, double* Pm, double* csum);
+// grad[n + d*ldo] = inv_ell_d (Gt[n + d*ldk] - XsT[n + d*ldk] csum[n])
+void launch_path_grad(hipStream_t s, int S, int D, long ldk, const double* Gt, const double* XsT, const double* csum, const double* inv_ell,
+                      double* grad, long ldo);
+// draw[j] = (live ? live[j] : j) / S, j < n
+void launch_path_draw_of_live(hipStream_t s, const int* live, int n, int S, int* draw);
+// per draw s (starts [s S, (s+1) S)): first maximum of -f; out[s (D + 2) + 0] = value, [+1] = index within the draw, [+2 ..] = x
+void launch_path_argmax(hipStream_t s, const double* f, int S, int n_draws, const double* x, long ldx, int D, double* out);
 
 // ---- kernels_map.hip -----------------------------------------------------------
 // MAP-gradient weights (replaces the (D+1) x N x N tensor of CalcLargeKYThetaDerivative, src/regressor.cpp:110-134):

@@ -413,13 +413,12 @@ __global__ __launch_bounds__(256, 3) void grad_gemm64_kernel(const double* __res
 }
 
 __global__ __launch_bounds__(256) void grad_reduce4_kernel(const double* __restrict__ part, int Sp, long ldk, double* __restrict__ Gs,
-                                                           double* __restrict__ Gm) {
+                                                           double* __restrict__ Gm, int passes) {
     const long idx = blockIdx.x * 256L + threadIdx.x;       // n + d * Sp, d < 64
     if (idx >= (long)Sp * 64) return;
     const long n = idx % Sp, d = idx / Sp;
     const long stride = (long)Sp * 64;
-#pragma unroll
-    for (int y = 0; y < 2; ++y) {
+    for (int y = 0; y < passes; ++y) {
         const double* p = part + (long)y * stride + idx;
         const double v = ((p[0] + p[2 * stride]) + p[4 * stride]) + p[6 * stride];
         (y == 0 ? Gs : Gm)[n + d * ldk] = v;
@@ -427,19 +426,20 @@ __global__ __launch_bounds__(256) void grad_reduce4_kernel(const double* __restr
 }
 
 void launch_grad_gemm(hipStream_t s, const double* P, const double* Cs, long ldk, int Sp, const double* XT, const double* XaT,
-                      long ld, int Np, int Dcols, double* Gs, double* Gm, double* part) {
+                      long ld, int Np, int Dcols, double* Gs, double* Gm, double* part, int passes) {
     ensure_dyn_lds((const void*)grad_gemm_kernel, GEMM_LDS_BYTES);
     ensure_dyn_lds((const void*)grad_gemm64_kernel, gemm_n64_lds_bytes<GRAD64_A_LD>());
     if (Dcols < 0) {   // caller signals D <= 64 by passing -Dcols
         const bool split = part != nullptr && grad_gemm_wants_split(Sp);
-        hipLaunchKernelGGL(grad_gemm64_kernel, dim3(Sp / GEMM_BM, 2, split ? 4 : 1), dim3(GEMM_THREADS), gemm_n64_lds_bytes<GRAD64_A_LD>(), s, P, Cs,
+        hipLaunchKernelGGL(grad_gemm64_kernel, dim3(Sp / GEMM_BM, passes, split ? 4 : 1), dim3(GEMM_THREADS), gemm_n64_lds_bytes<GRAD64_A_LD>(), s, P, Cs,
                            ldk, Sp, XT, XaT, ld, Np, Gs, Gm, part);
         if (split)
-            hipLaunchKernelGGL(grad_reduce4_kernel, dim3((unsigned)(((long)Sp * 64 + 255) / 256)), dim3(256), 0, s, part, Sp, ldk, Gs, Gm);
+            hipLaunchKernelGGL(grad_reduce4_kernel, dim3((unsigned)(((long)Sp * 64 + 255) / 256)), dim3(256), 0, s, part, Sp, ldk, Gs, Gm,
+                               passes);
         return;
     }
     const int nt = (Sp / GEMM_BM) * (Dcols / GEMM_BN);
-    hipLaunchKernelGGL(grad_gemm_kernel, dim3(nt, 2), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, P, Cs, ldk, Sp, XT, XaT, ld, Np, Dcols,
+    hipLaunchKernelGGL(grad_gemm_kernel, dim3(nt, passes), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, P, Cs, ldk, Sp, XT, XaT, ld, Np, Dcols,
                        Gs, Gm);
 }
 

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
+#include <random>
 #include <string>
 #include <sequential-line-search/acquisition-function.hpp>
 #include <sequential-line-search/gaussian-process-regressor.hpp>
@@ -316,5 +317,33 @@ namespace sequential_line_search
             }
         }
         return points;
+    }
+
+    std::vector<VectorXd> acquisition_func::FindNextPointsByThompsonSampling(const Regressor& regressor, const unsigned num_points,
+                                                                             const unsigned num_global_search_iters,
+                                                                             const unsigned num_local_search_iters,
+                                                                             const unsigned long long seed, const int num_frequencies)
+    {
+        // uniform starts in [0,1]^D as RandomStarts draws them, from a generator of their own so that `seed` fixes the whole batch
+        const unsigned num_dim = regressor.GetNumDims();
+        const unsigned S       = std::max(1u, num_global_search_iters);
+        MatrixXd       starts(num_dim, static_cast<long>(num_points) * S);
+        std::mt19937_64                        rng(seed);
+        std::uniform_real_distribution<double> uni(0.0, 1.0);
+        for (long j = 0; j < starts.cols(); ++j)
+            for (unsigned d = 0; d < num_dim; ++d) starts(d, j) = uni(rng);
+        return FindNextPointsByThompsonSamplingFromStarts(regressor, num_points, starts, num_local_search_iters, seed, num_frequencies);
+    }
+
+    std::vector<VectorXd> acquisition_func::FindNextPointsByThompsonSamplingFromStarts(const Regressor& regressor, const unsigned num_points,
+                                                                                       const MatrixXd& starts,
+                                                                                       const unsigned num_local_search_iters,
+                                                                                       const unsigned long long seed,
+                                                                                       const int num_frequencies)
+    {
+        if (num_points == 0) return {};
+        RequireHandle(regressor);
+        const PosteriorFunctionSamples draws = regressor.SamplePosteriorFunctions(static_cast<int>(num_points), seed, num_frequencies);
+        return draws.Maximize(starts, num_local_search_iters);
     }
 } // namespace sequential_line_search

@@ -1,5 +1,6 @@
 // PreferentialBayesianOptimizer facade (reference: src/preferential-bayesian-optimizer.cpp) -- the second caller of the
 // device path (PreferenceRegressor MAP + FindNextPoints).
+#include <string>
 #include <sequential-line-search/preference-data-manager.hpp>
 #include <sequential-line-search/preference-regressor.hpp>
 #include <sequential-line-search/preferential-bayesian-optimizer.hpp>
@@ -73,10 +74,12 @@ namespace sequential_line_search
         PerformMapEstimation(num_map_estimation_iters);
     }
 
-    // reference: :95-141 (heuristic of the parallel multi-start branch: 500 D starts, 10 D local evaluations)
-    void PreferentialBayesianOptimizer::DetermineNextQuery(const int num_global_search_iters, const int num_local_search_iters)
+    // Option 0 (current best) and options 1.. from `generate(num_options - 1, n_global, n_local)`; non-positive iteration counts take
+    // the reference's multi-start heuristic (:95-141: 500 D starts, 10 D local evaluations).  Shared by both query builders.
+    void PreferentialBayesianOptimizer::BuildNextQuery(const char* caller, const int num_global_search_iters, const int num_local_search_iters,
+                                                       const OptionGenerator& generate)
     {
-        if (!m_regressor) throw std::logic_error("PreferentialBayesianOptimizer::DetermineNextQuery called before any feedback");
+        if (!m_regressor) throw std::logic_error(std::string("PreferentialBayesianOptimizer::") + caller + " called before any feedback");
         const int num_dims = static_cast<int>(GetMaximizer().size());
         const int n_global = num_global_search_iters > 0 ? num_global_search_iters : 500 * num_dims;
         const int n_local  = num_local_search_iters > 0 ? num_local_search_iters : 10 * num_dims;
@@ -84,11 +87,27 @@ namespace sequential_line_search
         const VectorXd x_plus = (m_current_best_selection_strategy == CurrentBestSelectionStrategy::LargestExpectValue)
                                     ? m_regressor->FindArgMax()
                                     : m_data->GetLastSelectedDataPoint();
-        const std::vector<VectorXd> next = acquisition_func::FindNextPoints(*m_regressor, m_num_options - 1, n_global, n_local,
-                                                                            m_acquisition_func_type,
-                                                                            m_gaussian_process_upper_confidence_bound_hyperparam);
+        const std::vector<VectorXd> next = generate(m_num_options - 1, n_global, n_local);
         m_current_options[0] = x_plus;
         for (int i = 1; i < m_num_options; ++i) m_current_options[i] = next[i - 1];
+    }
+
+    void PreferentialBayesianOptimizer::DetermineNextQuery(const int num_global_search_iters, const int num_local_search_iters)
+    {
+        BuildNextQuery("DetermineNextQuery", num_global_search_iters, num_local_search_iters, [&](int q, int n_global, int n_local) {
+            return acquisition_func::FindNextPoints(*m_regressor, q, n_global, n_local, m_acquisition_func_type,
+                                                    m_gaussian_process_upper_confidence_bound_hyperparam);
+        });
+    }
+
+    void PreferentialBayesianOptimizer::DetermineNextQueryByThompsonSampling(const unsigned long long seed,
+                                                                             const int num_global_search_iters,
+                                                                             const int num_local_search_iters)
+    {
+        BuildNextQuery("DetermineNextQueryByThompsonSampling", num_global_search_iters, num_local_search_iters,
+                       [&](int q, int n_global, int n_local) {
+                           return acquisition_func::FindNextPointsByThompsonSampling(*m_regressor, q, n_global, n_local, seed);
+                       });
     }
 
     VectorXd PreferentialBayesianOptimizer::GetMaximizer() const { return m_current_options[0]; }

@@ -1,4 +1,5 @@
 // Regressor base + Gram builders over the C ABI (reference: src/regressor.cpp).
+#include <algorithm>
 #include <cmath>
 #include <sequential-line-search/regressor.hpp>
 #include <stdexcept>
@@ -154,6 +155,79 @@ namespace sequential_line_search
         MatrixXd   cov(M, M);
         device::Check(sls_gp_predict_cov(h, Xs.data(), static_cast<int>(M), nullptr, cov.data()), "sls_gp_predict_cov");
         return cov;
+    }
+
+    PosteriorFunctionSamples Regressor::SamplePosteriorFunctions(int num_draws, unsigned long long seed, int num_frequencies) const
+    {
+        sls_gp* h = GetDeviceHandle();
+        if (!h)
+            throw std::invalid_argument("Regressor::SamplePosteriorFunctions needs a device-resident regressor "
+                                        "(GaussianProcessRegressor / PreferenceRegressor)");
+        return PosteriorFunctionSamples(h, static_cast<int>(GetNumDims()), num_draws, seed, num_frequencies);
+    }
+
+    PosteriorFunctionSamples::PosteriorFunctionSamples(sls_gp* handle, int num_dims, int num_draws, unsigned long long seed,
+                                                       int num_frequencies)
+        : m_num_draws(num_draws), m_num_dims(num_dims)
+    {
+        device::Check(sls_path_create(handle, num_draws, num_frequencies, seed, &m_path), "sls_path_create");
+    }
+    PosteriorFunctionSamples::PosteriorFunctionSamples(PosteriorFunctionSamples&& o) noexcept
+        : m_path(o.m_path), m_num_draws(o.m_num_draws), m_num_dims(o.m_num_dims)
+    {
+        o.m_path = nullptr;
+    }
+    PosteriorFunctionSamples& PosteriorFunctionSamples::operator=(PosteriorFunctionSamples&& o) noexcept
+    {
+        if (this != &o)
+        {
+            if (m_path) sls_path_destroy(m_path);
+            m_path      = o.m_path;
+            m_num_draws = o.m_num_draws;
+            m_num_dims  = o.m_num_dims;
+            o.m_path    = nullptr;
+        }
+        return *this;
+    }
+    PosteriorFunctionSamples::~PosteriorFunctionSamples()
+    {
+        if (m_path) sls_path_destroy(m_path);
+    }
+
+    MatrixXd PosteriorFunctionSamples::Evaluate(const MatrixXd& Xs) const
+    {
+        const long M = Xs.cols();
+        MatrixXd   F(M, m_num_draws);
+        device::Check(sls_path_eval(m_path, Xs.data(), static_cast<int>(M), nullptr, F.data(), nullptr), "sls_path_eval");
+        return F;
+    }
+
+    VectorXd PosteriorFunctionSamples::EvaluateDerivative(const VectorXd& x, int draw) const
+    {
+        VectorXd g(x.size());
+        double   v = 0.0;
+        device::Check(sls_path_eval(m_path, x.data(), 1, &draw, &v, g.data()), "sls_path_eval");
+        return g;
+    }
+
+    std::vector<VectorXd> PosteriorFunctionSamples::Maximize(const MatrixXd& starts, unsigned num_local_search_iters,
+                                                             VectorXd* values) const
+    {
+        const long T = starts.cols();
+        if (T < m_num_draws || T % m_num_draws != 0)
+            throw std::invalid_argument("PosteriorFunctionSamples::Maximize: the start count must be a positive multiple of the draw count");
+        sls_lbfgs_opts o;
+        sls_lbfgs_default_opts(&o);
+        optim::SearchTolerances(&o.ftol_rel, &o.xtol_rel);   // the acquisition maximiser's local search tolerances
+        MatrixXd X(m_num_dims, m_num_draws);
+        VectorXd v(m_num_draws);
+        device::Check(sls_path_maximize(m_path, starts.data(), static_cast<int>(T / m_num_draws),
+                                        std::max(1, static_cast<int>(num_local_search_iters)), &o, X.data(), v.data(), nullptr),
+                      "sls_path_maximize");
+        if (values) *values = v;
+        std::vector<VectorXd> out;
+        for (int s = 0; s < m_num_draws; ++s) out.push_back(X.col(s));
+        return out;
     }
 
     MatrixXd Regressor::SamplePosterior(const MatrixXd& Xs, int num_samples, unsigned long long seed, double* jitter_used) const

@@ -1,0 +1,135 @@
+"""CPU-side checks of the pathwise posterior draws (sls_path_*): the numpy restatement (tests/path_ref.py) stands on the generator of
+posterior_ref; its random-feature kernel converges to the exact SE / Matern 5/2 kernels as F grows; the closed-form covariance of a
+pathwise draw becomes the exact posterior covariance when the feature kernel is replaced by the exact one; the generator layout has
+the prefix property over draws; and the package binds and exports the new entry points."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import path_ref as ph
+import posterior_ref as pr
+from util import sls
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize("seed,offset,n", [(0, 0, 9), (7, 5, 23), (2 ** 40 + 3, 1021, 14), (123, 4, 4)])
+def test_vectorised_normals_equal_posterior_ref(seed, offset, n):
+    assert np.array_equal(ph.normals(seed, offset, n), pr.normals(seed, offset, n))
+
+
+@pytest.mark.parametrize("kernel", [ph.SE, ph.MATERN52])
+def test_feature_kernel_converges_to_the_exact_kernel(kernel):
+    D, a = 3, 0.7
+    rng = np.random.default_rng(5)
+    ell = np.array([0.3, 0.5, 0.8])
+    XA = rng.uniform(0, 1, (D, 12))
+    XB = rng.uniform(0, 1, (D, 12))
+    theta = np.concatenate([[a], ell])
+    K = pr.ard_kernel(XA, XB, theta, kernel)
+    errs = []
+    for F in (256, 4096, 65536):
+        om = ph.frequencies(11, D, F, kernel)
+        err = np.abs(ph.feature_kernel(om, a, XA, XB, ell) - K).max()
+        # a Monte-Carlo average of F bounded terms (|a cos| <= a): the error is a few a / sqrt(F)
+        assert err <= 6 * a / np.sqrt(F), (F, err)
+        errs.append(err)
+    assert errs[-1] < errs[0]
+
+
+@pytest.mark.parametrize("kernel", [ph.SE, ph.MATERN52])
+def test_pathwise_covariance_with_the_exact_kernel_is_the_posterior(kernel):
+    D, N, M, b = 2, 25, 9, 0.02
+    rng = np.random.default_rng(kernel + 1)
+    X, Xs = rng.uniform(0, 1, (D, N)), rng.uniform(0, 1, (D, M))
+    y = np.sin(3 * X.sum(0))
+    theta = np.array([0.8, 0.4, 0.3])
+    Kss = pr.ard_kernel(Xs, Xs, theta, kernel)
+    KsX = pr.ard_kernel(Xs, X, theta, kernel)
+    KXX = pr.ard_kernel(X, X, theta, kernel)
+    Ky = KXX + b * np.eye(N)
+    cov = ph.pathwise_cov(Kss, KsX, KXX, KsX.T, Ky, b)
+    _, cov_exact, _ = pr.posterior(X, y, Xs, theta, b, kernel)
+    assert np.abs(cov - cov_exact).max() <= 1e-10 * theta[0]
+    # with a finite feature set it differs (the shared-basis error), by O(a / sqrt(F))
+    om = ph.frequencies(3, D, 512, kernel)
+    Ps, PX = ph.features(om, theta[0], Xs, theta[1:]), ph.features(om, theta[0], X, theta[1:])
+    cov_f = ph.pathwise_cov(Ps.T @ Ps, Ps.T @ PX, PX.T @ PX, KsX.T, Ky, b)
+    assert 0 < np.abs(cov_f - cov_exact).max() <= 10 * theta[0] / np.sqrt(512)
+
+
+def test_pathwise_covariance_matches_monte_carlo_of_the_restatement():
+    """The closed form is the covariance of the restatement's draws over w, w', eps (fixed frequencies): 2000 draws."""
+    D, N, M, b, F, S = 2, 12, 5, 0.05, 64, 2000
+    rng = np.random.default_rng(3)
+    X, Xs = rng.uniform(0, 1, (D, N)), rng.uniform(0, 1, (D, M))
+    y = np.cos(2 * X.sum(0))
+    theta = np.array([0.6, 0.5, 0.35])
+    ref = ph.PathRef(X, y, theta, b, ph.SE, S, F, seed=17)
+    Fs = ref.eval_all(Xs)
+    KsX = pr.ard_kernel(Xs, X, theta, ph.SE)
+    Ps, PX = ph.features(ref.om, theta[0], Xs, theta[1:]), ph.features(ref.om, theta[0], X, theta[1:])
+    cov = ph.pathwise_cov(Ps.T @ Ps, Ps.T @ PX, PX.T @ PX, KsX.T, ref.Ky, b)
+    C = np.cov(Fs)
+    sd = np.sqrt(np.outer(np.diag(cov), np.diag(cov)) + cov ** 2)      # sd of one product term of a Gaussian pair
+    assert np.all(np.abs(C - cov) <= 5 * sd / np.sqrt(S) + 1e-12)
+
+
+@pytest.mark.parametrize("kernel", [ph.SE, ph.MATERN52])
+def test_generator_layout_has_the_prefix_property(kernel):
+    D, N, F = 3, 7, 10
+    w4, wp4, e4 = ph.draw_normals(9, D, N, F, kernel, 4)
+    w2, wp2, e2 = ph.draw_normals(9, D, N, F, kernel, 2)
+    assert np.array_equal(w4[:, :2], w2) and np.array_equal(wp4[:, :2], wp2) and np.array_equal(e4[:, :2], e2)
+    # the frequencies do not depend on the number of draws, and the draw block starts right behind them
+    B0 = ph.block0(D, F, kernel)
+    assert B0 == F * D + (5 * F if kernel == ph.MATERN52 else 0)
+    assert np.array_equal(w4[:, 1], ph.normals(9, B0 + (2 * F + N), F))
+    assert np.array_equal(e4[:, 3], ph.normals(9, B0 + 3 * (2 * F + N) + 2 * F, N))
+
+
+def test_restatement_identity_at_the_data():
+    """f_s(X) = y - sqrt(b) eps_s - b v_s: the identity the GPU test checks, on the restatement itself."""
+    D, N, b = 2, 30, 0.01
+    rng = np.random.default_rng(4)
+    X = rng.uniform(0, 1, (D, N))
+    y = np.sin(4 * X[0]) * X[1]
+    theta = np.array([0.5, 0.3, 0.4])
+    ref = ph.PathRef(X, y, theta, b, ph.MATERN52, 3, 128, seed=2)
+    lhs = ref.eval_all(X)
+    rhs = y[:, None] - np.sqrt(b) * ref.eps - b * ref.v
+    assert np.abs(lhs - rhs).max() <= 1e-8
+
+
+def test_restatement_gradient_matches_central_differences():
+    D, N = 3, 20
+    rng = np.random.default_rng(8)
+    X = rng.uniform(0, 1, (D, N))
+    y = X.sum(0)
+    theta = np.array([0.9, 0.3, 0.6, 0.45])
+    for kernel in (ph.SE, ph.MATERN52):
+        ref = ph.PathRef(X, y, theta, 0.01, kernel, 4, 64, seed=5)
+        Xs = rng.uniform(0.1, 0.9, (D, 6))
+        dr = np.array([0, 1, 2, 3, 1, 0])
+        _, g = ref.eval(Xs, dr)
+        h = 1e-6
+        for d in range(D):
+            E = np.zeros_like(Xs)
+            E[d] = h
+            fd = (ref.eval(Xs + E, dr)[0] - ref.eval(Xs - E, dr)[0]) / (2 * h)
+            assert np.abs(fd - g[d]).max() <= 1e-6 * (1 + np.abs(g).max())
+
+
+def test_package_exports_the_path_calls():
+    m = sls()
+    names = ["sls_path_create", "sls_path_destroy", "sls_path_eval", "sls_path_maximize"]
+    for n in names:
+        assert n in m.EXPORTS
+    assert hasattr(m, "PathSamples")
+    for meth in ("eval", "eval_all", "maximize", "close"):
+        assert callable(getattr(m.PathSamples, meth))
+    txt = open(os.path.join(ROOT, "include", "sls_hip.h")).read()
+    for n in names:
+        assert re.search(r"\b" + n + r"\s*\(", txt)
