@@ -14,6 +14,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "lbfgs_driver.hpp"
 
 using namespace slsk;
 
@@ -205,16 +206,6 @@ bool potrf_gave_up(sls_ctx* c, int abort_flag, int attempt) {
 }
 }  // namespace slsk
 
-#define SLS_TRY slsk::note_entry(); try {
-#define SLS_CATCH                                   \
-    }                                               \
-    catch (const slsk::HipFail& f) { return f.code; } \
-    catch (const std::exception& e) {               \
-        slsk::set_error("exception: %s", e.what()); \
-        return SLS_ERR_INVALID;                     \
-    }                                               \
-    return SLS_OK;
-
 extern "C" const char* sls_last_error(void) { return slsk::g_err; }
 extern "C" int sls_version(void) { return 100; }
 
@@ -326,8 +317,7 @@ extern "C" int sls_device_trim_cache(int device) {
 
 extern "C" int sls_ctx_set_stream(sls_ctx* ctx, void* hip_stream) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (ctx) lock_ = std::unique_lock<std::recursive_mutex>(ctx->mtx);
+    CtxCall call_(ctx);
     SLS_REQUIRE(ctx, "ctx is NULL");
     SLS_HIP(hipStreamSynchronize(ctx->stream));
     ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
@@ -335,29 +325,27 @@ extern "C" int sls_ctx_set_stream(sls_ctx* ctx, void* hip_stream) {
 }
 extern "C" int sls_ctx_synchronize(sls_ctx* ctx) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (ctx) lock_ = std::unique_lock<std::recursive_mutex>(ctx->mtx);
+    CtxCall call_(ctx);
     SLS_REQUIRE(ctx, "ctx is NULL");
     SLS_HIP(hipStreamSynchronize(ctx->stream));
     SLS_CATCH
 }
 extern "C" int sls_ctx_set_candidate_chunk(sls_ctx* ctx, int chunk) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (ctx) lock_ = std::unique_lock<std::recursive_mutex>(ctx->mtx);
+    CtxCall call_(ctx);
     SLS_REQUIRE(ctx && chunk >= 128, "candidate chunk must be >= 128");
     ctx->cand_chunk = round_up(chunk, 128);
     SLS_CATCH
 }
 extern "C" int sls_prof_enable(sls_ctx* ctx, int on) {
     if (!ctx) return SLS_ERR_INVALID;
-    std::unique_lock<std::recursive_mutex> lock_(ctx->mtx);
+    CtxCall call_(ctx);
     ctx->prof_on = on != 0;
     return SLS_OK;
 }
 extern "C" int sls_prof_reset(sls_ctx* ctx) {
     if (!ctx) return SLS_ERR_INVALID;
-    std::unique_lock<std::recursive_mutex> lock_(ctx->mtx);
+    CtxCall call_(ctx);
     (void)hipStreamSynchronize(ctx->stream);
     ctx->prof_collect();
     ctx->prof.clear();
@@ -365,7 +353,7 @@ extern "C" int sls_prof_reset(sls_ctx* ctx) {
 }
 extern "C" int sls_prof_get(sls_ctx* ctx, const char* name, double* total_ms, long* launches) {
     if (!ctx || !name) return SLS_ERR_INVALID;
-    std::unique_lock<std::recursive_mutex> lock_(ctx->mtx);
+    CtxCall call_(ctx);
     (void)hipStreamSynchronize(ctx->stream);
     ctx->prof_collect();
     if (std::string(name) == "potrf_fallbacks") {          // not a timing: how often a single-launch Cholesky gave up
@@ -429,10 +417,7 @@ struct sls_gp {
     int ws_chunk = 0;
     // L-BFGS state
     DBuf pair_mu, pair_sg, pair_dmu, pair_dsg;
-    DBuf lb_x, lb_g, lb_dir, lb_xt, lb_scr, lb_S, lb_Y, lb_rho, lb_f, lb_t, lb_val, lb_grad, lb_xc;
-    DBuf lb_int_buf;          // pooled (a hipMalloc / hipFree pair per handle cost ~0.2 ms per submit of the reference's demo and synchronised the device)
-    int* lb_int = nullptr;    // lb_int_buf's block: hlen | hpos | nbt | done | live list A | live list B | live count (+ padding) | block counts
-    int lb_Sp = 0, lb_m = 0;
+    LbfgsWs lb;   // pooled blocks that live with the handle: a repeated maximisation costs no allocation
     // 0: sigma^2 = a - k^T K^-1 k with the explicit inverse (GaussianProcessRegressor); 1: a - |L^-1 k|^2, the Cholesky solve of
     // PreferenceRegressor (sls_gp_set_sigma_mode)
     int sigma_mode = 0;
@@ -597,8 +582,7 @@ static void gp_setup(sls_gp* g) {
 extern "C" int sls_gp_create(sls_ctx* ctx, const double* X, int D, int N, const double* y, const double* theta, double b,
                              int kernel, sls_gp** out) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (ctx) lock_ = std::unique_lock<std::recursive_mutex>(ctx->mtx);
+    CtxCall call_(ctx);
     SLS_REQUIRE(ctx && out, "sls_gp_create: NULL argument");
     SLS_REQUIRE(D >= 1 && N >= 1, "sls_gp_create: need D >= 1 and N >= 1 (got D=%d N=%d)", D, N);
     SLS_REQUIRE(X && y, "sls_gp_create: X / y is NULL");
@@ -619,11 +603,7 @@ extern "C" int sls_gp_create(sls_ctx* ctx, const double* X, int D, int N, const 
 
 extern "C" int sls_gp_refit_dev(sls_gp* g, const double* X_dev, const double* y_dev) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (g) {
-        lock_ = std::unique_lock<std::recursive_mutex>(g->ctx->mtx);
-        (void)hipSetDevice(g->ctx->device);   // the handle's device, whatever the caller's current device is
-    }
+    CtxCall call_(g);
     SLS_REQUIRE(g && X_dev && y_dev, "sls_gp_refit_dev: NULL argument");
     std::unique_lock<std::shared_mutex> state_(g->state_mtx);
     sls_ctx* c = g->ctx;
@@ -638,17 +618,9 @@ extern "C" int sls_gp_refit_dev(sls_gp* g, const double* X_dev, const double* y_
 extern "C" int sls_gp_destroy(sls_gp* gp) {
     if (!gp) return SLS_OK;
     slsk::note_entry();
-    sls_ctx* c = gp->ctx;
-    {
-        std::unique_lock<std::recursive_mutex> lock_(c->mtx);
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-        // evaluations that run on the context's slots without its lock (eval_in_slot) hold the state lock shared until their slot's
-        // stream has drained: taking it exclusively waits for them.  Released before the delete (it is a member).
-        { std::unique_lock<std::shared_mutex> drain_(gp->state_mtx); }
-        delete gp;
-    }
-    slsk::ctx_release(c);
+    // evaluations that run on the context's slots without its lock (eval_in_slot) hold the state lock shared until their slot's
+    // stream has drained: taking it exclusively waits for them
+    destroy_handle(gp, &gp->state_mtx);
     return SLS_OK;
 }
 
@@ -668,14 +640,14 @@ GpView gp_view(sls_gp* g) {
 
 extern "C" int sls_gp_generation(sls_gp* g, long* generation) {
     if (!g || !generation) return SLS_ERR_INVALID;
-    std::unique_lock<std::recursive_mutex> lock_(g->ctx->mtx);
+    CtxCall call_(g->ctx);
     *generation = g->generation;
     return SLS_OK;
 }
 
 extern "C" int sls_gp_get_summary(sls_gp* g, int* best_index, double* mu_best, double* logdet) {
     if (!g) return SLS_ERR_INVALID;
-    std::unique_lock<std::recursive_mutex> lock_(g->ctx->mtx);
+    CtxCall call_(g->ctx);
     if (best_index) *best_index = g->best_index;
     if (mu_best) *mu_best = g->mu_best;
     if (logdet) *logdet = g->logdet;
@@ -686,8 +658,7 @@ namespace slsk {
 int gp_export_inputs(sls_gp* g, int* D, int* N, int* kernel, int* sigma_mode, int* device, double* b, std::vector<double>* X,
                      std::vector<double>* y, std::vector<double>* theta) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_(g->ctx->mtx);
-    (void)hipSetDevice(g->ctx->device);
+    CtxCall call_(g);
     *D = g->D; *N = g->N; *kernel = g->kernel; *sigma_mode = g->sigma_mode; *device = g->ctx->device; *b = g->b;
     *theta = g->theta;
     X->resize((size_t)g->D * g->N);
@@ -701,11 +672,7 @@ int gp_export_inputs(sls_gp* g, int* D, int* N, int* kernel, int* sigma_mode, in
 
 extern "C" int sls_gp_set_sigma_mode(sls_gp* g, int mode) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (g) {
-        lock_ = std::unique_lock<std::recursive_mutex>(g->ctx->mtx);
-        (void)hipSetDevice(g->ctx->device);
-    }
+    CtxCall call_(g);
     SLS_REQUIRE(g && (mode == SLS_SIGMA_EXPLICIT_INVERSE || mode == SLS_SIGMA_CHOLESKY_SOLVE), "sls_gp_set_sigma_mode: bad argument");
     std::unique_lock<std::shared_mutex> state_(g->state_mtx);
     if (mode == SLS_SIGMA_CHOLESKY_SOLVE && g->sigma_mode != mode)
@@ -718,11 +685,7 @@ extern "C" int sls_gp_set_sigma_mode(sls_gp* g, int mode) {
 
 extern "C" int sls_gp_get_matrix(sls_gp* g, int what, double* out) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (g) {
-        lock_ = std::unique_lock<std::recursive_mutex>(g->ctx->mtx);
-        (void)hipSetDevice(g->ctx->device);   // the handle's device, whatever the caller's current device is
-    }
+    CtxCall call_(g);
     SLS_REQUIRE(g && out, "sls_gp_get_matrix: NULL argument");
     sls_ctx* c = g->ctx;
     const int N = g->N, Np = g->Np;
@@ -1086,11 +1049,7 @@ extern "C" int sls_gp_predict(sls_gp* g, const double* Xs, int M, double* mu, do
         so.mu = mu; so.sigma = sigma;
         if (eval_in_slot(g, Xs, M, so)) return SLS_OK;
     }
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (g) {
-        lock_ = std::unique_lock<std::recursive_mutex>(g->ctx->mtx);
-        (void)hipSetDevice(g->ctx->device);   // the handle's device, whatever the caller's current device is
-    }
+    CtxCall call_(g);
     SLS_REQUIRE(g && Xs && M >= 0, "sls_gp_predict: bad argument");
     if (M == 0) return SLS_OK;
     const int Mp = round_up(M, 128);
@@ -1109,11 +1068,7 @@ extern "C" int sls_gp_predict_grad(sls_gp* g, const double* Xs, int M, double* d
         so.dmu = dmu; so.dsigma = dsigma;
         if (eval_in_slot(g, Xs, M, so)) return SLS_OK;
     }
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (g) {
-        lock_ = std::unique_lock<std::recursive_mutex>(g->ctx->mtx);
-        (void)hipSetDevice(g->ctx->device);   // the handle's device, whatever the caller's current device is
-    }
+    CtxCall call_(g);
     SLS_REQUIRE(g && Xs && M >= 0, "sls_gp_predict_grad: bad argument");
     if (M == 0) return SLS_OK;
     const int Mp = round_up(M, 128), D = g->D;
@@ -1132,11 +1087,7 @@ extern "C" int sls_acq_eval(sls_gp* g, int acq_type, double ucb_h, const double*
         so.val = val; so.grad = grad; so.acq = acq_type; so.ucb_h = ucb_h;
         if (eval_in_slot(g, Xs, M, so)) return SLS_OK;
     }
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (g) {
-        lock_ = std::unique_lock<std::recursive_mutex>(g->ctx->mtx);
-        (void)hipSetDevice(g->ctx->device);   // the handle's device, whatever the caller's current device is
-    }
+    CtxCall call_(g);
     SLS_REQUIRE(g && Xs && M >= 0, "sls_acq_eval: bad argument");
     SLS_REQUIRE(acq_type == SLS_ACQ_EXPECTED_IMPROVEMENT || acq_type == SLS_ACQ_GP_UCB, "unknown acquisition type %d", acq_type);
     if (M == 0) return SLS_OK;
@@ -1196,18 +1147,6 @@ sls_lbfgs_opts slsk::read_lbfgs_opts(const sls_lbfgs_opts* in) {
     return o;
 }
 
-static void ensure_lbfgs(sls_gp* g, int Sp, int m) {
-    if (Sp <= g->lb_Sp && m <= g->lb_m) return;
-    const size_t D = g->D, S = Sp;
-    g->lb_x.ensure(S * D); g->lb_g.ensure(S * D); g->lb_dir.ensure(S * D); g->lb_xt.ensure(S * D); g->lb_scr.ensure(S * D);
-    const size_t Dh = D <= 16 ? 16 : (D <= 64 ? 64 : D);   // lbfgs_step_reg_kernel keeps rows of 4 DPL doubles per (start, pair)
-    g->lb_S.ensure(S * Dh * m); g->lb_Y.ensure(S * Dh * m); g->lb_rho.ensure(S * m);
-    g->lb_f.ensure(S); g->lb_t.ensure(S); g->lb_val.ensure(S); g->lb_grad.ensure(S * D); g->lb_xc.ensure(S * D);
-    g->lb_int_buf.ensure(((S * 6 + 128 + S / 1024 + 8) * sizeof(int) + 7) / 8);   // ... | count (64) | block counts
-    g->lb_int = reinterpret_cast<int*>(g->lb_int_buf.p);
-    g->lb_Sp = Sp; g->lb_m = m;
-}
-
 // value (+ gradient) of the acquisition at candidate-major points xr; gs != nullptr: sigma / dsigma come from gs
 // (objective_for_multiple_points, src/acquisition-function.cpp:63-110)
 static void eval_acq(sls_gp* g, sls_gp* gs, const double* xr, long ldr, int S, int acq_type, double ucb_h, double* val,
@@ -1239,16 +1178,9 @@ static void maximize_impl(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, con
     const sls_lbfgs_opts o = read_lbfgs_opts(opts_in);
     SLS_REQUIRE(o.history >= 1 && o.history <= 8, "L-BFGS history must be in 1..8");
     const int Sp = round_up(S, 128), D = g->D;
-    ensure_lbfgs(g, Sp, o.history);
+    g->lb.ensure(Sp, o.history, D);
     g->stat_issued = 0; g->stat_cap = (long)S * n_local; g->stat_rounds = 0; g->stat_live_end = 0;
-    LbfgsState st;
-    st.live = nullptr; st.nlive = S; st.ldv = Sp;
-    st.S = S; st.D = D; st.m = o.history; st.ld = Sp;
-    st.x = g->lb_x.p; st.g = g->lb_g.p; st.dir = g->lb_dir.p; st.xt = g->lb_xt.p; st.scr = g->lb_scr.p;
-    st.Sh = g->lb_S.p; st.Yh = g->lb_Y.p; st.rho = g->lb_rho.p; st.f = g->lb_f.p; st.t = g->lb_t.p;
-    st.hlen = g->lb_int; st.hpos = g->lb_int + Sp; st.nbt = g->lb_int + 2 * Sp; st.done = g->lb_int + 3 * Sp;
-    st.c1 = o.c1; st.shrink = o.shrink; st.gtol = o.gtol; st.max_backtracks = o.max_backtracks;
-    st.ftol_rel = o.ftol_rel; st.xtol_rel = o.xtol_rel;
+    LbfgsState st = g->lb.state(S, D, o);
     // Small problems: one wavefront per start runs the whole search in a single launch (kernels_wave.hip).  The choice
     // depends only on the fitted state and the start count, so repeated / sharded calls take the same path.
     bool used_wave = false;
@@ -1268,12 +1200,12 @@ static void maximize_impl(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, con
             w.ev_mu = w.ev_sigma = w.ev_dmu = w.ev_dsigma = w.ev_val = w.ev_grad = nullptr;
             // evaluations of starts that were still moving (finished starts run idle to keep the barriers uniform): counted
             // by the kernel into the live-count words of the integer scratch
-            unsigned long long* d_useful = reinterpret_cast<unsigned long long*>(g->lb_int + 6 * (size_t)Sp + 32);
+            unsigned long long* d_useful = g->lb.wave_useful();
             SLS_HIP(hipMemsetAsync(d_useful, 0, sizeof(unsigned long long), c->stream));
             w.useful = d_useful;
             long long* d_trace = nullptr;
             if (tune_set(TUNE_WAVE_TRACE)) {
-                d_trace = reinterpret_cast<long long*>(g->lb_int + 6 * (size_t)Sp + 64);
+                d_trace = g->lb.wave_trace();
                 SLS_HIP(hipMemsetAsync(d_trace, 0, 9 * sizeof(long long), c->stream));
                 w.trace = d_trace;
             }
@@ -1295,49 +1227,14 @@ static void maximize_impl(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, con
         }
     }
     if (!used_wave) {
-        // Lock-step rounds over the ACTIVE SET.  NLopt's max_evals is a cap per start, not a quota
-        // (src/acquisition-function.cpp:128-129): a start that can no longer move (stationary projected gradient, null
-        // step, exhausted backtracking) is finished.  After every round the starts still moving are compacted, in
-        // increasing order, into dense 128-wide tiles, so cross_gram / acq_gemm / grad_gemm only see live columns.  A
-        // candidate's arithmetic does not depend on the column it occupies, so every start ends with the same bits as
-        // in the uncompacted schedule (SLS_COMPACT=0: every start is re-evaluated every round; tests compare the two).
-        const bool compact = tune_on(TUNE_COMPACT);
-        int* live_a = g->lb_int + 4 * (size_t)Sp;
-        int* live_b = live_a + Sp;
-        int* d_count = live_b + Sp;
-        int* d_blocks = d_count + 64;     // per-block counts of the compaction
-        launch_clamp_starts(c->stream, starts_dev, D, S, st.xt, Sp, Sp);
-        const double* trial = st.xt;      // candidate-major trial points of this round, leading dimension Sp
-        const int* live = nullptr;        // identity
-        int nlive = S, moving = S;
-        st.ldv = Sp;
-        for (int ev = 0; ev < n_local && nlive > 0; ++ev) {
-            eval_acq(g, gs, trial, Sp, nlive, acq_type, ucb_h, g->lb_val.p, g->lb_grad.p, Sp);
-            g->stat_issued += compact ? nlive : moving;       // SLS_COMPACT=0 evaluates finished starts too: they do not count
-            g->stat_rounds += 1;
-            {
-                ProfScope ps(c, "lbfgs");
-                st.live = live; st.nlive = nlive;
-                launch_lbfgs_step(c->stream, st, g->lb_val.p, g->lb_grad.p, ev == 0);
-                if (ev + 1 < n_local) {
-                    int* live_next = (live == live_a) ? live_b : live_a;
-                    launch_compact_live(c->stream, live, nlive, st.done, live_next, d_count, d_blocks);
-                    if (compact) {
-                        launch_gather_trials(c->stream, st.xt, Sp, D, live_next, d_count, nlive, g->lb_xc.p, Sp);
-                        live = live_next;
-                        trial = g->lb_xc.p;
-                    }
-                }
-            }
-            if (ev + 1 < n_local) {
-                int cnt = 0;
-                SLS_HIP(hipMemcpyAsync(&cnt, d_count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-                sync(c);
-                if (compact) nlive = cnt;
-                else moving = cnt;                            // statistics only: the launch shapes stay at S
-            }
-        }
-        g->stat_live_end = compact ? nlive : moving;
+        // the lock-step rounds over the active set (lbfgs_driver.hpp)
+        LockstepStats ls;
+        lockstep_rounds(c, st, g->lb, starts_dev, S, n_local,
+                        [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
+                            eval_acq(g, gs, trial, ld, nlive, acq_type, ucb_h, val, grad, ld);
+                        },
+                        &ls);
+        g->stat_issued = ls.issued; g->stat_rounds = ls.rounds; g->stat_live_end = ls.live_end;
     }   // !used_wave
     // best start and its coordinates: one launch into the handle's mapped block, one synchronisation, no copies
     launch_argmax_neg_gather(c->stream, st.f, S, st.x, Sp, D, g->sum_dev + 8, wave_useful);
@@ -1357,7 +1254,7 @@ static void maximize_impl(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, con
 
 extern "C" int sls_acq_last_stats(sls_gp* g, long* evals_issued, long* evals_cap, int* rounds, int* live_at_end) {
     if (!g) return SLS_ERR_INVALID;
-    std::unique_lock<std::recursive_mutex> lock_(g->ctx->mtx);
+    CtxCall call_(g->ctx);
     if (evals_issued) *evals_issued = g->stat_issued;
     if (evals_cap) *evals_cap = g->stat_cap;
     if (rounds) *rounds = g->stat_rounds;
@@ -1369,11 +1266,7 @@ extern "C" int sls_acq_maximize(sls_gp* g, int acq_type, double ucb_h, const dou
                                 const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out,
                                 long* idx_out, double* x_stars, double* y_stars) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (g) {
-        lock_ = std::unique_lock<std::recursive_mutex>(g->ctx->mtx);
-        (void)hipSetDevice(g->ctx->device);   // the handle's device, whatever the caller's current device is
-    }
+    CtxCall call_(g);
     SLS_REQUIRE(g && starts, "sls_acq_maximize: NULL argument");
     SLS_REQUIRE(S >= 1, "sls_acq_maximize: need S >= 1");
     sls_ctx* c = g->ctx;
@@ -1393,11 +1286,7 @@ static void check_pair(sls_gp* g, sls_gp* gs) {
 extern "C" int sls_acq_maximize_pair(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, const double* starts, int S, int n_local,
                                      const sls_lbfgs_opts* opts, double* x_out, double* val_out, long* idx_out) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (g) {
-        lock_ = std::unique_lock<std::recursive_mutex>(g->ctx->mtx);
-        (void)hipSetDevice(g->ctx->device);   // the handle's device, whatever the caller's current device is
-    }
+    CtxCall call_(g);
     check_pair(g, gs);
     SLS_REQUIRE(starts && S >= 1, "sls_acq_maximize_pair: bad argument");
     sls_ctx* c = g->ctx;
@@ -1411,11 +1300,7 @@ extern "C" int sls_acq_maximize_pair(sls_gp* g, sls_gp* gs, int acq_type, double
 extern "C" int sls_acq_eval_pair(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, const double* Xs, int M, double* val,
                                  double* grad) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (g) {
-        lock_ = std::unique_lock<std::recursive_mutex>(g->ctx->mtx);
-        (void)hipSetDevice(g->ctx->device);   // the handle's device, whatever the caller's current device is
-    }
+    CtxCall call_(g);
     check_pair(g, gs);
     SLS_REQUIRE(Xs && M >= 0, "sls_acq_eval_pair: bad argument");
     SLS_REQUIRE(acq_type == SLS_ACQ_EXPECTED_IMPROVEMENT || acq_type == SLS_ACQ_GP_UCB, "unknown acquisition type %d", acq_type);
@@ -1434,11 +1319,7 @@ extern "C" int sls_acq_maximize_dev(sls_gp* g, int acq_type, double ucb_h, const
                                     const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out,
                                     long* idx_out) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (g) {
-        lock_ = std::unique_lock<std::recursive_mutex>(g->ctx->mtx);
-        (void)hipSetDevice(g->ctx->device);   // the handle's device, whatever the caller's current device is
-    }
+    CtxCall call_(g);
     SLS_REQUIRE(g && starts_dev, "sls_acq_maximize_dev: NULL argument");
     maximize_impl(g, nullptr, acq_type, ucb_h, starts_dev, S, n_local, opts, start_index_offset, x_out, val_out, idx_out, nullptr,
                   nullptr);
@@ -1448,8 +1329,7 @@ extern "C" int sls_acq_maximize_dev(sls_gp* g, int acq_type, double ucb_h, const
 // ---- free functions ----------------------------------------------------------------------------------------------
 extern "C" int sls_gram(sls_ctx* c, const double* X, int D, int N, const double* theta, double b, int kernel, double* K_out) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (c) lock_ = std::unique_lock<std::recursive_mutex>(c->mtx);
+    CtxCall call_(c);
     SLS_REQUIRE(c && X && K_out && D >= 1 && N >= 1, "sls_gram: bad argument");
     check_theta(theta, D);
     SLS_HIP(hipSetDevice(c->device));
@@ -1470,8 +1350,7 @@ extern "C" int sls_gram(sls_ctx* c, const double* X, int D, int N, const double*
 extern "C" int sls_gram_cross(sls_ctx* c, const double* X, int D, int N, const double* Xs, int M, const double* theta, int kernel,
                               double* Ks_out) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (c) lock_ = std::unique_lock<std::recursive_mutex>(c->mtx);
+    CtxCall call_(c);
     SLS_REQUIRE(c && X && Xs && Ks_out && D >= 1 && N >= 1 && M >= 1, "sls_gram_cross: bad argument");
     check_theta(theta, D);
     SLS_HIP(hipSetDevice(c->device));
@@ -1514,8 +1393,7 @@ static void upload_padded_spd(sls_ctx* c, DBuf& A, const double* src, int N, int
 
 extern "C" int sls_potrf(sls_ctx* c, double* A, int N) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (c) lock_ = std::unique_lock<std::recursive_mutex>(c->mtx);
+    CtxCall call_(c);
     SLS_REQUIRE(c && A && N >= 1, "sls_potrf: bad argument");
     SLS_HIP(hipSetDevice(c->device));
     const int Np = round_up(N, 128);
@@ -1545,8 +1423,7 @@ extern "C" int sls_potrf(sls_ctx* c, double* A, int N) {
 
 extern "C" int sls_potrs(sls_ctx* c, const double* L, int N, double* B, int nrhs) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (c) lock_ = std::unique_lock<std::recursive_mutex>(c->mtx);
+    CtxCall call_(c);
     SLS_REQUIRE(c && L && B && N >= 1 && nrhs >= 1, "sls_potrs: bad argument");
     SLS_HIP(hipSetDevice(c->device));
     const int Np = round_up(N, 128), Rp = round_up(nrhs, 128);
@@ -1566,8 +1443,7 @@ extern "C" int sls_potrs(sls_ctx* c, const double* L, int N, double* B, int nrhs
 
 extern "C" int sls_potri(sls_ctx* c, const double* L, int N, double* Ainv) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (c) lock_ = std::unique_lock<std::recursive_mutex>(c->mtx);
+    CtxCall call_(c);
     SLS_REQUIRE(c && L && Ainv && N >= 1, "sls_potri: bad argument");
     SLS_HIP(hipSetDevice(c->device));
     const int Np = round_up(N, 128);
@@ -1592,11 +1468,7 @@ extern "C" int sls_potri(sls_ctx* c, const double* L, int N, double* Ainv) {
 // the handle is rebuilt from scratch on the device instead (same results).
 extern "C" int sls_gp_append_point(sls_gp* g, const double* x, double y_new) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (g) {
-        lock_ = std::unique_lock<std::recursive_mutex>(g->ctx->mtx);
-        (void)hipSetDevice(g->ctx->device);   // the handle's device, whatever the caller's current device is
-    }
+    CtxCall call_(g);
     SLS_REQUIRE(g && x, "sls_gp_append_point: NULL argument");
     std::unique_lock<std::shared_mutex> state_(g->state_mtx);   // ends with gp_fetch_summary's synchronisation: the state is complete
     sls_ctx* c = g->ctx;

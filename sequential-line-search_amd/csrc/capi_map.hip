@@ -11,16 +11,6 @@
 
 using namespace slsk;
 
-#define SLS_TRY slsk::note_entry(); try {
-#define SLS_CATCH                                   \
-    }                                               \
-    catch (const slsk::HipFail& f) { return f.code; } \
-    catch (const std::exception& e) {               \
-        slsk::set_error("exception: %s", e.what()); \
-        return SLS_ERR_INVALID;                     \
-    }                                               \
-    return SLS_OK;
-
 struct sls_nll {
     sls_ctx* ctx = nullptr;
     int D = 0, N = 0, Np = 0, Dp = 0, Dcols = 0, kernel = 0;
@@ -69,8 +59,7 @@ struct sls_nll {
 
 extern "C" int sls_nll_create(sls_ctx* ctx, const double* X, int D, int N, int kernel, sls_nll** out) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (ctx) lock_ = std::unique_lock<std::recursive_mutex>(ctx->mtx);
+    CtxCall call_(ctx);
     SLS_REQUIRE(ctx && X && out && D >= 1 && N >= 1, "sls_nll_create: bad argument");
     SLS_REQUIRE(kernel == SLS_KERNEL_ARD_SQUARED_EXPONENTIAL || kernel == SLS_KERNEL_ARD_MATERN52, "unknown kernel %d", kernel);
     SLS_HIP(hipSetDevice(ctx->device));
@@ -102,7 +91,7 @@ extern "C" int sls_nll_create(sls_ctx* ctx, const double* X, int D, int N, int k
 
 extern "C" int sls_nll_set_tolerances(sls_nll* h, double ftol_rel, double xtol_rel) {
     if (!h) return SLS_ERR_INVALID;
-    std::unique_lock<std::recursive_mutex> lock_(h->ctx->mtx);
+    CtxCall call_(h->ctx);
     h->ftol_rel = ftol_rel > 0.0 ? ftol_rel : 0.0;
     h->xtol_rel = xtol_rel > 0.0 ? xtol_rel : 0.0;
     return SLS_OK;
@@ -111,14 +100,7 @@ extern "C" int sls_nll_set_tolerances(sls_nll* h, double ftol_rel, double xtol_r
 extern "C" int sls_nll_destroy(sls_nll* h) {
     if (!h) return SLS_OK;
     slsk::note_entry();
-    sls_ctx* c = h->ctx;
-    {
-        std::unique_lock<std::recursive_mutex> lock_(c->mtx);
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-        delete h;
-    }
-    slsk::ctx_release(c);
+    destroy_handle(h);
     return SLS_OK;
 }
 
@@ -327,11 +309,7 @@ static void nll_eval_impl(sls_nll* h, const double* y, const double* theta, doub
 extern "C" int sls_nll_eval(sls_nll* h, const double* y, const double* theta, double b, double* quad, double* logdet,
                             double* alpha, double* grad_theta, double* grad_b) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (h) {
-        lock_ = std::unique_lock<std::recursive_mutex>(h->ctx->mtx);
-        (void)hipSetDevice(h->ctx->device);   // the handle's device, whatever the caller's current device is
-    }
+    CtxCall call_(h);
     SLS_REQUIRE(h, "sls_nll_eval: NULL handle");
     nll_eval_impl(h, y, theta, b, quad, logdet, alpha, grad_theta, grad_b);
     SLS_CATCH
@@ -346,11 +324,7 @@ static double log_lognormal_d(double x, double mu, double s2) { return (mu - s2 
 
 extern "C" int sls_gp_nll_grad(sls_nll* h, const double* y, const double* x, double* value, double* grad) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (h) {
-        lock_ = std::unique_lock<std::recursive_mutex>(h->ctx->mtx);
-        (void)hipSetDevice(h->ctx->device);   // the handle's device, whatever the caller's current device is
-    }
+    CtxCall call_(h);
     SLS_REQUIRE(h && y && x, "sls_gp_nll_grad: NULL argument");
     const int D = h->D, N = h->N;
     // priors: src/gaussian-process-regressor.cpp:18-24
@@ -377,11 +351,7 @@ extern "C" int sls_gp_nll_grad(sls_nll* h, const double* y, const double* x, dou
 // larger problems are evaluated in turn.  A parameter set whose K_y is not positive definite gets -HUGE_VAL.
 extern "C" int sls_gp_nll_batch(sls_nll* h, const double* y, const double* xs, int B, double* values) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (h) {
-        lock_ = std::unique_lock<std::recursive_mutex>(h->ctx->mtx);
-        (void)hipSetDevice(h->ctx->device);
-    }
+    CtxCall call_(h);
     SLS_REQUIRE(h && y && xs && values && B >= 0, "sls_gp_nll_batch: bad argument");
     const int D = h->D, N = h->N;
     sls_ctx* c = h->ctx;
@@ -667,11 +637,7 @@ extern "C" int sls_pref_map_fit(sls_nll* h, const unsigned* prefs_flat, const in
                                 const double* z0, const double* lower, const double* upper, int max_evals, int evals_per_launch,
                                 double* z_out, double* value, int* evals_used) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (h) {
-        lock_ = std::unique_lock<std::recursive_mutex>(h->ctx->mtx);
-        (void)hipSetDevice(h->ctx->device);
-    }
+    CtxCall call_(h);
     SLS_REQUIRE(h && cfg && z0 && lower && upper && z_out && max_evals >= 1 && (n_prefs == 0 || (prefs_flat && pref_offsets)),
                 "sls_pref_map_fit: bad argument");
     if (!map_opt_supported(h)) {
@@ -686,11 +652,7 @@ extern "C" int sls_pref_map_fit(sls_nll* h, const unsigned* prefs_flat, const in
 extern "C" int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* lower, const double* upper, int max_evals,
                               int evals_per_launch, double* z_out, double* value, int* evals_used) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (h) {
-        lock_ = std::unique_lock<std::recursive_mutex>(h->ctx->mtx);
-        (void)hipSetDevice(h->ctx->device);
-    }
+    CtxCall call_(h);
     SLS_REQUIRE(h && y && z0 && lower && upper && z_out && max_evals >= 1, "sls_gp_map_fit: bad argument");
     if (!map_opt_supported(h)) {
         set_error("sls_gp_map_fit: N = %d, D = %d outside the device-resident optimiser (N <= 128, D <= 128)", h->N, h->D);
@@ -723,11 +685,7 @@ static void btl_derivative(const double* f, int n, double s, double* d) {
 extern "C" int sls_pref_objective(sls_nll* h, const unsigned* prefs_flat, const int* pref_offsets, int n_prefs, const double* x,
                                   const sls_pref_cfg* cfg, double* value, double* grad) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (h) {
-        lock_ = std::unique_lock<std::recursive_mutex>(h->ctx->mtx);
-        (void)hipSetDevice(h->ctx->device);   // the handle's device, whatever the caller's current device is
-    }
+    CtxCall call_(h);
     SLS_REQUIRE(h && x && cfg && (n_prefs == 0 || (prefs_flat && pref_offsets)), "sls_pref_objective: NULL argument");
     const int D = h->D, M = h->N;
     const bool use_map = cfg->use_map_hyperparams != 0;

@@ -1,6 +1,6 @@
 // C-ABI of the pathwise posterior function draws (include/sls_hip.h: sls_path_*): host orchestration of kernels_path.hip, the
 // cross Gram / gradient products of kernels_gram.hip / kernels_acq.hip, the block solve of kernels_tri.hip and the lock-step
-// L-BFGS of kernels_vec.hip.  No CPU fallback.
+// L-BFGS rounds of lbfgs_driver.hpp.  No CPU fallback.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -10,6 +10,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "lbfgs_driver.hpp"
 
 using namespace slsk;
 
@@ -17,16 +18,6 @@ namespace {
 
 constexpr int PATH_MAX_DRAWS = 4096;
 constexpr int PATH_MAX_FREQ = 16384;
-
-#define SLS_TRY slsk::note_entry(); try {
-#define SLS_CATCH                                   \
-    }                                               \
-    catch (const slsk::HipFail& f) { return f.code; } \
-    catch (const std::exception& e) {               \
-        slsk::set_error("exception: %s", e.what()); \
-        return SLS_ERR_INVALID;                     \
-    }                                               \
-    return SLS_OK;
 
 int* ints(DBuf& b, size_t n) {
     b.ensure((n + 1) / 2);
@@ -46,23 +37,6 @@ struct sls_path {
 };
 
 namespace {
-
-// the context's lock, the handle's state lock (shared), and a handle that still is what the object was made from
-struct PathCall {
-    std::unique_lock<std::recursive_mutex> ctx_lock;
-    std::shared_lock<std::shared_mutex> state_lock;
-    GpView g;
-    PathCall(sls_gp* gp, const sls_path* p, const char* who) : g(gp_view(gp)) {
-        ctx_lock = std::unique_lock<std::recursive_mutex>(g.ctx->mtx);
-        (void)hipSetDevice(g.ctx->device);
-        state_lock = std::shared_lock<std::shared_mutex>(*g.state);
-        g = gp_view(gp);
-        if (p)
-            SLS_REQUIRE(g.generation == p->generation,
-                        "%s: the GP handle was refitted or grown since sls_path_create (generation %ld, now %ld): create a new object",
-                        who, p->generation, g.generation);
-    }
-};
 
 // candidates per device pass: the chunk x Np blocks (K*, C*, Pm) and the chunk x 2Fp block (G / Phi) stay below 2^26 doubles each
 int chunk_of(int Np, int Fp) { return std::max(128, std::min(16384, ((1 << 26) / std::max(Np, 2 * Fp)) / 128 * 128)); }
@@ -159,20 +133,6 @@ void path_eval_device(sls_path* p, const GpView& g, EvalWs& w, const double* xr,
     }
 }
 
-// L-BFGS state of one sls_path_maximize call
-struct LbfgsWs {
-    DBuf x, g, dir, xt, scr, Sh, Yh, rho, f, t, val, grad, xc, ib;
-    int* ints = nullptr;
-    void ensure(int Sp, int m, int D) {
-        const size_t S = Sp;
-        x.ensure(S * D); g.ensure(S * D); dir.ensure(S * D); xt.ensure(S * D); scr.ensure(S * D);
-        const size_t Dh = D <= 16 ? 16 : (D <= 64 ? 64 : D);   // as capi.hip: lbfgs_step_reg_kernel's rows of 4 DPL doubles
-        Sh.ensure(S * Dh * m); Yh.ensure(S * Dh * m); rho.ensure(S * m);
-        f.ensure(S); t.ensure(S); val.ensure(S); grad.ensure(S * D); xc.ensure(S * D);
-        ints = ::ints(ib, S * 7 + 128 + S / 1024 + 8);   // hlen | hpos | nbt | done | live A | live B | count (64) | blocks | draws
-    }
-};
-
 }  // namespace
 
 extern "C" int sls_path_create(sls_gp* gp, int n_draws, int n_freq, unsigned long long seed, sls_path** out) {
@@ -181,7 +141,7 @@ extern "C" int sls_path_create(sls_gp* gp, int n_draws, int n_freq, unsigned lon
     *out = nullptr;
     SLS_REQUIRE(n_draws >= 1 && n_draws <= PATH_MAX_DRAWS, "sls_path_create: n_draws = %d (1 .. %d)", n_draws, PATH_MAX_DRAWS);
     SLS_REQUIRE(n_freq >= 1 && n_freq <= PATH_MAX_FREQ, "sls_path_create: n_freq = %d (1 .. %d)", n_freq, PATH_MAX_FREQ);
-    PathCall call(gp, nullptr, "sls_path_create");
+    GpReadCall call(gp);
     const GpView& g = call.g;
     sls_ctx* c = g.ctx;
     SLS_REQUIRE((long)g.N * n_draws < INT_MAX, "sls_path_create: N n_draws = %ld is too large", (long)g.N * n_draws);
@@ -228,14 +188,7 @@ extern "C" int sls_path_create(sls_gp* gp, int n_draws, int n_freq, unsigned lon
 
 extern "C" int sls_path_destroy(sls_path* p) {
     if (!p) return SLS_OK;
-    sls_ctx* c = p->ctx;
-    {
-        std::unique_lock<std::recursive_mutex> lock_(c->mtx);
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-        delete p;
-    }
-    ctx_release(c);
+    destroy_handle(p);
     return SLS_OK;
 }
 
@@ -250,7 +203,7 @@ extern "C" int sls_path_eval(sls_path* p, const double* Xs, int M, const int* dr
         for (int m = 0; m < M; ++m)
             SLS_REQUIRE(draw_of_point[m] >= 0 && draw_of_point[m] < p->n_draws, "sls_path_eval: draw_of_point[%d] = %d (n_draws = %d)", m,
                         draw_of_point[m], p->n_draws);
-    PathCall call(p->gp, p, "sls_path_eval");
+    GpReadCall call(p->gp, p->generation, "sls_path_eval");
     const GpView& g = call.g;
     sls_ctx* c = g.ctx;
     const int D = g.D, Mp = round_up(M, 128), nd = p->n_draws;
@@ -292,62 +245,25 @@ extern "C" int sls_path_maximize(sls_path* p, const double* starts, int S, int n
     SLS_REQUIRE((long)S * p->n_draws <= (1L << 26), "sls_path_maximize: n_draws S = %ld starts exceed 2^26", (long)S * p->n_draws);
     const sls_lbfgs_opts o = read_lbfgs_opts(opts);
     SLS_REQUIRE(o.history >= 1 && o.history <= 8, "L-BFGS history must be in 1..8");
-    PathCall call(p->gp, p, "sls_path_maximize");
+    GpReadCall call(p->gp, p->generation, "sls_path_maximize");
     const GpView& g = call.g;
     sls_ctx* c = g.ctx;
     const int D = g.D, nd = p->n_draws, T = S * nd, Sp = round_up(T, 128);
     LbfgsWs lb;
     EvalWs ws;
-    lb.ensure(Sp, o.history, D);
-    int* lb_int = lb.ints;
-    LbfgsState st;
-    st.live = nullptr; st.nlive = T; st.ldv = Sp;
-    st.S = T; st.D = D; st.m = o.history; st.ld = Sp;
-    st.x = lb.x.p; st.g = lb.g.p; st.dir = lb.dir.p; st.xt = lb.xt.p; st.scr = lb.scr.p;
-    st.Sh = lb.Sh.p; st.Yh = lb.Yh.p; st.rho = lb.rho.p; st.f = lb.f.p; st.t = lb.t.p;
-    st.hlen = lb_int; st.hpos = lb_int + Sp; st.nbt = lb_int + 2 * (size_t)Sp; st.done = lb_int + 3 * (size_t)Sp;
-    st.c1 = o.c1; st.shrink = o.shrink; st.gtol = o.gtol; st.max_backtracks = o.max_backtracks;
-    st.ftol_rel = o.ftol_rel; st.xtol_rel = o.xtol_rel;
-    int* live_a = lb_int + 4 * (size_t)Sp;
-    int* live_b = live_a + Sp;
-    int* d_count = live_b + Sp;
-    int* d_blocks = d_count + 64;
-    int* d_draw = d_blocks + Sp / 1024 + 8;
+    lb.ensure(Sp, o.history, D, Sp);
+    LbfgsState st = lb.state(T, D, o);
+    int* d_draw = lb.tail();   // the draw of every live column
     DBuf sd;
     sd.ensure((size_t)D * T);
     SLS_HIP(hipMemcpyAsync(sd.p, starts, (size_t)D * T * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    // The lock-step rounds of capi.hip's maximize_impl over the active set, with f_{live[j] / S} as the objective of compacted column
-    // j.  A candidate's arithmetic does not depend on its column, so SLS_COMPACT=0 (every start re-evaluated every round) ends with
-    // the same bits.
-    const bool compact = tune_on(TUNE_COMPACT);
-    launch_clamp_starts(c->stream, sd.p, D, T, st.xt, Sp, Sp);
-    const double* trial = st.xt;
-    const int* live = nullptr;
-    int nlive = T;
-    for (int ev = 0; ev < n_local && nlive > 0; ++ev) {
-        launch_path_draw_of_live(c->stream, live, nlive, S, d_draw);
-        path_eval_device(p, g, ws, trial, Sp, false, nlive, d_draw, lb.val.p, 0, lb.grad.p, Sp);
-        {
-            ProfScope ps(c, "lbfgs");
-            st.live = live; st.nlive = nlive;
-            launch_lbfgs_step(c->stream, st, lb.val.p, lb.grad.p, ev == 0);
-            if (ev + 1 < n_local) {
-                int* live_next = (live == live_a) ? live_b : live_a;
-                launch_compact_live(c->stream, live, nlive, st.done, live_next, d_count, d_blocks);
-                if (compact) {
-                    launch_gather_trials(c->stream, st.xt, Sp, D, live_next, d_count, nlive, lb.xc.p, Sp);
-                    live = live_next;
-                    trial = lb.xc.p;
-                }
-            }
-        }
-        if (ev + 1 < n_local && compact) {
-            int cnt = 0;
-            SLS_HIP(hipMemcpyAsync(&cnt, d_count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            SLS_HIP(hipStreamSynchronize(c->stream));
-            nlive = cnt;
-        }
-    }
+    // the shared lock-step rounds over the active set, with f_{live[j] / S} as the objective of compacted column j
+    lockstep_rounds(c, st, lb, sd.p, T, n_local,
+                    [&](const double* trial, long ld, int nlive, const int* live, double* val, double* grad) {
+                        launch_path_draw_of_live(c->stream, live, nlive, S, d_draw);
+                        path_eval_device(p, g, ws, trial, ld, false, nlive, d_draw, val, 0, grad, ld);
+                    },
+                    nullptr);
     DBuf best;
     best.ensure((size_t)nd * (D + 2));
     launch_path_argmax(c->stream, st.f, S, nd, st.x, Sp, D, best.p);

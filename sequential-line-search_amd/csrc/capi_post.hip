@@ -14,16 +14,6 @@ namespace {
 
 constexpr int POST_MAX_M = 8192;   // the largest factorisation this library has measured (README: potrf sizes)
 
-#define SLS_TRY slsk::note_entry(); try {
-#define SLS_CATCH                                   \
-    }                                               \
-    catch (const slsk::HipFail& f) { return f.code; } \
-    catch (const std::exception& e) {               \
-        slsk::set_error("exception: %s", e.what()); \
-        return SLS_ERR_INVALID;                     \
-    }                                               \
-    return SLS_OK;
-
 // Device blocks of one call (pool-backed: a repeated call of the same shape costs no hipMalloc).
 struct PostWs {
     int M = 0, Mp = 0;
@@ -84,19 +74,6 @@ void post_cov_device(const GpView& g, const double* Xs, int M, PostWs& w) {
     }
 }
 
-// shared argument checks and locks of the two GP entry points
-struct PostCall {
-    std::unique_lock<std::recursive_mutex> ctx_lock;
-    std::shared_lock<std::shared_mutex> state_lock;
-    GpView g;
-    explicit PostCall(sls_gp* gp) : g(gp_view(gp)) {
-        ctx_lock = std::unique_lock<std::recursive_mutex>(g.ctx->mtx);
-        (void)hipSetDevice(g.ctx->device);   // the handle's device, whatever the caller's current device is
-        state_lock = std::shared_lock<std::shared_mutex>(*g.state);
-        g = gp_view(gp);                     // re-read under the locks: a refit or an appended point may have changed it
-    }
-};
-
 }  // namespace
 
 extern "C" int sls_gp_predict_cov(sls_gp* gp, const double* Xs, int M, double* mu, double* cov) {
@@ -109,7 +86,7 @@ extern "C" int sls_gp_predict_cov(sls_gp* gp, const double* Xs, int M, double* m
     }
     if (M == 0) return SLS_OK;
     SLS_REQUIRE(Xs && cov, "sls_gp_predict_cov: Xs / cov is NULL");
-    PostCall call(gp);
+    GpReadCall call(gp);
     sls_ctx* c = call.g.ctx;
     PostWs w;
     post_cov_device(call.g, Xs, M, w);
@@ -133,7 +110,7 @@ extern "C" int sls_gp_sample_posterior(sls_gp* gp, const double* Xs, int M, int 
         return SLS_OK;
     }
     SLS_REQUIRE(Xs && samples, "sls_gp_sample_posterior: Xs / samples is NULL");
-    PostCall call(gp);
+    GpReadCall call(gp);
     sls_ctx* c = call.g.ctx;
     PostWs w;
     post_cov_device(call.g, Xs, M, w);
@@ -207,8 +184,7 @@ extern "C" int sls_gp_sample_posterior(sls_gp* gp, const double* Xs, int M, int 
 
 extern "C" int sls_random_normal(sls_ctx* ctx, unsigned long long seed, long offset, long n, double* out) {
     SLS_TRY
-    std::unique_lock<std::recursive_mutex> lock_;
-    if (ctx) lock_ = std::unique_lock<std::recursive_mutex>(ctx->mtx);
+    CtxCall call_(ctx);
     SLS_REQUIRE(ctx != nullptr, "sls_random_normal: ctx is NULL");
     SLS_REQUIRE(offset >= 0 && n >= 0, "sls_random_normal: offset = %ld, n = %ld", offset, n);
     if (n == 0) return SLS_OK;

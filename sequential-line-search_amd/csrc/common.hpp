@@ -62,6 +62,17 @@ struct HipFail {
         }                                      \
     } while (0)
 
+// Every C-ABI entry point that can fail: SLS_TRY ... SLS_CATCH around its body turn HipFail / exceptions into the return code.
+#define SLS_TRY slsk::note_entry(); try {
+#define SLS_CATCH                                   \
+    }                                               \
+    catch (const slsk::HipFail& f) { return f.code; } \
+    catch (const std::exception& e) {               \
+        slsk::set_error("exception: %s", e.what()); \
+        return SLS_ERR_INVALID;                     \
+    }                                               \
+    return SLS_OK;
+
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // Per-device cache of freed device blocks, keyed by exact size: hipMalloc / hipFree cost 50-300 us each and a GP handle owns
@@ -165,6 +176,48 @@ struct sls_ctx {
 namespace slsk {
 void ctx_retain(sls_ctx* c);     // a handle was created (caller holds c->mtx)
 void ctx_release(sls_ctx* c);    // a handle is gone (caller does NOT hold c->mtx: this may free the context)
+// The context's lock for the length of an entry point.  A NULL context / handle takes nothing: the entry point's own SLS_REQUIRE
+// reports it.  From a handle (anything with a ctx member): also the handle's device, whatever the caller's current device is.
+struct CtxCall {
+    std::unique_lock<std::recursive_mutex> lock;
+    explicit CtxCall(sls_ctx* c) {
+        if (c) lock = std::unique_lock<std::recursive_mutex>(c->mtx);
+    }
+    template <class H>
+    explicit CtxCall(H* h) : CtxCall(h ? h->ctx : nullptr) {
+        if (h) (void)hipSetDevice(h->ctx->device);
+    }
+};
+// Entry points that only read a fitted GP handle (capi_post.hip, capi_path.hip): the context's lock, the handle's device, the
+// handle's state lock (shared), and the view re-read under the locks -- a refit or an appended point may have changed it.
+// expect_generation >= 0: the handle must still be what an object derived from it (sls_path) was made from.
+struct GpReadCall {
+    GpView g;
+    CtxCall ctx_lock;
+    std::shared_lock<std::shared_mutex> state_lock;
+    explicit GpReadCall(sls_gp* gp, long expect_generation = -1, const char* who = "") : g(gp_view(gp)), ctx_lock(g.ctx) {
+        (void)hipSetDevice(g.ctx->device);
+        state_lock = std::shared_lock<std::shared_mutex>(*g.state);
+        g = gp_view(gp);
+        if (expect_generation >= 0)
+            SLS_REQUIRE(g.generation == expect_generation,
+                        "%s: the GP handle was refitted or grown since sls_path_create (generation %ld, now %ld): create a new object",
+                        who, expect_generation, g.generation);
+    }
+};
+// The tail of every handle's destroy: under the context's lock and on its device, drain the stream (and `drain`, a lock that work
+// off the context's stream holds shared), delete, and give the context's reference back outside the lock.
+template <class H>
+void destroy_handle(H* h, std::shared_mutex* drain = nullptr) {
+    sls_ctx* c = h->ctx;
+    {
+        CtxCall call(h);
+        (void)hipStreamSynchronize(c->stream);
+        if (drain) { std::unique_lock<std::shared_mutex> wait_(*drain); }   // released before the delete (it may be a member)
+        delete h;
+    }
+    ctx_release(c);
+}
 // RAII kernel-timing scope: records HIP events on the context's stream when profiling is enabled.
 struct ProfScope {
     sls_ctx* c;
