@@ -1,5 +1,5 @@
 """numpy restatement of the pathwise posterior function draws (sls_path_*, tests/test_gpu_path_sample.py,
-tests/test_path_sample_cpu.py), following the generator layout include/sls_hip.h documents:
+tests/test_gpu_path_edges.py, tests/test_path_sample_cpu.py), following the generator layout include/sls_hip.h documents:
 
   f_s(x) = sqrt(a/F) sum_l [ w_{s,l} cos(om_l . x~) + w'_{s,l} sin(om_l . x~) ]  +  sum_i v_{s,i} k(x, x_i)
   v_s    = K_y^-1 ( y - f_prior,s(X) - sqrt(b) eps_s ),   x~ = (x - 0.5) / l
@@ -30,6 +30,21 @@ def normals(seed, offset, n):
     z = np.stack([r01 * np.cos(t01), r01 * np.sin(t01), r23 * np.cos(t23), r23 * np.sin(t23)], axis=1).ravel()
     s = offset - 4 * b0
     return z[s:s + n]
+
+
+def round_up(n, k):
+    return (n + k - 1) // k * k
+
+
+def eval_chunk(Np, Fp):
+    """Candidates per device pass of sls_path_eval / sls_path_maximize (capi_path.hip, chunk_of): 2^26 / max(Np, 2 Fp), rounded down
+    to 128 and clamped to 128 .. 16384; Np = round_up(N, 128), Fp = round_up(F, 128)."""
+    return max(128, min(16384, ((1 << 26) // max(Np, 2 * Fp)) // 128 * 128))
+
+
+def create_rows(Np, Fp):
+    """Training rows per block of the prior at the data in sls_path_create: 2^26 / (2 Fp), rounded down to 128, within 128 .. Np."""
+    return max(128, min(Np, ((1 << 26) // (2 * Fp)) // 128 * 128))
 
 
 def block0(D, F, kernel):
@@ -132,3 +147,9 @@ class PathRef:
         l2 = (self.ell ** 2)[:, None]
         grad = grad - (Xs * cv.sum(axis=1)[None, :] - self.X @ cv.T) / l2
         return val, grad
+
+    def data_identity(self, rows=None):
+        """y_i - sqrt(b) eps_{s,i} - b v_{s,i} for the training rows `rows` (all by default), rows x n_draws: what f_s(x_i) equals,
+        since K v_s = r_s - b v_s and r_s = y - f_prior,s(X) - sqrt(b) eps_s."""
+        rows = slice(None) if rows is None else rows
+        return self.y[rows, None] - np.sqrt(self.b) * self.eps[rows] - self.b * self.v[rows]

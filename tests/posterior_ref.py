@@ -1,4 +1,5 @@
-"""numpy restatements behind the joint-posterior tests (tests/test_gpu_posterior.py, tests/test_posterior_api_cpu.py): the ARD
+"""numpy restatements behind the joint-posterior tests (tests/test_gpu_posterior.py, tests/test_gpu_posterior_edges.py,
+tests/test_posterior_api_cpu.py): the ARD
 kernels, the latent posterior covariance in its triangular form, and the normal generator of sls_random_normal /
 sls_gp_sample_posterior (Philox4x64-10 as numpy.random.Philox runs it, the uniform map, Box-Muller)."""
 import numpy as np
@@ -32,6 +33,32 @@ def posterior(X, y, Xs, theta, b, kernel):
     mu = Ks.T @ sla.cho_solve((L, True), y)
     ev = np.linalg.eigvalsh(Ky)
     return mu, Kss - W.T @ W, ev[-1] / ev[0]
+
+
+def pick_rows(M, n, seed, always=()):
+    """A fixed set of n distinct rows of 0 .. M - 1 (sorted) that contains every row of `always` below M: the rows at which a test
+    compares a covariance too large for a full host reference."""
+    keep = sorted({int(r) for r in always if 0 <= r < M})
+    rest = np.setdiff1d(np.arange(M), keep)
+    extra = np.random.default_rng(seed).choice(rest, size=min(max(n - len(keep), 0), rest.size), replace=False)
+    return np.sort(np.concatenate([np.asarray(keep, dtype=np.int64), extra.astype(np.int64)]))
+
+
+def posterior_rows(X, y, Xs, theta, b, kernel, rows):
+    """(mu[rows], cov[rows, :]) of posterior(): K(Xs[rows], Xs) - W[:, rows]^T W, without the M x M prior block."""
+    N = X.shape[1]
+    rows = np.asarray(rows)
+    L = np.linalg.cholesky(ard_kernel(X, X, theta, kernel) + b * np.eye(N))
+    Ks = ard_kernel(X, Xs, theta, kernel)
+    W = sla.solve_triangular(L, Ks, lower=True)
+    mu = Ks[:, rows].T @ sla.cho_solve((L, True), y)
+    return mu, ard_kernel(Xs[:, rows], Xs, theta, kernel) - W[:, rows].T @ W
+
+
+def sample_chunk(Mp):
+    """Samples per device pass of sls_gp_sample_posterior at Mp = round_up(M, 128) padded points (capi_post.hip): 2^24 / Mp, rounded
+    down to 128, at least 128.  A test of the second chunk restates the rule here and asserts that its shape crosses it."""
+    return max(128, ((1 << 24) // Mp) // 128 * 128)
 
 
 def philox_block(seed, block):

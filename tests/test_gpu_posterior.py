@@ -161,6 +161,8 @@ def test_reproducibility_and_prefix_property(m, ctx):
     F2, j2 = gp.sample_posterior(Xs, 4097, 77)
     assert j1 == j2
     assert np.array_equal(F1[:, :4097], F2)
+    # the second chunk continues the stream: its samples are not the first chunk's over again
+    assert not np.any(F1[:, 4096:] == F1[:, :4])
     F3, _ = gp.sample_posterior(Xs, 3, 77)
     assert np.array_equal(F1[:, :3], F3)
     F4, _ = gp.sample_posterior(Xs, 3, 78)

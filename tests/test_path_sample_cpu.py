@@ -133,3 +133,41 @@ def test_package_exports_the_path_calls():
     txt = open(os.path.join(ROOT, "include", "sls_hip.h")).read()
     for n in names:
         assert re.search(r"\b" + n + r"\s*\(", txt)
+
+
+def test_host_split_rules():
+    """The chunk and row-block rules of capi_path.hip as the GPU edge tests restate them, at the values DESIGN.md quotes: one
+    8192-row block at (N, F) = (2048, 4096), chunks of 8192 at the full size (8192, 2048), 2048 at F = 16384."""
+    assert ph.eval_chunk(2048, 4096) == 8192 and ph.eval_chunk(8192, 2048) == 8192 and ph.eval_chunk(128, 16384) == 2048
+    assert ph.eval_chunk(128, 128) == 16384 and ph.eval_chunk(2 ** 20, 128) == 128
+    assert ph.create_rows(2048, 4096) == 2048 and ph.create_rows(2304, 16384) == 2048 and ph.create_rows(16384, 4096) == 8192
+    assert ph.create_rows(128, 16384) == 128
+    src = open(os.path.join(ROOT, "sequential-line-search_amd", "csrc", "capi_path.hip")).read()
+    assert "std::max(128, std::min(16384, ((1 << 26) / std::max(Np, 2 * Fp)) / 128 * 128))" in src
+    assert "std::max(128, std::min(Np, ((1 << 26) / (2 * Fp)) / 128 * 128))" in src
+
+
+@pytest.mark.parametrize("kernel", [ph.SE, ph.MATERN52])
+def test_sliced_eval_and_data_identity_equal_the_full_forms(kernel):
+    """PathRef.eval / eval_all on a slice of the points are the slice of the full call (each point is evaluated by itself), and
+    data_identity on a row subset is the subset of the identity at all the data: the GPU edge tests lean on both."""
+    D, N, b, nd, F, M = 3, 30, 0.02, 4, 96, 50
+    rng = np.random.default_rng(6 + kernel)
+    X = rng.uniform(0, 1, (D, N))
+    y = np.sin(3 * X.sum(0))
+    theta = np.array([0.6, 0.3, 0.45, 0.5])
+    ref = ph.PathRef(X, y, theta, b, kernel, nd, F, seed=8)
+    Xs = rng.uniform(0, 1, (D, M))
+    dr = rng.integers(0, nd, M)
+    v, g = ref.eval(Xs, dr)
+    allv = ref.eval_all(Xs)
+    sl = slice(31, 47)
+    vs, gs = ref.eval(Xs[:, sl], dr[sl])
+    scale = theta[0] + np.abs(ref.v).max() * theta[0] * N
+    assert np.abs(vs - v[sl]).max() <= 1e-13 * scale and np.abs(gs - g[:, sl]).max() <= 1e-13 * scale / theta[1:].min()
+    assert np.abs(ref.eval_all(Xs[:, sl]) - allv[sl]).max() <= 1e-13 * scale
+    assert np.abs(allv[np.arange(M), dr] - v).max() <= 1e-13 * scale
+    rows = np.arange(17, 30)
+    full = ref.data_identity()
+    assert full.shape == (N, nd) and np.array_equal(ref.data_identity(rows), full[rows])
+    assert np.abs(ref.eval_all(X[:, rows]) - ref.data_identity(rows)).max() <= 1e-8

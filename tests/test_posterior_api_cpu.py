@@ -102,3 +102,31 @@ def test_normal_restatement_layout():
     th01, th23 = 2 * np.pi * pr.uniform(x[1]), 2 * np.pi * pr.uniform(x[3])
     assert z[4:8].tolist() == [r01 * np.cos(th01), r01 * np.sin(th01), r23 * np.cos(th23), r23 * np.sin(th23)]
     assert pr.normals(9, 5, 6).tolist() == z[5:11].tolist()
+
+
+@pytest.mark.parametrize("kernel", [pr.SE, pr.MATERN52])
+def test_row_subset_posterior_equals_the_full_posterior(kernel):
+    """posterior_rows (the reference of the M = 8191 / 8192 covariance tests) against posterior at M = 300."""
+    D, N, M, b = 5, 40, 300, 0.01
+    rng = np.random.default_rng(21 + kernel)
+    X, Xs = rng.uniform(0, 1, (D, N)), rng.uniform(0, 1, (D, M))
+    y = np.sin(2 * X.sum(0))
+    theta = np.concatenate([[0.5], rng.uniform(0.3, 0.6, D)])
+    rows = pr.pick_rows(M, 32, seed=3, always=(0, 127, 128, 299, 300, 8191))
+    assert rows.size == 32 and np.all(np.diff(rows) > 0) and rows[0] == 0 and rows[-1] == 299
+    assert {0, 127, 128, 299} <= set(rows.tolist()) and rows.max() < M
+    assert np.array_equal(rows, pr.pick_rows(M, 32, seed=3, always=(0, 127, 128, 299, 300, 8191)))
+    mu, cov, _ = pr.posterior(X, y, Xs, theta, b, kernel)
+    mu_r, cov_r = pr.posterior_rows(X, y, Xs, theta, b, kernel, rows)
+    assert cov_r.shape == (32, M)
+    # the same factor and the same triangular solve; only the blocking of the products differs
+    assert np.abs(cov_r - cov[rows]).max() <= 1e-14 * theta[0] * N
+    assert np.abs(mu_r - mu[rows]).max() <= 1e-14 * (np.abs(mu).max() + theta[0]) * N
+
+
+def test_sample_chunk_rule():
+    """The host rule of sls_gp_sample_posterior as the GPU tests restate it: 4096 samples per pass at M = 4096, 2048 at 8192."""
+    assert pr.sample_chunk(4096) == 4096 and pr.sample_chunk(8192) == 2048 and pr.sample_chunk(128) == 131072
+    assert pr.sample_chunk(3 * 128) == (2 ** 24 // 384) // 128 * 128 and pr.sample_chunk(2 ** 24) == 128
+    src = open(os.path.join(ROOT, "sequential-line-search_amd", "csrc", "capi_post.hip")).read()
+    assert "std::max(128, ((1 << 24) / Mp) / 128 * 128)" in src
