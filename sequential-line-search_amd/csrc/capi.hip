@@ -291,7 +291,6 @@ static void ctx_destroy_now(sls_ctx* ctx) {
             (void)hipStreamSynchronize(s->stream);
             (void)hipStreamDestroy(s->stream);
         }
-        if (s->host) ctx->host_give(s->host, s->bytes, true);
     }
     ctx->slots.clear();
     for (auto& b : ctx->host_free) (void)hipHostFree(b.p);
@@ -407,13 +406,11 @@ struct sls_gp {
     long* d_idx = nullptr;             // idx_buf's block (pooled: a hipMalloc / hipFree pair per handle synchronised the device)
     // what the host reads after a fit -- max mu, log|K_y|, arg max, the factorisation's two info words -- in a page-locked block the
     // last kernel of the fit writes directly (mapped): one synchronisation, no copies back (they were three blocking pageable copies)
-    double* sum_host = nullptr;
-    double* sum_dev = nullptr;
-    size_t sum_bytes = 0;
+    HostBuf sum;
     int best_index = 0;
     double mu_best = 0, logdet = 0;
     // evaluation workspace (grown on demand)
-    DBuf Ks, Cs, P, Vs, parts, Gs, Gm, Gpart, XsT, ns, raw, outv, outg, outm, outs;
+    DBuf Ks, Cs, P, Vs, parts, Gs, Gm, Gpart, XsT, ns, raw, outv;
     int ws_chunk = 0;
     // L-BFGS state
     DBuf pair_mu, pair_sg, pair_dmu, pair_dsg;
@@ -428,36 +425,22 @@ struct sls_gp {
     long stat_issued = 0, stat_cap = 0;
     int stat_rounds = 0, stat_live_end = 0;
     // page-locked, device-mapped block for small value-only evaluations (query points in, values out: no copy calls)
-    double* zc_host = nullptr;
-    double* zc_dev = nullptr;
-    size_t zc_bytes = 0;
+    HostBuf zc;
     // page-locked staging of host-supplied query points and their results (predict / acquisition entry points on the tiled path):
     // uploads and downloads are truly asynchronous, one synchronisation per call (pageable buffers: blocking staged copies, a
     // synchronisation behind each, and a fresh 0.5 MB temporary per transfer)
+    HostBuf io;
+    double* io_stage(size_t doubles) {
+        if (io.host && doubles * 8 > io.bytes) (void)hipStreamSynchronize(ctx->stream);   // an upload from the old block may still be in flight (growth is rare)
+        io.ensure(ctx, doubles * 8, false);
+        return io.host;
+    }
     // Concurrent const evaluations (src/acquisition-function.cpp:125-144: Predict* of ONE regressor from hardware_concurrency worker
     // threads).  A small evaluation (a few query points on a wave-path handle) does not take the context's lock: it borrows a SLOT of
     // the handle -- a stream of its own and a page-locked, device-mapped block for the query points and the results -- under a
     // SHARED lock on the fitted state; everything that changes the state (refit, appended point, sigma mode) holds it exclusively.
     // The slots belong to the CONTEXT (sls_ctx::slots): a stream costs ~1 ms to create and the facade builds a new handle per submit.
     std::shared_mutex state_mtx;
-    double* io_host = nullptr;
-    size_t io_bytes = 0;
-    double* io_stage(size_t doubles) {
-        if (doubles * 8 > io_bytes) {
-            if (io_host) {
-                (void)hipStreamSynchronize(ctx->stream);   // an upload from the old block may still be in flight (growth is rare)
-                ctx->host_give(io_host, io_bytes, false);
-            }
-            io_host = nullptr;
-            io_host = static_cast<double*>(ctx->host_take(doubles * 8, false, &io_bytes));
-        }
-        return io_host;
-    }
-    ~sls_gp() {   // sls_gp_destroy holds the context's lock
-        if (sum_host) ctx->host_give(sum_host, sum_bytes, true);
-        if (zc_host) ctx->host_give(zc_host, zc_bytes, true);
-        if (io_host) ctx->host_give(io_host, io_bytes, false);
-    }
 };
 
 // N <= 128: the whole fit is one single-workgroup launch (kernels_small.hip); SLS_FIT_SMALL=0 forces the tiled pipeline (A/B, tests)
@@ -477,7 +460,7 @@ static void gp_fit_device(sls_gp* g) {
         f.D = D; f.N = N; f.Dcols = g->Dcols; f.a = g->a; f.b = g->b;
         f.XT = g->XT.p; f.nx = g->nx.p; f.XaT = g->XaT.p; f.L = g->L.p; f.Linv = g->Linv.p; f.U = g->U.p; f.Kinv = g->Kinv.p;
         f.alpha = g->alpha.p; f.mu_data = g->mu_data.p; f.scal = g->scal.p; f.d_idx = g->d_idx; f.info = c->d_info;
-        f.summary = g->sum_dev;
+        f.summary = g->sum.dev;
         f.x_lds = tune_on(TUNE_SMALL_XLDS) ? 1 : 0;
         SLS_HIP(hipMemsetAsync(c->d_info, 0, 64, c->stream));
         ProfScope ps(c, "fit_small");
@@ -527,13 +510,13 @@ static void gp_fit_device(sls_gp* g) {
     launch_scale_rows(c->stream, g->XT.p, g->alpha.p, g->XaT.p, Np, Np, g->Dcols);
     if (g->sigma_mode == 1) launch_transpose_full(c->stream, g->Linv.p, g->U.p, Np);   // every block of U = (L^-1)^T
     // mu at the data points, its first maximum, log|K_y| and the info words: one launch, results straight into the mapped block
-    launch_fit_summary(c->stream, g->y.p, g->alpha.p, g->b, N, g->mu_data.p, g->L.p, Np, c->d_info, g->scal.p, g->d_idx, g->sum_dev);
+    launch_fit_summary(c->stream, g->y.p, g->alpha.p, g->b, N, g->mu_data.p, g->L.p, Np, c->d_info, g->scal.p, g->d_idx, g->sum.dev);
 }
 
 static void gp_fetch_summary(sls_gp* g, int attempt = 0) {
     sls_ctx* c = g->ctx;
     sync(c);                         // the fit's last kernel has written the mapped block
-    const double* sm = g->sum_host;
+    const double* sm = g->sum.host;
     const int info[2] = {(int)sm[3], (int)sm[4]};
     if (potrf_gave_up(c, info[1], attempt)) {
         gp_fit_device(g);            // once more, on the multi-launch schedule (the fit rebuilds K_y from X)
@@ -563,11 +546,7 @@ static void gp_setup(sls_gp* g) {
     g->ws_chunk = 0;   // the evaluation workspace depends on Np
     g->idx_buf.ensure(8);
     g->d_idx = reinterpret_cast<long*>(g->idx_buf.p);
-    if (!g->sum_host) {
-        // [0..5) the fit's summary, [8..16 + D) the maximiser's best start
-        g->sum_host = static_cast<double*>(ctx->host_take((size_t)(16 + D) * 8, true, &g->sum_bytes));
-        SLS_HIP(hipHostGetDevicePointer((void**)&g->sum_dev, g->sum_host, 0));
-    }
+    g->sum.ensure(ctx, (size_t)(16 + D) * 8, true);   // [0..5) the fit's summary, [8..16 + D) the maximiser's best start
     g->il_h.assign(g->Dcols, 0.0);
     g->ypad_h.assign(Np, 0.0);
     for (int d = 0; d < D; ++d) g->il_h[d] = 1.0 / g->theta[1 + d];
@@ -764,8 +743,9 @@ static void ensure_eval_ws(sls_gp* g, int chunk) {
     g->ws_chunk = chunk;
 }
 
+// What one evaluation wants; any output may be NULL.  At the entry points the pointers are the caller's host arrays (row outputs
+// dmu, dsigma, grad: D x M column-major); below them, candidate-major device outputs with leading dimension ldo (eval_block).
 struct EvalOut {
-    // candidate-major device outputs with leading dimension ldo (full candidate count, padded); any may be NULL
     long ldo = 0;
     double *mu = nullptr, *sigma = nullptr, *dmu = nullptr, *dsigma = nullptr, *val = nullptr, *grad = nullptr;
     int acq = SLS_ACQ_EXPECTED_IMPROVEMENT;
@@ -856,23 +836,37 @@ static void eval_candidates(sls_gp* g, const double* xr, long ldr, int S, const 
     }
 }
 
-// Small problems: one wavefront per query point (kernels_wave.hip, evaluation-only mode) instead of the tiled pipeline.
-// Xs_dev: D x M column-major device copy of the query points; outputs as in EvalOut.
-static bool eval_small(sls_gp* g, const double* Xs_dev, int M, const EvalOut& o) {
-    const bool allow = tune_on(TUNE_WAVE_PATH);
-    if (!allow || g->Np > WAVE_PATH_MAX_NP || g->D > WAVE_PATH_MAX_D || M > 4096) return false;
-    sls_ctx* c = g->ctx;
-    WaveArgs w;
-    w.S = M; w.D = g->D; w.N = g->N; w.Np = g->Np; w.m = 1; w.n_local = 0; w.acq = o.acq;
+// Small problems: one wavefront per query point / start (kernels_wave.hip) instead of the tiled pipeline.  The answer depends
+// only on the fitted state and the count, so repeated / sharded calls take the same path.  D never changes for a handle
+// (wave_path_dims); Np grows with appended points, so whoever works without the context's lock asks under the state lock.
+constexpr int WAVE_PATH_MAX_POINTS = 4096;   // query points / starts per launch
+static bool wave_path_dims(const sls_gp* g) { return tune_on(TUNE_WAVE_PATH) && g->D <= WAVE_PATH_MAX_D; }
+static bool wave_path_applies(const sls_gp* g, int count) {
+    return wave_path_dims(g) && g->Np <= WAVE_PATH_MAX_NP && count <= WAVE_PATH_MAX_POINTS;
+}
+// the model half of WaveArgs: everything that comes from the fitted state
+static void wave_model_args(const sls_gp* g, WaveArgs& w) {
+    w.D = g->D; w.N = g->N; w.Np = g->Np;
     w.matern = g->kernel == SLS_KERNEL_ARD_MATERN52;
-    w.a = g->a; w.mu_best = g->mu_best; w.ucb_h = o.ucb_h; w.c1 = 0; w.shrink = 0; w.gtol = 0; w.max_backtracks = 0;
-    w.XT = g->XT.p; w.inv_ell = g->inv_ell.p; w.Kinv = g->Kinv.p; w.alpha = g->alpha.p; w.starts = Xs_dev;
+    w.a = g->a; w.mu_best = g->mu_best;
+    w.XT = g->XT.p; w.inv_ell = g->inv_ell.p; w.Kinv = g->Kinv.p; w.alpha = g->alpha.p;
     w.solve_sigma = g->sigma_mode == 1; w.Linv = g->Linv.p; w.U = g->U.p;
-    w.x_out = nullptr; w.f_out = nullptr; w.ld = o.ldo;
+    w.useful = nullptr;
+}
+// evaluation-only mode on stream s.  Xs_dev: D x M column-major device copy of the query points; outputs as in EvalOut (device).
+static void wave_eval(const sls_gp* g, hipStream_t s, const double* Xs_dev, int M, const EvalOut& o) {
+    WaveArgs w;
+    wave_model_args(g, w);
+    w.S = M; w.m = 1; w.n_local = 0; w.acq = o.acq; w.ucb_h = o.ucb_h;
+    w.c1 = 0; w.shrink = 0; w.gtol = 0; w.max_backtracks = 0;
+    w.starts = Xs_dev; w.x_out = nullptr; w.f_out = nullptr; w.ld = o.ldo;
     w.ev_mu = o.mu; w.ev_sigma = o.sigma; w.ev_dmu = o.dmu; w.ev_dsigma = o.dsigma; w.ev_val = o.val; w.ev_grad = o.grad;
-    ProfScope ps(c, "acq_wave");
-    launch_maximize_wave(c->stream, w);
-    return true;
+    launch_maximize_wave(s, w);
+}
+// ... on the context's stream (the caller has asked wave_path_applies)
+static void eval_small(sls_gp* g, const double* Xs_dev, int M, const EvalOut& o) {
+    ProfScope ps(g->ctx, "acq_wave");
+    wave_eval(g, g->ctx->stream, Xs_dev, M, o);
 }
 
 // host D x M column-major -> device candidate-major raw coordinates (clamping is NOT applied here)
@@ -890,87 +884,116 @@ static void upload_candidates(sls_gp* g, const double* Xs, int M, DBuf& raw, int
 // evaluate M host-supplied query points (D x M column-major) into the candidate-major device outputs of `o`
 static void eval_host_points(sls_gp* g, const double* Xs, int M, int Mp, const EvalOut& o) {
     sls_ctx* c = g->ctx;
-    const bool allow = tune_on(TUNE_WAVE_PATH);
     const size_t n = (size_t)g->D * M;
-    if (allow && g->Np <= WAVE_PATH_MAX_NP && g->D <= WAVE_PATH_MAX_D && M <= 4096) {
-        g->raw.ensure(n);
-        if (n <= IO_STAGE_MAX && tune_on(TUNE_IO_STAGE)) {   // through the page-locked block: a copy from pageable memory blocks the host
-            double* st = g->io_stage(n);
-            std::memcpy(st, Xs, n * sizeof(double));
-            h2d(c, g->raw.p, st, n);
-        } else
-            h2d(c, g->raw.p, Xs, n);
-        if (eval_small(g, g->raw.p, M, o)) return;
-    }
-    if (n <= IO_STAGE_MAX && tune_on(TUNE_IO_STAGE)) {   // SLS_IO_STAGE=0: the transposing pageable upload of rounds 1-3 (A/B, tests)
-        // as handed over (point-major), through page-locked memory: no transposition on the host, no synchronisation behind the upload
-        double* st = g->io_stage(n);
-        std::memcpy(st, Xs, n * sizeof(double));
-        g->raw.ensure(n);
-        h2d(c, g->raw.p, st, n);
-        eval_candidates(g, g->raw.p, 0, M, o, true);
+    const bool wave = wave_path_applies(g, M);
+    const bool staged = n <= IO_STAGE_MAX && tune_on(TUNE_IO_STAGE);
+    if (!wave && !staged) {   // SLS_IO_STAGE=0: the transposing pageable upload of rounds 1-3 (A/B, tests)
+        upload_candidates(g, Xs, M, g->raw, Mp);
+        eval_candidates(g, g->raw.p, Mp, M, o);
         return;
     }
-    upload_candidates(g, Xs, M, g->raw, Mp);
-    eval_candidates(g, g->raw.p, Mp, M, o);
+    // as handed over (point-major): no transposition on the host, no synchronisation behind the upload
+    g->raw.ensure(n);
+    const double* src = Xs;
+    if (staged) {   // through the page-locked block: a copy from pageable memory blocks the host
+        double* st = g->io_stage(n);
+        std::memcpy(st, Xs, n * sizeof(double));
+        src = st;
+    }
+    h2d(c, g->raw.p, src, n);
+    if (wave) eval_small(g, g->raw.p, M, o);
+    else eval_candidates(g, g->raw.p, 0, M, o, true);
 }
 
-// Results back to the host: up to two candidate-major device arrays (rows x Mp each; rows = 1: a vector, rows = D: transposed into
-// D x M column-major) with ONE synchronisation, through the page-locked staging block when they fit.
-static void download_cm2(sls_gp* g, const double* devA, double* hostA, const double* devB, double* hostB, int M, int Mp, int rows) {
-    sls_ctx* c = g->ctx;
-    const size_t each = (size_t)Mp * rows;
-    const int cnt = (hostA ? 1 : 0) + (hostB ? 1 : 0);
-    if (cnt == 0) {
-        sync(c);   // nothing to fetch, but the evaluation in flight reads the staging block the next call writes into
+// ---- result blocks ---------------------------------------------------------------------------------------------
+// The outputs a call asked for, one behind the other in ONE block: mu | sigma | val | dmu | dsigma | grad, the absent ones left
+// out, each candidate-major with leading dimension ld (1 row, or D rows for dmu / dsigma / grad).  The same layout serves the
+// device outputs of the general path, the mapped blocks of the small paths and the host's copy of either.
+static size_t eval_block_doubles(const EvalOut& want, int D, long ld) {
+    const int vecs = (want.mu != nullptr) + (want.sigma != nullptr) + (want.val != nullptr);
+    const int mats = (want.dmu != nullptr) + (want.dsigma != nullptr) + (want.grad != nullptr);
+    return (size_t)(vecs + (size_t)mats * D) * ld;
+}
+static EvalOut eval_block(const EvalOut& want, double* base, int D, long ld) {
+    EvalOut b = want;
+    b.ldo = ld;
+    auto place = [&](double* asked, int rows) {
+        double* at = asked ? base : nullptr;
+        if (asked) base += (size_t)rows * ld;
+        return at;
+    };
+    b.mu = place(want.mu, 1); b.sigma = place(want.sigma, 1); b.val = place(want.val, 1);
+    b.dmu = place(want.dmu, D); b.dsigma = place(want.dsigma, D); b.grad = place(want.grad, D);
+    return b;
+}
+// candidate-major src[m + r * ld] (rows x ld) into the caller's array: rows = 1: a vector of M; rows = D: D x M column-major
+static void cm_to_host(const double* src, long ld, int rows, int M, double* host) {
+    if (!host) return;
+    if (rows == 1) std::copy(src, src + M, host);
+    else
+        for (int m = 0; m < M; ++m)
+            for (int r = 0; r < rows; ++r) host[r + (size_t)m * rows] = src[(size_t)m + (size_t)r * ld];
+}
+// a block `at` (eval_block over host-readable memory) into the arrays the caller named in `want`
+static void eval_block_to_host(const EvalOut& want, const EvalOut& at, int D, int M) {
+    cm_to_host(at.mu, at.ldo, 1, M, want.mu); cm_to_host(at.sigma, at.ldo, 1, M, want.sigma); cm_to_host(at.val, at.ldo, 1, M, want.val);
+    cm_to_host(at.dmu, at.ldo, D, M, want.dmu); cm_to_host(at.dsigma, at.ldo, D, M, want.dsigma); cm_to_host(at.grad, at.ldo, D, M, want.grad);
+}
+// n doubles of device memory where the host can read them on return: the handle's page-locked staging block when they fit,
+// `pageable` otherwise; ONE synchronisation
+static double* fetch(sls_gp* g, const double* dev, size_t n, std::vector<double>& pageable) {
+    double* t;
+    if (n <= IO_STAGE_MAX) t = g->io_stage(n);
+    else {
+        pageable.resize(n);
+        t = pageable.data();
+    }
+    d2h(g->ctx, t, dev, n);
+    sync(g->ctx);
+    return t;
+}
+// one candidate-major device array (rows x Mp) back to the host
+static void download_cm(sls_gp* g, const double* dev, int M, int Mp, int rows, double* host /* rows x M col-major or M */) {
+    std::vector<double> pageable;
+    cm_to_host(fetch(g, dev, (size_t)Mp * rows, pageable), Mp, rows, M, host);
+}
+// every output of a call back to the host: the device block behind eval_block(want, dev, D, Mp) in one copy
+static void download_block(sls_gp* g, const EvalOut& want, const double* dev, int M, int Mp) {
+    const size_t n = eval_block_doubles(want, g->D, Mp);
+    if (n == 0) {
+        sync(g->ctx);   // nothing to fetch, but the evaluation in flight reads the staging block the next call writes into
         return;
     }
     std::vector<double> pageable;
-    double* t;
-    if (each * cnt <= IO_STAGE_MAX) t = g->io_stage(each * cnt);
-    else {
-        pageable.resize(each * cnt);
-        t = pageable.data();
-    }
-    double* tA = t;
-    double* tB = hostA ? t + each : t;
-    if (hostA) d2h(c, tA, devA, each);
-    if (hostB) d2h(c, tB, devB, each);
-    sync(c);
-    auto out = [&](const double* src, double* host) {
-        if (rows == 1) std::copy(src, src + M, host);
-        else
-            for (int m = 0; m < M; ++m)
-                for (int d = 0; d < rows; ++d) host[d + (size_t)m * rows] = src[(size_t)m + (size_t)d * Mp];
-    };
-    if (hostA) out(tA, hostA);
-    if (hostB) out(tB, hostB);
-}
-static void download_cm(sls_gp* g, const double* dev, int M, int Mp, int rows, double* host /* rows x M col-major or M */) {
-    download_cm2(g, dev, host, nullptr, nullptr, M, Mp, rows);
+    eval_block_to_host(want, eval_block(want, fetch(g, dev, n, pageable), g->D, Mp), g->D, M);
 }
 
-// ---- concurrent small evaluations (sls_gp::EvalSlot) ---------------------------------------------------------
-// What one call wants; any pointer may be NULL.  Row outputs (dmu, dsigma, grad) are D x M column-major on the host.
-struct SmallEvalOut {
-    double *mu = nullptr, *sigma = nullptr, *dmu = nullptr, *dsigma = nullptr, *val = nullptr, *grad = nullptr;
-    int acq = SLS_ACQ_EXPECTED_IMPROVEMENT;
-    double ucb_h = 1.0;
-};
+// Small evaluations through a device-mapped block: [D x M query points][eval_block with ld = M].  The kernel reads the points from
+// and writes the results to host memory: no copy calls.  mapped_in fills the block and returns the device's view of the outputs;
+// mapped_out, behind the stream's synchronisation, hands the results to the caller.
+static size_t mapped_bytes(const EvalOut& want, int D, int M) { return ((size_t)D * M + eval_block_doubles(want, D, M)) * sizeof(double); }
+static EvalOut mapped_in(const HostBuf& blk, const double* Xs, int D, int M, const EvalOut& want) {
+    std::memcpy(blk.host, Xs, sizeof(double) * (size_t)D * M);
+    return eval_block(want, blk.dev + (size_t)D * M, D, M);
+}
+static void mapped_out(const HostBuf& blk, int D, int M, const EvalOut& want) {
+    eval_block_to_host(want, eval_block(want, blk.host + (size_t)D * M, D, M), D, M);
+}
+
+// ---- concurrent small evaluations (sls_ctx::EvalSlot) ---------------------------------------------------------
 constexpr int SLOT_MAX_POINTS = 64;
 // true: evaluated (results are in the caller's arrays).  false: not applicable -- the caller takes the context's lock and the
 // general path.  Holds no lock of the context; the caller must NOT hold it either (a mutator waiting for the state lock would
 // then wait for this call, not the other way round -- there is no inversion, but the point of the path is to stay off that lock).
-static bool eval_in_slot(sls_gp* g, const double* Xs, int M, const SmallEvalOut& o) {
+static bool eval_in_slot(sls_gp* g, const double* Xs, int M, const EvalOut& want) {
     sls_ctx* c = g->ctx;
-    if (M < 1 || M > SLOT_MAX_POINTS || !tune_on(TUNE_EVAL_SLOTS) || !tune_on(TUNE_WAVE_PATH) || c->prof_on) return false;
-    if (g->D > WAVE_PATH_MAX_D) return false;          // D never changes for a handle
+    if (M < 1 || M > SLOT_MAX_POINTS || !tune_on(TUNE_EVAL_SLOTS) || c->prof_on) return false;
+    if (!wave_path_dims(g)) return false;              // D never changes for a handle
     (void)hipSetDevice(c->device);
     const int D = g->D;
     // Lock order: the slot (and, for the rare growth of its block, the context's lock, released again) FIRST, the shared lock on the
     // fitted state LAST and on its own.  Mutators hold the context's lock and then the state lock exclusively: taking the context's
     // lock under the shared state lock here would deadlock against them.
-    const size_t n_in = (size_t)D * M, n_out = (size_t)(3 + 3 * D) * M;
     // ---- borrow a slot ----
     sls_ctx::EvalSlot* slot = nullptr;
     {
@@ -1000,132 +1023,66 @@ static bool eval_in_slot(sls_gp* g, const double* Xs, int M, const SmallEvalOut&
         }
     } release{c, slot};
     if (!slot->stream) SLS_HIP(hipStreamCreateWithFlags(&slot->stream, hipStreamNonBlocking));
-    const size_t need = (n_in + n_out) * sizeof(double);
-    if (need > slot->bytes) {
+    const size_t need = mapped_bytes(want, D, M);
+    if (need > slot->block.bytes) {
         std::lock_guard<std::recursive_mutex> ctx_lock(c->mtx);   // the context's page-locked pool is not thread safe; growth is rare
-        if (slot->host) c->host_give(slot->host, slot->bytes, true);
-        slot->host = nullptr;
-        slot->bytes = 0;
-        slot->host = static_cast<double*>(c->host_take(std::max(need, (size_t)(4 + 4 * D) * SLOT_MAX_POINTS * sizeof(double)), true, &slot->bytes));
-        SLS_HIP(hipHostGetDevicePointer((void**)&slot->dev, slot->host, 0));
+        slot->block.ensure(c, need, true, (size_t)(4 + 4 * D) * SLOT_MAX_POINTS * sizeof(double));
     }
     std::shared_lock<std::shared_mutex> state_(g->state_mtx);
-    if (g->Np > WAVE_PATH_MAX_NP) return false;        // grown past the wave path by appended points: the general path
-    std::memcpy(slot->host, Xs, n_in * sizeof(double));
-    double* od = slot->dev + n_in;       // device view of the outputs: mu | sigma | val | dmu | dsigma | grad, candidate-major, ld = M
-    double* oh = slot->host + n_in;
-    WaveArgs w;
-    w.S = M; w.D = D; w.N = g->N; w.Np = g->Np; w.m = 1; w.n_local = 0; w.acq = o.acq;
-    w.matern = g->kernel == SLS_KERNEL_ARD_MATERN52;
-    w.a = g->a; w.mu_best = g->mu_best; w.ucb_h = o.ucb_h; w.c1 = 0; w.shrink = 0; w.gtol = 0; w.max_backtracks = 0;
-    w.XT = g->XT.p; w.inv_ell = g->inv_ell.p; w.Kinv = g->Kinv.p; w.alpha = g->alpha.p; w.starts = slot->dev;
-    w.solve_sigma = g->sigma_mode == 1; w.Linv = g->Linv.p; w.U = g->U.p;
-    w.x_out = nullptr; w.f_out = nullptr; w.ld = M;
-    w.ev_mu = o.mu ? od : nullptr;
-    w.ev_sigma = o.sigma ? od + M : nullptr;
-    w.ev_val = o.val ? od + 2 * (size_t)M : nullptr;
-    w.ev_dmu = o.dmu ? od + 3 * (size_t)M : nullptr;
-    w.ev_dsigma = o.dsigma ? od + (size_t)(3 + D) * M : nullptr;
-    w.ev_grad = o.grad ? od + (size_t)(3 + 2 * D) * M : nullptr;
-    launch_maximize_wave(slot->stream, w);
+    if (!wave_path_applies(g, M)) return false;        // grown past the wave path by appended points: the general path
+    const EvalOut od = mapped_in(slot->block, Xs, D, M, want);
+    wave_eval(g, slot->stream, slot->block.dev, M, od);
     SLS_HIP(hipStreamSynchronize(slot->stream));
-    auto vec = [&](double* host, size_t off) {
-        if (host) std::memcpy(host, oh + off, sizeof(double) * M);
-    };
-    auto rows = [&](double* host, size_t off) {
-        if (!host) return;
-        for (int m = 0; m < M; ++m)
-            for (int d = 0; d < D; ++d) host[d + (size_t)m * D] = oh[off + (size_t)m + (size_t)d * M];
-    };
-    vec(o.mu, 0); vec(o.sigma, M); vec(o.val, 2 * (size_t)M);
-    rows(o.dmu, 3 * (size_t)M); rows(o.dsigma, (size_t)(3 + D) * M); rows(o.grad, (size_t)(3 + 2 * D) * M);
+    mapped_out(slot->block, D, M, want);
     return true;
 }
 
-extern "C" int sls_gp_predict(sls_gp* g, const double* Xs, int M, double* mu, double* sigma) {
+// The body of sls_gp_predict, sls_gp_predict_grad and sls_acq_eval: `want` names the caller's arrays (any may be NULL).
+static int eval_entry(const char* who, sls_gp* g, const double* Xs, int M, const EvalOut& want) {
     SLS_TRY
-    if (g && Xs && M >= 1 && M <= SLOT_MAX_POINTS) {
-        SmallEvalOut so;
-        so.mu = mu; so.sigma = sigma;
-        if (eval_in_slot(g, Xs, M, so)) return SLS_OK;
-    }
+    const bool acq_ok = want.acq == SLS_ACQ_EXPECTED_IMPROVEMENT || want.acq == SLS_ACQ_GP_UCB;
+    if (g && Xs && M >= 1 && M <= SLOT_MAX_POINTS && acq_ok && eval_in_slot(g, Xs, M, want)) return SLS_OK;
     CtxCall call_(g);
-    SLS_REQUIRE(g && Xs && M >= 0, "sls_gp_predict: bad argument");
+    SLS_REQUIRE(g && Xs && M >= 0, "%s: bad argument", who);
+    SLS_REQUIRE(acq_ok, "unknown acquisition type %d", want.acq);
     if (M == 0) return SLS_OK;
-    const int Mp = round_up(M, 128);
-    g->outm.ensure(Mp); g->outs.ensure(Mp);
-    EvalOut o;
-    o.ldo = Mp; o.mu = g->outm.p; o.sigma = g->outs.p;
-    eval_host_points(g, Xs, M, Mp, o);
-    download_cm2(g, g->outm.p, mu, g->outs.p, sigma, M, Mp, 1);
+    sls_ctx* c = g->ctx;
+    const int Mp = round_up(M, 128), D = g->D;
+    // Value-only evaluation of a small batch on a small problem -- one iteration of DIRECT (host/direct.cpp; the reference's
+    // default global phase, src/acquisition-function.cpp:155-165) -- : the query points are read from, and the values written to,
+    // a page-locked block the device maps: ONE launch + one synchronisation per call instead of upload + launch + download
+    // (~60 -> ~30 us per call; ten calls per SubmitFeedbackData).  SLS_EVAL_ZEROCOPY=0: the copying path.
+    const bool value_only = want.val && eval_block_doubles(want, D, 1) == 1;
+    if (value_only && tune_on(TUNE_EVAL_ZEROCOPY) && wave_path_applies(g, M)) {
+        const size_t need = mapped_bytes(want, D, M);
+        g->zc.ensure(c, need, true, need * 2);
+        eval_small(g, g->zc.dev, M, mapped_in(g->zc, Xs, D, M, want));
+        sync(c);
+        mapped_out(g->zc, D, M, want);
+        return SLS_OK;
+    }
+    g->outv.ensure(eval_block_doubles(want, D, Mp));
+    eval_host_points(g, Xs, M, Mp, eval_block(want, g->outv.p, D, Mp));
+    download_block(g, want, g->outv.p, M, Mp);
     SLS_CATCH
+}
+
+extern "C" int sls_gp_predict(sls_gp* g, const double* Xs, int M, double* mu, double* sigma) {
+    EvalOut want;
+    want.mu = mu; want.sigma = sigma;
+    return eval_entry("sls_gp_predict", g, Xs, M, want);
 }
 
 extern "C" int sls_gp_predict_grad(sls_gp* g, const double* Xs, int M, double* dmu, double* dsigma) {
-    SLS_TRY
-    if (g && Xs && M >= 1 && M <= SLOT_MAX_POINTS) {
-        SmallEvalOut so;
-        so.dmu = dmu; so.dsigma = dsigma;
-        if (eval_in_slot(g, Xs, M, so)) return SLS_OK;
-    }
-    CtxCall call_(g);
-    SLS_REQUIRE(g && Xs && M >= 0, "sls_gp_predict_grad: bad argument");
-    if (M == 0) return SLS_OK;
-    const int Mp = round_up(M, 128), D = g->D;
-    g->outv.ensure((size_t)Mp * D); g->outg.ensure((size_t)Mp * D);
-    EvalOut o;
-    o.ldo = Mp; o.dmu = g->outv.p; o.dsigma = g->outg.p;
-    eval_host_points(g, Xs, M, Mp, o);
-    download_cm2(g, g->outv.p, dmu, g->outg.p, dsigma, M, Mp, D);
-    SLS_CATCH
+    EvalOut want;
+    want.dmu = dmu; want.dsigma = dsigma;
+    return eval_entry("sls_gp_predict_grad", g, Xs, M, want);
 }
 
 extern "C" int sls_acq_eval(sls_gp* g, int acq_type, double ucb_h, const double* Xs, int M, double* val, double* grad) {
-    SLS_TRY
-    if (g && Xs && M >= 1 && M <= SLOT_MAX_POINTS && (acq_type == SLS_ACQ_EXPECTED_IMPROVEMENT || acq_type == SLS_ACQ_GP_UCB)) {
-        SmallEvalOut so;
-        so.val = val; so.grad = grad; so.acq = acq_type; so.ucb_h = ucb_h;
-        if (eval_in_slot(g, Xs, M, so)) return SLS_OK;
-    }
-    CtxCall call_(g);
-    SLS_REQUIRE(g && Xs && M >= 0, "sls_acq_eval: bad argument");
-    SLS_REQUIRE(acq_type == SLS_ACQ_EXPECTED_IMPROVEMENT || acq_type == SLS_ACQ_GP_UCB, "unknown acquisition type %d", acq_type);
-    if (M == 0) return SLS_OK;
-    const int Mp = round_up(M, 128), D = g->D;
-    {
-        // Value-only evaluation of a small batch on a small problem -- one iteration of DIRECT (host/direct.cpp; the reference's
-        // default global phase, src/acquisition-function.cpp:155-165) -- : the query points are read from, and the values written to,
-        // a page-locked block the device maps: ONE launch + one synchronisation per call instead of upload + launch + download
-        // (~60 -> ~30 us per call; ten calls per SubmitFeedbackData).  SLS_EVAL_ZEROCOPY=0: the copying path.
-        if (!grad && val && tune_on(TUNE_WAVE_PATH) && tune_on(TUNE_EVAL_ZEROCOPY) && g->Np <= WAVE_PATH_MAX_NP &&
-            D <= WAVE_PATH_MAX_D && M <= 4096) {
-            sls_ctx* c = g->ctx;
-            const size_t need = ((size_t)D * M + M) * sizeof(double);
-            if (need > g->zc_bytes) {
-                if (g->zc_host) c->host_give(g->zc_host, g->zc_bytes, true);
-                g->zc_host = nullptr;
-                g->zc_bytes = 0;
-                g->zc_host = static_cast<double*>(c->host_take(need * 2, true, &g->zc_bytes));
-                SLS_HIP(hipHostGetDevicePointer((void**)&g->zc_dev, g->zc_host, 0));
-            }
-            std::memcpy(g->zc_host, Xs, sizeof(double) * (size_t)D * M);
-            EvalOut oz;
-            oz.ldo = Mp; oz.val = g->zc_dev + (size_t)D * M; oz.acq = acq_type; oz.ucb_h = ucb_h;
-            if (eval_small(g, g->zc_dev, M, oz)) {
-                sync(c);
-                std::memcpy(val, g->zc_host + (size_t)D * M, sizeof(double) * M);
-                return SLS_OK;
-            }
-        }
-    }
-    g->outm.ensure(Mp);
-    if (grad) g->outg.ensure((size_t)Mp * D);
-    EvalOut o;
-    o.ldo = Mp; o.val = g->outm.p; o.grad = grad ? g->outg.p : nullptr; o.acq = acq_type; o.ucb_h = ucb_h;
-    eval_host_points(g, Xs, M, Mp, o);
-    if (val) download_cm(g, g->outm.p, M, Mp, 1, val);
-    if (grad) download_cm(g, g->outg.p, M, Mp, D, grad);
-    SLS_CATCH
+    EvalOut want;
+    want.val = val; want.grad = grad; want.acq = acq_type; want.ucb_h = ucb_h;
+    return eval_entry("sls_acq_eval", g, Xs, M, want);
 }
 
 // ---- multi-start maximiser -------------------------------------------------------------------------------------
@@ -1169,6 +1126,43 @@ static void eval_acq(sls_gp* g, sls_gp* gs, const double* xr, long ldr, int S, i
                    ucb_h, val, grad);
 }
 
+// The whole multi-start search in one launch, one wavefront per start (the caller has asked wave_path_applies).  Returns the device
+// counter of useful evaluations: those of starts that were still moving (finished starts run idle to keep the barriers uniform),
+// counted by the kernel into the live-count words of the integer scratch.
+static const unsigned long long* maximize_wave(sls_gp* g, int acq_type, double ucb_h, const double* starts_dev, int S, int n_local,
+                                               const sls_lbfgs_opts& o, const LbfgsState& st, int Sp) {
+    sls_ctx* c = g->ctx;
+    WaveArgs w;
+    wave_model_args(g, w);
+    w.S = S; w.m = o.history; w.n_local = n_local; w.acq = acq_type; w.ucb_h = ucb_h;
+    w.c1 = o.c1; w.shrink = o.shrink; w.gtol = o.gtol; w.max_backtracks = o.max_backtracks;
+    w.ftol_rel = o.ftol_rel; w.xtol_rel = o.xtol_rel;
+    w.starts = starts_dev; w.x_out = st.x; w.f_out = st.f; w.ld = Sp;
+    w.ev_mu = w.ev_sigma = w.ev_dmu = w.ev_dsigma = w.ev_val = w.ev_grad = nullptr;
+    unsigned long long* d_useful = g->lb.wave_useful();
+    SLS_HIP(hipMemsetAsync(d_useful, 0, sizeof(unsigned long long), c->stream));
+    w.useful = d_useful;
+    long long* d_trace = nullptr;
+    if (tune_set(TUNE_WAVE_TRACE)) {
+        d_trace = g->lb.wave_trace();
+        SLS_HIP(hipMemsetAsync(d_trace, 0, 9 * sizeof(long long), c->stream));
+        w.trace = d_trace;
+    }
+    {
+        ProfScope ps(c, "acq_wave");
+        launch_maximize_wave(c->stream, w);
+    }
+    if (d_trace) {
+        long long tr[9] = {};
+        SLS_HIP(hipMemcpyAsync(tr, d_trace, sizeof(tr), hipMemcpyDeviceToHost, c->stream));
+        sync(c);
+        fprintf(stderr, "wave trace (us): S %d N %d D %d evals %lld | kvec %.1f  Kinv.k %.1f  sums %.1f  grad+acq %.1f  direction %.1f  "
+                "bookkeeping %.1f  total %.1f  (shader clock %.0f MHz)\n", S, g->N, g->D, tr[6], tr[0] * 0.01, tr[1] * 0.01, tr[2] * 0.01, tr[3] * 0.01, tr[4] * 0.01,
+                tr[5] * 0.01, tr[7] * 0.01, tr[7] > 0 ? (double)tr[8] / (tr[7] * 0.01) : 0.0);
+    }
+    return d_useful;
+}
+
 static void maximize_impl(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, const double* starts_dev, int S, int n_local,
                           const sls_lbfgs_opts* opts_in, long off, double* x_out, double* val_out, long* idx_out,
                           double* x_stars, double* y_stars) {
@@ -1181,52 +1175,12 @@ static void maximize_impl(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, con
     g->lb.ensure(Sp, o.history, D);
     g->stat_issued = 0; g->stat_cap = (long)S * n_local; g->stat_rounds = 0; g->stat_live_end = 0;
     LbfgsState st = g->lb.state(S, D, o);
-    // Small problems: one wavefront per start runs the whole search in a single launch (kernels_wave.hip).  The choice
-    // depends only on the fitted state and the start count, so repeated / sharded calls take the same path.
-    bool used_wave = false;
+    // Small problems: one wavefront per start runs the whole search in a single launch (kernels_wave.hip)
     const unsigned long long* wave_useful = nullptr;   // the one-wavefront-per-start run's count of useful evaluations (device)
-    {
-        const bool allow = tune_on(TUNE_WAVE_PATH);
-        if (allow && !gs && g->Np <= WAVE_PATH_MAX_NP && D <= WAVE_PATH_MAX_D && S <= 4096) {
-            WaveArgs w;
-            w.S = S; w.D = D; w.N = g->N; w.Np = g->Np; w.m = o.history; w.n_local = n_local; w.acq = acq_type;
-            w.matern = g->kernel == SLS_KERNEL_ARD_MATERN52;
-            w.a = g->a; w.mu_best = g->mu_best; w.ucb_h = ucb_h; w.c1 = o.c1; w.shrink = o.shrink; w.gtol = o.gtol;
-            w.max_backtracks = o.max_backtracks;
-            w.ftol_rel = o.ftol_rel; w.xtol_rel = o.xtol_rel;
-            w.XT = g->XT.p; w.inv_ell = g->inv_ell.p; w.Kinv = g->Kinv.p; w.alpha = g->alpha.p; w.starts = starts_dev;
-            w.solve_sigma = g->sigma_mode == 1; w.Linv = g->Linv.p; w.U = g->U.p;
-            w.x_out = st.x; w.f_out = st.f; w.ld = Sp;
-            w.ev_mu = w.ev_sigma = w.ev_dmu = w.ev_dsigma = w.ev_val = w.ev_grad = nullptr;
-            // evaluations of starts that were still moving (finished starts run idle to keep the barriers uniform): counted
-            // by the kernel into the live-count words of the integer scratch
-            unsigned long long* d_useful = g->lb.wave_useful();
-            SLS_HIP(hipMemsetAsync(d_useful, 0, sizeof(unsigned long long), c->stream));
-            w.useful = d_useful;
-            long long* d_trace = nullptr;
-            if (tune_set(TUNE_WAVE_TRACE)) {
-                d_trace = g->lb.wave_trace();
-                SLS_HIP(hipMemsetAsync(d_trace, 0, 9 * sizeof(long long), c->stream));
-                w.trace = d_trace;
-            }
-            {
-                ProfScope ps(c, "acq_wave");
-                launch_maximize_wave(c->stream, w);
-            }
-            if (d_trace) {
-                long long tr[9] = {};
-                SLS_HIP(hipMemcpyAsync(tr, d_trace, sizeof(tr), hipMemcpyDeviceToHost, c->stream));
-                sync(c);
-                fprintf(stderr, "wave trace (us): S %d N %d D %d evals %lld | kvec %.1f  Kinv.k %.1f  sums %.1f  grad+acq %.1f  direction %.1f  "
-                        "bookkeeping %.1f  total %.1f  (shader clock %.0f MHz)\n", S, g->N, D, tr[6], tr[0] * 0.01, tr[1] * 0.01, tr[2] * 0.01, tr[3] * 0.01, tr[4] * 0.01,
-                        tr[5] * 0.01, tr[7] * 0.01, tr[7] > 0 ? (double)tr[8] / (tr[7] * 0.01) : 0.0);
-            }
-            wave_useful = d_useful;   // read back with the best start, behind the one synchronisation of the run
-            g->stat_rounds = n_local;
-            used_wave = true;
-        }
-    }
-    if (!used_wave) {
+    if (!gs && wave_path_applies(g, S)) {
+        wave_useful = maximize_wave(g, acq_type, ucb_h, starts_dev, S, n_local, o, st, Sp);   // read back with the best start
+        g->stat_rounds = n_local;
+    } else {
         // the lock-step rounds over the active set (lbfgs_driver.hpp)
         LockstepStats ls;
         lockstep_rounds(c, st, g->lb, starts_dev, S, n_local,
@@ -1235,11 +1189,11 @@ static void maximize_impl(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, con
                         },
                         &ls);
         g->stat_issued = ls.issued; g->stat_rounds = ls.rounds; g->stat_live_end = ls.live_end;
-    }   // !used_wave
+    }
     // best start and its coordinates: one launch into the handle's mapped block, one synchronisation, no copies
-    launch_argmax_neg_gather(c->stream, st.f, S, st.x, Sp, D, g->sum_dev + 8, wave_useful);
+    launch_argmax_neg_gather(c->stream, st.f, S, st.x, Sp, D, g->sum.dev + 8, wave_useful);
     sync(c);
-    const double* best = g->sum_host + 8;
+    const double* best = g->sum.host + 8;
     const long bi = (long)best[1];
     if (wave_useful) g->stat_issued = (long)best[2];
     if (val_out) *val_out = best[0];
@@ -1307,11 +1261,14 @@ extern "C" int sls_acq_eval_pair(sls_gp* g, sls_gp* gs, int acq_type, double ucb
     if (M == 0) return SLS_OK;
     const int Mp = round_up(M, 128), D = g->D;
     upload_candidates(g, Xs, M, g->raw, Mp);
-    g->outm.ensure(Mp);
-    if (grad) g->outg.ensure((size_t)Mp * D);
-    eval_acq(g, gs, g->raw.p, Mp, M, acq_type, ucb_h, g->outm.p, grad ? g->outg.p : nullptr, Mp);
-    if (val) download_cm(g, g->outm.p, M, Mp, 1, val);
-    if (grad) download_cm(g, g->outg.p, M, Mp, D, grad);
+    std::vector<double> unused;   // launch_combine always writes the values
+    if (!val) unused.resize(M);
+    EvalOut want;
+    want.val = val ? val : unused.data(); want.grad = grad;
+    g->outv.ensure(eval_block_doubles(want, D, Mp));
+    const EvalOut o = eval_block(want, g->outv.p, D, Mp);
+    eval_acq(g, gs, g->raw.p, Mp, M, acq_type, ucb_h, o.val, o.grad, Mp);
+    download_block(g, want, g->outv.p, M, Mp);
     SLS_CATCH
 }
 
@@ -1516,7 +1473,7 @@ extern "C" int sls_gp_append_point(sls_gp* g, const double* x, double y_new) {
     launch_scale_rows(c->stream, g->XT.p, g->alpha.p, g->XaT.p, Np, Np, g->Dcols);
     if (g->sigma_mode == 1) launch_transpose_full(c->stream, g->Linv.p, g->U.p, Np);   // the rank-1 growth does not maintain U
     SLS_HIP(hipMemsetAsync(c->d_info, 0, 64, c->stream));
-    launch_fit_summary(c->stream, g->y.p, g->alpha.p, g->b, N + 1, g->mu_data.p, g->L.p, Np, c->d_info, g->scal.p, g->d_idx, g->sum_dev);
+    launch_fit_summary(c->stream, g->y.p, g->alpha.p, g->b, N + 1, g->mu_data.p, g->L.p, Np, c->d_info, g->scal.p, g->d_idx, g->sum.dev);
     gp_fetch_summary(g);
     SLS_REQUIRE(std::isfinite(g->logdet), "sls_gp_append_point: the extended K_y is not positive definite");
     SLS_CATCH

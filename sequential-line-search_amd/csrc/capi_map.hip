@@ -23,9 +23,7 @@ struct sls_nll {
     double ftol_rel = 0.0, xtol_rel = 0.0;   // sls_nll_set_tolerances
     // results of the one-workgroup evaluation (kernels_small.hip): page-locked host memory the kernel writes DIRECTLY (mapped),
     // read after the stream synchronisation -- no device-to-host copy call per evaluation
-    double* small_host = nullptr;      // host address
-    double* small_host_dev = nullptr;  // the same memory as the device sees it
-    size_t small_host_bytes = 0, mo_out_bytes = 0;
+    HostBuf small_host;
     // device-resident MAP fit (map_opt_kernel): index image of the preference tuples (uploaded when it changes), the vectors of
     // a call, the optimiser state, the result block in mapped host memory, a page-locked staging block
     DBuf mo_idx, mo_vec, mo_state, mo_btl;
@@ -34,27 +32,17 @@ struct sls_nll {
     DBuf bt_L, bt_T, bt_XT, bt_nx, bt_il, bt_sync, bt_out;
     int bt_P = 0;
     std::vector<int> mo_idx_host;      // what mo_idx holds
-    double* mo_out = nullptr;          // mapped: host address
-    double* mo_out_dev = nullptr;
-    char* mo_stage = nullptr;          // page-locked
-    size_t mo_stage_bytes = 0;
+    HostBuf mo_out;                    // mapped
+    HostBuf mo_stage;                  // page-locked
     // Page-locked, device-MAPPED block of the tiled evaluation in flight: [Dcols] inverse length scales, [Np] targets, [8 + Dcols]
     // results.  The kernels read the length scales from it and write the results into it directly, and the targets are uploaded
     // only when they change (a MAP fit evaluates the same y hundreds of times): in steady state an evaluation makes no copy call
     // at all.  (With pageable buffers every hipMemcpyAsync was a blocking staged copy: two up, four or five back per evaluation.)
-    double* il_stage = nullptr;        // host address
-    double* il_stage_dev = nullptr;    // the same memory as the device sees it
-    size_t il_stage_bytes = 0;
+    HostBuf il_stage;
     bool y_on_device = false;          // y.p holds y_stage()'s contents
-    double* y_stage() const { return il_stage + Dcols; }
-    double* res_stage() const { return il_stage + Dcols + Np; }
-    double* res_dev() const { return il_stage_dev + Dcols + Np; }
-    ~sls_nll() {   // page-locked blocks go back to the context (sls_nll_destroy holds its lock)
-        ctx->host_give(il_stage, il_stage_bytes, true);
-        ctx->host_give(small_host, small_host_bytes, true);
-        ctx->host_give(mo_out, mo_out_bytes, true);
-        ctx->host_give(mo_stage, mo_stage_bytes, false);
-    }
+    double* y_stage() const { return il_stage.host + Dcols; }
+    double* res_stage() const { return il_stage.host + Dcols + Np; }
+    double* res_dev() const { return il_stage.dev + Dcols + Np; }
 };
 
 extern "C" int sls_nll_create(sls_ctx* ctx, const double* X, int D, int N, int kernel, sls_nll** out) {
@@ -109,10 +97,7 @@ extern "C" int sls_nll_destroy(sls_nll* h) {
 // own results and hands them to nll_factor_accept: one host synchronisation per evaluation instead of two (the one in the
 // middle left the GPU idle for 40-100 us of a 3.1 ms evaluation at N = 4096).  false: (theta, b) is the cached factor.
 static void nll_stage_ensure(sls_nll* h) {
-    if (h->il_stage) return;
-    h->il_stage = static_cast<double*>(h->ctx->host_take((size_t)(2 * h->Dcols + h->Np + 8) * 8, true, &h->il_stage_bytes));
-    SLS_HIP(hipHostGetDevicePointer((void**)&h->il_stage_dev, h->il_stage, 0));
-    h->y_on_device = false;
+    if (h->il_stage.ensure(h->ctx, (size_t)(2 * h->Dcols + h->Np + 8) * 8, true)) h->y_on_device = false;
 }
 static bool nll_factor_enqueue(sls_nll* h, const double* theta, double b) {
     sls_ctx* c = h->ctx;
@@ -125,7 +110,7 @@ static bool nll_factor_enqueue(sls_nll* h, const double* theta, double b) {
     // Staged in a page-locked block of the handle: the upload is enqueued like everything else (a local buffer needed a
     // synchronisation here, in the middle of the evaluation).  The previous evaluation on this handle ended with one, so the block is free.
     nll_stage_ensure(h);
-    double* il = h->il_stage;
+    double* il = h->il_stage.host;
     for (int d = 0; d < h->Dcols; ++d) il[d] = 0.0;
     for (int d = 0; d < D; ++d) {
         SLS_REQUIRE(theta[1 + d] > 0.0, "length scale %d must be positive", d);
@@ -133,7 +118,7 @@ static bool nll_factor_enqueue(sls_nll* h, const double* theta, double b) {
     }
     // no upload: the kernels read the mapped block (1 KB; the previous evaluation on this handle ended with a synchronisation)
     KernelSpec ks{h->kernel, theta[0]};
-    launch_prep_points(c->stream, h->X.p, D, N, h->il_stage_dev, h->XT.p, Np, Np, h->Dcols, h->nx.p);
+    launch_prep_points(c->stream, h->X.p, D, N, h->il_stage.dev, h->XT.p, Np, Np, h->Dcols, h->nx.p);
     launch_gram_sym(c->stream, h->XT.p, Np, h->Dp, h->nx.p, Np, N, ks, b, h->L.p, true);
     SLS_HIP(hipMemsetAsync(c->d_info, 0, 64, c->stream));
     c->potrf_tick_rearm();
@@ -186,12 +171,9 @@ static void nll_small_eval(sls_nll* h, const double* y, const double* theta, dou
     args.x_lds = tune_on(TUNE_SMALL_XLDS) ? 1 : 0;
     args.info = c->d_info;
     const bool zero_copy = tune_on(TUNE_SMALL_ZEROCOPY);
-    if (zero_copy && !h->small_host) {
-        h->small_host = static_cast<double*>(c->host_take(NLL_SMALL_OUT_DOUBLES * sizeof(double), true, &h->small_host_bytes));
-        SLS_HIP(hipHostGetDevicePointer((void**)&h->small_host_dev, h->small_host, 0));
-    }
+    if (zero_copy) h->small_host.ensure(c, NLL_SMALL_OUT_DOUBLES * sizeof(double), true);
     h->small_out.ensure(NLL_SMALL_OUT_DOUBLES);
-    args.out = zero_copy ? h->small_host_dev : h->small_out.p;
+    args.out = zero_copy ? h->small_host.dev : h->small_out.p;
     args.in_dev = nullptr;
     args.batch = 1; args.in_stride = 0; args.out_stride = 0;
     std::vector<double> in;   // staging for the D > 32 upload: must outlive the stream synchronisation below
@@ -214,7 +196,7 @@ static void nll_small_eval(sls_nll* h, const double* y, const double* theta, dou
     const int nout = alpha ? NLL_SMALL_OUT_ALPHA + N : NLL_SMALL_OUT_ALPHA;
     if (zero_copy) {
         SLS_HIP(hipStreamSynchronize(c->stream));
-        out = h->small_host;
+        out = h->small_host.host;
     } else {
         SLS_HIP(hipMemcpyAsync(out_stack, h->small_out.p, nout * 8, hipMemcpyDeviceToHost, c->stream));
         SLS_HIP(hipStreamSynchronize(c->stream));
@@ -280,7 +262,7 @@ static void nll_eval_impl(sls_nll* h, const double* y, const double* theta, doub
             launch_gemm_splitk_nt(c->stream, h->G.p, Np, h->XT.p, Np, h->Y.p, Np, (long)Np * h->Dcols, nt, h->Dcols / 128, Np, yc);
             // the partial products of Y and the partial row sums (G 1) left by nll_weight, both added in chunk order
             launch_sum_chunks(c->stream, h->Y.p, (long)Np * h->Dcols, yc, (long)Np * h->Dcols, h->gemv_part.p, Np, nt, h->svec.p);
-            launch_lengthscale_grad(c->stream, h->XT.p, h->Y.p, h->svec.p, h->il_stage_dev, Np, N, D, h->res_dev() + 8, h->parts.p, nparts,
+            launch_lengthscale_grad(c->stream, h->XT.p, h->Y.p, h->svec.p, h->il_stage.dev, Np, N, D, h->res_dev() + 8, h->parts.p, nparts,
                                     h->alpha.p, h->y.p, h->Kinv.p, Np, h->res_dev(), Lf, inf);
         } else {
             launch_nll_scalars(c->stream, h->parts.p, nparts, h->alpha.p, h->y.p, h->Kinv.p, Np, N, h->res_dev(), Lf, inf);
@@ -532,16 +514,8 @@ static void map_opt_run(sls_nll* h, const MapOptProblem& pb, const double* z0, c
     }
     const size_t vec_doubles = (size_t)3 * n + N;
     const size_t need = idx.size() * sizeof(int) + 8 + vec_doubles * 8;
-    if (need > h->mo_stage_bytes) {
-        c->host_give(h->mo_stage, h->mo_stage_bytes, false);
-        h->mo_stage = nullptr;
-        h->mo_stage_bytes = 0;
-        h->mo_stage = static_cast<char*>(c->host_take(need * 2, false, &h->mo_stage_bytes));
-    }
-    if (!h->mo_out) {
-        h->mo_out = static_cast<double*>(c->host_take(MAP_OPT_OUT_DOUBLES * sizeof(double), true, &h->mo_out_bytes));
-        SLS_HIP(hipHostGetDevicePointer((void**)&h->mo_out_dev, h->mo_out, 0));
-    }
+    h->mo_stage.ensure(c, need, false, need * 2);
+    h->mo_out.ensure(c, MAP_OPT_OUT_DOUBLES * sizeof(double), true);
     {
         const double* before = h->mo_idx.p;
         h->mo_idx.ensure((idx.size() + 1) / 2 + 1);
@@ -551,7 +525,7 @@ static void map_opt_run(sls_nll* h, const MapOptProblem& pb, const double* z0, c
     h->mo_state.ensure(MAP_OPT_STATE_DOUBLES + MAP_OPT_TRACE_SLOTS);   // + the optional section trace
     h->mo_btl.ensure(std::max(F, 1));
     // the previous call's copies have completed (every call ends with a stream synchronisation): the staging block is free
-    double* vst = reinterpret_cast<double*>(h->mo_stage);
+    double* vst = h->mo_stage.host;
     std::memcpy(vst, z0, sizeof(double) * n);
     std::memcpy(vst + n, lower, sizeof(double) * n);
     std::memcpy(vst + 2 * n, upper, sizeof(double) * n);
@@ -559,7 +533,7 @@ static void map_opt_run(sls_nll* h, const MapOptProblem& pb, const double* z0, c
     else std::memset(vst + 3 * n, 0, sizeof(double) * N);
     SLS_HIP(hipMemcpyAsync(h->mo_vec.p, vst, vec_doubles * 8, hipMemcpyHostToDevice, c->stream));
     if (idx != h->mo_idx_host) {
-        int* ist = reinterpret_cast<int*>(h->mo_stage + vec_doubles * 8);
+        int* ist = reinterpret_cast<int*>(vst + vec_doubles);
         std::memcpy(ist, idx.data(), idx.size() * sizeof(int));
         SLS_HIP(hipMemcpyAsync(h->mo_idx.p, ist, idx.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
         h->mo_idx_host = idx;
@@ -582,7 +556,7 @@ static void map_opt_run(sls_nll* h, const MapOptProblem& pb, const double* z0, c
     a.xtol_rel = h->xtol_rel;
     a.eval_only = eval_only ? 1 : 0;
     a.state = h->mo_state.p;
-    a.out = h->mo_out_dev;
+    a.out = h->mo_out.dev;
     a.info = c->d_info;
     a.trace = nullptr;
     if (tune_set(TUNE_MAP_TRACE) && !eval_only) {
@@ -592,7 +566,7 @@ static void map_opt_run(sls_nll* h, const MapOptProblem& pb, const double* z0, c
     const bool stepwise = !eval_only && evals_per_launch > 0 && evals_per_launch < max_evals;
     a.budget = stepwise ? evals_per_launch : a.max_evals;
     a.fresh = 1;
-    const double* out = h->mo_out;
+    const double* out = h->mo_out.host;
     for (;;) {
         launch_map_opt(c->stream, h->kernel, a);
         SLS_HIP(hipStreamSynchronize(c->stream));

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <condition_variable>
@@ -105,6 +106,28 @@ struct DBuf {
     }
 };
 
+// Owning page-locked host block from a context's pool (sls_ctx::host_take / host_give), device-mapped on request.  The block
+// remembers the context it was taken from, so release() and the destructor need no argument.  The pool is not thread safe and this
+// type takes NO lock: every ensure / release / destruction runs with that context's lock held (CtxCall; destroy_handle for the
+// members of a handle) or where nobody else can reach the context any more (ctx_destroy_now, before host_free is walked).
+struct HostBuf {
+    double* host = nullptr;
+    double* dev = nullptr;   // mapped blocks: the same memory as the device sees it
+    size_t bytes = 0;
+    HostBuf() = default;
+    HostBuf(const HostBuf&) = delete;
+    HostBuf& operator=(const HostBuf&) = delete;
+    ~HostBuf() { release(); }
+    void release();
+    // At least `need` bytes: a block that is large enough stays; otherwise the old one goes back and `take` bytes (default: need)
+    // are taken.  The object is empty while it takes, so a throwing host_take leaves no dangling pointer.  true: the block is new.
+    bool ensure(sls_ctx* c, size_t need, bool mapped_, size_t take = 0);
+
+   private:
+    sls_ctx* ctx = nullptr;
+    bool mapped = false;
+};
+
 struct ProfEntry {
     double ms = 0;
     long launches = 0;
@@ -145,9 +168,7 @@ struct sls_ctx {
     // kept for the life of the context
     struct EvalSlot {
         hipStream_t stream = nullptr;
-        double* host = nullptr;
-        double* dev = nullptr;
-        size_t bytes = 0;
+        slsk::HostBuf block;   // query points in, results out
         bool busy = false;
     };
     std::mutex slot_mtx;
@@ -174,6 +195,20 @@ struct sls_ctx {
 };
 
 namespace slsk {
+inline void HostBuf::release() {
+    if (host) ctx->host_give(host, bytes, mapped);
+    host = dev = nullptr;
+    bytes = 0;
+}
+inline bool HostBuf::ensure(sls_ctx* c, size_t need, bool mapped_, size_t take) {
+    if (host && need <= bytes) return false;
+    release();
+    ctx = c;
+    mapped = mapped_;
+    host = static_cast<double*>(c->host_take(std::max(need, take), mapped, &bytes));
+    if (mapped) SLS_HIP(hipHostGetDevicePointer((void**)&dev, host, 0));
+    return true;
+}
 void ctx_retain(sls_ctx* c);     // a handle was created (caller holds c->mtx)
 void ctx_release(sls_ctx* c);    // a handle is gone (caller does NOT hold c->mtx: this may free the context)
 // The context's lock for the length of an entry point.  A NULL context / handle takes nothing: the entry point's own SLS_REQUIRE
