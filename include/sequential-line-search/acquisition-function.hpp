@@ -107,6 +107,31 @@ namespace sequential_line_search
                                                                                 const unsigned         num_local_search_iters,
                                                                                 const unsigned long long seed = 0,
                                                                                 const int num_frequencies = 2048);
+
+        /// Max-value entropy search (not in the reference; Wang & Jegelka 2017, include/sls_hip.h sls_mes_*).
+        /// A Monte-Carlo sample of the maximum VALUE of the latent function: the maxima of num_samples pathwise posterior draws
+        /// (stream `seed`, num_frequencies random features), each maximised from num_global_search_iters uniform starts of the
+        /// generator FindNextPointsByThompsonSampling uses, clamped from below at the mean at the best data point (the maximum of a
+        /// function is at least its value there).  num_samples <= 4096.
+        Eigen::VectorXd SampleMaxValues(const Regressor& regressor, const unsigned num_samples = 64,
+                                        const unsigned num_global_search_iters = 100, const unsigned num_local_search_iters = 50,
+                                        const unsigned long long seed = 0, const int num_frequencies = 2048);
+        /// alpha(x) = mean_k g((y*_k - mu(x)) / sigma(x)) for the columns of Xs on the sample max_values of y* (and its gradient,
+        /// D x M, if grad != nullptr): one device pass.
+        Eigen::VectorXd CalcMaxValueEntropies(const Regressor& regressor, const Eigen::MatrixXd& Xs, const Eigen::VectorXd& max_values,
+                                              Eigen::MatrixXd* grad = nullptr);
+        /// Maximiser of alpha over [0,1]^D: SampleMaxValues, then one L-BFGS of num_local_search_iters evaluations (the tolerances
+        /// of GetLocalSearchTolerances) from each of num_global_search_iters uniform starts of a generator seeded with `seed`, all
+        /// in lock step on the device.  The same seed gives the same point.  value (may be nullptr) receives alpha there.
+        Eigen::VectorXd FindNextPointByMaxValueEntropySearch(const Regressor& regressor, const unsigned num_max_value_samples = 64,
+                                                             const unsigned num_global_search_iters = 100,
+                                                             const unsigned num_local_search_iters  = 50,
+                                                             const unsigned long long seed = 0, const int num_frequencies = 2048,
+                                                             double* value = nullptr);
+        /// The same from an explicit sample of y* and an explicit start set (D x S).
+        Eigen::VectorXd FindNextPointByMaxValueEntropySearchFromStarts(const Regressor& regressor, const Eigen::VectorXd& max_values,
+                                                                       const Eigen::MatrixXd& starts,
+                                                                       const unsigned num_local_search_iters, double* value = nullptr);
     } // namespace acquisition_func
 } // namespace sequential_line_search
 

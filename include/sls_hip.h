@@ -258,6 +258,37 @@ int sls_path_eval(sls_path* p, const double* Xs, int M, const int* draw_of_point
 int sls_path_maximize(sls_path* p, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts, double* x_out,
                       double* val_out, long* idx_out);
 
+/* ---- max-value entropy search (not in the reference) -------------------------------------------------------------------
+ * MES (Wang & Jegelka, ICML 2017): the expected reduction of the entropy of the maximum VALUE y* of the latent function, estimated
+ * on K samples y*_1..y*_K of that maximum -- the per-draw maxima val_out of sls_path_maximize are such a sample.  For a point x
+ * with mu = PredictMu(x) and sigma = PredictSigma(x) in the handle's current sigma mode (the quantities of sls_gp_predict, formed as
+ * sls_acq_eval forms them on the tiled evaluation; sls_gp_predict's other routes agree with them to cond(K_y) eps, not to the bit):
+ *   gamma_k       = (y*_k - mu) / sigma
+ *   g(t)          = 1/2 t r(t) - log Phi(t),   r = phi / Phi        g'(t) = -1/2 r(t) (1 + t (t + r(t)))
+ *   alpha(x)      = (1/K) sum_k g(gamma_k)                          (every sum over k in increasing k)
+ *   grad alpha(x) = -(1/sigma) [ A1 grad mu + A2 grad sigma ],  A1 = (1/K) sum_k g'(gamma_k),  A2 = (1/K) sum_k gamma_k g'(gamma_k)
+ * There is no mu - mu_best term that can underflow.  Guard (the one of expected improvement): sigma < 1e-10, or a NaN in the value or
+ * in any gradient component, gives the value 0 and the zero gradient.
+ * Phi never underflows: for t < 0, with e = erfcx(-t / sqrt 2), r = sqrt(2/pi) / e and log Phi = log(e / 2) - t^2 / 2; for t >= 0
+ * Phi = erfc(-t / sqrt 2) / 2 and log Phi = log1p(-erfc(t / sqrt 2) / 2).  c = 1 + t (t + r) cancels to ~2 / t^2 for large negative t
+ * (the direct form loses ~t^4 eps / 2 relative): for t < -30, c = u (2 + u (-10 + u (74 + u (-706 + 8162 u)))) with u = 1 / t^2.
+ * g is accurate to a few eps max(1, t^2) (for t << 0 it is the O(log |t|) difference of two O(t^2) terms), g' to ~1e-10 relative.
+ * One lane per point and fixed summation orders: a point's bits depend on neither its column, the other points of the call nor the
+ * candidate chunk.  Both GP calls always take the tiled evaluation (never the single-launch path of small problems or the
+ * evaluation slots) and hold the context's lock for the whole call, as the handle's other large calls do; y_star is uploaded once
+ * per call. */
+#define SLS_MES_MAX_SAMPLES 4096
+/* g[i] = g(t[i]), dg[i] = g'(t[i]); either out pointer may be NULL; n >= 0.  The scalar terms on their own (a test hook, as
+ * sls_random_normal is for the generator). */
+int sls_mes_terms(sls_ctx* ctx, const double* t, long n, double* g, double* dg);
+/* alpha at the M points Xs (D x M): val (M), grad (D x M, may be NULL); 1 <= K <= SLS_MES_MAX_SAMPLES and every y_star finite: else
+ * SLS_ERR_INVALID; M = 0 is a no-op. */
+int sls_mes_eval(sls_gp* gp, const double* y_star, int K, const double* Xs, int M, double* val, double* grad);
+/* sls_acq_maximize with alpha as the objective: same outputs, same semantics of idx_out / x_stars / y_stars / sls_acq_last_stats. */
+int sls_mes_maximize(sls_gp* gp, const double* y_star, int K, const double* starts, int S, int n_local,
+                     const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
+                     double* x_stars, double* y_stars);
+
 /* ---- multi-GPU maximisation ------------------------------------------------------------------------------
  * FindGlobalSolution's multi-start loop (src/acquisition-function.cpp:121-153) shards over its starts: the iterations share
  * only the const regressor (:125-141).  Every GPU holds a replica of the fitted state, runs a contiguous slice of the starts
@@ -379,7 +410,8 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
  * "lbfgs"; the posterior calls: "post_v" (V = K* L^-T), "post_cov" (the covariance tiles), "post_potrf" (chol(cov + j I), one launch
  * per jitter tried), "post_sample" (normals + the sample product); the path draws: "path_setup" (normals, frequencies, weights,
  * f_prior(X)), "path_solve" (v = K_y^-1 r), "path_prior" (the random-feature prior of an evaluation), "path_data" (the data term
- * on cross_gram's K*; cross_gram and grad_gemm count under their own names); "potrf_fallbacks": launches = how often a single-launch
+ * on cross_gram's K*; cross_gram and grad_gemm count under their own names); "mes" (the MES combiner, one launch per evaluation of
+ * sls_mes_eval / round of sls_mes_maximize); "potrf_fallbacks": launches = how often a single-launch
  * factorisation gave up and was recomputed. */
 int sls_prof_enable(sls_ctx* ctx, int on);
 int sls_prof_reset(sls_ctx* ctx);

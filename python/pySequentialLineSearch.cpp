@@ -3,7 +3,8 @@
 // python-examples recipes run unchanged on the MI355X path.  Vectors / matrices cross the boundary as numpy float64
 // arrays (the reference relies on pybind11/eigen.h; Eigen is not available here, hence the small casters below).
 // Additions: set_random_seed(), set/get_global_search_strategy(), set/get_devices(), and batched predict_mean_stdev /
-// acquisition_values on (D, M) arrays.
+// acquisition_values on (D, M) arrays; GaussianProcessRegressor (fixed hyper-parameters) with sample_max_values(),
+// calc_max_value_entropies() and find_next_point_by_max_value_entropy_search().
 #include <pybind11/functional.h>
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -11,6 +12,7 @@
 
 #include <sequential-line-search/acquisition-function.hpp>
 #include <sequential-line-search/device.hpp>
+#include <sequential-line-search/gaussian-process-regressor.hpp>
 #include <sequential-line-search/preference-regressor.hpp>
 #include <sequential-line-search/preferential-bayesian-optimizer.hpp>
 #include <sequential-line-search/sequential-line-search.hpp>
@@ -105,6 +107,30 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
     py::enum_<KernelType>(m, "KernelType", py::arithmetic())
         .value("ArdSquaredExponentialKernel", KernelType::ArdSquaredExponentialKernel)
         .value("ArdMatern52Kernel", KernelType::ArdMatern52Kernel);
+
+    // max-value entropy search on a regressor with fixed hyper-parameters (acquisition-function.hpp)
+    py::class_<Regressor>(m, "Regressor");
+    py::class_<GaussianProcessRegressor, Regressor>(m, "GaussianProcessRegressor")
+        .def(py::init<const MatrixXd&, const VectorXd&, const VectorXd&, double, const KernelType, bool>(), "X"_a, "y"_a,
+             "kernel_hyperparams"_a, "noise_hyperparam"_a, "kernel_type"_a = KernelType::ArdMatern52Kernel,
+             "materialize_matrices"_a = false);
+    m.def("sample_max_values", &acquisition_func::SampleMaxValues, "regressor"_a, "num_samples"_a = 64,
+          "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50, "seed"_a = 0ULL, "num_frequencies"_a = 2048);
+    m.def("calc_max_value_entropies",
+          [](const Regressor& r, const MatrixXd& Xs, const VectorXd& max_values) {
+              return acquisition_func::CalcMaxValueEntropies(r, Xs, max_values);
+          },
+          "regressor"_a, "points"_a, "max_values"_a);
+    m.def("find_next_point_by_max_value_entropy_search",
+          [](const Regressor& r, unsigned num_max_value_samples, unsigned num_global_search_iters, unsigned num_local_search_iters,
+             unsigned long long seed, int num_frequencies) {
+              double         value = 0.0;
+              const VectorXd x     = acquisition_func::FindNextPointByMaxValueEntropySearch(
+                  r, num_max_value_samples, num_global_search_iters, num_local_search_iters, seed, num_frequencies, &value);
+              return std::make_pair(x, value);
+          },
+          "regressor"_a, "num_max_value_samples"_a = 64, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50,
+          "seed"_a = 0ULL, "num_frequencies"_a = 2048);
 
     using SliderEndsGenerator = std::function<std::pair<VectorXd, VectorXd>(const int)>;
     m.def("generate_random_slider_ends", &GenerateRandomSliderEnds, "num_dims"_a);

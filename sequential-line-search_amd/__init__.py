@@ -62,6 +62,7 @@ EXPORTS = [
     "sls_comm_destroy", "sls_comm_allgather_best", "sls_device_trim_cache", "sls_tuning_reload", "sls_gp_generation",
     "sls_gp_predict_cov", "sls_gp_sample_posterior", "sls_random_normal",
     "sls_path_create", "sls_path_destroy", "sls_path_eval", "sls_path_maximize",
+    "sls_mes_terms", "sls_mes_eval", "sls_mes_maximize",
 ]
 
 
@@ -139,6 +140,13 @@ class Context:
         _ck(lib().sls_random_normal(self.h, C.c_ulonglong(int(seed)), C.c_long(int(offset)), C.c_long(int(n)),
                                     _p(out) if n > 0 else None))
         return out
+
+    def mes_terms(self, t):
+        """(g(t), g'(t)) of max-value entropy search for an array of t (sls_mes_terms)."""
+        t = np.ascontiguousarray(np.asarray(t, dtype=np.float64).ravel())
+        g, dg = np.empty(t.size), np.empty(t.size)
+        _ck(lib().sls_mes_terms(self.h, _p(t), C.c_long(t.size), _p(g), _p(dg)))
+        return g, dg
 
     # ---- free functions (src/regressor.cpp) ----
     def gram(self, X, theta, b, kernel):
@@ -297,6 +305,27 @@ class GP:
                                        C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val),
                                        C.byref(idx)))
         return dict(index=idx.value, x=x, value=val.value)
+
+    def mes_eval(self, y_star, Xs, want_grad=True):
+        """Max-value entropy search at the columns of Xs on the samples y_star of the maximum value (sls_mes_eval)."""
+        y_star, Xs = _f(y_star).ravel(), _f(Xs)
+        M = Xs.shape[1]
+        val = np.empty(M)
+        grad = np.empty((self.D, M), order="F") if want_grad else None
+        _ck(lib().sls_mes_eval(self.h, _p(y_star), y_star.size, _p(Xs), M, _p(val), _p(grad) if want_grad else None))
+        return (val, grad) if want_grad else val
+
+    def mes_maximize(self, y_star, starts, n_local, offset=0, want_all=True, opts=None):
+        """acq_maximize with max-value entropy search on the samples y_star as the objective (sls_mes_maximize)."""
+        y_star, starts = _f(y_star).ravel(), _f(starts)
+        S = starts.shape[1]
+        x, val, idx = np.empty(self.D), C.c_double(), C.c_long()
+        xs = np.empty((self.D, S), order="F") if want_all else None
+        ys = np.empty(S) if want_all else None
+        _ck(lib().sls_mes_maximize(self.h, _p(y_star), y_star.size, _p(starts), S, int(n_local),
+                                   C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val),
+                                   C.byref(idx), _p(xs) if want_all else None, _p(ys) if want_all else None))
+        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
 
     def last_stats(self):
         """Evaluation counts of the last acq_maximize* call (sls_acq_last_stats)."""
@@ -580,6 +609,11 @@ class Comm:
         xo, vo, io = np.empty_like(x), C.c_double(), C.c_long()
         _ck(lib().sls_comm_allgather_best(self.h, C.c_double(value), C.c_long(index), _p(x), len(x), C.byref(vo), C.byref(io), _p(xo)))
         return vo.value, io.value, xo
+
+
+def mes_terms(ctx, t):
+    """(g(t), g'(t)) of max-value entropy search, evaluated on the device of `ctx` (sls_mes_terms)."""
+    return ctx.mes_terms(t)
 
 
 def merge_rank_results(results):

@@ -1106,8 +1106,27 @@ sls_lbfgs_opts slsk::read_lbfgs_opts(const sls_lbfgs_opts* in) {
 
 // value (+ gradient) of the acquisition at candidate-major points xr; gs != nullptr: sigma / dsigma come from gs
 // (objective_for_multiple_points, src/acquisition-function.cpp:63-110)
+// mes != nullptr: max-value entropy search instead (acq_type, ucb_h and gs are not used): mu, sigma and their gradients of g in the
+// handle's pair blocks, then the MES combiner on the y* samples
+struct MesSamples {
+    const double* y_star;   // device, K doubles
+    int K;
+};
 static void eval_acq(sls_gp* g, sls_gp* gs, const double* xr, long ldr, int S, int acq_type, double ucb_h, double* val,
-                     double* grad, long ldo) {
+                     double* grad, long ldo, const MesSamples* mes = nullptr) {
+    if (mes) {
+        const size_t D = g->D;
+        g->pair_mu.ensure(ldo); g->pair_sg.ensure(ldo);
+        if (grad) { g->pair_dmu.ensure(ldo * D); g->pair_dsg.ensure(ldo * D); }
+        EvalOut a;
+        a.ldo = ldo; a.mu = g->pair_mu.p; a.sigma = g->pair_sg.p;
+        a.dmu = grad ? g->pair_dmu.p : nullptr; a.dsigma = grad ? g->pair_dsg.p : nullptr;
+        eval_candidates(g, xr, ldr, S, a);
+        ProfScope ps(g->ctx, "mes");
+        launch_mes_combine(g->ctx->stream, S, (int)D, ldo, g->pair_mu.p, g->pair_sg.p, g->pair_dmu.p, g->pair_dsg.p, mes->y_star,
+                           mes->K, val, grad);
+        return;
+    }
     if (!gs) {
         EvalOut eo;
         eo.ldo = ldo; eo.val = val; eo.grad = grad; eo.acq = acq_type; eo.ucb_h = ucb_h;
@@ -1165,10 +1184,10 @@ static const unsigned long long* maximize_wave(sls_gp* g, int acq_type, double u
 
 static void maximize_impl(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, const double* starts_dev, int S, int n_local,
                           const sls_lbfgs_opts* opts_in, long off, double* x_out, double* val_out, long* idx_out,
-                          double* x_stars, double* y_stars) {
+                          double* x_stars, double* y_stars, const MesSamples* mes = nullptr) {
     sls_ctx* c = g->ctx;
     SLS_REQUIRE(S >= 1 && n_local >= 1, "sls_acq_maximize: need S >= 1 and n_local >= 1");
-    SLS_REQUIRE(acq_type == SLS_ACQ_EXPECTED_IMPROVEMENT || acq_type == SLS_ACQ_GP_UCB, "unknown acquisition type %d", acq_type);
+    SLS_REQUIRE(mes || acq_type == SLS_ACQ_EXPECTED_IMPROVEMENT || acq_type == SLS_ACQ_GP_UCB, "unknown acquisition type %d", acq_type);
     const sls_lbfgs_opts o = read_lbfgs_opts(opts_in);
     SLS_REQUIRE(o.history >= 1 && o.history <= 8, "L-BFGS history must be in 1..8");
     const int Sp = round_up(S, 128), D = g->D;
@@ -1177,7 +1196,7 @@ static void maximize_impl(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, con
     LbfgsState st = g->lb.state(S, D, o);
     // Small problems: one wavefront per start runs the whole search in a single launch (kernels_wave.hip)
     const unsigned long long* wave_useful = nullptr;   // the one-wavefront-per-start run's count of useful evaluations (device)
-    if (!gs && wave_path_applies(g, S)) {
+    if (!gs && !mes && wave_path_applies(g, S)) {   // (the wave kernel has no MES objective: always the general path)
         wave_useful = maximize_wave(g, acq_type, ucb_h, starts_dev, S, n_local, o, st, Sp);   // read back with the best start
         g->stat_rounds = n_local;
     } else {
@@ -1185,7 +1204,7 @@ static void maximize_impl(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, con
         LockstepStats ls;
         lockstep_rounds(c, st, g->lb, starts_dev, S, n_local,
                         [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
-                            eval_acq(g, gs, trial, ld, nlive, acq_type, ucb_h, val, grad, ld);
+                            eval_acq(g, gs, trial, ld, nlive, acq_type, ucb_h, val, grad, ld, mes);
                         },
                         &ls);
         g->stat_issued = ls.issued; g->stat_rounds = ls.rounds; g->stat_live_end = ls.live_end;
@@ -1280,6 +1299,80 @@ extern "C" int sls_acq_maximize_dev(sls_gp* g, int acq_type, double ucb_h, const
     SLS_REQUIRE(g && starts_dev, "sls_acq_maximize_dev: NULL argument");
     maximize_impl(g, nullptr, acq_type, ucb_h, starts_dev, S, n_local, opts, start_index_offset, x_out, val_out, idx_out, nullptr,
                   nullptr);
+    SLS_CATCH
+}
+
+// ---- max-value entropy search (include/sls_hip.h) ------------------------------------------------------------------
+// the y* samples of a call, validated and uploaded once
+static void upload_max_values(const char* who, sls_gp* g, const double* y_star, int K, DBuf& ys) {
+    SLS_REQUIRE(y_star != nullptr, "%s: y_star is NULL", who);
+    SLS_REQUIRE(K >= 1 && K <= SLS_MES_MAX_SAMPLES, "%s: K = %d (1 .. %d)", who, K, SLS_MES_MAX_SAMPLES);
+    for (int k = 0; k < K; ++k) SLS_REQUIRE(std::isfinite(y_star[k]), "%s: y_star[%d] is not finite", who, k);
+    ys.ensure((size_t)K);
+    h2d(g->ctx, ys.p, y_star, (size_t)K);
+}
+
+extern "C" int sls_mes_terms(sls_ctx* ctx, const double* t, long n, double* g, double* dg) {
+    SLS_TRY
+    CtxCall call_(ctx);
+    SLS_REQUIRE(ctx != nullptr, "sls_mes_terms: ctx is NULL");
+    SLS_REQUIRE(n >= 0, "sls_mes_terms: n = %ld", n);
+    if (n == 0 || (!g && !dg)) return SLS_OK;
+    SLS_REQUIRE(t != nullptr, "sls_mes_terms: t is NULL");
+    SLS_HIP(hipSetDevice(ctx->device));
+    const long chunk = std::min(n, 1L << 22);
+    DBuf buf;
+    buf.ensure((size_t)3 * chunk);
+    for (long i0 = 0; i0 < n; i0 += chunk) {
+        const long m = std::min(chunk, n - i0);
+        h2d(ctx, buf.p, t + i0, (size_t)m);
+        launch_mes_terms(ctx->stream, buf.p, m, g ? buf.p + chunk : nullptr, dg ? buf.p + 2 * chunk : nullptr);
+        if (g) d2h(ctx, g + i0, buf.p + chunk, (size_t)m);
+        if (dg) d2h(ctx, dg + i0, buf.p + 2 * chunk, (size_t)m);
+        sync(ctx);   // buf is refilled by the next chunk
+    }
+    SLS_CATCH
+}
+
+extern "C" int sls_mes_eval(sls_gp* g, const double* y_star, int K, const double* Xs, int M, double* val, double* grad) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g != nullptr, "sls_mes_eval: gp is NULL");
+    SLS_REQUIRE(M >= 0, "sls_mes_eval: M = %d", M);
+    DBuf ys;
+    upload_max_values("sls_mes_eval", g, y_star, K, ys);
+    if (M == 0) {
+        sync(g->ctx);
+        return SLS_OK;
+    }
+    SLS_REQUIRE(Xs != nullptr, "sls_mes_eval: Xs is NULL");
+    SLS_REQUIRE(val != nullptr, "sls_mes_eval: val is NULL");
+    const int Mp = round_up(M, 128), D = g->D;
+    upload_candidates(g, Xs, M, g->raw, Mp);
+    EvalOut want;
+    want.val = val; want.grad = grad;
+    g->outv.ensure(eval_block_doubles(want, D, Mp));
+    const EvalOut o = eval_block(want, g->outv.p, D, Mp);
+    const MesSamples mes{ys.p, K};
+    eval_acq(g, nullptr, g->raw.p, Mp, M, 0, 0.0, o.val, o.grad, Mp, &mes);
+    download_block(g, want, g->outv.p, M, Mp);
+    SLS_CATCH
+}
+
+extern "C" int sls_mes_maximize(sls_gp* g, const double* y_star, int K, const double* starts, int S, int n_local,
+                                const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
+                                double* x_stars, double* y_stars) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g != nullptr, "sls_mes_maximize: gp is NULL");
+    SLS_REQUIRE(starts != nullptr, "sls_mes_maximize: starts is NULL");
+    SLS_REQUIRE(S >= 1 && n_local >= 1, "sls_mes_maximize: need S >= 1 and n_local >= 1 (S = %d, n_local = %d)", S, n_local);
+    DBuf ys, sd;
+    upload_max_values("sls_mes_maximize", g, y_star, K, ys);
+    sd.ensure((size_t)g->D * S);
+    h2d(g->ctx, sd.p, starts, (size_t)g->D * S);
+    const MesSamples mes{ys.p, K};
+    maximize_impl(g, nullptr, 0, 0.0, sd.p, S, n_local, opts, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars, &mes);
     SLS_CATCH
 }
 

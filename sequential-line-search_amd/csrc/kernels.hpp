@@ -222,6 +222,17 @@ void launch_finalize(hipStream_t s, const FinalizeArgs& a);
 void launch_combine(hipStream_t s, int S, int D, long ld, const double* mu, const double* sigma, const double* dmu,
                     const double* dsigma, int acq, double mu_best, double ucb_h, double* val, double* grad);
 
+// ---- kernels_mes.hip: max-value entropy search (sls_mes_*) ---------------------------------------------------------------
+// With gamma_k = (y_star[k] - mu[n]) / sigma[n], g(t) = 1/2 t r - log Phi, g' = -1/2 r (1 + t (t + r)), r = phi / Phi:
+//   val[n] = (1/K) sum_k g(gamma_k);  grad[n + d*ld] = -(1 / sigma[n]) (A1 dmu[n + d*ld] + A2 dsigma[n + d*ld]),
+//   A1 = (1/K) sum_k g'(gamma_k), A2 = (1/K) sum_k gamma_k g'(gamma_k), every sum in increasing k.
+// sigma < 1e-10 or a NaN in the value or the gradient: value 0, gradient 0.  Arrays candidate-major with leading dimension ld;
+// grad may be NULL (dmu, dsigma are then not read); y_star: K doubles on the device.
+void launch_mes_combine(hipStream_t s, int S, int D, long ld, const double* mu, const double* sigma, const double* dmu,
+                        const double* dsigma, const double* y_star, int K, double* val, double* grad);
+// g[i] = g(t[i]), dg[i] = g'(t[i]), i < n; either output may be NULL
+void launch_mes_terms(hipStream_t s, const double* t, long n, double* g, double* dg);
+
 struct LbfgsState {
     int S, D, m;
     long ld;                  // Sp

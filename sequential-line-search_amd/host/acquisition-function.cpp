@@ -62,6 +62,17 @@ namespace sequential_line_search
             return starts;
         }
 
+        // uniform starts in [0,1]^D as RandomStarts draws them, from a generator of their own so that `seed` fixes the whole batch
+        MatrixXd SeededStarts(unsigned num_dim, long count, unsigned long long seed)
+        {
+            MatrixXd                               starts(num_dim, count);
+            std::mt19937_64                        rng(seed);
+            std::uniform_real_distribution<double> uni(0.0, 1.0);
+            for (long j = 0; j < count; ++j)
+                for (unsigned d = 0; d < num_dim; ++d) starts(d, j) = uni(rng);
+            return starts;
+        }
+
         GlobalSearchStrategy InitialStrategy()
         {
             if (const char* env = std::getenv("SLS_GLOBAL_SEARCH"))
@@ -324,15 +335,10 @@ namespace sequential_line_search
                                                                              const unsigned num_local_search_iters,
                                                                              const unsigned long long seed, const int num_frequencies)
     {
-        // uniform starts in [0,1]^D as RandomStarts draws them, from a generator of their own so that `seed` fixes the whole batch
-        const unsigned num_dim = regressor.GetNumDims();
-        const unsigned S       = std::max(1u, num_global_search_iters);
-        MatrixXd       starts(num_dim, static_cast<long>(num_points) * S);
-        std::mt19937_64                        rng(seed);
-        std::uniform_real_distribution<double> uni(0.0, 1.0);
-        for (long j = 0; j < starts.cols(); ++j)
-            for (unsigned d = 0; d < num_dim; ++d) starts(d, j) = uni(rng);
-        return FindNextPointsByThompsonSamplingFromStarts(regressor, num_points, starts, num_local_search_iters, seed, num_frequencies);
+        const unsigned S = std::max(1u, num_global_search_iters);
+        return FindNextPointsByThompsonSamplingFromStarts(regressor, num_points,
+                                                          SeededStarts(regressor.GetNumDims(), static_cast<long>(num_points) * S, seed),
+                                                          num_local_search_iters, seed, num_frequencies);
     }
 
     std::vector<VectorXd> acquisition_func::FindNextPointsByThompsonSamplingFromStarts(const Regressor& regressor, const unsigned num_points,
@@ -345,5 +351,64 @@ namespace sequential_line_search
         RequireHandle(regressor);
         const PosteriorFunctionSamples draws = regressor.SamplePosteriorFunctions(static_cast<int>(num_points), seed, num_frequencies);
         return draws.Maximize(starts, num_local_search_iters);
+    }
+
+    // ---- max-value entropy search (include/sls_hip.h sls_mes_*; Wang & Jegelka 2017) ----
+    VectorXd acquisition_func::SampleMaxValues(const Regressor& regressor, const unsigned num_samples,
+                                               const unsigned num_global_search_iters, const unsigned num_local_search_iters,
+                                               const unsigned long long seed, const int num_frequencies)
+    {
+        if (num_samples == 0) return VectorXd();
+        sls_gp*        h = RequireHandle(regressor);
+        const unsigned S = std::max(1u, num_global_search_iters);
+        const PosteriorFunctionSamples draws = regressor.SamplePosteriorFunctions(static_cast<int>(num_samples), seed, num_frequencies);
+        VectorXd                       values;
+        draws.Maximize(SeededStarts(regressor.GetNumDims(), static_cast<long>(num_samples) * S, seed), num_local_search_iters, &values);
+        // the maximum of a function is at least its value at the best data point (a local search may have ended below it)
+        double mu_best = 0.0;
+        device::Check(sls_gp_get_summary(h, nullptr, &mu_best, nullptr), "sls_gp_get_summary");
+        for (long k = 0; k < values.size(); ++k) values(k) = std::max(values(k), mu_best);
+        return values;
+    }
+
+    VectorXd acquisition_func::CalcMaxValueEntropies(const Regressor& regressor, const MatrixXd& Xs, const VectorXd& max_values,
+                                                     MatrixXd* grad)
+    {
+        const long M = Xs.cols();
+        VectorXd   v = VectorXd::Zero(M);
+        if (grad) *grad = MatrixXd::Zero(Xs.rows(), M);
+        if (regressor.GetSmallY().rows() == 0) return v;
+        device::Check(sls_mes_eval(RequireHandle(regressor), max_values.data(), static_cast<int>(max_values.size()), Xs.data(),
+                                   static_cast<int>(M), v.data(), grad ? grad->data() : nullptr),
+                      "sls_mes_eval");
+        return v;
+    }
+
+    VectorXd acquisition_func::FindNextPointByMaxValueEntropySearchFromStarts(const Regressor& regressor, const VectorXd& max_values,
+                                                                              const MatrixXd& starts,
+                                                                              const unsigned  num_local_search_iters, double* value)
+    {
+        VectorXd             x(starts.rows());
+        double               v     = 0.0;
+        long                 idx   = 0;
+        const sls_lbfgs_opts lopts = LocalSearchOpts();   // GetLocalSearchTolerances
+        device::Check(sls_mes_maximize(RequireHandle(regressor), max_values.data(), static_cast<int>(max_values.size()), starts.data(),
+                                       static_cast<int>(starts.cols()), std::max(1, static_cast<int>(num_local_search_iters)), &lopts, 0,
+                                       x.data(), &v, &idx, nullptr, nullptr),
+                      "sls_mes_maximize");
+        if (value) *value = v;
+        return x;
+    }
+
+    VectorXd acquisition_func::FindNextPointByMaxValueEntropySearch(const Regressor& regressor, const unsigned num_max_value_samples,
+                                                                    const unsigned num_global_search_iters,
+                                                                    const unsigned num_local_search_iters, const unsigned long long seed,
+                                                                    const int num_frequencies, double* value)
+    {
+        const VectorXd max_values =
+            SampleMaxValues(regressor, num_max_value_samples, num_global_search_iters, num_local_search_iters, seed, num_frequencies);
+        return FindNextPointByMaxValueEntropySearchFromStarts(
+            regressor, max_values, SeededStarts(regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed),
+            num_local_search_iters, value);
     }
 } // namespace sequential_line_search
