@@ -217,7 +217,14 @@ int sls_acq_eval_pair(sls_gp* gp_mean, sls_gp* gp_sigma, int acq_type, double uc
                       double* grad);
 int sls_acq_maximize_pair(sls_gp* gp_mean, sls_gp* gp_sigma, int acq_type, double ucb_h, const double* starts, int S, int n_local,
                           const sls_lbfgs_opts* opts, double* x_out, double* val_out, long* idx_out);
-/* Re-fit an existing handle in place from device-resident X (D x N), y (N): the timed "GP fit" of bench.py. */
+/* Re-fit an existing handle in place from device-resident X (D x N), y (N): the timed "GP fit" of bench.py.  D, N, theta, b, the
+ * kernel and the sigma mode stay those of the handle; X_dev / y_dev are read on the context's stream (sls_ctx_set_stream) and copied:
+ * the caller's buffers are free again on return.
+ * On an error from the fit (SLS_ERR_NOT_SPD: K_y is not positive definite) the handle's data are the new X, y but its fitted state is
+ * UNDEFINED until the next successful sls_gp_refit_dev: the matrices, the summary and every evaluation may mix the old fit and the
+ * failed one, and the evaluation entry points do not detect this (they return SLS_OK).  sls_gp_generation has changed, so objects
+ * derived from the old fit (sls_path) are refused.  The handle stays valid for sls_gp_refit_dev and sls_gp_destroy, the context for
+ * everything. */
 int sls_gp_refit_dev(sls_gp* gp, const double* X_dev, const double* y_dev);
 
 /* ---- pathwise posterior function draws (not in the reference) ---------------------------------------------------------

@@ -31,7 +31,10 @@ inline void ensure_dyn_lds(const void* fn, int bytes) {
     std::lock_guard<std::mutex> lock(mtx);
     int& have = done[{dev, fn}];
     if (bytes > have) {
-        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        // A runtime may refuse the opt-in and launch the kernel all the same (HIP 7.0 answers hipErrorInvalidValue to the 160 KB of
+        // maximize_wave_kernel).  The refusal must not stay behind as the thread's last error: an application that shares the
+        // runtime and checks hipGetLastError after its own launches (PyTorch does) would report it as its own failure.
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) (void)hipGetLastError();
         have = bytes;
     }
 }
