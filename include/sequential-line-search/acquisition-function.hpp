@@ -14,6 +14,10 @@ namespace sequential_line_search
     {
         ExpectedImprovement,
         GaussianProcessUpperConfidenceBound,
+        /// log of ExpectedImprovement, formed in log space (not in the reference; include/sls_hip.h "log expected improvement"): it
+        /// neither underflows nor loses its gradient far below the incumbent.  The hyperparameter is ignored.  Device-resident
+        /// regressors only: for any other Regressor every function below throws std::invalid_argument.
+        LogExpectedImprovement,
     };
 
     /// How FindNextPoint / FindNextPoints search [0,1]^D (reference: the two branches of FindGlobalSolution,

@@ -47,6 +47,8 @@ extern "C" {
 /* include/sequential-line-search/acquisition-function.hpp:11-15 */
 #define SLS_ACQ_EXPECTED_IMPROVEMENT 0
 #define SLS_ACQ_GP_UCB 1
+/* not in the reference: log-space expected improvement ("log expected improvement" below); ucb_h is ignored */
+#define SLS_ACQ_LOG_EXPECTED_IMPROVEMENT 2
 
 #define SLS_OK 0
 #define SLS_ERR_INVALID (-1)
@@ -296,6 +298,35 @@ int sls_mes_maximize(sls_gp* gp, const double* y_star, int K, const double* star
                      const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
                      double* x_stars, double* y_stars);
 
+/* ---- log expected improvement (not in the reference) -------------------------------------------------------------------
+ * acq_type SLS_ACQ_LOG_EXPECTED_IMPROVEMENT, accepted wherever an acq_type is taken (sls_acq_eval, sls_acq_maximize,
+ * sls_acq_maximize_dev, sls_acq_eval_pair, sls_acq_maximize_pair, sls_multi_acq_maximize); every returned value (val, val_out,
+ * y_stars, the record gathered across GPUs) is then a LogEI value.  Expected improvement diff Phi + sigma phi underflows to exactly 0
+ * with its gradient once u = (mu - mu_best) / sigma < ~-38.6 and cancels before that; LogEI = log EI is formed without Phi.
+ * With mu, sigma as the tiled evaluation forms them in the handle's sigma mode (see max-value entropy search above), diff = mu -
+ * mu_best, u = diff / sigma and r = phi / Phi as MES forms it:
+ *   u <  0: e = erfcx(-u / sqrt 2), r = sqrt(2/pi) / e, log Phi = log(e / 2) - u^2 / 2;   u >= 0: Phi = erfc(-u / sqrt 2) / 2, r = phi / Phi
+ *   w(u)     = h / Phi = r + u      direct for u >= -30; for u < -30 (r + u cancels to ~1/|u| and the direct form loses u^2 eps of it)
+ *                                   w = (c - 1) / u, c = t (2 + t (-10 + t (74 + t (-706 + 8162 t)))), t = 1 / u^2 (the series of MES)
+ *   log h(u) = log Phi + log w      (u < 0);    log(phi + u Phi)   (u >= 0, no cancellation),      h = phi + u Phi
+ *   B1 = 1 / w (= Phi / h),  B2 = r / w (= phi / h)
+ *   LogEI      = log sigma + log h(u)
+ *   grad LogEI = (1 / sigma) (B1 grad mu + B2 grad sigma)
+ * Guard (the conditions of expected improvement): sigma < 1e-10, or a NaN in the value or in any gradient component, gives the value
+ * SLS_LOG_EI_FLOOR and the zero gradient.  The floor is finite on purpose: the Armijo test, the relative stopping tests and DIRECT's
+ * rectangle selection stay in finite arithmetic; a start on the floor is stationary and leaves the batch, a trial step onto it is
+ * rejected.  The guard looks for NaN only, as expected improvement's does: every result is finite for |u| < 1e154, which sigma >= 1e-10
+ * gives for any |mu - mu_best| < 1e144; beyond that u^2 overflows, an infinite mu gives u = -inf, and the value is -inf (with an
+ * infinite B1), which is not caught.  log h is accurate to a few eps max(1, u^2), B1 and B2 to ~2e-13 relative (the series' first omitted term at u = -30).
+ * One lane per point and a fixed operation order: a point's bits depend on neither its column, the other points of the call nor the
+ * candidate chunk.  LogEI always takes the tiled evaluation plus one combiner launch (never the single-launch path of small
+ * problems, the zero-copy path or the evaluation slots) and holds the context's lock for the whole call, as the handle's other
+ * large calls do. */
+#define SLS_LOG_EI_FLOOR (-1.0e300)
+/* log_h[i] = log h(u[i]), b1[i] = Phi / h, b2[i] = phi / h; any out pointer may be NULL; n >= 0 (n < 0: SLS_ERR_INVALID).  The scalar
+ * terms on their own (a test hook, as sls_mes_terms is). */
+int sls_logei_terms(sls_ctx* ctx, const double* u, long n, double* log_h, double* b1, double* b2);
+
 /* ---- multi-GPU maximisation ------------------------------------------------------------------------------
  * FindGlobalSolution's multi-start loop (src/acquisition-function.cpp:121-153) shards over its starts: the iterations share
  * only the const regressor (:125-141).  Every GPU holds a replica of the fitted state, runs a contiguous slice of the starts
@@ -418,7 +449,8 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
  * per jitter tried), "post_sample" (normals + the sample product); the path draws: "path_setup" (normals, frequencies, weights,
  * f_prior(X)), "path_solve" (v = K_y^-1 r), "path_prior" (the random-feature prior of an evaluation), "path_data" (the data term
  * on cross_gram's K*; cross_gram and grad_gemm count under their own names); "mes" (the MES combiner, one launch per evaluation of
- * sls_mes_eval / round of sls_mes_maximize); "potrf_fallbacks": launches = how often a single-launch
+ * sls_mes_eval / round of sls_mes_maximize); "logei" (the LogEI combiner, one launch per evaluation / round of a type-2
+ * call); "potrf_fallbacks": launches = how often a single-launch
  * factorisation gave up and was recomputed. */
 int sls_prof_enable(sls_ctx* ctx, int on);
 int sls_prof_reset(sls_ctx* ctx);

@@ -4,7 +4,7 @@
 // arrays (the reference relies on pybind11/eigen.h; Eigen is not available here, hence the small casters below).
 // Additions: set_random_seed(), set/get_global_search_strategy(), set/get_devices(), and batched predict_mean_stdev /
 // acquisition_values on (D, M) arrays; GaussianProcessRegressor (fixed hyper-parameters) with sample_max_values(),
-// calc_max_value_entropies() and find_next_point_by_max_value_entropy_search().
+// calc_max_value_entropies(), find_next_point_by_max_value_entropy_search() and find_next_point_direct().
 #include <pybind11/functional.h>
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -103,7 +103,8 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
         .value("LastSelection", CurrentBestSelectionStrategy::LastSelection);
     py::enum_<AcquisitionFuncType>(m, "AcquisitionFuncType", py::arithmetic())
         .value("ExpectedImprovement", AcquisitionFuncType::ExpectedImprovement)
-        .value("GaussianProcessUpperConfidenceBound", AcquisitionFuncType::GaussianProcessUpperConfidenceBound);
+        .value("GaussianProcessUpperConfidenceBound", AcquisitionFuncType::GaussianProcessUpperConfidenceBound)
+        .value("LogExpectedImprovement", AcquisitionFuncType::LogExpectedImprovement);
     py::enum_<KernelType>(m, "KernelType", py::arithmetic())
         .value("ArdSquaredExponentialKernel", KernelType::ArdSquaredExponentialKernel)
         .value("ArdMatern52Kernel", KernelType::ArdMatern52Kernel);
@@ -131,6 +132,19 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
           },
           "regressor"_a, "num_max_value_samples"_a = 64, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50,
           "seed"_a = 0ULL, "num_frequencies"_a = 2048);
+
+    // DIRECT, then one L-BFGS from its result (acquisition_func::FindNextPointDirect) on such a regressor: (point, value)
+    m.def("find_next_point_direct",
+          [](const Regressor& r, unsigned num_global_search_iters, unsigned num_local_search_iters, AcquisitionFuncType func_type,
+             double hyperparam) {
+              double         value = 0.0;
+              const VectorXd x =
+                  acquisition_func::FindNextPointDirect(r, num_global_search_iters, num_local_search_iters, func_type, hyperparam, &value);
+              return std::make_pair(x, value);
+          },
+          "regressor"_a, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50,
+          "acquisition_func_type"_a = AcquisitionFuncType::ExpectedImprovement,
+          "gaussian_process_upper_confidence_bound_hyperparam"_a = 1.0);
 
     using SliderEndsGenerator = std::function<std::pair<VectorXd, VectorXd>(const int)>;
     m.def("generate_random_slider_ends", &GenerateRandomSliderEnds, "num_dims"_a);

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("SLS_HIP_LIB") or os.path.join(_HERE, "libsls_hip.so")
 
 KERNEL_SE, KERNEL_MATERN52 = 0, 1
 ACQ_EI, ACQ_UCB = 0, 1
+ACQ_LOG_EI = 2   # log-space expected improvement (SLS_ACQ_LOG_EXPECTED_IMPROVEMENT); ucb_h is ignored
 GP_K_Y, GP_K_Y_INV, GP_CHOL_L, GP_ALPHA, GP_MU_DATA = 0, 1, 2, 3, 4
 
 _dp = C.POINTER(C.c_double)
@@ -62,7 +63,7 @@ EXPORTS = [
     "sls_comm_destroy", "sls_comm_allgather_best", "sls_device_trim_cache", "sls_tuning_reload", "sls_gp_generation",
     "sls_gp_predict_cov", "sls_gp_sample_posterior", "sls_random_normal",
     "sls_path_create", "sls_path_destroy", "sls_path_eval", "sls_path_maximize",
-    "sls_mes_terms", "sls_mes_eval", "sls_mes_maximize",
+    "sls_mes_terms", "sls_mes_eval", "sls_mes_maximize", "sls_logei_terms",
 ]
 
 
@@ -147,6 +148,13 @@ class Context:
         g, dg = np.empty(t.size), np.empty(t.size)
         _ck(lib().sls_mes_terms(self.h, _p(t), C.c_long(t.size), _p(g), _p(dg)))
         return g, dg
+
+    def logei_terms(self, u):
+        """(log h(u), Phi/h, phi/h) of log expected improvement, h = phi + u Phi, for an array of u (sls_logei_terms)."""
+        u = np.ascontiguousarray(np.asarray(u, dtype=np.float64).ravel())
+        log_h, b1, b2 = np.empty(u.size), np.empty(u.size), np.empty(u.size)
+        _ck(lib().sls_logei_terms(self.h, _p(u), C.c_long(u.size), _p(log_h), _p(b1), _p(b2)))
+        return log_h, b1, b2
 
     # ---- free functions (src/regressor.cpp) ----
     def gram(self, X, theta, b, kernel):

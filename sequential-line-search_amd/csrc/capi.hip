@@ -1037,15 +1037,98 @@ static bool eval_in_slot(sls_gp* g, const double* Xs, int M, const EvalOut& want
     return true;
 }
 
+// value (+ gradient) of the acquisition at candidate-major points xr; gs != nullptr: sigma / dsigma come from gs
+// (objective_for_multiple_points, src/acquisition-function.cpp:63-110)
+// mes != nullptr: max-value entropy search instead (acq_type, ucb_h and gs are not used): mu, sigma and their gradients of g in the
+// handle's pair blocks, then the MES combiner on the y* samples
+// acq_type SLS_ACQ_LOG_EXPECTED_IMPROVEMENT: mu / dmu of g and sigma / dsigma of gs (of g if there is none) in g's pair blocks, then the
+// LogEI combiner with g's mu_best
+struct MesSamples {
+    const double* y_star;   // device, K doubles
+    int K;
+};
+static void eval_acq(sls_gp* g, sls_gp* gs, const double* xr, long ldr, int S, int acq_type, double ucb_h, double* val,
+                     double* grad, long ldo, const MesSamples* mes = nullptr) {
+    if (mes) {
+        const size_t D = g->D;
+        g->pair_mu.ensure(ldo); g->pair_sg.ensure(ldo);
+        if (grad) { g->pair_dmu.ensure(ldo * D); g->pair_dsg.ensure(ldo * D); }
+        EvalOut a;
+        a.ldo = ldo; a.mu = g->pair_mu.p; a.sigma = g->pair_sg.p;
+        a.dmu = grad ? g->pair_dmu.p : nullptr; a.dsigma = grad ? g->pair_dsg.p : nullptr;
+        eval_candidates(g, xr, ldr, S, a);
+        ProfScope ps(g->ctx, "mes");
+        launch_mes_combine(g->ctx->stream, S, (int)D, ldo, g->pair_mu.p, g->pair_sg.p, g->pair_dmu.p, g->pair_dsg.p, mes->y_star,
+                           mes->K, val, grad);
+        return;
+    }
+    if (acq_type == SLS_ACQ_LOG_EXPECTED_IMPROVEMENT) {   // the single-handle and the pair objective from one path
+        const size_t D = g->D;
+        g->pair_mu.ensure(ldo); g->pair_sg.ensure(ldo);
+        if (grad) { g->pair_dmu.ensure(ldo * D); g->pair_dsg.ensure(ldo * D); }
+        EvalOut a;
+        a.ldo = ldo; a.mu = g->pair_mu.p; a.dmu = grad ? g->pair_dmu.p : nullptr;
+        EvalOut b;
+        b.ldo = ldo;
+        EvalOut& sg = gs ? b : a;
+        sg.sigma = g->pair_sg.p; sg.dsigma = grad ? g->pair_dsg.p : nullptr;
+        eval_candidates(g, xr, ldr, S, a);
+        if (gs) eval_candidates(gs, xr, ldr, S, b);
+        ProfScope ps(g->ctx, "logei");
+        launch_logei_combine(g->ctx->stream, S, (int)D, ldo, g->pair_mu.p, g->pair_sg.p, g->pair_dmu.p, g->pair_dsg.p, g->mu_best, val,
+                             grad);
+        return;
+    }
+    if (!gs) {
+        EvalOut eo;
+        eo.ldo = ldo; eo.val = val; eo.grad = grad; eo.acq = acq_type; eo.ucb_h = ucb_h;
+        eval_candidates(g, xr, ldr, S, eo);
+        return;
+    }
+    const size_t D = g->D;
+    g->pair_mu.ensure(ldo); g->pair_sg.ensure(ldo);
+    if (grad) { g->pair_dmu.ensure(ldo * D); g->pair_dsg.ensure(ldo * D); }
+    EvalOut a, b;
+    a.ldo = ldo; a.mu = g->pair_mu.p; a.dmu = grad ? g->pair_dmu.p : nullptr;
+    b.ldo = ldo; b.sigma = g->pair_sg.p; b.dsigma = grad ? g->pair_dsg.p : nullptr;
+    eval_candidates(g, xr, ldr, S, a);
+    eval_candidates(gs, xr, ldr, S, b);
+    launch_combine(g->ctx->stream, S, (int)D, ldo, g->pair_mu.p, g->pair_sg.p, g->pair_dmu.p, g->pair_dsg.p, acq_type, g->mu_best,
+                   ucb_h, val, grad);
+}
+
+// eval_acq at M >= 1 host-supplied points (D x M column-major) through the transposing upload, results to the caller's arrays
+static void eval_acq_points(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, const double* Xs, int M, double* val, double* grad) {
+    const int Mp = round_up(M, 128), D = g->D;
+    upload_candidates(g, Xs, M, g->raw, Mp);
+    std::vector<double> unused;   // the combiners always write the values
+    if (!val) unused.resize(M);
+    EvalOut want;
+    want.val = val ? val : unused.data(); want.grad = grad;
+    g->outv.ensure(eval_block_doubles(want, D, Mp));
+    const EvalOut o = eval_block(want, g->outv.p, D, Mp);
+    eval_acq(g, gs, g->raw.p, Mp, M, acq_type, ucb_h, o.val, o.grad, Mp);
+    download_block(g, want, g->outv.p, M, Mp);
+}
+
+static bool known_acq(int acq_type) {
+    return acq_type == SLS_ACQ_EXPECTED_IMPROVEMENT || acq_type == SLS_ACQ_GP_UCB || acq_type == SLS_ACQ_LOG_EXPECTED_IMPROVEMENT;
+}
 // The body of sls_gp_predict, sls_gp_predict_grad and sls_acq_eval: `want` names the caller's arrays (any may be NULL).
 static int eval_entry(const char* who, sls_gp* g, const double* Xs, int M, const EvalOut& want) {
     SLS_TRY
-    const bool acq_ok = want.acq == SLS_ACQ_EXPECTED_IMPROVEMENT || want.acq == SLS_ACQ_GP_UCB;
-    if (g && Xs && M >= 1 && M <= SLOT_MAX_POINTS && acq_ok && eval_in_slot(g, Xs, M, want)) return SLS_OK;
+    // LogEI has no objective in the one-wavefront-per-start kernel: neither the slots nor the zero-copy path, always the tiled one
+    const bool logei = want.acq == SLS_ACQ_LOG_EXPECTED_IMPROVEMENT;
+    const bool slot_acq = want.acq == SLS_ACQ_EXPECTED_IMPROVEMENT || want.acq == SLS_ACQ_GP_UCB;
+    if (g && Xs && M >= 1 && M <= SLOT_MAX_POINTS && slot_acq && eval_in_slot(g, Xs, M, want)) return SLS_OK;
     CtxCall call_(g);
     SLS_REQUIRE(g && Xs && M >= 0, "%s: bad argument", who);
-    SLS_REQUIRE(acq_ok, "unknown acquisition type %d", want.acq);
+    SLS_REQUIRE(known_acq(want.acq), "unknown acquisition type %d", want.acq);
     if (M == 0) return SLS_OK;
+    if (logei) {
+        eval_acq_points(g, nullptr, want.acq, want.ucb_h, Xs, M, want.val, want.grad);
+        return SLS_OK;
+    }
     sls_ctx* c = g->ctx;
     const int Mp = round_up(M, 128), D = g->D;
     // Value-only evaluation of a small batch on a small problem -- one iteration of DIRECT (host/direct.cpp; the reference's
@@ -1104,47 +1187,6 @@ sls_lbfgs_opts slsk::read_lbfgs_opts(const sls_lbfgs_opts* in) {
     return o;
 }
 
-// value (+ gradient) of the acquisition at candidate-major points xr; gs != nullptr: sigma / dsigma come from gs
-// (objective_for_multiple_points, src/acquisition-function.cpp:63-110)
-// mes != nullptr: max-value entropy search instead (acq_type, ucb_h and gs are not used): mu, sigma and their gradients of g in the
-// handle's pair blocks, then the MES combiner on the y* samples
-struct MesSamples {
-    const double* y_star;   // device, K doubles
-    int K;
-};
-static void eval_acq(sls_gp* g, sls_gp* gs, const double* xr, long ldr, int S, int acq_type, double ucb_h, double* val,
-                     double* grad, long ldo, const MesSamples* mes = nullptr) {
-    if (mes) {
-        const size_t D = g->D;
-        g->pair_mu.ensure(ldo); g->pair_sg.ensure(ldo);
-        if (grad) { g->pair_dmu.ensure(ldo * D); g->pair_dsg.ensure(ldo * D); }
-        EvalOut a;
-        a.ldo = ldo; a.mu = g->pair_mu.p; a.sigma = g->pair_sg.p;
-        a.dmu = grad ? g->pair_dmu.p : nullptr; a.dsigma = grad ? g->pair_dsg.p : nullptr;
-        eval_candidates(g, xr, ldr, S, a);
-        ProfScope ps(g->ctx, "mes");
-        launch_mes_combine(g->ctx->stream, S, (int)D, ldo, g->pair_mu.p, g->pair_sg.p, g->pair_dmu.p, g->pair_dsg.p, mes->y_star,
-                           mes->K, val, grad);
-        return;
-    }
-    if (!gs) {
-        EvalOut eo;
-        eo.ldo = ldo; eo.val = val; eo.grad = grad; eo.acq = acq_type; eo.ucb_h = ucb_h;
-        eval_candidates(g, xr, ldr, S, eo);
-        return;
-    }
-    const size_t D = g->D;
-    g->pair_mu.ensure(ldo); g->pair_sg.ensure(ldo);
-    if (grad) { g->pair_dmu.ensure(ldo * D); g->pair_dsg.ensure(ldo * D); }
-    EvalOut a, b;
-    a.ldo = ldo; a.mu = g->pair_mu.p; a.dmu = grad ? g->pair_dmu.p : nullptr;
-    b.ldo = ldo; b.sigma = g->pair_sg.p; b.dsigma = grad ? g->pair_dsg.p : nullptr;
-    eval_candidates(g, xr, ldr, S, a);
-    eval_candidates(gs, xr, ldr, S, b);
-    launch_combine(g->ctx->stream, S, (int)D, ldo, g->pair_mu.p, g->pair_sg.p, g->pair_dmu.p, g->pair_dsg.p, acq_type, g->mu_best,
-                   ucb_h, val, grad);
-}
-
 // The whole multi-start search in one launch, one wavefront per start (the caller has asked wave_path_applies).  Returns the device
 // counter of useful evaluations: those of starts that were still moving (finished starts run idle to keep the barriers uniform),
 // counted by the kernel into the live-count words of the integer scratch.
@@ -1187,7 +1229,7 @@ static void maximize_impl(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, con
                           double* x_stars, double* y_stars, const MesSamples* mes = nullptr) {
     sls_ctx* c = g->ctx;
     SLS_REQUIRE(S >= 1 && n_local >= 1, "sls_acq_maximize: need S >= 1 and n_local >= 1");
-    SLS_REQUIRE(mes || acq_type == SLS_ACQ_EXPECTED_IMPROVEMENT || acq_type == SLS_ACQ_GP_UCB, "unknown acquisition type %d", acq_type);
+    SLS_REQUIRE(mes || known_acq(acq_type), "unknown acquisition type %d", acq_type);
     const sls_lbfgs_opts o = read_lbfgs_opts(opts_in);
     SLS_REQUIRE(o.history >= 1 && o.history <= 8, "L-BFGS history must be in 1..8");
     const int Sp = round_up(S, 128), D = g->D;
@@ -1196,7 +1238,8 @@ static void maximize_impl(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, con
     LbfgsState st = g->lb.state(S, D, o);
     // Small problems: one wavefront per start runs the whole search in a single launch (kernels_wave.hip)
     const unsigned long long* wave_useful = nullptr;   // the one-wavefront-per-start run's count of useful evaluations (device)
-    if (!gs && !mes && wave_path_applies(g, S)) {   // (the wave kernel has no MES objective: always the general path)
+    // (the wave kernel has neither the MES nor the LogEI objective: those always take the general path)
+    if (!gs && !mes && acq_type != SLS_ACQ_LOG_EXPECTED_IMPROVEMENT && wave_path_applies(g, S)) {
         wave_useful = maximize_wave(g, acq_type, ucb_h, starts_dev, S, n_local, o, st, Sp);   // read back with the best start
         g->stat_rounds = n_local;
     } else {
@@ -1276,18 +1319,9 @@ extern "C" int sls_acq_eval_pair(sls_gp* g, sls_gp* gs, int acq_type, double ucb
     CtxCall call_(g);
     check_pair(g, gs);
     SLS_REQUIRE(Xs && M >= 0, "sls_acq_eval_pair: bad argument");
-    SLS_REQUIRE(acq_type == SLS_ACQ_EXPECTED_IMPROVEMENT || acq_type == SLS_ACQ_GP_UCB, "unknown acquisition type %d", acq_type);
+    SLS_REQUIRE(known_acq(acq_type), "unknown acquisition type %d", acq_type);
     if (M == 0) return SLS_OK;
-    const int Mp = round_up(M, 128), D = g->D;
-    upload_candidates(g, Xs, M, g->raw, Mp);
-    std::vector<double> unused;   // launch_combine always writes the values
-    if (!val) unused.resize(M);
-    EvalOut want;
-    want.val = val ? val : unused.data(); want.grad = grad;
-    g->outv.ensure(eval_block_doubles(want, D, Mp));
-    const EvalOut o = eval_block(want, g->outv.p, D, Mp);
-    eval_acq(g, gs, g->raw.p, Mp, M, acq_type, ucb_h, o.val, o.grad, Mp);
-    download_block(g, want, g->outv.p, M, Mp);
+    eval_acq_points(g, gs, acq_type, ucb_h, Xs, M, val, grad);
     SLS_CATCH
 }
 
@@ -1329,6 +1363,31 @@ extern "C" int sls_mes_terms(sls_ctx* ctx, const double* t, long n, double* g, d
         launch_mes_terms(ctx->stream, buf.p, m, g ? buf.p + chunk : nullptr, dg ? buf.p + 2 * chunk : nullptr);
         if (g) d2h(ctx, g + i0, buf.p + chunk, (size_t)m);
         if (dg) d2h(ctx, dg + i0, buf.p + 2 * chunk, (size_t)m);
+        sync(ctx);   // buf is refilled by the next chunk
+    }
+    SLS_CATCH
+}
+
+extern "C" int sls_logei_terms(sls_ctx* ctx, const double* u, long n, double* log_h, double* b1, double* b2) {
+    SLS_TRY
+    CtxCall call_(ctx);
+    SLS_REQUIRE(ctx != nullptr, "sls_logei_terms: ctx is NULL");
+    SLS_REQUIRE(n >= 0, "sls_logei_terms: n = %ld", n);
+    if (n == 0 || (!log_h && !b1 && !b2)) return SLS_OK;
+    SLS_REQUIRE(u != nullptr, "sls_logei_terms: u is NULL");
+    SLS_HIP(hipSetDevice(ctx->device));
+    const long chunk = std::min(n, 1L << 22);
+    DBuf buf;
+    buf.ensure((size_t)4 * chunk);
+    double* const host[3] = {log_h, b1, b2};
+    double* dev[3];
+    for (int k = 0; k < 3; ++k) dev[k] = host[k] ? buf.p + (k + 1) * chunk : nullptr;
+    for (long i0 = 0; i0 < n; i0 += chunk) {
+        const long m = std::min(chunk, n - i0);
+        h2d(ctx, buf.p, u + i0, (size_t)m);
+        launch_logei_terms(ctx->stream, buf.p, m, dev[0], dev[1], dev[2]);
+        for (int k = 0; k < 3; ++k)
+            if (host[k]) d2h(ctx, host[k] + i0, dev[k], (size_t)m);
         sync(ctx);   // buf is refilled by the next chunk
     }
     SLS_CATCH

@@ -236,6 +236,16 @@ void launch_mes_combine(hipStream_t s, int S, int D, long ld, const double* mu, 
 // g[i] = g(t[i]), dg[i] = g'(t[i]), i < n; either output may be NULL
 void launch_mes_terms(hipStream_t s, const double* t, long n, double* g, double* dg);
 
+// ---- kernels_logei.hip: log expected improvement (SLS_ACQ_LOG_EXPECTED_IMPROVEMENT) --------------------------------------
+// With u = (mu[n] - mu_best) / sigma[n] and log h, B1 = Phi / h, B2 = phi / h of h = phi + u Phi (include/sls_hip.h):
+//   val[n] = log sigma[n] + log h(u);  grad[n + d*ld] = (1 / sigma[n]) (B1 dmu[n + d*ld] + B2 dsigma[n + d*ld]).
+// sigma < 1e-10 or a NaN in the value or the gradient: value SLS_LOG_EI_FLOOR, gradient 0.  Arrays candidate-major with leading
+// dimension ld; grad may be NULL (dmu, dsigma are then not read).
+void launch_logei_combine(hipStream_t s, int S, int D, long ld, const double* mu, const double* sigma, const double* dmu,
+                          const double* dsigma, double mu_best, double* val, double* grad);
+// log_h[i], b1[i], b2[i] of u[i], i < n; any output may be NULL
+void launch_logei_terms(hipStream_t s, const double* u, long n, double* log_h, double* b1, double* b2);
+
 struct LbfgsState {
     int S, D, m;
     long ld;                  // Sp

@@ -24,7 +24,15 @@ namespace sequential_line_search
     {
         int AcqId(AcquisitionFuncType t)
         {
+            if (t == AcquisitionFuncType::LogExpectedImprovement) return SLS_ACQ_LOG_EXPECTED_IMPROVEMENT;
             return t == AcquisitionFuncType::ExpectedImprovement ? SLS_ACQ_EXPECTED_IMPROVEMENT : SLS_ACQ_GP_UCB;
+        }
+        // LogExpectedImprovement exists on the device only (there is no host erfcx): the stance of RequireHandle
+        void RefuseLogEiOnHost(AcquisitionFuncType t)
+        {
+            if (t == AcquisitionFuncType::LogExpectedImprovement)
+                throw std::invalid_argument("acquisition_func: LogExpectedImprovement needs a device-resident regressor "
+                                            "(GaussianProcessRegressor / PreferenceRegressor); there is no host fallback");
         }
 
         // mathtoolbox::GetExpectedImprovement / ...Derivative for regressors WITHOUT a device
@@ -34,6 +42,7 @@ namespace sequential_line_search
 
         double GenericValue(const Regressor& r, const VectorXd& x, AcquisitionFuncType type, double h)
         {
+            RefuseLogEiOnHost(type);
             const double mu = r.PredictMu(x), sigma = r.PredictSigma(x);
             if (type == AcquisitionFuncType::GaussianProcessUpperConfidenceBound) return mu + h * sigma;
             const double diff = mu - r.PredictMu(r.PredictMaximumPointFromData());
@@ -43,6 +52,7 @@ namespace sequential_line_search
         }
         VectorXd GenericDerivative(const Regressor& r, const VectorXd& x, AcquisitionFuncType type, double h)
         {
+            RefuseLogEiOnHost(type);
             const VectorXd dm = r.PredictMuDerivative(x), ds = r.PredictSigmaDerivative(x);
             if (type == AcquisitionFuncType::GaussianProcessUpperConfidenceBound) return dm + h * ds;
             const double mu = r.PredictMu(x), sigma = r.PredictSigma(x);
