@@ -6,6 +6,7 @@
 #include <memory>
 #include <sequential-line-search/eigen-lite.hpp>
 #include <sequential-line-search/regressor.hpp>
+#include <utility>
 #include <vector>
 
 namespace sequential_line_search
@@ -136,6 +137,27 @@ namespace sequential_line_search
         Eigen::VectorXd FindNextPointByMaxValueEntropySearchFromStarts(const Regressor& regressor, const Eigen::VectorXd& max_values,
                                                                        const Eigen::MatrixXd& starts,
                                                                        const unsigned num_local_search_iters, double* value = nullptr);
+
+        /// Expected utility of the best option of a query pair (not in the reference; the q = 2 case of qEUBO, Astudillo et al.
+        /// 2023, include/sls_hip.h sls_eubo_*): EUBO(x, x') = E[max(f(x), f(x'))] under the joint posterior of the two options,
+        /// for the pairs (Xa.col(m), Xb.col(m)) (both D x M), and its gradients in x (grad_a, D x M) and x' (grad_b, D x M) where
+        /// asked for: one device pass.  Device-resident regressors only (std::invalid_argument otherwise).
+        Eigen::VectorXd CalcExpectedUtilitiesOfBestOption(const Regressor& regressor, const Eigen::MatrixXd& Xa, const Eigen::MatrixXd& Xb,
+                                                          Eigen::MatrixXd* grad_a = nullptr, Eigen::MatrixXd* grad_b = nullptr);
+        /// Maximiser (x, x') of EUBO over [0,1]^D x [0,1]^D: one L-BFGS of num_local_search_iters evaluations (the tolerances of
+        /// GetLocalSearchTolerances) over the 2D coordinates from each of num_global_search_iters uniform starts of the generator
+        /// FindNextPointByMaxValueEntropySearch uses, seeded with `seed`, all in lock step on the device.  The same seed gives the
+        /// same pair.  value (may be nullptr) receives EUBO there.
+        std::pair<Eigen::VectorXd, Eigen::VectorXd> FindNextQueryPairByExpectedUtility(const Regressor& regressor,
+                                                                                       const unsigned   num_global_search_iters = 100,
+                                                                                       const unsigned   num_local_search_iters  = 50,
+                                                                                       const unsigned long long seed = 0,
+                                                                                       double*                  value = nullptr);
+        /// The same from an explicit start set (2D x S: rows 0..D-1 start x, rows D..2D-1 start x').
+        std::pair<Eigen::VectorXd, Eigen::VectorXd> FindNextQueryPairByExpectedUtilityFromStarts(const Regressor&       regressor,
+                                                                                                 const Eigen::MatrixXd& starts,
+                                                                                                 const unsigned num_local_search_iters,
+                                                                                                 double*        value = nullptr);
     } // namespace acquisition_func
 } // namespace sequential_line_search
 

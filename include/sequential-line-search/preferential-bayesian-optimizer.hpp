@@ -53,6 +53,13 @@ namespace sequential_line_search
         /// the same heuristic as DetermineNextQuery.
         void DetermineNextQueryByThompsonSampling(const unsigned long long seed, const int num_global_search_iters = 0,
                                                   const int num_local_search_iters = 0);
+        /// Opt-in alternative for two-option queries: BOTH options are the maximiser (x, x') of the expected utility of the best
+        /// option E[max(f(x), f(x'))] (acquisition_func::FindNextQueryPairByExpectedUtility with start stream `seed`); the current
+        /// best is not forced into the query.  The option with the larger posterior mean becomes option 0 (GetMaximizer()).
+        /// num_options != 2 throws std::invalid_argument; before any feedback it throws as DetermineNextQuery does; non-positive
+        /// arguments select the same heuristic as DetermineNextQuery.
+        void DetermineNextQueryByExpectedUtility(const unsigned long long seed, const int num_global_search_iters = 0,
+                                                 const int num_local_search_iters = 0);
 
         const std::vector<Eigen::VectorXd>& GetCurrentOptions() const { return m_current_options; }
         Eigen::VectorXd                     GetMaximizer() const;

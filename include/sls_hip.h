@@ -72,7 +72,10 @@ int sls_ctx_destroy(sls_ctx* ctx);
 /* Run on a caller-owned hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL restores the own stream. */
 int sls_ctx_set_stream(sls_ctx* ctx, void* hip_stream);
 int sls_ctx_synchronize(sls_ctx* ctx);
-/* Upper bound on candidates evaluated per device pass (workspace = 3 * chunk * N_pad doubles). Default 16384. */
+/* Upper bound on candidates evaluated per device pass (workspace = 3 * chunk * N_pad doubles). Default 16384.
+ * The pair objective (sls_eubo_*) evaluates max(128, chunk / 2 rounded down to 128) PAIRS per pass -- two cross-covariance blocks,
+ * their difference and one product block per pair --, so its workspace stays at about what a single-point acquisition uses at the
+ * same setting. */
 int sls_ctx_set_candidate_chunk(sls_ctx* ctx, int chunk);
 
 /* Device blocks released by handles and calls are cached per device (exact-size reuse; at most SLS_POOL_MB, default 16384,
@@ -327,6 +330,47 @@ int sls_mes_maximize(sls_gp* gp, const double* y_star, int K, const double* star
  * terms on their own (a test hook, as sls_mes_terms is). */
 int sls_logei_terms(sls_ctx* ctx, const double* u, long n, double* log_h, double* b1, double* b2);
 
+/* ---- expected utility of the best option of a query pair (not in the reference) -----------------------------------------
+ * EUBO for a pair, the q = 2 case of qEUBO (Astudillo et al., AISTATS 2023): EUBO(x, x') = E[ max(f(x), f(x')) ] under the
+ * posterior, in closed form.  It is the one-step-optimal criterion for a two-option preference query and the only acquisition here
+ * that uses the posterior covariance BETWEEN two candidates.  The handle has data X, theta = (a, l), K_y and alpha; a pair (x, x')
+ * lies in [0,1]^D x [0,1]^D:
+ *   k_x = k(X, x),  k_x' = k(X, x'),  d = k_x - k_x',  w = K_y^-1 d
+ *   mu = k_x . alpha,  mu' = k_x' . alpha,  delta = mu - mu'
+ *   s^2 = Var[f(x) - f(x')] = 2a - 2 k(x, x') - d^T K_y^-1 d      (latent covariance, no b on the diagonal: cov00 + cov11 - 2 cov01
+ *                                                                   of sls_gp_predict_cov at the two points)
+ *   u = delta / s,  Phi = erfc(-u / sqrt 2) / 2,  Phi' = erfc(u / sqrt 2) / 2,  phi = exp(-u^2 / 2) / sqrt(2 pi)
+ *   EUBO = mu Phi + mu' Phi' + s phi
+ * Gradients, with dk(x, x_i)/dx_d = -c_i (x~_d - x~_i,d) inv_ell_d, x~ = (x - 0.5) o inv_ell, and c12 the derivative weight of
+ * k(x, x'):
+ *   T_x,d   = inv_ell_d ( x~_d sum_i c_x,i w_i - sum_i c_x,i w_i x~_i,d ),   T_x',d likewise with c_x', x~'
+ *   e_d     = c12 (x~_d - x~'_d) inv_ell_d
+ *   ds^2/dx_d = 2 e_d + 2 T_x,d         ds^2/dx'_d = -2 e_d - 2 T_x',d
+ *   grad_x EUBO  = Phi  grad mu(x)  + phi grad_x  s^2 / (2 s)
+ *   grad_x' EUBO = Phi' grad mu(x') + phi grad_x' s^2 / (2 s)
+ * Guard: !(s^2 > 0), or s < 1e-10, or a NaN in the value or in any of the 2D gradient components, gives the value fmax(mu, mu') --
+ * the limit as s -> 0 -- and the zero gradient (of all 2D components).  A collapsed pair (x = x') is therefore stationary and leaves
+ * the maximiser's batch, as the guarded points of expected improvement do.  The gradient is formed, and looked at by the guard,
+ * whether or not it is asked for: a pair's value does not depend on that.
+ * No log form is needed: far below the other option (|u| >~ 38) Phi or Phi' is exactly 0 and that option gets no mean gradient, but
+ * the value carries the other option's mean itself and stays correct.
+ * w and d^T K_y^-1 d are formed from d exactly as the tiled evaluation forms K_y^-1 k and k^T K_y^-1 k from k in the handle's sigma
+ * mode: the explicit inverse (mode 0), or |L^-1 d|^2 and w = L^-T (L^-1 d) (mode 1, the handles of a PreferenceRegressor).
+ * The value's three products and two sums are separate operations (no fused multiply-add), and every other operation is symmetric
+ * in the two options: (x, x') and (x', x) give values within the rounding of the final sum and mirrored gradients.
+ * One lane per pair and fixed summation orders: a pair's bits depend on neither its column, the other pairs of the call, the
+ * candidate chunk nor SLS_COMPACT.  Both calls always take the tiled evaluation (never the single-launch path of small problems,
+ * the zero-copy path or the evaluation slots) and hold the context's lock and the handle's state lock (shared) for the whole call.
+ * Per pass max(128, candidate chunk / 2 rounded down to 128) pairs are evaluated (sls_ctx_set_candidate_chunk). */
+/* pairs: 2D x M column-major, rows 0..D-1 = x, D..2D-1 = x'.  val (M, may be NULL), grad (2D x M, may be NULL).  M = 0 is a no-op;
+ * a NULL handle, NULL pairs or M < 0 is SLS_ERR_INVALID. */
+int sls_eubo_eval(sls_gp* gp, const double* pairs, int M, double* val, double* grad);
+/* sls_acq_maximize over [0,1]^(2D) with EUBO as the objective: starts 2D x S, x_out 2D, x_stars 2D x S; idx_out / y_stars /
+ * start_index_offset / sls_acq_last_stats as sls_acq_maximize.  S < 1 or n_local < 1 is SLS_ERR_INVALID. */
+int sls_eubo_maximize(sls_gp* gp, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts,
+                      long start_index_offset, double* x_out, double* val_out, long* idx_out,
+                      double* x_stars, double* y_stars);
+
 /* ---- multi-GPU maximisation ------------------------------------------------------------------------------
  * FindGlobalSolution's multi-start loop (src/acquisition-function.cpp:121-153) shards over its starts: the iterations share
  * only the const regressor (:125-141).  Every GPU holds a replica of the fitted state, runs a contiguous slice of the starts
@@ -450,8 +494,9 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
  * f_prior(X)), "path_solve" (v = K_y^-1 r), "path_prior" (the random-feature prior of an evaluation), "path_data" (the data term
  * on cross_gram's K*; cross_gram and grad_gemm count under their own names); "mes" (the MES combiner, one launch per evaluation of
  * sls_mes_eval / round of sls_mes_maximize); "logei" (the LogEI combiner, one launch per evaluation / round of a type-2
- * call); "potrf_fallbacks": launches = how often a single-launch
- * factorisation gave up and was recomputed. */
+ * call); "eubo" (the two kernels of the pair objective, pair_diff and eubo_finalize: two launches per pass of sls_eubo_eval /
+ * per pass and round of sls_eubo_maximize; its GEMMs count under "cross_gram", "acq_gemm", "var_gemm", "grad_gemm");
+ * "potrf_fallbacks": launches = how often a single-launch factorisation gave up and was recomputed. */
 int sls_prof_enable(sls_ctx* ctx, int on);
 int sls_prof_reset(sls_ctx* ctx);
 int sls_prof_get(sls_ctx* ctx, const char* name, double* total_ms, long* launches);

@@ -133,6 +133,22 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
           "regressor"_a, "num_max_value_samples"_a = 64, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50,
           "seed"_a = 0ULL, "num_frequencies"_a = 2048);
 
+    // expected utility of the best option of a query pair (acquisition-function.hpp): values for the pairs (points_a.col(m),
+    // points_b.col(m)), and the maximising pair with its value: (x, x', value)
+    m.def("calc_expected_utilities_of_best_option",
+          [](const Regressor& r, const MatrixXd& Xa, const MatrixXd& Xb) {
+              return acquisition_func::CalcExpectedUtilitiesOfBestOption(r, Xa, Xb);
+          },
+          "regressor"_a, "points_a"_a, "points_b"_a);
+    m.def("find_next_query_pair_by_expected_utility",
+          [](const Regressor& r, unsigned num_global_search_iters, unsigned num_local_search_iters, unsigned long long seed) {
+              double     value = 0.0;
+              const auto q =
+                  acquisition_func::FindNextQueryPairByExpectedUtility(r, num_global_search_iters, num_local_search_iters, seed, &value);
+              return std::make_tuple(q.first, q.second, value);
+          },
+          "regressor"_a, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50, "seed"_a = 0ULL);
+
     // DIRECT, then one L-BFGS from its result (acquisition_func::FindNextPointDirect) on such a regressor: (point, value)
     m.def("find_next_point_direct",
           [](const Regressor& r, unsigned num_global_search_iters, unsigned num_local_search_iters, AcquisitionFuncType func_type,
@@ -196,6 +212,8 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
         .def("determine_next_query", &PreferentialBayesianOptimizer::DetermineNextQuery, "num_global_search_iters"_a = 0,
              "num_local_search_iters"_a = 0)
         .def("determine_next_query_by_thompson_sampling", &PreferentialBayesianOptimizer::DetermineNextQueryByThompsonSampling,
+             "seed"_a, "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0)
+        .def("determine_next_query_by_expected_utility", &PreferentialBayesianOptimizer::DetermineNextQueryByExpectedUtility,
              "seed"_a, "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0)
         .def("get_current_options", &PreferentialBayesianOptimizer::GetCurrentOptions)
         .def("get_maximizer", &PreferentialBayesianOptimizer::GetMaximizer)

@@ -64,6 +64,7 @@ EXPORTS = [
     "sls_gp_predict_cov", "sls_gp_sample_posterior", "sls_random_normal",
     "sls_path_create", "sls_path_destroy", "sls_path_eval", "sls_path_maximize",
     "sls_mes_terms", "sls_mes_eval", "sls_mes_maximize", "sls_logei_terms",
+    "sls_eubo_eval", "sls_eubo_maximize",
 ]
 
 
@@ -333,6 +334,33 @@ class GP:
         _ck(lib().sls_mes_maximize(self.h, _p(y_star), y_star.size, _p(starts), S, int(n_local),
                                    C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val),
                                    C.byref(idx), _p(xs) if want_all else None, _p(ys) if want_all else None))
+        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+
+    def eubo_eval(self, pairs, want_grad=True):
+        """Expected utility of the best option E[max(f(x), f(x'))] at the columns of pairs (2D x M: rows 0..D-1 = x, D..2D-1 = x'),
+        sls_eubo_eval; the gradient is 2D x M in the same row order."""
+        pairs = _f(pairs)
+        if pairs.ndim != 2 or pairs.shape[0] != 2 * self.D:
+            raise SlsError(f"eubo_eval: pairs must be 2D x M = {2 * self.D} x M, got {pairs.shape}")
+        M = pairs.shape[1]
+        val = np.empty(M)
+        grad = np.empty((2 * self.D, M), order="F") if want_grad else None
+        _ck(lib().sls_eubo_eval(self.h, _p(pairs), M, _p(val), _p(grad) if want_grad else None))
+        return (val, grad) if want_grad else val
+
+    def eubo_maximize(self, starts, n_local, offset=0, want_all=True, opts=None):
+        """acq_maximize over [0,1]^(2D) with the pair objective of eubo_eval (sls_eubo_maximize): starts 2D x S, x and x_stars have
+        2D rows."""
+        starts = _f(starts)
+        if starts.ndim != 2 or starts.shape[0] != 2 * self.D:
+            raise SlsError(f"eubo_maximize: starts must be 2D x S = {2 * self.D} x S, got {starts.shape}")
+        S = starts.shape[1]
+        x, val, idx = np.empty(2 * self.D), C.c_double(), C.c_long()
+        xs = np.empty((2 * self.D, S), order="F") if want_all else None
+        ys = np.empty(S) if want_all else None
+        _ck(lib().sls_eubo_maximize(self.h, _p(starts), S, int(n_local), C.byref(opts) if opts is not None else None,
+                                    C.c_long(offset), _p(x), C.byref(val), C.byref(idx), _p(xs) if want_all else None,
+                                    _p(ys) if want_all else None))
         return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
 
     def last_stats(self):

@@ -415,6 +415,11 @@ struct sls_gp {
     // L-BFGS state
     DBuf pair_mu, pair_sg, pair_dmu, pair_dsg;
     LbfgsWs lb;   // pooled blocks that live with the handle: a repeated maximisation costs no allocation
+    // the second option's evaluation workspace of the pair objective (sls_eubo_*; the first option uses the blocks above) and the
+    // difference Kd of the two cross-covariance blocks; grown on demand, sized for eubo_np / eubo_chunk
+    DBuf eubo_Ks, eubo_Cs, eubo_XsT, eubo_ns, eubo_parts, eubo_Gs, eubo_Gm, eubo_Kd;
+    int eubo_chunk = 0, eubo_np = 0;
+    HostBuf eubo_best;   // mapped: the pair maximiser's best start (8 + 2D doubles; `sum` holds 8 + D)
     // 0: sigma^2 = a - k^T K^-1 k with the explicit inverse (GaussianProcessRegressor); 1: a - |L^-1 k|^2, the Cholesky solve of
     // PreferenceRegressor (sls_gp_set_sigma_mode)
     int sigma_mode = 0;
@@ -1432,6 +1437,185 @@ extern "C" int sls_mes_maximize(sls_gp* g, const double* y_star, int K, const do
     h2d(g->ctx, sd.p, starts, (size_t)g->D * S);
     const MesSamples mes{ys.p, K};
     maximize_impl(g, nullptr, 0, 0.0, sd.p, S, n_local, opts, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars, &mes);
+    SLS_CATCH
+}
+
+// ---- expected utility of the best option of a query pair (include/sls_hip.h) -----------------------------------------
+// pairs per pass: half the candidate chunk (two cross-covariance blocks per pair), so the workspace stays at what a single-point
+// acquisition uses at the same chunk setting
+static int eubo_pairs_per_pass(const sls_ctx* c) { return std::max(128, c->cand_chunk / 2 / 128 * 128); }
+
+static void ensure_eubo_ws(sls_gp* g, int chunk) {
+    ensure_eval_ws(g, chunk);   // option x: the handle's own blocks
+    if (chunk <= g->eubo_chunk && g->eubo_np == g->Np) return;
+    const size_t Np = g->Np, C = std::max(chunk, g->eubo_np == g->Np ? g->eubo_chunk : 0);
+    const size_t nbt = Np / 128;
+    g->eubo_Ks.ensure(C * Np);
+    if (g->kernel == SLS_KERNEL_ARD_MATERN52) g->eubo_Cs.ensure(C * Np);
+    g->eubo_Kd.ensure(C * Np);
+    g->eubo_parts.ensure(6 * nbt * C);   // mu, ca: one per row tile; kw (not used), cw: one per half row tile
+    g->eubo_Gs.ensure(C * g->Dcols);
+    g->eubo_Gm.ensure(C * g->Dcols);
+    g->eubo_XsT.ensure(C * g->Dcols);
+    g->eubo_ns.ensure(C);
+    g->eubo_chunk = (int)C;
+    g->eubo_np = g->Np;
+}
+
+// EUBO (+ its 2D gradient, grad may be NULL) at S pairs, candidate-major raw coordinates xr[n + r*ldr]: rows 0..D-1 the option x,
+// rows D..2D-1 the option x'.  val / grad candidate-major with leading dimension ldo (grad: 2D rows).  Always the tiled kernels;
+// the gradient products are formed whether or not grad is asked for (the guard looks at them).
+static void eval_pairs(sls_gp* g, const double* xr, long ldr, int S, double* val, double* grad, long ldo) {
+    sls_ctx* c = g->ctx;
+    const int Np = g->Np, N = g->N, D = g->D;
+    const int chunk_max = std::min(round_up(S, 128), eubo_pairs_per_pass(c));
+    ensure_eubo_ws(g, chunk_max);
+    const int nbt = Np / 128;
+    const bool matern = g->kernel == SLS_KERNEL_ARD_MATERN52;
+    const bool solve = g->sigma_mode == 1;
+    if (solve) g->Vs.ensure((size_t)chunk_max * Np);
+    KernelSpec ks{g->kernel, g->a};
+    for (int s0 = 0; s0 < S; s0 += chunk_max) {
+        const int sc = std::min(chunk_max, S - s0);
+        const int Sp = round_up(sc, 128);
+        const long ldk = Sp;
+        double* Ks[2] = {g->Ks.p, g->eubo_Ks.p};
+        double* Cs[2] = {matern ? g->Cs.p : g->Ks.p, matern ? g->eubo_Cs.p : g->eubo_Ks.p};
+        double* XsT[2] = {g->XsT.p, g->eubo_XsT.p};
+        double* ns[2] = {g->ns.p, g->eubo_ns.p};
+        double* Gs[2] = {g->Gs.p, g->eubo_Gs.p};
+        double* Gm[2] = {g->Gm.p, g->eubo_Gm.p};
+        double* mu_part[2] = {g->parts.p, g->eubo_parts.p};
+        double *ca_part[2], *kw_part[2], *cw_part[2];
+        for (int o = 0; o < 2; ++o) {
+            ca_part[o] = mu_part[o] + (size_t)nbt * ldk;
+            kw_part[o] = ca_part[o] + (size_t)nbt * ldk;
+            cw_part[o] = kw_part[o] + (size_t)2 * nbt * ldk;
+        }
+        double* kw_solve = solve ? cw_part[0] + (size_t)2 * nbt * ldk : nullptr;   // the handle's parts block has 10 nbt rows
+        for (int o = 0; o < 2; ++o) {
+            ProfScope ps(c, "cross_gram");
+            launch_prep_cands(c->stream, xr + (size_t)o * D * ldr + s0, ldr, D, sc, g->inv_ell.p, XsT[o], ldk, Sp, g->Dcols, ns[o]);
+            launch_cross_gram(c->stream, XsT[o], ldk, ns[o], Sp, g->XT.p, Np, g->nx.p, Np, N, g->Dp, ks, g->alpha.p, Ks[o], Cs[o], ldk,
+                              mu_part[o], ca_part[o]);
+        }
+        {
+            ProfScope ps(c, "eubo");
+            launch_pair_diff(c->stream, Ks[0], Ks[1], ldk, Np, g->eubo_Kd.p);
+        }
+        if (solve) {
+            // w = K_y^-1 d as L^-T (L^-1 d): V = Kd L^-T once, then the tile kernel with (L^-1)^T in the place of K^-1 (eval_candidates'
+            // solve_grad branch); d^T K_y^-1 d = |L^-1 d|^2 from the triangular contraction
+            {
+                ProfScope ps(c, "acq_gemm");
+                launch_gemm_plain(c->stream, g->eubo_Kd.p, ldk, false, g->Linv.p, Np, false, g->Vs.p, ldk, Sp / 128, Np / 128, Np, 1.0, 0.0);
+            }
+            ProfScope ps(c, "var_gemm");
+            launch_var_gemm(c->stream, g->eubo_Kd.p, ldk, Sp, g->Linv.p, Np, kw_solve, kw_solve + (size_t)2 * nbt * ldk);
+        }
+        int split_first = 0x7fffffff;
+        for (int o = 0; o < 2; ++o) {
+            {
+                // P = C*_o .* W and the c_o . w sums; Cs is never the first operand here, so the tile kernel also forms d . w
+                ProfScope ps(c, "acq_gemm");
+                split_first = launch_acq_gemm(c->stream, solve ? g->Vs.p : g->eubo_Kd.p, Cs[o], ldk, Sp, solve ? g->U.p : g->Kinv.p, Np,
+                                              g->P.p, kw_part[o], cw_part[o], c->d_info + 32);
+            }
+            ProfScope ps(c, "grad_gemm");
+            double* part = nullptr;
+            if (D <= 64 && grad_gemm_wants_split(Sp)) {
+                g->Gpart.ensure((size_t)8 * Sp * 64);
+                part = g->Gpart.p;
+            }
+            launch_grad_gemm(c->stream, g->P.p, Cs[o], ldk, Sp, g->XT.p, g->XaT.p, Np, Np, D <= 64 ? -g->Dcols : g->Dcols, Gs[o], Gm[o], part);
+        }
+        {
+            ProfScope ps(c, "eubo");
+            EuboFinalizeArgs f;
+            f.S = sc; f.D = D; f.nbt = nbt; f.ntm = Sp / 128; f.split_first = split_first; f.kernel = g->kernel; f.ldk = ldk;
+            for (int o = 0; o < 2; ++o) {
+                f.mu_part[o] = mu_part[o]; f.ca_part[o] = ca_part[o]; f.cw_part[o] = cw_part[o];
+                f.Gs[o] = Gs[o]; f.Gm[o] = Gm[o]; f.XsT[o] = XsT[o];
+            }
+            f.kw_part = kw_part[0]; f.kw_solve_part = kw_solve; f.inv_ell = g->inv_ell.p; f.a = g->a;
+            f.ldo = ldo;
+            f.val = val ? val + s0 : nullptr;
+            f.grad = grad ? grad + s0 : nullptr;
+            launch_eubo_finalize(c->stream, f);
+        }
+    }
+}
+
+extern "C" int sls_eubo_eval(sls_gp* g, const double* pairs, int M, double* val, double* grad) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g != nullptr, "sls_eubo_eval: gp is NULL");
+    SLS_REQUIRE(pairs != nullptr, "sls_eubo_eval: pairs is NULL");
+    SLS_REQUIRE(M >= 0, "sls_eubo_eval: M = %d", M);
+    if (M == 0) return SLS_OK;
+    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
+    sls_ctx* c = g->ctx;
+    const int Mp = round_up(M, 128), D2 = 2 * g->D;
+    // host 2D x M column-major -> candidate-major raw coordinates (padding columns at the centre of the box)
+    std::vector<double> t((size_t)Mp * D2, 0.5);
+    for (int m = 0; m < M; ++m)
+        for (int r = 0; r < D2; ++r) t[(size_t)m + (size_t)r * Mp] = pairs[r + (size_t)m * D2];
+    g->raw.ensure((size_t)Mp * D2);
+    h2d(c, g->raw.p, t.data(), (size_t)Mp * D2);
+    sync(c);
+    std::vector<double> unused;   // the kernel always writes the values
+    if (!val) unused.resize(M);
+    EvalOut want;
+    want.val = val ? val : unused.data(); want.grad = grad;
+    const size_t n = eval_block_doubles(want, D2, Mp);
+    g->outv.ensure(n);
+    const EvalOut o = eval_block(want, g->outv.p, D2, Mp);
+    eval_pairs(g, g->raw.p, Mp, M, o.val, o.grad, Mp);
+    std::vector<double> pageable;
+    eval_block_to_host(want, eval_block(want, fetch(g, g->outv.p, n, pageable), D2, Mp), D2, M);
+    SLS_CATCH
+}
+
+extern "C" int sls_eubo_maximize(sls_gp* g, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts,
+                                 long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars,
+                                 double* y_stars) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g != nullptr, "sls_eubo_maximize: gp is NULL");
+    SLS_REQUIRE(starts != nullptr, "sls_eubo_maximize: starts is NULL");
+    SLS_REQUIRE(S >= 1 && n_local >= 1, "sls_eubo_maximize: need S >= 1 and n_local >= 1 (S = %d, n_local = %d)", S, n_local);
+    const sls_lbfgs_opts o = read_lbfgs_opts(opts);
+    SLS_REQUIRE(o.history >= 1 && o.history <= 8, "L-BFGS history must be in 1..8");
+    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
+    sls_ctx* c = g->ctx;
+    // the maximiser of sls_acq_maximize over [0,1]^(2D): every block sized by the number of variables is sized for 2D here (the
+    // optimiser's workspace, the mapped block of the best start, the downloads); the handle's own sizes stay as they are
+    const int Sp = round_up(S, 128), D2 = 2 * g->D;
+    DBuf sd;
+    sd.ensure((size_t)D2 * S);
+    h2d(c, sd.p, starts, (size_t)D2 * S);
+    g->lb.ensure(Sp, o.history, D2);
+    g->eubo_best.ensure(c, (size_t)(8 + D2) * sizeof(double), true);
+    g->stat_issued = 0; g->stat_cap = (long)S * n_local; g->stat_rounds = 0; g->stat_live_end = 0;
+    LbfgsState st = g->lb.state(S, D2, o);
+    LockstepStats ls;
+    lockstep_rounds(c, st, g->lb, sd.p, S, n_local,
+                    [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
+                        eval_pairs(g, trial, ld, nlive, val, grad, ld);   // the trial block of x' is trial + D ld
+                    },
+                    &ls);
+    g->stat_issued = ls.issued; g->stat_rounds = ls.rounds; g->stat_live_end = ls.live_end;
+    launch_argmax_neg_gather(c->stream, st.f, S, st.x, Sp, D2, g->eubo_best.dev, nullptr);
+    sync(c);
+    const double* best = g->eubo_best.host;
+    if (val_out) *val_out = best[0];
+    if (idx_out) *idx_out = (long)best[1] + start_index_offset;
+    if (x_out) std::copy(best + 8, best + 8 + D2, x_out);
+    if (x_stars) download_cm(g, st.x, S, Sp, D2, x_stars);
+    if (y_stars) {
+        download_cm(g, st.f, S, Sp, 1, y_stars);
+        for (int i = 0; i < S; ++i) y_stars[i] = -y_stars[i];
+    }
     SLS_CATCH
 }
 

@@ -246,6 +246,29 @@ void launch_logei_combine(hipStream_t s, int S, int D, long ld, const double* mu
 // log_h[i], b1[i], b2[i] of u[i], i < n; any output may be NULL
 void launch_logei_terms(hipStream_t s, const double* u, long n, double* log_h, double* b1, double* b2);
 
+// ---- kernels_eubo.hip: expected utility of the best option of a query pair (sls_eubo_*) ----------------------------------
+// Kd[n + i*ldk] = Ka[n + i*ldk] - Kb[n + i*ldk] over the whole padded block (ldk x Np doubles, both multiples of 128)
+void launch_pair_diff(hipStream_t s, const double* Ka, const double* Kb, long ldk, int Np, double* Kd);
+// The pair objective on the reduced sums (include/sls_hip.h).  Index 0 of every two-element member is the option x, index 1 is x'.
+// mu_part / ca_part: cross_gram's partials of each option; kw_part: acq_gemm's k.w partials of d = k_x - k_x' (d^T K_y^-1 d);
+// cw_part: acq_gemm's c.w partials of (Kd, C*_x) and (Kd, C*_x'); Gs / Gm: grad_gemm's products of each option.  Half-tile slots
+// from split_first on as in FinalizeArgs.  kw_solve_part != nullptr: d^T K_y^-1 d = |L^-1 d|^2 from var_gemm's sums instead.
+struct EuboFinalizeArgs {
+    int S, D, nbt;            // pairs in this chunk, dims of ONE option, number of 128-row tiles of i
+    int ntm, split_first;
+    int kernel;               // SLS_KERNEL_*: k(x, x') and its derivative weight come from kernel_kc
+    long ldk;
+    const double *mu_part[2], *ca_part[2], *cw_part[2], *Gs[2], *Gm[2], *XsT[2];
+    const double *kw_part, *inv_ell;
+    const double* kw_solve_part = nullptr;
+    double a;
+    // outputs, candidate-major with leading dimension ldo, offset already applied: val (may be NULL), grad (may be NULL): rows
+    // 0..D-1 the gradient in x, rows D..2D-1 the gradient in x'
+    long ldo;
+    double *val, *grad;
+};
+void launch_eubo_finalize(hipStream_t s, const EuboFinalizeArgs& a);
+
 struct LbfgsState {
     int S, D, m;
     long ld;                  // Sp

@@ -421,4 +421,78 @@ namespace sequential_line_search
             regressor, max_values, SeededStarts(regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed),
             num_local_search_iters, value);
     }
+
+    // ---- expected utility of the best option of a query pair (include/sls_hip.h sls_eubo_*; Astudillo et al. 2023) ----
+    namespace
+    {
+        sls_gp* RequireHandleForPairs(const Regressor& r)
+        {
+            sls_gp* h = r.GetDeviceHandle();
+            if (!h)
+                throw std::invalid_argument("acquisition_func: the expected utility of the best option needs a device-resident regressor "
+                                            "(GaussianProcessRegressor / PreferenceRegressor); there is no host fallback");
+            return h;
+        }
+    } // namespace
+
+    VectorXd acquisition_func::CalcExpectedUtilitiesOfBestOption(const Regressor& regressor, const MatrixXd& Xa, const MatrixXd& Xb,
+                                                                 MatrixXd* grad_a, MatrixXd* grad_b)
+    {
+        sls_gp* h = RequireHandleForPairs(regressor);
+        if (Xa.rows() != Xb.rows() || Xa.cols() != Xb.cols())
+            throw std::invalid_argument("CalcExpectedUtilitiesOfBestOption: Xa and Xb must have the same shape");
+        const long D = Xa.rows(), M = Xa.cols();
+        MatrixXd   pairs(2 * D, M);
+        for (long m = 0; m < M; ++m)
+            for (long d = 0; d < D; ++d)
+            {
+                pairs(d, m)     = Xa(d, m);
+                pairs(D + d, m) = Xb(d, m);
+            }
+        VectorXd       v = VectorXd::Zero(M);
+        const bool     want_grad = grad_a || grad_b;
+        MatrixXd       g(want_grad ? 2 * D : 0, want_grad ? M : 0);
+        device::Check(sls_eubo_eval(h, pairs.data(), static_cast<int>(M), v.data(), want_grad ? g.data() : nullptr), "sls_eubo_eval");
+        for (int o = 0; o < 2; ++o)
+        {
+            MatrixXd* out = o == 0 ? grad_a : grad_b;
+            if (!out) continue;
+            *out = MatrixXd(D, M);
+            for (long m = 0; m < M; ++m)
+                for (long d = 0; d < D; ++d) (*out)(d, m) = g(o * D + d, m);
+        }
+        return v;
+    }
+
+    std::pair<VectorXd, VectorXd> acquisition_func::FindNextQueryPairByExpectedUtilityFromStarts(const Regressor& regressor,
+                                                                                                const MatrixXd&  starts,
+                                                                                                const unsigned   num_local_search_iters,
+                                                                                                double*          value)
+    {
+        sls_gp*    h = RequireHandleForPairs(regressor);
+        const long D = regressor.GetNumDims();
+        if (starts.rows() != 2 * D || starts.cols() < 1)
+            throw std::invalid_argument("FindNextQueryPairByExpectedUtilityFromStarts: starts must be 2D x S with S >= 1");
+        VectorXd             x(2 * D);
+        double               v     = 0.0;
+        long                 idx   = 0;
+        const sls_lbfgs_opts lopts = LocalSearchOpts();   // GetLocalSearchTolerances
+        device::Check(sls_eubo_maximize(h, starts.data(), static_cast<int>(starts.cols()),
+                                        std::max(1, static_cast<int>(num_local_search_iters)), &lopts, 0, x.data(), &v, &idx, nullptr,
+                                        nullptr),
+                      "sls_eubo_maximize");
+        if (value) *value = v;
+        return std::make_pair(x.segment(0, D), x.segment(D, D));
+    }
+
+    std::pair<VectorXd, VectorXd> acquisition_func::FindNextQueryPairByExpectedUtility(const Regressor& regressor,
+                                                                                      const unsigned   num_global_search_iters,
+                                                                                      const unsigned   num_local_search_iters,
+                                                                                      const unsigned long long seed, double* value)
+    {
+        RequireHandleForPairs(regressor);
+        return FindNextQueryPairByExpectedUtilityFromStarts(
+            regressor, SeededStarts(2 * regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed), num_local_search_iters,
+            value);
+    }
 } // namespace sequential_line_search

@@ -110,6 +110,24 @@ namespace sequential_line_search
                        });
     }
 
+    void PreferentialBayesianOptimizer::DetermineNextQueryByExpectedUtility(const unsigned long long seed,
+                                                                            const int num_global_search_iters,
+                                                                            const int num_local_search_iters)
+    {
+        if (m_num_options != 2)
+            throw std::invalid_argument("PreferentialBayesianOptimizer::DetermineNextQueryByExpectedUtility: the pair criterion needs "
+                                        "num_options == 2");
+        if (!m_regressor)
+            throw std::logic_error("PreferentialBayesianOptimizer::DetermineNextQueryByExpectedUtility called before any feedback");
+        const int num_dims = static_cast<int>(GetMaximizer().size());
+        const int n_global = num_global_search_iters > 0 ? num_global_search_iters : 500 * num_dims;
+        const int n_local  = num_local_search_iters > 0 ? num_local_search_iters : 10 * num_dims;
+        const std::pair<VectorXd, VectorXd> q = acquisition_func::FindNextQueryPairByExpectedUtility(*m_regressor, n_global, n_local, seed);
+        const bool first_is_better = m_regressor->PredictMu(q.first) >= m_regressor->PredictMu(q.second);
+        m_current_options[0] = first_is_better ? q.first : q.second;
+        m_current_options[1] = first_is_better ? q.second : q.first;
+    }
+
     VectorXd PreferentialBayesianOptimizer::GetMaximizer() const { return m_current_options[0]; }
 
     double PreferentialBayesianOptimizer::GetPreferenceValueMean(const VectorXd& point) const
