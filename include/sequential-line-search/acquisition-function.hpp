@@ -158,6 +158,28 @@ namespace sequential_line_search
                                                                                                  const Eigen::MatrixXd& starts,
                                                                                                  const unsigned num_local_search_iters,
                                                                                                  double*        value = nullptr);
+
+        /// A whole query of num_options >= 1 options by the expected utility of the best option on posterior draws (not in the
+        /// reference; qEUBO, Astudillo et al. 2023, include/sls_hip.h sls_qeubo_*): num_draws pathwise posterior draws (stream
+        /// `seed`, num_frequencies random features) fix the estimator (1 / num_draws) sum_s max_i f_s(x_i), which is maximised over
+        /// [0,1]^(num_options D) jointly: one L-BFGS of num_local_search_iters evaluations (the tolerances of
+        /// GetLocalSearchTolerances) from each of num_global_search_iters uniform starts of the generator
+        /// FindNextQueryPairByExpectedUtility uses, seeded with `seed`, all in lock step on the device.  The same seed gives the same
+        /// query.  value (may be nullptr) receives the utility there.  Device-resident regressors only (std::invalid_argument
+        /// otherwise).
+        std::vector<Eigen::VectorXd> FindNextQueryByExpectedUtility(const Regressor& regressor, const int num_options,
+                                                                    const unsigned num_draws = 256,
+                                                                    const unsigned num_global_search_iters = 100,
+                                                                    const unsigned num_local_search_iters = 50,
+                                                                    const unsigned long long seed = 0, const int num_frequencies = 2048,
+                                                                    double* value = nullptr);
+        /// The same from an explicit start set ((num_options D) x S: rows iD..iD+D-1 start option i).
+        std::vector<Eigen::VectorXd> FindNextQueryByExpectedUtilityFromStarts(const Regressor& regressor, const int num_options,
+                                                                              const Eigen::MatrixXd& starts,
+                                                                              const unsigned num_draws = 256,
+                                                                              const unsigned num_local_search_iters = 50,
+                                                                              const unsigned long long seed = 0,
+                                                                              const int num_frequencies = 2048, double* value = nullptr);
     } // namespace acquisition_func
 } // namespace sequential_line_search
 

@@ -199,6 +199,26 @@ namespace Eigen
         Index               m_r, m_c;
         std::vector<double> m_v;
     };
+
+    /// Integer matrix (column-major): counts that come back from the device (win counts of a query's options).
+    class MatrixXi
+    {
+    public:
+        MatrixXi() : m_r(0), m_c(0) {}
+        MatrixXi(Index r, Index c) : m_r(r), m_c(c), m_v(static_cast<size_t>(r * c), 0) {}
+        static MatrixXi Zero(Index r, Index c) { return MatrixXi(r, c); }
+        Index      rows() const { return m_r; }
+        Index      cols() const { return m_c; }
+        Index      size() const { return m_r * m_c; }
+        int*       data() { return m_v.data(); }
+        const int* data() const { return m_v.data(); }
+        int&       operator()(Index i, Index j) { return m_v[static_cast<size_t>(i + j * m_r)]; }
+        int        operator()(Index i, Index j) const { return m_v[static_cast<size_t>(i + j * m_r)]; }
+
+    private:
+        Index            m_r, m_c;
+        std::vector<int> m_v;
+    };
 } // namespace Eigen
 
 #endif // !SLS_HAVE_REAL_EIGEN

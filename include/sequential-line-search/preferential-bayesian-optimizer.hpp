@@ -60,6 +60,12 @@ namespace sequential_line_search
         /// arguments select the same heuristic as DetermineNextQuery.
         void DetermineNextQueryByExpectedUtility(const unsigned long long seed, const int num_global_search_iters = 0,
                                                  const int num_local_search_iters = 0);
+        /// Opt-in alternative for ANY num_options >= 2: ALL options are the joint maximiser of the expected utility of the best
+        /// option on num_draws posterior draws (acquisition_func::FindNextQueryByExpectedUtility with draw and start stream `seed`).
+        /// The option with the largest posterior mean is moved to position 0 (GetMaximizer()); the others keep their order.  Before
+        /// any feedback it throws as DetermineNextQuery does; non-positive iteration counts select the same heuristic.
+        void DetermineNextQueryByExpectedUtilityOfDraws(const unsigned long long seed, const int num_draws = 256,
+                                                        const int num_global_search_iters = 0, const int num_local_search_iters = 0);
 
         const std::vector<Eigen::VectorXd>& GetCurrentOptions() const { return m_current_options; }
         Eigen::VectorXd                     GetMaximizer() const;

@@ -92,6 +92,19 @@ namespace sequential_line_search
         /// best end point.  values (may be nullptr) receives the draws' maxima.
         std::vector<Eigen::VectorXd> Maximize(const Eigen::MatrixXd& starts, unsigned num_local_search_iters,
                                               Eigen::VectorXd* values = nullptr) const;
+        /// Expected utility of the best of q = options.size() options on these draws (qEUBO, Astudillo et al. 2023; include/sls_hip.h
+        /// sls_qeubo_*): set m is (options[0].col(m), .., options[q-1].col(m)), every options[i] D x M, 1 <= q <= 16.  Returns the M
+        /// values; grads (may be nullptr) receives q matrices D x M, the gradient with respect to each option; win_counts (may be
+        /// nullptr) q x M, the number of draws each option wins (win_counts / GetNumDraws() estimates the probability that it is
+        /// chosen).  One device pass.
+        Eigen::VectorXd CalcExpectedUtilitiesOfBestOption(const std::vector<Eigen::MatrixXd>& options,
+                                                          std::vector<Eigen::MatrixXd>* grads = nullptr,
+                                                          Eigen::MatrixXi* win_counts = nullptr) const;
+        /// Maximiser of that utility over [0,1]^(qD): starts is (num_options D) x S, rows iD..iD+D-1 start option i; one lock-step
+        /// bounded L-BFGS of num_local_search_iters evaluations per start (the acquisition maximiser's local search tolerances),
+        /// the best end point split into its num_options options.  value (may be nullptr) receives the utility there.
+        std::vector<Eigen::VectorXd> MaximizeExpectedUtilityOfBestOption(int num_options, const Eigen::MatrixXd& starts,
+                                                                         unsigned num_local_search_iters, double* value = nullptr) const;
 
     private:
         sls_path* m_path      = nullptr;

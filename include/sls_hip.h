@@ -371,6 +371,46 @@ int sls_eubo_maximize(sls_gp* gp, const double* starts, int S, int n_local, cons
                       long start_index_offset, double* x_out, double* val_out, long* idx_out,
                       double* x_stars, double* y_stars);
 
+/* ---- expected utility of the best of q options on posterior draws (not in the reference) -----------------------------------
+ * qEUBO (Astudillo et al., AISTATS 2023) for any number of options: E[ max_i f(x_i) ] has no closed form beyond q = 2; the estimator
+ * is a sample average over FIXED posterior draws, maximised as a deterministic function.  The draws are those of a path object p
+ * (n_draws = S draws f_s, F frequencies): they share one feature basis and are linear in their weights (W, V).  For a set of q
+ * options (x_0..x_{q-1}), each in [0,1]^D:
+ *   v_{i,s} = f_s(x_i)                                  (the function sls_path_eval evaluates; formed here on tile GEMMs, see below)
+ *   i*(s)   = the LOWEST i with v_{i,s} = max_j v_{j,s}  (strictly-greater scan over i = 0..q-1: first wins on ties)
+ *   wins_i  = #{ s : i*(s) = i }
+ *   qEUBO   = ( sum_s v_{i*(s),s} ) / S                  (one lane per set, from zero, increasing s, ONE division at the end)
+ *   m_i     = 0/1 indicator vector of { s : i*(s) = i }  (length S; padded draws are 0)
+ *   Wbar_i  = W m_i  (2F),   Vbar_i = V m_i  (N)         (aggregated weights: plain sums of the winners' columns)
+ *   grad_{x_i} qEUBO = ( grad fbar_i(x_i) ) / S,  fbar_i = the path function with weights (Wbar_i, Vbar_i)
+ * An option that wins no draw gets an exactly zero gradient; q = 1 gives the mean of the draws.  wins_i / S estimates the probability
+ * that the user picks option i.
+ * Guard: a NaN among the set's q S values or its qD gradient components gives the value SLS_QEUBO_FLOOR (finite for the reasons
+ * SLS_LOG_EI_FLOOR is) and the zero gradient.  The gradient is formed, and looked at by the guard, whether or not it is asked for.
+ * Route per pass: cross_gram for the q points of every set; every draw at every point as Phi^T W + K* V on the tile GEMM (so the
+ * summation order differs from sls_path_eval's gathered data term: the two agree to rounding, not to the bit); one lane per set picks
+ * the winners and writes the 0/1 mask; Wbar = W mask and Vbar = V mask on the tile GEMM (depth n_draws); the gathered route of
+ * sls_path_eval on (Wbar, Vbar) gives grad fbar_i(x_i).  No q x q factorisation per set.
+ * A set's bits depend on neither its column, the other sets of the call, the number of sets per pass nor SLS_COMPACT.  Permuting the
+ * options of a set permutes wins and the gradient blocks and leaves the value's bits unchanged.
+ * Sets per pass: points = min(candidate chunk (sls_ctx_set_candidate_chunk, counted in POINTS), 2^26 / max(Rp, Np + 2 Fp)) with Np, Fp,
+ * Rp = N, F, n_draws rounded up to 128 -- every block of a pass (values and mask: points x Rp; Wbar, Vbar; K*, C*, [Pm | G]) stays
+ * below 2^26 doubles -- and sets = max(128, points / q rounded down to 128).  The floor of 128 sets (one tile) is the one exception to
+ * both bounds: a pass then holds 128 q points whatever the candidate chunk or the 2^26 rule say (a chunk below 128 q; or q = 16 with
+ * Np + 2 Fp > 32768), and its blocks may exceed 2^26 doubles (at most 2048 points; indices are 64-bit).
+ * Locks are those of sls_path_eval / sls_path_maximize; a path whose handle was refitted, grown or switched in sigma mode is refused
+ * (SLS_ERR_INVALID), as by the other sls_path_* calls. */
+#define SLS_QEUBO_MAX_OPTIONS 16
+#define SLS_QEUBO_FLOOR (-1.0e300)
+/* sets: qD x M column-major, rows iD..iD+D-1 = option i.  val (M), grad (qD x M), wins (q x M ints): each may be NULL.  M = 0 is a
+ * no-op; q outside 1..SLS_QEUBO_MAX_OPTIONS, M < 0, NULL p or NULL sets is SLS_ERR_INVALID. */
+int sls_qeubo_eval(sls_path* p, int q, const double* sets, int M, double* val, double* grad, int* wins);
+/* sls_acq_maximize over [0,1]^(qD) with qEUBO as the objective: starts qD x S_starts, x_out qD, x_stars qD x S_starts; idx_out /
+ * y_stars / start_index_offset / sls_acq_last_stats (of the path's handle) as sls_acq_maximize.  S_starts < 1 or n_local < 1 is
+ * SLS_ERR_INVALID. */
+int sls_qeubo_maximize(sls_path* p, int q, const double* starts, int S_starts, int n_local, const sls_lbfgs_opts* opts,
+                       long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars, double* y_stars);
+
 /* ---- multi-GPU maximisation ------------------------------------------------------------------------------
  * FindGlobalSolution's multi-start loop (src/acquisition-function.cpp:121-153) shards over its starts: the iterations share
  * only the const regressor (:125-141).  Every GPU holds a replica of the fitted state, runs a contiguous slice of the starts
@@ -496,6 +536,10 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
  * sls_mes_eval / round of sls_mes_maximize); "logei" (the LogEI combiner, one launch per evaluation / round of a type-2
  * call); "eubo" (the two kernels of the pair objective, pair_diff and eubo_finalize: two launches per pass of sls_eubo_eval /
  * per pass and round of sls_eubo_maximize; its GEMMs count under "cross_gram", "acq_gemm", "var_gemm", "grad_gemm");
+ * "qeubo" (qeubo_select and qeubo_finish: two launches per pass of sls_qeubo_eval / per pass and round of sls_qeubo_maximize) and
+ * "qeubo_agg" (its two aggregation GEMMs Wbar = W mask, Vbar = V mask), "qeubo_data_gemm" (the data term K* V of the every-draw values
+ * on the tile GEMM, where sls_path_eval runs path_data's gathered dot; the reused stages count under "cross_gram", "path_prior",
+ * "path_data", "path_grad_gemm");
  * "potrf_fallbacks": launches = how often a single-launch factorisation gave up and was recomputed. */
 int sls_prof_enable(sls_ctx* ctx, int on);
 int sls_prof_reset(sls_ctx* ctx);

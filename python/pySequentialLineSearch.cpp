@@ -67,6 +67,26 @@ namespace pybind11
                 return a.release();
             }
         };
+        template <> struct type_caster<Eigen::MatrixXi>
+        {
+            PYBIND11_TYPE_CASTER(Eigen::MatrixXi, const_name("numpy.ndarray[int32[m, n]]"));
+            bool load(handle src, bool)
+            {
+                auto a = array_t<int, array::forcecast>::ensure(src);
+                if (!a || a.ndim() != 2) return false;
+                value = Eigen::MatrixXi(a.shape(0), a.shape(1));
+                for (ssize_t i = 0; i < a.shape(0); ++i)
+                    for (ssize_t j = 0; j < a.shape(1); ++j) value(i, j) = a.at(i, j);
+                return true;
+            }
+            static handle cast(const Eigen::MatrixXi& m, return_value_policy, handle)
+            {
+                array_t<int> a({m.rows(), m.cols()});
+                for (long i = 0; i < m.rows(); ++i)
+                    for (long j = 0; j < m.cols(); ++j) a.mutable_at(i, j) = m(i, j);
+                return a.release();
+            }
+        };
     } // namespace detail
 } // namespace pybind11
 #else
@@ -149,6 +169,53 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
           },
           "regressor"_a, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50, "seed"_a = 0ULL);
 
+    // expected utility of the best of q options on posterior draws (regressor.hpp, acquisition-function.hpp): the draws as an object
+    // -- calc_... returns (values, [gradient per option], win counts q x M), maximize_... (options, value) -- and the whole query
+    // with its value: (options, value)
+    py::class_<PosteriorFunctionSamples>(m, "PosteriorFunctionSamples")
+        .def("get_num_draws", &PosteriorFunctionSamples::GetNumDraws)
+        .def("evaluate", &PosteriorFunctionSamples::Evaluate, "points"_a)
+        .def("calc_expected_utilities_of_best_option",
+             [](const PosteriorFunctionSamples& s, const std::vector<MatrixXd>& options) {
+                 std::vector<MatrixXd> grads;
+                 Eigen::MatrixXi       wins;
+                 const VectorXd        v = s.CalcExpectedUtilitiesOfBestOption(options, &grads, &wins);
+                 return std::make_tuple(v, grads, wins);
+             },
+             "options"_a)
+        .def("maximize_expected_utility_of_best_option",
+             [](const PosteriorFunctionSamples& s, int num_options, const MatrixXd& starts, unsigned num_local_search_iters) {
+                 double     value = 0.0;
+                 const auto q     = s.MaximizeExpectedUtilityOfBestOption(num_options, starts, num_local_search_iters, &value);
+                 return std::make_pair(q, value);
+             },
+             "num_options"_a, "starts"_a, "num_local_search_iters"_a = 50);
+    m.def("sample_posterior_functions",
+          [](const Regressor& r, int num_draws, unsigned long long seed, int num_frequencies) {
+              return r.SamplePosteriorFunctions(num_draws, seed, num_frequencies);
+          },
+          "regressor"_a, "num_draws"_a, "seed"_a = 0ULL, "num_frequencies"_a = 2048, py::keep_alive<0, 1>());
+    m.def("find_next_query_by_expected_utility",
+          [](const Regressor& r, int num_options, unsigned num_draws, unsigned num_global_search_iters, unsigned num_local_search_iters,
+             unsigned long long seed, int num_frequencies) {
+              double     value = 0.0;
+              const auto q     = acquisition_func::FindNextQueryByExpectedUtility(r, num_options, num_draws, num_global_search_iters,
+                                                                              num_local_search_iters, seed, num_frequencies, &value);
+              return std::make_pair(q, value);
+          },
+          "regressor"_a, "num_options"_a, "num_draws"_a = 256, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50,
+          "seed"_a = 0ULL, "num_frequencies"_a = 2048);
+    m.def("find_next_query_by_expected_utility_from_starts",
+          [](const Regressor& r, int num_options, const MatrixXd& starts, unsigned num_draws, unsigned num_local_search_iters,
+             unsigned long long seed, int num_frequencies) {
+              double     value = 0.0;
+              const auto q     = acquisition_func::FindNextQueryByExpectedUtilityFromStarts(r, num_options, starts, num_draws,
+                                                                                        num_local_search_iters, seed, num_frequencies, &value);
+              return std::make_pair(q, value);
+          },
+          "regressor"_a, "num_options"_a, "starts"_a, "num_draws"_a = 256, "num_local_search_iters"_a = 50, "seed"_a = 0ULL,
+          "num_frequencies"_a = 2048);
+
     // DIRECT, then one L-BFGS from its result (acquisition_func::FindNextPointDirect) on such a regressor: (point, value)
     m.def("find_next_point_direct",
           [](const Regressor& r, unsigned num_global_search_iters, unsigned num_local_search_iters, AcquisitionFuncType func_type,
@@ -215,6 +282,8 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
              "seed"_a, "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0)
         .def("determine_next_query_by_expected_utility", &PreferentialBayesianOptimizer::DetermineNextQueryByExpectedUtility,
              "seed"_a, "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0)
+        .def("determine_next_query_by_expected_utility_of_draws", &PreferentialBayesianOptimizer::DetermineNextQueryByExpectedUtilityOfDraws,
+             "seed"_a, "num_draws"_a = 256, "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0)
         .def("get_current_options", &PreferentialBayesianOptimizer::GetCurrentOptions)
         .def("get_maximizer", &PreferentialBayesianOptimizer::GetMaximizer)
         .def("get_preference_value_mean", &PreferentialBayesianOptimizer::GetPreferenceValueMean, "point"_a)

@@ -64,7 +64,7 @@ EXPORTS = [
     "sls_gp_predict_cov", "sls_gp_sample_posterior", "sls_random_normal",
     "sls_path_create", "sls_path_destroy", "sls_path_eval", "sls_path_maximize",
     "sls_mes_terms", "sls_mes_eval", "sls_mes_maximize", "sls_logei_terms",
-    "sls_eubo_eval", "sls_eubo_maximize",
+    "sls_eubo_eval", "sls_eubo_maximize", "sls_qeubo_eval", "sls_qeubo_maximize",
 ]
 
 
@@ -373,6 +373,9 @@ class GP:
         _ck(lib().sls_gp_refit_dev(self.h, C.c_void_p(X_dev_ptr), C.c_void_p(y_dev_ptr)))
 
 
+QEUBO_MAX_OPTIONS = 16   # SLS_QEUBO_MAX_OPTIONS
+
+
 class PathSamples:
     """n_draws pathwise posterior function draws of a fitted GP handle (sls_path_*): F = n_freq shared random frequencies, normal
     stream `seed`.  A draw can be evaluated anywhere and maximised over [0,1]^D (Thompson sampling)."""
@@ -425,6 +428,43 @@ class PathSamples:
         _ck(lib().sls_path_maximize(self.h, _p(starts), S, int(n_local), C.byref(opts) if opts is not None else None, _p(x), _p(val),
                                     idx.ctypes.data_as(C.POINTER(C.c_long))))
         return dict(x=x, value=val, index=idx)
+
+    def qeubo_eval(self, sets, q, want_grad=True, want_wins=False):
+        """Expected utility of the best of q options on the draws (sls_qeubo_eval) at the columns of sets (qD x M: rows iD..iD+D-1 =
+        option i): values (M,), then with want_grad the gradient (qD, M), then with want_wins the win counts (q, M) int32."""
+        sets = _f(sets)
+        q = int(q)
+        if not 1 <= q <= QEUBO_MAX_OPTIONS:
+            raise SlsError(f"qeubo_eval: q = {q} (1 .. {QEUBO_MAX_OPTIONS})")
+        if sets.ndim != 2 or sets.shape[0] != q * self.D:
+            raise SlsError(f"qeubo_eval: sets must be qD x M = {q * self.D} x M, got {sets.shape}")
+        M = sets.shape[1]
+        val = np.empty(M)
+        grad = np.empty((q * self.D, M), order="F") if want_grad else None
+        wins = np.zeros((q, M), dtype=np.int32, order="F") if want_wins else None
+        _ck(lib().sls_qeubo_eval(self.h, q, _p(sets), M, _p(val), _p(grad) if want_grad else None,
+                                 wins.ctypes.data_as(C.POINTER(C.c_int)) if want_wins else None))
+        out = (val,) + ((grad,) if want_grad else ()) + ((wins,) if want_wins else ())
+        return out if len(out) > 1 else val
+
+    def qeubo_maximize(self, starts, q, n_local, offset=0, want_all=True, opts=None):
+        """acq_maximize over [0,1]^(qD) with the set objective of qeubo_eval (sls_qeubo_maximize): starts qD x S, x and x_stars have
+        qD rows.  GP.last_stats() of the path's handle reports the run."""
+        starts = _f(starts)
+        q = int(q)
+        if not 1 <= q <= QEUBO_MAX_OPTIONS:
+            raise SlsError(f"qeubo_maximize: q = {q} (1 .. {QEUBO_MAX_OPTIONS})")
+        if starts.ndim != 2 or starts.shape[0] != q * self.D:
+            raise SlsError(f"qeubo_maximize: starts must be qD x S = {q * self.D} x S, got {starts.shape}")
+        S = starts.shape[1]
+        rows = starts.shape[0]
+        x, val, idx = np.empty(rows), C.c_double(), C.c_long()
+        xs = np.empty((rows, S), order="F") if want_all else None
+        ys = np.empty(S) if want_all else None
+        _ck(lib().sls_qeubo_maximize(self.h, q, _p(starts), S, int(n_local), C.byref(opts) if opts is not None else None,
+                                     C.c_long(offset), _p(x), C.byref(val), C.byref(idx), _p(xs) if want_all else None,
+                                     _p(ys) if want_all else None))
+        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
 
 
 class PrefCfg(C.Structure):

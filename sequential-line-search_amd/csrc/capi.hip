@@ -620,6 +620,9 @@ GpView gp_view(sls_gp* g) {
     v.state = &g->state_mtx;
     return v;
 }
+void gp_set_acq_stats(sls_gp* g, long issued, long cap, int rounds, int live_end) {
+    g->stat_issued = issued; g->stat_cap = cap; g->stat_rounds = rounds; g->stat_live_end = live_end;
+}
 }  // namespace slsk
 
 extern "C" int sls_gp_generation(sls_gp* g, long* generation) {

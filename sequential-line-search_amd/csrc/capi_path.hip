@@ -1,6 +1,6 @@
-// C-ABI of the pathwise posterior function draws (include/sls_hip.h: sls_path_*): host orchestration of kernels_path.hip, the
-// cross Gram / gradient products of kernels_gram.hip / kernels_acq.hip, the block solve of kernels_tri.hip and the lock-step
-// L-BFGS rounds of lbfgs_driver.hpp.  No CPU fallback.
+// C-ABI of the pathwise posterior function draws (include/sls_hip.h: sls_path_*, and sls_qeubo_* on them): host orchestration of
+// kernels_path.hip and kernels_qeubo.hip, the cross Gram / gradient products of kernels_gram.hip / kernels_acq.hip, the tile GEMM
+// and block solve of kernels_tri.hip and the lock-step L-BFGS rounds of lbfgs_driver.hpp.  No CPU fallback.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -275,6 +275,232 @@ extern "C" int sls_path_maximize(sls_path* p, const double* starts, int S, int n
         if (val_out) val_out[s] = b[0];
         if (idx_out) idx_out[s] = (long)b[1];
         if (x_out) std::copy(b + 2, b + 2 + D, x_out + (size_t)s * D);
+    }
+    SLS_CATCH
+}
+
+// ---- expected utility of the best of q options on the draws (include/sls_hip.h) ---------------------------------------------
+namespace {
+
+// Sets per pass.  points = q sets; every points-sized block -- values / mask (points x Rp), Wbar (2Fp x points), Vbar (Np x points),
+// K*, C* (points x Np), [Pm | G] (points x (Np + 2Fp): the features of the every-draw form use G's 2Fp columns) -- stays below 2^26
+// doubles, and points stay within the context's candidate chunk; whole 128-set tiles, never fewer than one.  That floor is the ONE
+// exception to both bounds: a pass then holds 128 q points (at most 2048) whatever they say -- a candidate chunk below 128 q, or
+// max(Rp, Np + 2 Fp) > 2^26 / (128 q) (e.g. q = 16 with Np + 2 Fp > 32768).  Blocks may then exceed 2^26 doubles; every index into
+// them is a long, so the bound is one on memory, not on addressing (at most 2048 x (8192 + 2 x 16384) doubles = 640 MB for [Pm | G]
+// at the largest N this library factorises).
+int qeubo_sets_per_pass(const sls_ctx* c, int q, int Np, int Fp, int Rp) {
+    const int points = std::min(c->cand_chunk, (1 << 26) / std::max(Rp, Np + 2 * Fp));
+    return std::max(128, points / q / 128 * 128);
+}
+
+struct QeuboWs {
+    DBuf XsT, ns, Ks, Cs, PG, csum, vpart, Gt, B2, Gpart, VM, Wbar, Vbar, sum, fbar, gpt, badb, identb;
+    bool b2_ready = false;
+    int* bad = nullptr;     // one flag per set of the pass
+    int* ident = nullptr;   // ident[j] = j: point j is evaluated under aggregated column j
+    int ident_n = 0;
+    void ensure(sls_ctx* c, const sls_path* p, const GpView& g, int Pp, int Sp) {
+        const size_t P = Pp, Np = g.Np, Fp = p->Fp;
+        XsT.ensure(P * g.Dcols);
+        ns.ensure(P);
+        Ks.ensure(P * Np);
+        if (g.kernel == SLS_KERNEL_ARD_MATERN52) Cs.ensure(P * Np);
+        PG.ensure(P * (Np + 2 * Fp));
+        csum.ensure(P);
+        vpart.ensure(P * (Fp / 128));
+        Gt.ensure(P * g.Dcols);
+        VM.ensure(P * p->Rp);
+        Wbar.ensure(2 * Fp * P);
+        Vbar.ensure(Np * P);
+        sum.ensure(Sp);
+        fbar.ensure(P);
+        gpt.ensure(P * g.D);
+        bad = ints(badb, (size_t)Sp);
+        if (Pp > ident_n) {
+            ident = ints(identb, (size_t)Pp);
+            launch_path_draw_of_live(c->stream, nullptr, Pp, 1, ident);
+            ident_n = Pp;
+        }
+    }
+};
+
+// qEUBO (+ its qD gradient and the win counts; val, grad, wins may each be nullptr) at M sets, candidate-major raw coordinates
+// xr[n + r*ldr], rows iD..iD+D-1 the option i.  val[n], grad[n + r*ldo], wins[n + i*ldw].  The gradient is formed, and looked at by the
+// guard, whether or not it is asked for: a set's value does not depend on that.
+void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const double* xr, long ldr, int M, double* val, double* grad,
+                       long ldo, int* wins, long ldw) {
+    sls_ctx* c = g.ctx;
+    const int D = g.D, Np = g.Np, Fp = p->Fp, Rp = p->Rp, S = p->n_draws;
+    const int pass_max = std::min(round_up(M, 128), qeubo_sets_per_pass(c, q, Np, Fp, Rp));
+    w.ensure(c, p, g, q * pass_max, pass_max);
+    KernelSpec ks{g.kernel, g.a};
+    double* Cs = g.kernel == SLS_KERNEL_ARD_MATERN52 ? w.Cs.p : w.Ks.p;
+    const long Kc = (long)Np + Fp;
+    if (!w.b2_ready) {
+        w.B2.ensure((size_t)Kc * g.Dcols);
+        SLS_HIP(hipMemcpy2DAsync(w.B2.p, Kc * 8, g.XT, (size_t)Np * 8, (size_t)Np * 8, g.Dcols, hipMemcpyDeviceToDevice, c->stream));
+        SLS_HIP(hipMemcpy2DAsync(w.B2.p + Np, Kc * 8, p->Om.p, (size_t)Fp * 8, (size_t)Fp * 8, g.Dcols, hipMemcpyDeviceToDevice, c->stream));
+        w.b2_ready = true;
+    }
+    for (int s0 = 0; s0 < M; s0 += pass_max) {
+        const int sc = std::min(pass_max, M - s0), Sp = round_up(sc, 128), Pp = q * Sp;
+        double* Pm = w.PG.p;
+        double* G = w.PG.p + (size_t)Pp * Np;
+        {
+            ProfScope ps(c, "cross_gram");
+            for (int i = 0; i < q; ++i)
+                launch_prep_cands(c->stream, xr + (size_t)i * D * ldr + s0, ldr, D, sc, g.inv_ell, w.XsT.p + (size_t)i * Sp, Pp, Sp, g.Dcols,
+                                  w.ns.p + (size_t)i * Sp);
+            launch_cross_gram(c->stream, w.XsT.p, Pp, w.ns.p, Pp, g.XT, g.Np, g.nx, Np, g.N, g.Dp, ks, nullptr, w.Ks.p, Cs, Pp, nullptr,
+                              nullptr);
+        }
+        {
+            // every draw at every point: Phi^T W, then K* V accumulated onto it, both on the tile GEMM
+            ProfScope ps(c, "path_prior");
+            launch_path_feat(c->stream, w.XsT.p, Pp, g.Dp, Pp, p->Om.p, Fp, p->W.p, 2L * Fp, nullptr, Pp, G, Pp, nullptr, 0);
+            launch_gemm_plain(c->stream, G, Pp, false, p->W.p, 2L * Fp, true, w.VM.p, Pp, Pp / 128, Rp / 128, 2 * Fp, 1.0, 0.0);
+        }
+        {
+            ProfScope ps(c, "qeubo_data_gemm");
+            launch_gemm_plain(c->stream, w.Ks.p, Pp, false, p->V.p, Np, true, w.VM.p, Pp, Pp / 128, Rp / 128, Np, 1.0, 1.0);
+        }
+        {
+            ProfScope ps(c, "qeubo");
+            launch_qeubo_select(c->stream, sc, Sp, q, S, Rp, w.VM.p, Pp, w.sum.p, wins ? wins + s0 : nullptr, ldw, w.bad);
+        }
+        {
+            // aggregated weights of every point: the sums of the columns of W / V over the draws its option wins
+            ProfScope ps(c, "qeubo_agg");
+            launch_gemm_plain(c->stream, p->W.p, 2L * Fp, false, w.VM.p, Pp, false, w.Wbar.p, 2L * Fp, 2 * Fp / 128, Pp / 128, Rp, 1.0, 0.0);
+            launch_gemm_plain(c->stream, p->V.p, Np, false, w.VM.p, Pp, false, w.Vbar.p, Np, Np / 128, Pp / 128, Rp, 1.0, 0.0);
+        }
+        {
+            // the gathered route of a path evaluation with point j under "draw" j of (Wbar, Vbar)
+            ProfScope ps(c, "path_prior");
+            launch_path_feat(c->stream, w.XsT.p, Pp, g.Dp, Pp, p->Om.p, Fp, w.Wbar.p, 2L * Fp, w.ident, Pp, G, Pp, w.vpart.p, Pp);
+            // fbar = fbar_i(x_i) is scratch with no consumer: the reused kernels accumulate a value beside the gradient weights, and
+            // path_data adds onto it, so it starts from path_feat's chunk sums rather than from whatever the block held
+            launch_path_vsum(c->stream, w.vpart.p, Pp, Fp / 128, Pp, w.fbar.p);
+        }
+        {
+            ProfScope ps(c, "path_data");
+            launch_path_data(c->stream, w.Ks.p, Cs, Pp, g.N, Np, w.Vbar.p, Np, w.ident, 0, 0, Pp, w.fbar.p, Pm, w.csum.p);
+        }
+        {
+            ProfScope ps(c, "path_grad_gemm");
+            double* part = nullptr;
+            if (D <= 64 && grad_gemm_wants_split(Pp)) {
+                w.Gpart.ensure((size_t)8 * Pp * 64);
+                part = w.Gpart.p;
+            }
+            launch_grad_gemm(c->stream, Pm, nullptr, Pp, Pp, w.B2.p, nullptr, Kc, (int)Kc, D <= 64 ? -g.Dcols : g.Dcols, w.Gt.p, nullptr, part,
+                             1);
+        }
+        {
+            ProfScope ps(c, "path_data");
+            launch_path_grad(c->stream, Pp, D, Pp, w.Gt.p, w.XsT.p, w.csum.p, g.inv_ell, w.gpt.p, Pp);
+        }
+        {
+            ProfScope ps(c, "qeubo");
+            launch_qeubo_finish(c->stream, sc, Sp, q, D, S, w.sum.p, w.bad, w.gpt.p, Pp, val ? val + s0 : nullptr, grad ? grad + s0 : nullptr,
+                                ldo);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int sls_qeubo_eval(sls_path* p, int q, const double* sets, int M, double* val, double* grad, int* wins) {
+    SLS_TRY
+    SLS_REQUIRE(p != nullptr, "sls_qeubo_eval: p is NULL");
+    SLS_REQUIRE(q >= 1 && q <= SLS_QEUBO_MAX_OPTIONS, "sls_qeubo_eval: q = %d (1 .. %d)", q, SLS_QEUBO_MAX_OPTIONS);
+    SLS_REQUIRE(M >= 0, "sls_qeubo_eval: M = %d", M);
+    SLS_REQUIRE(sets != nullptr, "sls_qeubo_eval: sets is NULL");
+    GpReadCall call(p->gp, p->generation, "sls_qeubo_eval");
+    if (M == 0) return SLS_OK;
+    const GpView& g = call.g;
+    sls_ctx* c = g.ctx;
+    const int qD = q * g.D, Mp = round_up(M, 128);
+    // host qD x M column-major -> candidate-major raw coordinates
+    std::vector<double> t((size_t)Mp * qD, 0.5);
+    for (int m = 0; m < M; ++m)
+        for (int r = 0; r < qD; ++r) t[(size_t)m + (size_t)r * Mp] = sets[r + (size_t)m * qD];
+    DBuf raw, out, wb;
+    raw.ensure(t.size());
+    SLS_HIP(hipMemcpyAsync(raw.p, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    out.ensure((size_t)Mp * (1 + qD));
+    int* d_wins = wins ? ints(wb, (size_t)Mp * q) : nullptr;
+    QeuboWs ws;
+    qeubo_eval_device(p, g, ws, q, raw.p, Mp, M, out.p, grad ? out.p + Mp : nullptr, Mp, d_wins, Mp);
+    std::vector<double> oh((size_t)Mp * (grad ? 1 + qD : 1));
+    std::vector<int> wh;
+    SLS_HIP(hipMemcpyAsync(oh.data(), out.p, oh.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (wins) {
+        wh.resize((size_t)Mp * q);
+        SLS_HIP(hipMemcpyAsync(wh.data(), d_wins, wh.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    }
+    SLS_HIP(hipStreamSynchronize(c->stream));
+    for (int m = 0; m < M; ++m) {
+        if (val) val[m] = oh[m];
+        if (grad)
+            for (int r = 0; r < qD; ++r) grad[r + (size_t)m * qD] = oh[(size_t)Mp * (1 + r) + m];
+        if (wins)
+            for (int i = 0; i < q; ++i) wins[i + (size_t)m * q] = wh[(size_t)m + (size_t)i * Mp];
+    }
+    SLS_CATCH
+}
+
+extern "C" int sls_qeubo_maximize(sls_path* p, int q, const double* starts, int S_starts, int n_local, const sls_lbfgs_opts* opts,
+                                  long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars,
+                                  double* y_stars) {
+    SLS_TRY
+    SLS_REQUIRE(p && starts, "sls_qeubo_maximize: NULL argument");
+    SLS_REQUIRE(q >= 1 && q <= SLS_QEUBO_MAX_OPTIONS, "sls_qeubo_maximize: q = %d (1 .. %d)", q, SLS_QEUBO_MAX_OPTIONS);
+    SLS_REQUIRE(S_starts >= 1 && n_local >= 1, "sls_qeubo_maximize: need S_starts >= 1 and n_local >= 1 (S_starts = %d, n_local = %d)",
+                S_starts, n_local);
+    const sls_lbfgs_opts o = read_lbfgs_opts(opts);
+    SLS_REQUIRE(o.history >= 1 && o.history <= 8, "L-BFGS history must be in 1..8");
+    GpReadCall call(p->gp, p->generation, "sls_qeubo_maximize");
+    const GpView& g = call.g;
+    sls_ctx* c = g.ctx;
+    // the maximiser of sls_acq_maximize over [0,1]^(qD): one start = one set of q options
+    const int S = S_starts, qD = q * g.D, Sp = round_up(S, 128);
+    LbfgsWs lb;
+    QeuboWs ws;
+    lb.ensure(Sp, o.history, qD);
+    LbfgsState st = lb.state(S, qD, o);
+    DBuf sd, best;
+    sd.ensure((size_t)qD * S);
+    best.ensure((size_t)8 + qD);
+    SLS_HIP(hipMemcpyAsync(sd.p, starts, (size_t)qD * S * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    gp_set_acq_stats(p->gp, 0, (long)S * n_local, 0, 0);
+    LockstepStats ls;
+    lockstep_rounds(c, st, lb, sd.p, S, n_local,
+                    [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
+                        qeubo_eval_device(p, g, ws, q, trial, ld, nlive, val, grad, ld, nullptr, 0);
+                    },
+                    &ls);
+    gp_set_acq_stats(p->gp, ls.issued, (long)S * n_local, ls.rounds, ls.live_end);
+    launch_argmax_neg_gather(c->stream, st.f, S, st.x, Sp, qD, best.p, nullptr);
+    std::vector<double> bh((size_t)8 + qD), xh, fh;
+    SLS_HIP(hipMemcpyAsync(bh.data(), best.p, bh.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (x_stars) {
+        xh.resize((size_t)Sp * qD);
+        SLS_HIP(hipMemcpyAsync(xh.data(), st.x, xh.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (y_stars) {
+        fh.resize(Sp);
+        SLS_HIP(hipMemcpyAsync(fh.data(), st.f, fh.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    SLS_HIP(hipStreamSynchronize(c->stream));
+    if (val_out) *val_out = bh[0];
+    if (idx_out) *idx_out = (long)bh[1] + start_index_offset;
+    if (x_out) std::copy(bh.begin() + 8, bh.begin() + 8 + qD, x_out);
+    for (int n = 0; n < S; ++n) {
+        if (x_stars)
+            for (int r = 0; r < qD; ++r) x_stars[r + (size_t)n * qD] = xh[(size_t)n + (size_t)r * Sp];
+        if (y_stars) y_stars[n] = -fh[n];
     }
     SLS_CATCH
 }

@@ -39,6 +39,8 @@ struct GpView {
     std::shared_mutex* state;
 };
 GpView gp_view(sls_gp* g);
+// what sls_acq_last_stats reports for the handle: set by a maximiser that runs outside capi.hip (sls_qeubo_maximize)
+void gp_set_acq_stats(sls_gp* g, long issued, long cap, int rounds, int live_end);
 // sls_lbfgs_opts as the caller's struct_size declares it, over the library's defaults (capi.hip)
 sls_lbfgs_opts read_lbfgs_opts(const sls_lbfgs_opts* in);
 

@@ -473,6 +473,18 @@ void launch_path_draw_of_live(hipStream_t s, const int* live, int n, int S, int*
 // per draw s (starts [s S, (s+1) S)): first maximum of -f; out[s (D + 2) + 0] = value, [+1] = index within the draw, [+2 ..] = x
 void launch_path_argmax(hipStream_t s, const double* f, int S, int n_draws, const double* x, long ldx, int D, double* out);
 
+// ---- kernels_qeubo.hip: expected utility of the best of q options on posterior draws (sls_qeubo_*) ------------------------
+// Points of a pass are option-major: option i of set n is point i*Sp + n (Sp = the pass's sets rounded up to 128).
+// V[i*Sp + n + s*ldv] = f_s(x_i) on entry (Rp rows s, the every-draw values).  One lane per set: sum[n] = sum over s < S (increasing) of
+// max_i, the lowest i winning ties; wins[n + i*ldw] = draws option i wins (wins may be NULL); bad[n] = 1 if any value is not a number.
+// V is overwritten in place by the 0/1 winner indicator, cleared for s >= S and for the padding sets n in [nsets, Sp).
+void launch_qeubo_select(hipStream_t s, int nsets, int Sp, int q, int S, int Rp, double* V, long ldv, double* sum, int* wins, long ldw,
+                         int* bad);
+// val[n] = sum[n] / S, grad[n + (i*D + d)*ldo] = gpt[i*Sp + n + d*ldg] / S for n < nsets; bad[n] or a NaN among them: value
+// SLS_QEUBO_FLOOR and the zero gradient.  val / grad may be NULL.
+void launch_qeubo_finish(hipStream_t s, int nsets, int Sp, int q, int D, int S, const double* sum, const int* bad, const double* gpt,
+                         long ldg, double* val, double* grad, long ldo);
+
 // ---- kernels_map.hip -----------------------------------------------------------
 // MAP-gradient weights (replaces the (D+1) x N x N tensor of CalcLargeKYThetaDerivative, src/regressor.cpp:110-134):
 // G[j + k*Np] = 1/2 (alpha_j alpha_k - Kinv_jk) c_jk  (0 in the padding);  wk_part[tile] = sum over the tile of

@@ -425,7 +425,7 @@ namespace sequential_line_search
     // ---- expected utility of the best option of a query pair (include/sls_hip.h sls_eubo_*; Astudillo et al. 2023) ----
     namespace
     {
-        sls_gp* RequireHandleForPairs(const Regressor& r)
+        sls_gp* RequireDeviceHandleForExpectedUtility(const Regressor& r)
         {
             sls_gp* h = r.GetDeviceHandle();
             if (!h)
@@ -438,7 +438,7 @@ namespace sequential_line_search
     VectorXd acquisition_func::CalcExpectedUtilitiesOfBestOption(const Regressor& regressor, const MatrixXd& Xa, const MatrixXd& Xb,
                                                                  MatrixXd* grad_a, MatrixXd* grad_b)
     {
-        sls_gp* h = RequireHandleForPairs(regressor);
+        sls_gp* h = RequireDeviceHandleForExpectedUtility(regressor);
         if (Xa.rows() != Xb.rows() || Xa.cols() != Xb.cols())
             throw std::invalid_argument("CalcExpectedUtilitiesOfBestOption: Xa and Xb must have the same shape");
         const long D = Xa.rows(), M = Xa.cols();
@@ -469,7 +469,7 @@ namespace sequential_line_search
                                                                                                 const unsigned   num_local_search_iters,
                                                                                                 double*          value)
     {
-        sls_gp*    h = RequireHandleForPairs(regressor);
+        sls_gp*    h = RequireDeviceHandleForExpectedUtility(regressor);
         const long D = regressor.GetNumDims();
         if (starts.rows() != 2 * D || starts.cols() < 1)
             throw std::invalid_argument("FindNextQueryPairByExpectedUtilityFromStarts: starts must be 2D x S with S >= 1");
@@ -490,9 +490,37 @@ namespace sequential_line_search
                                                                                       const unsigned   num_local_search_iters,
                                                                                       const unsigned long long seed, double* value)
     {
-        RequireHandleForPairs(regressor);
+        RequireDeviceHandleForExpectedUtility(regressor);
         return FindNextQueryPairByExpectedUtilityFromStarts(
             regressor, SeededStarts(2 * regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed), num_local_search_iters,
             value);
+    }
+
+    // ---- expected utility of the best of q options on posterior draws (include/sls_hip.h sls_qeubo_*) ----
+    std::vector<VectorXd> acquisition_func::FindNextQueryByExpectedUtilityFromStarts(const Regressor& regressor, const int num_options,
+                                                                                     const MatrixXd& starts, const unsigned num_draws,
+                                                                                     const unsigned           num_local_search_iters,
+                                                                                     const unsigned long long seed,
+                                                                                     const int num_frequencies, double* value)
+    {
+        RequireDeviceHandleForExpectedUtility(regressor);
+        const PosteriorFunctionSamples draws =
+            regressor.SamplePosteriorFunctions(static_cast<int>(std::max(1u, num_draws)), seed, num_frequencies);
+        return draws.MaximizeExpectedUtilityOfBestOption(num_options, starts, num_local_search_iters, value);
+    }
+
+    std::vector<VectorXd> acquisition_func::FindNextQueryByExpectedUtility(const Regressor& regressor, const int num_options,
+                                                                           const unsigned num_draws,
+                                                                           const unsigned num_global_search_iters,
+                                                                           const unsigned num_local_search_iters,
+                                                                           const unsigned long long seed, const int num_frequencies,
+                                                                           double* value)
+    {
+        RequireDeviceHandleForExpectedUtility(regressor);
+        if (num_options < 1 || num_options > SLS_QEUBO_MAX_OPTIONS)
+            throw std::invalid_argument("FindNextQueryByExpectedUtility: 1 .. 16 options");
+        return FindNextQueryByExpectedUtilityFromStarts(
+            regressor, num_options, SeededStarts(num_options * regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed),
+            num_draws, num_local_search_iters, seed, num_frequencies, value);
     }
 } // namespace sequential_line_search

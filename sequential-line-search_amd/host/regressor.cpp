@@ -230,6 +230,60 @@ namespace sequential_line_search
         return out;
     }
 
+    VectorXd PosteriorFunctionSamples::CalcExpectedUtilitiesOfBestOption(const std::vector<MatrixXd>& options, std::vector<MatrixXd>* grads,
+                                                                         Eigen::MatrixXi* win_counts) const
+    {
+        const long q = static_cast<long>(options.size());
+        if (q < 1 || q > SLS_QEUBO_MAX_OPTIONS)
+            throw std::invalid_argument("PosteriorFunctionSamples::CalcExpectedUtilitiesOfBestOption: 1 .. 16 options");
+        const long D = m_num_dims, M = options[0].cols();
+        for (const MatrixXd& X : options)
+            if (X.rows() != D || X.cols() != M)
+                throw std::invalid_argument("PosteriorFunctionSamples::CalcExpectedUtilitiesOfBestOption: every option block must be D x M");
+        MatrixXd sets(q * D, M);
+        for (long i = 0; i < q; ++i)
+            for (long m = 0; m < M; ++m)
+                for (long d = 0; d < D; ++d) sets(i * D + d, m) = options[i](d, m);
+        VectorXd v = VectorXd::Zero(M);
+        MatrixXd g(grads ? q * D : 0, grads ? M : 0);
+        if (win_counts) *win_counts = Eigen::MatrixXi::Zero(q, M);
+        device::Check(sls_qeubo_eval(m_path, static_cast<int>(q), sets.data(), static_cast<int>(M), v.data(), grads ? g.data() : nullptr,
+                                     win_counts ? win_counts->data() : nullptr),
+                      "sls_qeubo_eval");
+        if (grads)
+        {
+            grads->assign(q, MatrixXd(D, M));
+            for (long i = 0; i < q; ++i)
+                for (long m = 0; m < M; ++m)
+                    for (long d = 0; d < D; ++d) (*grads)[i](d, m) = g(i * D + d, m);
+        }
+        return v;
+    }
+
+    std::vector<VectorXd> PosteriorFunctionSamples::MaximizeExpectedUtilityOfBestOption(int num_options, const MatrixXd& starts,
+                                                                                        unsigned num_local_search_iters, double* value) const
+    {
+        if (num_options < 1 || num_options > SLS_QEUBO_MAX_OPTIONS)
+            throw std::invalid_argument("PosteriorFunctionSamples::MaximizeExpectedUtilityOfBestOption: 1 .. 16 options");
+        const long D = m_num_dims;
+        if (starts.rows() != num_options * D || starts.cols() < 1)
+            throw std::invalid_argument("PosteriorFunctionSamples::MaximizeExpectedUtilityOfBestOption: starts must be (num_options D) x S "
+                                        "with S >= 1");
+        sls_lbfgs_opts o;
+        sls_lbfgs_default_opts(&o);
+        optim::SearchTolerances(&o.ftol_rel, &o.xtol_rel);   // the acquisition maximiser's local search tolerances
+        VectorXd x(num_options * D);
+        double   v   = 0.0;
+        long     idx = 0;
+        device::Check(sls_qeubo_maximize(m_path, num_options, starts.data(), static_cast<int>(starts.cols()),
+                                         std::max(1, static_cast<int>(num_local_search_iters)), &o, 0, x.data(), &v, &idx, nullptr, nullptr),
+                      "sls_qeubo_maximize");
+        if (value) *value = v;
+        std::vector<VectorXd> out;
+        for (int i = 0; i < num_options; ++i) out.push_back(x.segment(i * D, D));
+        return out;
+    }
+
     MatrixXd Regressor::SamplePosterior(const MatrixXd& Xs, int num_samples, unsigned long long seed, double* jitter_used) const
     {
         sls_gp* h = GetDeviceHandle();
