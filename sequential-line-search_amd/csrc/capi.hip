@@ -367,12 +367,6 @@ extern "C" int sls_prof_get(sls_ctx* ctx, const char* name, double* total_ms, lo
 }
 
 // ---- helpers --------------------------------------------------------------------------------------------
-static void h2d(sls_ctx* c, double* dst, const double* src, size_t n) {
-    SLS_HIP(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-}
-static void d2h(sls_ctx* c, double* dst, const double* src, size_t n) {
-    SLS_HIP(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-}
 static void sync(sls_ctx* c) { SLS_HIP(hipStreamSynchronize(c->stream)); }
 // Up to this many doubles of query points / results / matrices go through a handle's page-locked staging block (32 MB); larger
 // transfers take the plain (pageable, blocking) copies.
@@ -877,16 +871,13 @@ static void eval_small(sls_gp* g, const double* Xs_dev, int M, const EvalOut& o)
     wave_eval(g, g->ctx->stream, Xs_dev, M, o);
 }
 
-// host D x M column-major -> device candidate-major raw coordinates (clamping is NOT applied here)
-static void upload_candidates(sls_gp* g, const double* Xs, int M, DBuf& raw, int Mp) {
-    sls_ctx* c = g->ctx;
-    const int D = g->D;
-    std::vector<double> t((size_t)Mp * D, 0.5);
-    for (int m = 0; m < M; ++m)
-        for (int d = 0; d < D; ++d) t[(size_t)m + (size_t)d * Mp] = Xs[d + (size_t)m * D];
-    raw.ensure((size_t)Mp * D);
-    h2d(c, raw.p, t.data(), (size_t)Mp * D);
-    sync(c);
+// host rows x M column-major (rows = D; 2D for query pairs) -> the handle's candidate-major raw coordinates (clamping is NOT
+// applied here)
+static void upload_candidates(sls_gp* g, const double* Xs, int rows, int M, int Mp) {
+    const std::vector<double> t = host_to_cm(Xs, rows, M, Mp);
+    g->raw.ensure(t.size());
+    h2d(g->ctx, g->raw.p, t.data(), t.size());
+    sync(g->ctx);
 }
 
 // evaluate M host-supplied query points (D x M column-major) into the candidate-major device outputs of `o`
@@ -896,7 +887,7 @@ static void eval_host_points(sls_gp* g, const double* Xs, int M, int Mp, const E
     const bool wave = wave_path_applies(g, M);
     const bool staged = n <= IO_STAGE_MAX && tune_on(TUNE_IO_STAGE);
     if (!wave && !staged) {   // SLS_IO_STAGE=0: the transposing pageable upload of rounds 1-3 (A/B, tests)
-        upload_candidates(g, Xs, M, g->raw, Mp);
+        upload_candidates(g, Xs, g->D, M, Mp);
         eval_candidates(g, g->raw.p, Mp, M, o);
         return;
     }
@@ -934,14 +925,6 @@ static EvalOut eval_block(const EvalOut& want, double* base, int D, long ld) {
     b.dmu = place(want.dmu, D); b.dsigma = place(want.dsigma, D); b.grad = place(want.grad, D);
     return b;
 }
-// candidate-major src[m + r * ld] (rows x ld) into the caller's array: rows = 1: a vector of M; rows = D: D x M column-major
-static void cm_to_host(const double* src, long ld, int rows, int M, double* host) {
-    if (!host) return;
-    if (rows == 1) std::copy(src, src + M, host);
-    else
-        for (int m = 0; m < M; ++m)
-            for (int r = 0; r < rows; ++r) host[r + (size_t)m * rows] = src[(size_t)m + (size_t)r * ld];
-}
 // a block `at` (eval_block over host-readable memory) into the arrays the caller named in `want`
 static void eval_block_to_host(const EvalOut& want, const EvalOut& at, int D, int M) {
     cm_to_host(at.mu, at.ldo, 1, M, want.mu); cm_to_host(at.sigma, at.ldo, 1, M, want.sigma); cm_to_host(at.val, at.ldo, 1, M, want.val);
@@ -960,20 +943,15 @@ static double* fetch(sls_gp* g, const double* dev, size_t n, std::vector<double>
     sync(g->ctx);
     return t;
 }
-// one candidate-major device array (rows x Mp) back to the host
-static void download_cm(sls_gp* g, const double* dev, int M, int Mp, int rows, double* host /* rows x M col-major or M */) {
-    std::vector<double> pageable;
-    cm_to_host(fetch(g, dev, (size_t)Mp * rows, pageable), Mp, rows, M, host);
-}
-// every output of a call back to the host: the device block behind eval_block(want, dev, D, Mp) in one copy
-static void download_block(sls_gp* g, const EvalOut& want, const double* dev, int M, int Mp) {
-    const size_t n = eval_block_doubles(want, g->D, Mp);
+// every output of a call back to the host: the device block behind eval_block(want, dev, rows, Mp) in one copy
+static void download_block(sls_gp* g, const EvalOut& want, const double* dev, int rows, int M, int Mp) {
+    const size_t n = eval_block_doubles(want, rows, Mp);
     if (n == 0) {
         sync(g->ctx);   // nothing to fetch, but the evaluation in flight reads the staging block the next call writes into
         return;
     }
     std::vector<double> pageable;
-    eval_block_to_host(want, eval_block(want, fetch(g, dev, n, pageable), g->D, Mp), g->D, M);
+    eval_block_to_host(want, eval_block(want, fetch(g, dev, n, pageable), rows, Mp), rows, M);
 }
 
 // Small evaluations through a device-mapped block: [D x M query points][eval_block with ld = M].  The kernel reads the points from
@@ -1055,68 +1033,54 @@ struct MesSamples {
     const double* y_star;   // device, K doubles
     int K;
 };
+// mu / dmu of g and sigma / dsigma of gs (of g when there is no gs) at the S points into g's pair blocks, leading dimension ldo
+static void eval_pair_blocks(sls_gp* g, sls_gp* gs, const double* xr, long ldr, int S, bool want_grad, long ldo) {
+    const size_t D = g->D;
+    g->pair_mu.ensure(ldo); g->pair_sg.ensure(ldo);
+    if (want_grad) { g->pair_dmu.ensure(ldo * D); g->pair_dsg.ensure(ldo * D); }
+    EvalOut a, b;
+    a.ldo = b.ldo = ldo;
+    a.mu = g->pair_mu.p; a.dmu = want_grad ? g->pair_dmu.p : nullptr;
+    EvalOut& sg = gs ? b : a;
+    sg.sigma = g->pair_sg.p; sg.dsigma = want_grad ? g->pair_dsg.p : nullptr;
+    eval_candidates(g, xr, ldr, S, a);
+    if (gs) eval_candidates(gs, xr, ldr, S, b);
+}
 static void eval_acq(sls_gp* g, sls_gp* gs, const double* xr, long ldr, int S, int acq_type, double ucb_h, double* val,
                      double* grad, long ldo, const MesSamples* mes = nullptr) {
-    if (mes) {
-        const size_t D = g->D;
-        g->pair_mu.ensure(ldo); g->pair_sg.ensure(ldo);
-        if (grad) { g->pair_dmu.ensure(ldo * D); g->pair_dsg.ensure(ldo * D); }
-        EvalOut a;
-        a.ldo = ldo; a.mu = g->pair_mu.p; a.sigma = g->pair_sg.p;
-        a.dmu = grad ? g->pair_dmu.p : nullptr; a.dsigma = grad ? g->pair_dsg.p : nullptr;
-        eval_candidates(g, xr, ldr, S, a);
-        ProfScope ps(g->ctx, "mes");
-        launch_mes_combine(g->ctx->stream, S, (int)D, ldo, g->pair_mu.p, g->pair_sg.p, g->pair_dmu.p, g->pair_dsg.p, mes->y_star,
-                           mes->K, val, grad);
-        return;
-    }
-    if (acq_type == SLS_ACQ_LOG_EXPECTED_IMPROVEMENT) {   // the single-handle and the pair objective from one path
-        const size_t D = g->D;
-        g->pair_mu.ensure(ldo); g->pair_sg.ensure(ldo);
-        if (grad) { g->pair_dmu.ensure(ldo * D); g->pair_dsg.ensure(ldo * D); }
-        EvalOut a;
-        a.ldo = ldo; a.mu = g->pair_mu.p; a.dmu = grad ? g->pair_dmu.p : nullptr;
-        EvalOut b;
-        b.ldo = ldo;
-        EvalOut& sg = gs ? b : a;
-        sg.sigma = g->pair_sg.p; sg.dsigma = grad ? g->pair_dsg.p : nullptr;
-        eval_candidates(g, xr, ldr, S, a);
-        if (gs) eval_candidates(gs, xr, ldr, S, b);
-        ProfScope ps(g->ctx, "logei");
-        launch_logei_combine(g->ctx->stream, S, (int)D, ldo, g->pair_mu.p, g->pair_sg.p, g->pair_dmu.p, g->pair_dsg.p, g->mu_best, val,
-                             grad);
-        return;
-    }
-    if (!gs) {
+    sls_ctx* c = g->ctx;
+    if (!mes && !gs && acq_type != SLS_ACQ_LOG_EXPECTED_IMPROVEMENT) {   // EI / UCB of one handle: finalize forms them itself
         EvalOut eo;
         eo.ldo = ldo; eo.val = val; eo.grad = grad; eo.acq = acq_type; eo.ucb_h = ucb_h;
         eval_candidates(g, xr, ldr, S, eo);
         return;
     }
-    const size_t D = g->D;
-    g->pair_mu.ensure(ldo); g->pair_sg.ensure(ldo);
-    if (grad) { g->pair_dmu.ensure(ldo * D); g->pair_dsg.ensure(ldo * D); }
-    EvalOut a, b;
-    a.ldo = ldo; a.mu = g->pair_mu.p; a.dmu = grad ? g->pair_dmu.p : nullptr;
-    b.ldo = ldo; b.sigma = g->pair_sg.p; b.dsigma = grad ? g->pair_dsg.p : nullptr;
-    eval_candidates(g, xr, ldr, S, a);
-    eval_candidates(gs, xr, ldr, S, b);
-    launch_combine(g->ctx->stream, S, (int)D, ldo, g->pair_mu.p, g->pair_sg.p, g->pair_dmu.p, g->pair_dsg.p, acq_type, g->mu_best,
-                   ucb_h, val, grad);
+    eval_pair_blocks(g, mes ? nullptr : gs, xr, ldr, S, grad != nullptr, ldo);
+    const double *mu = g->pair_mu.p, *sg = g->pair_sg.p, *dmu = g->pair_dmu.p, *dsg = g->pair_dsg.p;
+    if (mes) {
+        ProfScope ps(c, "mes");
+        launch_mes_combine(c->stream, S, g->D, ldo, mu, sg, dmu, dsg, mes->y_star, mes->K, val, grad);
+    } else if (acq_type == SLS_ACQ_LOG_EXPECTED_IMPROVEMENT) {
+        ProfScope ps(c, "logei");
+        launch_logei_combine(c->stream, S, g->D, ldo, mu, sg, dmu, dsg, g->mu_best, val, grad);
+    } else {
+        launch_combine(c->stream, S, g->D, ldo, mu, sg, dmu, dsg, acq_type, g->mu_best, ucb_h, val, grad);
+    }
 }
 
 // eval_acq at M >= 1 host-supplied points (D x M column-major) through the transposing upload, results to the caller's arrays
-static void eval_acq_points(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, const double* Xs, int M, double* val, double* grad) {
+static void eval_acq_points(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, const double* Xs, int M, double* val, double* grad,
+                            const MesSamples* mes = nullptr) {
     const int Mp = round_up(M, 128), D = g->D;
-    upload_candidates(g, Xs, M, g->raw, Mp);
+    upload_candidates(g, Xs, D, M, Mp);
     std::vector<double> unused;   // the combiners always write the values
     if (!val) unused.resize(M);
     EvalOut want;
     want.val = val ? val : unused.data(); want.grad = grad;
     g->outv.ensure(eval_block_doubles(want, D, Mp));
     const EvalOut o = eval_block(want, g->outv.p, D, Mp);
-    eval_acq(g, gs, g->raw.p, Mp, M, acq_type, ucb_h, o.val, o.grad, Mp);
-    download_block(g, want, g->outv.p, M, Mp);
+    eval_acq(g, gs, g->raw.p, Mp, M, acq_type, ucb_h, o.val, o.grad, Mp, mes);
+    download_block(g, want, g->outv.p, D, M, Mp);
 }
 
 static bool known_acq(int acq_type) {
@@ -1154,7 +1118,7 @@ static int eval_entry(const char* who, sls_gp* g, const double* Xs, int M, const
     }
     g->outv.ensure(eval_block_doubles(want, D, Mp));
     eval_host_points(g, Xs, M, Mp, eval_block(want, g->outv.p, D, Mp));
-    download_block(g, want, g->outv.p, M, Mp);
+    download_block(g, want, g->outv.p, D, M, Mp);
     SLS_CATCH
 }
 
@@ -1198,15 +1162,18 @@ sls_lbfgs_opts slsk::read_lbfgs_opts(const sls_lbfgs_opts* in) {
 // The whole multi-start search in one launch, one wavefront per start (the caller has asked wave_path_applies).  Returns the device
 // counter of useful evaluations: those of starts that were still moving (finished starts run idle to keep the barriers uniform),
 // counted by the kernel into the live-count words of the integer scratch.
-static const unsigned long long* maximize_wave(sls_gp* g, int acq_type, double ucb_h, const double* starts_dev, int S, int n_local,
-                                               const sls_lbfgs_opts& o, const LbfgsState& st, int Sp) {
+static const unsigned long long* maximize_wave(sls_gp* g, int acq_type, double ucb_h, const double* starts_dev,
+                                               const MultistartRun& r) {
     sls_ctx* c = g->ctx;
+    const sls_lbfgs_opts& o = r.o;
+    const LbfgsState& st = r.st;
+    const int S = st.S;
     WaveArgs w;
     wave_model_args(g, w);
-    w.S = S; w.m = o.history; w.n_local = n_local; w.acq = acq_type; w.ucb_h = ucb_h;
+    w.S = S; w.m = o.history; w.n_local = r.n_local; w.acq = acq_type; w.ucb_h = ucb_h;
     w.c1 = o.c1; w.shrink = o.shrink; w.gtol = o.gtol; w.max_backtracks = o.max_backtracks;
     w.ftol_rel = o.ftol_rel; w.xtol_rel = o.xtol_rel;
-    w.starts = starts_dev; w.x_out = st.x; w.f_out = st.f; w.ld = Sp;
+    w.starts = starts_dev; w.x_out = st.x; w.f_out = st.f; w.ld = st.ld;
     w.ev_mu = w.ev_sigma = w.ev_dmu = w.ev_dsigma = w.ev_val = w.ev_grad = nullptr;
     unsigned long long* d_useful = g->lb.wave_useful();
     SLS_HIP(hipMemsetAsync(d_useful, 0, sizeof(unsigned long long), c->stream));
@@ -1232,48 +1199,42 @@ static const unsigned long long* maximize_wave(sls_gp* g, int acq_type, double u
     return d_useful;
 }
 
-static void maximize_impl(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, const double* starts_dev, int S, int n_local,
-                          const sls_lbfgs_opts* opts_in, long off, double* x_out, double* val_out, long* idx_out,
+// fetch of maximize_finish on the sls_gp routes: through the handle's page-locked stage
+static auto staged_fetch(sls_gp* g, std::vector<double>& pageable) {
+    return [g, &pageable](const double* dev, size_t n) { return fetch(g, dev, n, pageable); };
+}
+
+// The body of sls_acq_maximize, _pair, _dev and sls_mes_maximize (`who`): the shared maximiser (lbfgs_driver.hpp) with one of two
+// searches, and the handle's mapped block for the best start -- one launch, one synchronisation, no copies.
+// starts: D x S column-major, on the host (uploaded here) or already on the device.
+static void maximize_impl(const char* who, sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, const double* starts, bool starts_on_host,
+                          int S, int n_local, const sls_lbfgs_opts* opts_in, long off, double* x_out, double* val_out, long* idx_out,
                           double* x_stars, double* y_stars, const MesSamples* mes = nullptr) {
     sls_ctx* c = g->ctx;
-    SLS_REQUIRE(S >= 1 && n_local >= 1, "sls_acq_maximize: need S >= 1 and n_local >= 1");
     SLS_REQUIRE(mes || known_acq(acq_type), "unknown acquisition type %d", acq_type);
-    const sls_lbfgs_opts o = read_lbfgs_opts(opts_in);
-    SLS_REQUIRE(o.history >= 1 && o.history <= 8, "L-BFGS history must be in 1..8");
-    const int Sp = round_up(S, 128), D = g->D;
-    g->lb.ensure(Sp, o.history, D);
-    g->stat_issued = 0; g->stat_cap = (long)S * n_local; g->stat_rounds = 0; g->stat_live_end = 0;
-    LbfgsState st = g->lb.state(S, D, o);
-    // Small problems: one wavefront per start runs the whole search in a single launch (kernels_wave.hip)
-    const unsigned long long* wave_useful = nullptr;   // the one-wavefront-per-start run's count of useful evaluations (device)
+    MultistartRun r = maximize_begin(who, g, g->lb, opts_in, S, n_local, g->D);
+    DBuf sd;
+    if (starts_on_host) {
+        sd.ensure((size_t)g->D * S);
+        h2d(c, sd.p, starts, (size_t)g->D * S);
+    }
+    const double* starts_dev = starts_on_host ? sd.p : starts;
+    LockstepStats ls;
     // (the wave kernel has neither the MES nor the LogEI objective: those always take the general path)
     if (!gs && !mes && acq_type != SLS_ACQ_LOG_EXPECTED_IMPROVEMENT && wave_path_applies(g, S)) {
-        wave_useful = maximize_wave(g, acq_type, ucb_h, starts_dev, S, n_local, o, st, Sp);   // read back with the best start
-        g->stat_rounds = n_local;
+        // Small problems: one wavefront per start runs the whole search in a single launch (kernels_wave.hip)
+        ls.issued_dev = maximize_wave(g, acq_type, ucb_h, starts_dev, r);
+        ls.rounds = n_local;
     } else {
-        // the lock-step rounds over the active set (lbfgs_driver.hpp)
-        LockstepStats ls;
-        lockstep_rounds(c, st, g->lb, starts_dev, S, n_local,
+        lockstep_rounds(c, r.st, g->lb, starts_dev, S, n_local,
                         [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
                             eval_acq(g, gs, trial, ld, nlive, acq_type, ucb_h, val, grad, ld, mes);
                         },
                         &ls);
-        g->stat_issued = ls.issued; g->stat_rounds = ls.rounds; g->stat_live_end = ls.live_end;
     }
-    // best start and its coordinates: one launch into the handle's mapped block, one synchronisation, no copies
-    launch_argmax_neg_gather(c->stream, st.f, S, st.x, Sp, D, g->sum.dev + 8, wave_useful);
-    sync(c);
-    const double* best = g->sum.host + 8;
-    const long bi = (long)best[1];
-    if (wave_useful) g->stat_issued = (long)best[2];
-    if (val_out) *val_out = best[0];
-    if (idx_out) *idx_out = bi + off;
-    if (x_out) std::copy(best + 8, best + 8 + D, x_out);
-    if (x_stars) download_cm(g, st.x, S, Sp, D, x_stars);
-    if (y_stars) {
-        download_cm(g, st.f, S, Sp, 1, y_stars);
-        for (int i = 0; i < S; ++i) y_stars[i] = -y_stars[i];
-    }
+    std::vector<double> pageable;
+    maximize_finish(c, r, ls, BestBlock{g->sum.dev + 8, g->sum.host + 8, false}, staged_fetch(g, pageable), off, x_out, val_out,
+                    idx_out, x_stars, y_stars);
 }
 
 extern "C" int sls_acq_last_stats(sls_gp* g, long* evals_issued, long* evals_cap, int* rounds, int* live_at_end) {
@@ -1292,13 +1253,8 @@ extern "C" int sls_acq_maximize(sls_gp* g, int acq_type, double ucb_h, const dou
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g && starts, "sls_acq_maximize: NULL argument");
-    SLS_REQUIRE(S >= 1, "sls_acq_maximize: need S >= 1");
-    sls_ctx* c = g->ctx;
-    DBuf sd;
-    sd.ensure((size_t)g->D * S);
-    h2d(c, sd.p, starts, (size_t)g->D * S);
-    maximize_impl(g, nullptr, acq_type, ucb_h, sd.p, S, n_local, opts, start_index_offset, x_out, val_out, idx_out, x_stars,
-                  y_stars);
+    maximize_impl("sls_acq_maximize", g, nullptr, acq_type, ucb_h, starts, true, S, n_local, opts, start_index_offset, x_out, val_out,
+                  idx_out, x_stars, y_stars);
     SLS_CATCH
 }
 
@@ -1312,12 +1268,9 @@ extern "C" int sls_acq_maximize_pair(sls_gp* g, sls_gp* gs, int acq_type, double
     SLS_TRY
     CtxCall call_(g);
     check_pair(g, gs);
-    SLS_REQUIRE(starts && S >= 1, "sls_acq_maximize_pair: bad argument");
-    sls_ctx* c = g->ctx;
-    DBuf sd;
-    sd.ensure((size_t)g->D * S);
-    h2d(c, sd.p, starts, (size_t)g->D * S);
-    maximize_impl(g, gs, acq_type, ucb_h, sd.p, S, n_local, opts, 0, x_out, val_out, idx_out, nullptr, nullptr);
+    SLS_REQUIRE(starts, "sls_acq_maximize_pair: starts is NULL");
+    maximize_impl("sls_acq_maximize_pair", g, gs, acq_type, ucb_h, starts, true, S, n_local, opts, 0, x_out, val_out, idx_out, nullptr,
+                  nullptr);
     SLS_CATCH
 }
 
@@ -1339,8 +1292,8 @@ extern "C" int sls_acq_maximize_dev(sls_gp* g, int acq_type, double ucb_h, const
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g && starts_dev, "sls_acq_maximize_dev: NULL argument");
-    maximize_impl(g, nullptr, acq_type, ucb_h, starts_dev, S, n_local, opts, start_index_offset, x_out, val_out, idx_out, nullptr,
-                  nullptr);
+    maximize_impl("sls_acq_maximize_dev", g, nullptr, acq_type, ucb_h, starts_dev, false, S, n_local, opts, start_index_offset, x_out,
+                  val_out, idx_out, nullptr, nullptr);
     SLS_CATCH
 }
 
@@ -1354,51 +1307,42 @@ static void upload_max_values(const char* who, sls_gp* g, const double* y_star, 
     h2d(g->ctx, ys.p, y_star, (size_t)K);
 }
 
-extern "C" int sls_mes_terms(sls_ctx* ctx, const double* t, long n, double* g, double* dg) {
+// The scalar terms on their own (test hooks): n inputs through `launch(in, m, out)` in chunks, out[k] (device) for the outputs
+// the caller named in host[k] (nullptr for the others), k < nout
+template <class Launch>
+static int scalar_terms(const char* who, sls_ctx* ctx, const double* in, long n, int nout, double* const* host, Launch&& launch) {
     SLS_TRY
     CtxCall call_(ctx);
-    SLS_REQUIRE(ctx != nullptr, "sls_mes_terms: ctx is NULL");
-    SLS_REQUIRE(n >= 0, "sls_mes_terms: n = %ld", n);
-    if (n == 0 || (!g && !dg)) return SLS_OK;
-    SLS_REQUIRE(t != nullptr, "sls_mes_terms: t is NULL");
+    SLS_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
+    SLS_REQUIRE(n >= 0, "%s: n = %ld", who, n);
+    if (n == 0 || std::all_of(host, host + nout, [](const double* h) { return h == nullptr; })) return SLS_OK;
+    SLS_REQUIRE(in != nullptr, "%s: the input array is NULL", who);
     SLS_HIP(hipSetDevice(ctx->device));
     const long chunk = std::min(n, 1L << 22);
     DBuf buf;
-    buf.ensure((size_t)3 * chunk);
-    for (long i0 = 0; i0 < n; i0 += chunk) {
-        const long m = std::min(chunk, n - i0);
-        h2d(ctx, buf.p, t + i0, (size_t)m);
-        launch_mes_terms(ctx->stream, buf.p, m, g ? buf.p + chunk : nullptr, dg ? buf.p + 2 * chunk : nullptr);
-        if (g) d2h(ctx, g + i0, buf.p + chunk, (size_t)m);
-        if (dg) d2h(ctx, dg + i0, buf.p + 2 * chunk, (size_t)m);
-        sync(ctx);   // buf is refilled by the next chunk
-    }
-    SLS_CATCH
-}
-
-extern "C" int sls_logei_terms(sls_ctx* ctx, const double* u, long n, double* log_h, double* b1, double* b2) {
-    SLS_TRY
-    CtxCall call_(ctx);
-    SLS_REQUIRE(ctx != nullptr, "sls_logei_terms: ctx is NULL");
-    SLS_REQUIRE(n >= 0, "sls_logei_terms: n = %ld", n);
-    if (n == 0 || (!log_h && !b1 && !b2)) return SLS_OK;
-    SLS_REQUIRE(u != nullptr, "sls_logei_terms: u is NULL");
-    SLS_HIP(hipSetDevice(ctx->device));
-    const long chunk = std::min(n, 1L << 22);
-    DBuf buf;
-    buf.ensure((size_t)4 * chunk);
-    double* const host[3] = {log_h, b1, b2};
+    buf.ensure((size_t)(1 + nout) * chunk);
     double* dev[3];
-    for (int k = 0; k < 3; ++k) dev[k] = host[k] ? buf.p + (k + 1) * chunk : nullptr;
+    for (int k = 0; k < nout; ++k) dev[k] = host[k] ? buf.p + (k + 1) * chunk : nullptr;
     for (long i0 = 0; i0 < n; i0 += chunk) {
         const long m = std::min(chunk, n - i0);
-        h2d(ctx, buf.p, u + i0, (size_t)m);
-        launch_logei_terms(ctx->stream, buf.p, m, dev[0], dev[1], dev[2]);
-        for (int k = 0; k < 3; ++k)
+        h2d(ctx, buf.p, in + i0, (size_t)m);
+        launch(buf.p, m, dev);
+        for (int k = 0; k < nout; ++k)
             if (host[k]) d2h(ctx, host[k] + i0, dev[k], (size_t)m);
         sync(ctx);   // buf is refilled by the next chunk
     }
     SLS_CATCH
+}
+extern "C" int sls_mes_terms(sls_ctx* ctx, const double* t, long n, double* g, double* dg) {
+    double* const host[2] = {g, dg};
+    return scalar_terms("sls_mes_terms", ctx, t, n, 2, host,
+                        [&](const double* in, long m, double* const* out) { launch_mes_terms(ctx->stream, in, m, out[0], out[1]); });
+}
+extern "C" int sls_logei_terms(sls_ctx* ctx, const double* u, long n, double* log_h, double* b1, double* b2) {
+    double* const host[3] = {log_h, b1, b2};
+    return scalar_terms("sls_logei_terms", ctx, u, n, 3, host, [&](const double* in, long m, double* const* out) {
+        launch_logei_terms(ctx->stream, in, m, out[0], out[1], out[2]);
+    });
 }
 
 extern "C" int sls_mes_eval(sls_gp* g, const double* y_star, int K, const double* Xs, int M, double* val, double* grad) {
@@ -1414,15 +1358,8 @@ extern "C" int sls_mes_eval(sls_gp* g, const double* y_star, int K, const double
     }
     SLS_REQUIRE(Xs != nullptr, "sls_mes_eval: Xs is NULL");
     SLS_REQUIRE(val != nullptr, "sls_mes_eval: val is NULL");
-    const int Mp = round_up(M, 128), D = g->D;
-    upload_candidates(g, Xs, M, g->raw, Mp);
-    EvalOut want;
-    want.val = val; want.grad = grad;
-    g->outv.ensure(eval_block_doubles(want, D, Mp));
-    const EvalOut o = eval_block(want, g->outv.p, D, Mp);
     const MesSamples mes{ys.p, K};
-    eval_acq(g, nullptr, g->raw.p, Mp, M, 0, 0.0, o.val, o.grad, Mp, &mes);
-    download_block(g, want, g->outv.p, M, Mp);
+    eval_acq_points(g, nullptr, 0, 0.0, Xs, M, val, grad, &mes);
     SLS_CATCH
 }
 
@@ -1433,13 +1370,11 @@ extern "C" int sls_mes_maximize(sls_gp* g, const double* y_star, int K, const do
     CtxCall call_(g);
     SLS_REQUIRE(g != nullptr, "sls_mes_maximize: gp is NULL");
     SLS_REQUIRE(starts != nullptr, "sls_mes_maximize: starts is NULL");
-    SLS_REQUIRE(S >= 1 && n_local >= 1, "sls_mes_maximize: need S >= 1 and n_local >= 1 (S = %d, n_local = %d)", S, n_local);
-    DBuf ys, sd;
+    DBuf ys;
     upload_max_values("sls_mes_maximize", g, y_star, K, ys);
-    sd.ensure((size_t)g->D * S);
-    h2d(g->ctx, sd.p, starts, (size_t)g->D * S);
     const MesSamples mes{ys.p, K};
-    maximize_impl(g, nullptr, 0, 0.0, sd.p, S, n_local, opts, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars, &mes);
+    maximize_impl("sls_mes_maximize", g, nullptr, 0, 0.0, starts, true, S, n_local, opts, start_index_offset, x_out, val_out, idx_out,
+                  x_stars, y_stars, &mes);
     SLS_CATCH
 }
 
@@ -1557,25 +1492,16 @@ extern "C" int sls_eubo_eval(sls_gp* g, const double* pairs, int M, double* val,
     SLS_REQUIRE(M >= 0, "sls_eubo_eval: M = %d", M);
     if (M == 0) return SLS_OK;
     std::shared_lock<std::shared_mutex> state_(g->state_mtx);
-    sls_ctx* c = g->ctx;
     const int Mp = round_up(M, 128), D2 = 2 * g->D;
-    // host 2D x M column-major -> candidate-major raw coordinates (padding columns at the centre of the box)
-    std::vector<double> t((size_t)Mp * D2, 0.5);
-    for (int m = 0; m < M; ++m)
-        for (int r = 0; r < D2; ++r) t[(size_t)m + (size_t)r * Mp] = pairs[r + (size_t)m * D2];
-    g->raw.ensure((size_t)Mp * D2);
-    h2d(c, g->raw.p, t.data(), (size_t)Mp * D2);
-    sync(c);
+    upload_candidates(g, pairs, D2, M, Mp);
     std::vector<double> unused;   // the kernel always writes the values
     if (!val) unused.resize(M);
     EvalOut want;
     want.val = val ? val : unused.data(); want.grad = grad;
-    const size_t n = eval_block_doubles(want, D2, Mp);
-    g->outv.ensure(n);
+    g->outv.ensure(eval_block_doubles(want, D2, Mp));
     const EvalOut o = eval_block(want, g->outv.p, D2, Mp);
     eval_pairs(g, g->raw.p, Mp, M, o.val, o.grad, Mp);
-    std::vector<double> pageable;
-    eval_block_to_host(want, eval_block(want, fetch(g, g->outv.p, n, pageable), D2, Mp), D2, M);
+    download_block(g, want, g->outv.p, D2, M, Mp);
     SLS_CATCH
 }
 
@@ -1586,39 +1512,25 @@ extern "C" int sls_eubo_maximize(sls_gp* g, const double* starts, int S, int n_l
     CtxCall call_(g);
     SLS_REQUIRE(g != nullptr, "sls_eubo_maximize: gp is NULL");
     SLS_REQUIRE(starts != nullptr, "sls_eubo_maximize: starts is NULL");
-    SLS_REQUIRE(S >= 1 && n_local >= 1, "sls_eubo_maximize: need S >= 1 and n_local >= 1 (S = %d, n_local = %d)", S, n_local);
-    const sls_lbfgs_opts o = read_lbfgs_opts(opts);
-    SLS_REQUIRE(o.history >= 1 && o.history <= 8, "L-BFGS history must be in 1..8");
     std::shared_lock<std::shared_mutex> state_(g->state_mtx);
     sls_ctx* c = g->ctx;
     // the maximiser of sls_acq_maximize over [0,1]^(2D): every block sized by the number of variables is sized for 2D here (the
     // optimiser's workspace, the mapped block of the best start, the downloads); the handle's own sizes stay as they are
-    const int Sp = round_up(S, 128), D2 = 2 * g->D;
+    const int D2 = 2 * g->D;
+    MultistartRun r = maximize_begin("sls_eubo_maximize", g, g->lb, opts, S, n_local, D2);
     DBuf sd;
     sd.ensure((size_t)D2 * S);
     h2d(c, sd.p, starts, (size_t)D2 * S);
-    g->lb.ensure(Sp, o.history, D2);
     g->eubo_best.ensure(c, (size_t)(8 + D2) * sizeof(double), true);
-    g->stat_issued = 0; g->stat_cap = (long)S * n_local; g->stat_rounds = 0; g->stat_live_end = 0;
-    LbfgsState st = g->lb.state(S, D2, o);
     LockstepStats ls;
-    lockstep_rounds(c, st, g->lb, sd.p, S, n_local,
+    lockstep_rounds(c, r.st, g->lb, sd.p, S, n_local,
                     [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
                         eval_pairs(g, trial, ld, nlive, val, grad, ld);   // the trial block of x' is trial + D ld
                     },
                     &ls);
-    g->stat_issued = ls.issued; g->stat_rounds = ls.rounds; g->stat_live_end = ls.live_end;
-    launch_argmax_neg_gather(c->stream, st.f, S, st.x, Sp, D2, g->eubo_best.dev, nullptr);
-    sync(c);
-    const double* best = g->eubo_best.host;
-    if (val_out) *val_out = best[0];
-    if (idx_out) *idx_out = (long)best[1] + start_index_offset;
-    if (x_out) std::copy(best + 8, best + 8 + D2, x_out);
-    if (x_stars) download_cm(g, st.x, S, Sp, D2, x_stars);
-    if (y_stars) {
-        download_cm(g, st.f, S, Sp, 1, y_stars);
-        for (int i = 0; i < S; ++i) y_stars[i] = -y_stars[i];
-    }
+    std::vector<double> pageable;
+    maximize_finish(c, r, ls, BestBlock{g->eubo_best.dev, g->eubo_best.host, false}, staged_fetch(g, pageable), start_index_offset,
+                    x_out, val_out, idx_out, x_stars, y_stars);
     SLS_CATCH
 }
 
@@ -1782,7 +1694,7 @@ extern "C" int sls_gp_append_point(sls_gp* g, const double* x, double y_new) {
         return SLS_OK;
     }
     // candidate-major upload of the single point, cross covariances k = k(X, x) through the regular evaluation kernels
-    upload_candidates(g, x, 1, g->raw, 128);
+    upload_candidates(g, x, D, 1, 128);
     ensure_eval_ws(g, 128);
     g->outv.ensure(4 * (size_t)Np + 8);
     double* kvec = g->outv.p;            // k (Np, strided copy of Ks row 0)

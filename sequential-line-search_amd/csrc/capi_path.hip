@@ -209,7 +209,7 @@ extern "C" int sls_path_eval(sls_path* p, const double* Xs, int M, const int* dr
     const int D = g.D, Mp = round_up(M, 128), nd = p->n_draws;
     DBuf raw, vout, gout, dbuf;
     raw.ensure((size_t)D * M);
-    SLS_HIP(hipMemcpyAsync(raw.p, Xs, (size_t)D * M * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    h2d(c, raw.p, Xs, (size_t)D * M);
     if (draw_of_point) {
         int* d_draw = ints(dbuf, (size_t)M);
         SLS_HIP(hipMemcpyAsync(d_draw, draw_of_point, (size_t)M * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -217,16 +217,11 @@ extern "C" int sls_path_eval(sls_path* p, const double* Xs, int M, const int* dr
         if (grad) gout.ensure((size_t)Mp * D);
         EvalWs ws;
         path_eval_device(p, g, ws, raw.p, 0, true, M, d_draw, vout.p, 0, grad ? gout.p : nullptr, Mp);
-        SLS_HIP(hipMemcpyAsync(val, vout.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        std::vector<double> gh;
-        if (grad) {
-            gh.resize((size_t)Mp * D);
-            SLS_HIP(hipMemcpyAsync(gh.data(), gout.p, gh.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        }
+        d2h(c, val, vout.p, (size_t)M);
+        std::vector<double> gh(grad ? (size_t)Mp * D : 0);
+        if (grad) d2h(c, gh.data(), gout.p, gh.size());
         SLS_HIP(hipStreamSynchronize(c->stream));
-        if (grad)
-            for (int m = 0; m < M; ++m)
-                for (int d = 0; d < D; ++d) grad[d + (size_t)m * D] = gh[m + (size_t)d * Mp];
+        cm_to_host(gh.data(), Mp, D, M, grad);
     } else {
         vout.ensure((size_t)Mp * p->Rp);
         EvalWs ws;
@@ -241,24 +236,23 @@ extern "C" int sls_path_maximize(sls_path* p, const double* starts, int S, int n
                                  double* val_out, long* idx_out) {
     SLS_TRY
     SLS_REQUIRE(p && starts, "sls_path_maximize: NULL argument");
-    SLS_REQUIRE(S >= 1 && n_local >= 1, "sls_path_maximize: need S >= 1 and n_local >= 1 (S = %d, n_local = %d)", S, n_local);
-    SLS_REQUIRE((long)S * p->n_draws <= (1L << 26), "sls_path_maximize: n_draws S = %ld starts exceed 2^26", (long)S * p->n_draws);
-    const sls_lbfgs_opts o = read_lbfgs_opts(opts);
-    SLS_REQUIRE(o.history >= 1 && o.history <= 8, "L-BFGS history must be in 1..8");
+    SLS_REQUIRE(S >= 1 && (long)S * p->n_draws <= (1L << 26), "sls_path_maximize: S = %d starts per draw (1 .. 2^26 / n_draws)", S);
     GpReadCall call(p->gp, p->generation, "sls_path_maximize");
     const GpView& g = call.g;
     sls_ctx* c = g.ctx;
     const int D = g.D, nd = p->n_draws, T = S * nd, Sp = round_up(T, 128);
+    // the shared prologue and search over all T = n_draws S starts at once; the winner is per DRAW, so the epilogue below is this
+    // entry point's own (and sls_acq_last_stats, which speaks of one winner's run, is left alone)
     LbfgsWs lb;
     EvalWs ws;
-    lb.ensure(Sp, o.history, D, Sp);
-    LbfgsState st = lb.state(T, D, o);
+    MultistartRun r = maximize_begin("sls_path_maximize", nullptr, lb, opts, T, n_local, D, Sp);
+    const LbfgsState& st = r.st;
     int* d_draw = lb.tail();   // the draw of every live column
     DBuf sd;
     sd.ensure((size_t)D * T);
-    SLS_HIP(hipMemcpyAsync(sd.p, starts, (size_t)D * T * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    // the shared lock-step rounds over the active set, with f_{live[j] / S} as the objective of compacted column j
-    lockstep_rounds(c, st, lb, sd.p, T, n_local,
+    h2d(c, sd.p, starts, (size_t)D * T);
+    // f_{live[j] / S} is the objective of compacted column j
+    lockstep_rounds(c, r.st, lb, sd.p, T, n_local,
                     [&](const double* trial, long ld, int nlive, const int* live, double* val, double* grad) {
                         launch_path_draw_of_live(c->stream, live, nlive, S, d_draw);
                         path_eval_device(p, g, ws, trial, ld, false, nlive, d_draw, val, 0, grad, ld);
@@ -268,7 +262,7 @@ extern "C" int sls_path_maximize(sls_path* p, const double* starts, int S, int n
     best.ensure((size_t)nd * (D + 2));
     launch_path_argmax(c->stream, st.f, S, nd, st.x, Sp, D, best.p);
     std::vector<double> bh((size_t)nd * (D + 2));
-    SLS_HIP(hipMemcpyAsync(bh.data(), best.p, bh.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    d2h(c, bh.data(), best.p, bh.size());
     SLS_HIP(hipStreamSynchronize(c->stream));
     for (int s = 0; s < nd; ++s) {
         const double* b = bh.data() + (size_t)s * (D + 2);
@@ -422,32 +416,22 @@ extern "C" int sls_qeubo_eval(sls_path* p, int q, const double* sets, int M, dou
     const GpView& g = call.g;
     sls_ctx* c = g.ctx;
     const int qD = q * g.D, Mp = round_up(M, 128);
-    // host qD x M column-major -> candidate-major raw coordinates
-    std::vector<double> t((size_t)Mp * qD, 0.5);
-    for (int m = 0; m < M; ++m)
-        for (int r = 0; r < qD; ++r) t[(size_t)m + (size_t)r * Mp] = sets[r + (size_t)m * qD];
+    const std::vector<double> t = host_to_cm(sets, qD, M, Mp);   // alive until the synchronisation below
     DBuf raw, out, wb;
     raw.ensure(t.size());
-    SLS_HIP(hipMemcpyAsync(raw.p, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    h2d(c, raw.p, t.data(), t.size());
     out.ensure((size_t)Mp * (1 + qD));
     int* d_wins = wins ? ints(wb, (size_t)Mp * q) : nullptr;
     QeuboWs ws;
     qeubo_eval_device(p, g, ws, q, raw.p, Mp, M, out.p, grad ? out.p + Mp : nullptr, Mp, d_wins, Mp);
     std::vector<double> oh((size_t)Mp * (grad ? 1 + qD : 1));
-    std::vector<int> wh;
-    SLS_HIP(hipMemcpyAsync(oh.data(), out.p, oh.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (wins) {
-        wh.resize((size_t)Mp * q);
-        SLS_HIP(hipMemcpyAsync(wh.data(), d_wins, wh.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    }
+    std::vector<int> wh(wins ? (size_t)Mp * q : 0);
+    d2h(c, oh.data(), out.p, oh.size());
+    if (wins) SLS_HIP(hipMemcpyAsync(wh.data(), d_wins, wh.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     SLS_HIP(hipStreamSynchronize(c->stream));
-    for (int m = 0; m < M; ++m) {
-        if (val) val[m] = oh[m];
-        if (grad)
-            for (int r = 0; r < qD; ++r) grad[r + (size_t)m * qD] = oh[(size_t)Mp * (1 + r) + m];
-        if (wins)
-            for (int i = 0; i < q; ++i) wins[i + (size_t)m * q] = wh[(size_t)m + (size_t)i * Mp];
-    }
+    cm_to_host(oh.data(), Mp, 1, M, val);
+    cm_to_host(oh.data() + Mp, Mp, qD, M, grad);
+    cm_to_host(wh.data(), Mp, q, M, wins);
     SLS_CATCH
 }
 
@@ -457,50 +441,32 @@ extern "C" int sls_qeubo_maximize(sls_path* p, int q, const double* starts, int 
     SLS_TRY
     SLS_REQUIRE(p && starts, "sls_qeubo_maximize: NULL argument");
     SLS_REQUIRE(q >= 1 && q <= SLS_QEUBO_MAX_OPTIONS, "sls_qeubo_maximize: q = %d (1 .. %d)", q, SLS_QEUBO_MAX_OPTIONS);
-    SLS_REQUIRE(S_starts >= 1 && n_local >= 1, "sls_qeubo_maximize: need S_starts >= 1 and n_local >= 1 (S_starts = %d, n_local = %d)",
-                S_starts, n_local);
-    const sls_lbfgs_opts o = read_lbfgs_opts(opts);
-    SLS_REQUIRE(o.history >= 1 && o.history <= 8, "L-BFGS history must be in 1..8");
     GpReadCall call(p->gp, p->generation, "sls_qeubo_maximize");
     const GpView& g = call.g;
     sls_ctx* c = g.ctx;
-    // the maximiser of sls_acq_maximize over [0,1]^(qD): one start = one set of q options
-    const int S = S_starts, qD = q * g.D, Sp = round_up(S, 128);
+    // the maximiser of sls_acq_maximize over [0,1]^(qD): one start = one set of q options.  Workspaces are per call; the best start
+    // and every fetch come back through pageable memory.
+    const int S = S_starts, qD = q * g.D;
     LbfgsWs lb;
     QeuboWs ws;
-    lb.ensure(Sp, o.history, qD);
-    LbfgsState st = lb.state(S, qD, o);
+    MultistartRun r = maximize_begin("sls_qeubo_maximize", p->gp, lb, opts, S, n_local, qD);
     DBuf sd, best;
     sd.ensure((size_t)qD * S);
     best.ensure((size_t)8 + qD);
-    SLS_HIP(hipMemcpyAsync(sd.p, starts, (size_t)qD * S * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    gp_set_acq_stats(p->gp, 0, (long)S * n_local, 0, 0);
+    h2d(c, sd.p, starts, (size_t)qD * S);
     LockstepStats ls;
-    lockstep_rounds(c, st, lb, sd.p, S, n_local,
+    lockstep_rounds(c, r.st, lb, sd.p, S, n_local,
                     [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
                         qeubo_eval_device(p, g, ws, q, trial, ld, nlive, val, grad, ld, nullptr, 0);
                     },
                     &ls);
-    gp_set_acq_stats(p->gp, ls.issued, (long)S * n_local, ls.rounds, ls.live_end);
-    launch_argmax_neg_gather(c->stream, st.f, S, st.x, Sp, qD, best.p, nullptr);
-    std::vector<double> bh((size_t)8 + qD), xh, fh;
-    SLS_HIP(hipMemcpyAsync(bh.data(), best.p, bh.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (x_stars) {
-        xh.resize((size_t)Sp * qD);
-        SLS_HIP(hipMemcpyAsync(xh.data(), st.x, xh.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    }
-    if (y_stars) {
-        fh.resize(Sp);
-        SLS_HIP(hipMemcpyAsync(fh.data(), st.f, fh.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    }
-    SLS_HIP(hipStreamSynchronize(c->stream));
-    if (val_out) *val_out = bh[0];
-    if (idx_out) *idx_out = (long)bh[1] + start_index_offset;
-    if (x_out) std::copy(bh.begin() + 8, bh.begin() + 8 + qD, x_out);
-    for (int n = 0; n < S; ++n) {
-        if (x_stars)
-            for (int r = 0; r < qD; ++r) x_stars[r + (size_t)n * qD] = xh[(size_t)n + (size_t)r * Sp];
-        if (y_stars) y_stars[n] = -fh[n];
-    }
+    std::vector<double> bh((size_t)8 + qD), pageable;
+    auto fetch = [&](const double* dev, size_t n) {
+        pageable.resize(n);
+        d2h(c, pageable.data(), dev, n);
+        SLS_HIP(hipStreamSynchronize(c->stream));
+        return pageable.data();
+    };
+    maximize_finish(c, r, ls, BestBlock{best.p, bh.data(), true}, fetch, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars);
     SLS_CATCH
 }

@@ -39,7 +39,7 @@ struct GpView {
     std::shared_mutex* state;
 };
 GpView gp_view(sls_gp* g);
-// what sls_acq_last_stats reports for the handle: set by a maximiser that runs outside capi.hip (sls_qeubo_maximize)
+// what sls_acq_last_stats reports for the handle: the one place every maximiser stores it (lbfgs_driver.hpp)
 void gp_set_acq_stats(sls_gp* g, long issued, long cap, int rounds, int live_end);
 // sls_lbfgs_opts as the caller's struct_size declares it, over the library's defaults (capi.hip)
 sls_lbfgs_opts read_lbfgs_opts(const sls_lbfgs_opts* in);
@@ -268,4 +268,27 @@ struct ProfScope {
         if (c->prof_on) c->prof_end(name, e0);
     }
 };
+
+// n doubles between host and device, asynchronous on the context's stream
+inline void h2d(sls_ctx* c, double* dst, const double* src, size_t n) {
+    SLS_HIP(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+}
+inline void d2h(sls_ctx* c, double* dst, const double* src, size_t n) {
+    SLS_HIP(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+}
+// The two host-side transposes of the entry points.  The caller's points are rows x M column-major (X[r + m*rows]); the kernels
+// read candidate-major blocks t[m + r*ld].  host_to_cm pads the columns M .. Mp with the centre of the box.
+inline std::vector<double> host_to_cm(const double* X, int rows, int M, int Mp) {
+    std::vector<double> t((size_t)Mp * rows, 0.5);
+    for (int m = 0; m < M; ++m)
+        for (int r = 0; r < rows; ++r) t[(size_t)m + (size_t)r * Mp] = X[r + (size_t)m * rows];
+    return t;
+}
+// candidate-major src[m + r*ld] into the caller's array (NULL: not asked for): rows = 1: a vector of M; else rows x M column-major
+template <class T>
+void cm_to_host(const T* src, long ld, int rows, int M, T* host) {
+    if (!host) return;
+    for (int m = 0; m < M; ++m)
+        for (int r = 0; r < rows; ++r) host[r + (size_t)m * rows] = src[(size_t)m + (size_t)r * ld];
+}
 }  // namespace slsk

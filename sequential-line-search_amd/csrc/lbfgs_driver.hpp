@@ -1,5 +1,6 @@
-// Host side of the lock-step multistart L-BFGS (kernels_acq.hip: lbfgs_step, compact_live, gather_trials): the device blocks of one
-// run and the round loop over the active set that sls_acq_maximize* (capi.hip) and sls_path_maximize (capi_path.hip) share.
+// Host side of the multistart L-BFGS maximisers (kernels_acq.hip: lbfgs_step, compact_live, gather_trials): the device blocks of
+// one run, the lock-step round loop over the active set, and the maximiser around it that every *_maximize entry point shares --
+// maximize_begin (options, workspace, statistics), a search the caller supplies, maximize_finish (winner and per-start results).
 #pragma once
 #include "common.hpp"
 
@@ -50,6 +51,8 @@ struct LbfgsWs {
 struct LockstepStats {
     long issued = 0;             // evaluations of starts that were still moving
     int rounds = 0, live_end = 0;
+    // a search that counts `issued` on the device instead: maximize_finish reads the counter back with the best start
+    const unsigned long long* issued_dev = nullptr;
 };
 
 // Lock-step rounds over the ACTIVE SET.  NLopt's max_evals is a cap per start, not a quota (src/acquisition-function.cpp:128-129): a
@@ -98,6 +101,66 @@ void lockstep_rounds(sls_ctx* c, LbfgsState& st, LbfgsWs& ws, const double* star
     }
     s.live_end = compact ? nlive : moving;
     if (stats) *stats = s;
+}
+
+// ---- the maximiser around a search ------------------------------------------------------------------------------------------------
+// One run over S starts in nvar variables (D; 2D for query pairs; qD for sets of q options).
+struct MultistartRun {
+    sls_lbfgs_opts o;
+    LbfgsState st;       // st.S starts, st.D variables, leading dimension st.ld = round_up(S, 128)
+    int n_local;
+    sls_gp* stats_of;    // the handle whose sls_acq_last_stats this run is (nullptr: none)
+};
+
+// Prologue: the caller's options over the defaults, the workspace (the handle's on the sls_gp routes, so that a repeated call costs no
+// allocation; tail_ints as in LbfgsWs::ensure) and the statistics of a run that has not evaluated anything yet.
+inline MultistartRun maximize_begin(const char* who, sls_gp* stats_of, LbfgsWs& ws, const sls_lbfgs_opts* opts, int S, int n_local,
+                                    int nvar, size_t tail_ints = 0) {
+    SLS_REQUIRE(S >= 1 && n_local >= 1, "%s: need S >= 1 and n_local >= 1 (S = %d, n_local = %d)", who, S, n_local);
+    const sls_lbfgs_opts o = read_lbfgs_opts(opts);
+    SLS_REQUIRE(o.history >= 1 && o.history <= 8, "%s: L-BFGS history must be in 1..8 (got %d)", who, o.history);
+    ws.ensure(round_up(S, 128), o.history, nvar, tail_ints);
+    MultistartRun r;
+    r.o = o;
+    r.st = ws.state(S, nvar, o);
+    r.n_local = n_local;
+    r.stats_of = stats_of;
+    if (stats_of) gp_set_acq_stats(stats_of, 0, (long)S * n_local, 0, 0);
+    return r;
+}
+
+// Between the two, the search: lockstep_rounds with the caller's objective, or anything else that leaves the starts' end points in
+// st.x and their negated values in st.f on the context's stream and says what it did in a LockstepStats.
+
+// The best start's block, 8 + nvar doubles (launch_argmax_neg_gather): a mapped block as the device and the host see it, or
+// (copy) a device block and pageable memory it is copied to ahead of the synchronisation.
+struct BestBlock {
+    double* dev;
+    double* host;
+    bool copy;
+};
+
+// Epilogue of a maximiser with ONE winner: first maximum of -f and its point in one launch, ONE synchronisation, the statistics, then
+// what the caller asked for -- value, index (+ off) and point of the winner; every start's end point (x_stars, nvar x S column-major)
+// and value (y_stars).  fetch(dev, n): n doubles of device memory where the host can read them on return (one synchronisation each).
+template <class Fetch>
+void maximize_finish(sls_ctx* c, const MultistartRun& r, const LockstepStats& ls, BestBlock best, Fetch&& fetch, long off,
+                     double* x_out, double* val_out, long* idx_out, double* x_stars, double* y_stars) {
+    const LbfgsState& st = r.st;
+    const int S = st.S, nvar = st.D;
+    launch_argmax_neg_gather(c->stream, st.f, S, st.x, st.ld, nvar, best.dev, ls.issued_dev);
+    if (best.copy) d2h(c, best.host, best.dev, (size_t)8 + nvar);
+    SLS_HIP(hipStreamSynchronize(c->stream));
+    const double* b = best.host;
+    if (r.stats_of) gp_set_acq_stats(r.stats_of, ls.issued_dev ? (long)b[2] : ls.issued, (long)S * r.n_local, ls.rounds, ls.live_end);
+    if (val_out) *val_out = b[0];
+    if (idx_out) *idx_out = (long)b[1] + off;
+    if (x_out) std::copy(b + 8, b + 8 + nvar, x_out);
+    if (x_stars) cm_to_host(fetch(st.x, (size_t)st.ld * nvar), st.ld, nvar, S, x_stars);
+    if (y_stars) {
+        const double* f = fetch(st.f, (size_t)st.ld);
+        for (int i = 0; i < S; ++i) y_stars[i] = -f[i];
+    }
 }
 
 }  // namespace slsk
