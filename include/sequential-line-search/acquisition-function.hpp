@@ -180,6 +180,30 @@ namespace sequential_line_search
                                                                               const unsigned num_local_search_iters = 50,
                                                                               const unsigned long long seed = 0,
                                                                               const int num_frequencies = 2048, double* value = nullptr);
+
+        /// A batch of num_points >= 1 points chosen jointly by noisy expected improvement on posterior draws (not in the reference;
+        /// qNEI, Letham et al. 2019, include/sls_hip.h sls_qnei_*): num_draws pathwise posterior draws (SamplePosteriorFunctions with
+        /// stream `seed` and num_frequencies random features) fix the estimator (1 / num_draws) sum_s max(0, max_i f_s(x_i) - t_s)
+        /// with the incumbent t_s = max_j f_s(X_j) taken per draw over the regressor's data (MaxOverPoints(GetLargeX())) -- unlike
+        /// FindNextPoints, which improves on a known number --, maximised over [0,1]^(num_points D) jointly: one L-BFGS of
+        /// num_local_search_iters evaluations (the tolerances of GetLocalSearchTolerances) from each of num_global_search_iters
+        /// uniform starts of the generator FindNextQueryByExpectedUtility uses, seeded with `seed`, all in lock step on the device.
+        /// The same seed gives the same points.  value (may be nullptr) receives the improvement there.  Device-resident regressors
+        /// only (std::invalid_argument otherwise).
+        std::vector<Eigen::VectorXd> FindNextPointsByNoisyExpectedImprovement(const Regressor& regressor, const int num_points,
+                                                                              const unsigned num_draws = 256,
+                                                                              const unsigned num_global_search_iters = 100,
+                                                                              const unsigned num_local_search_iters = 50,
+                                                                              const unsigned long long seed = 0,
+                                                                              const int num_frequencies = 2048, double* value = nullptr);
+        /// The same from an explicit start set ((num_points D) x S: rows iD..iD+D-1 start point i).
+        std::vector<Eigen::VectorXd> FindNextPointsByNoisyExpectedImprovementFromStarts(const Regressor& regressor, const int num_points,
+                                                                                        const Eigen::MatrixXd& starts,
+                                                                                        const unsigned num_draws = 256,
+                                                                                        const unsigned num_local_search_iters = 50,
+                                                                                        const unsigned long long seed = 0,
+                                                                                        const int num_frequencies = 2048,
+                                                                                        double* value = nullptr);
     } // namespace acquisition_func
 } // namespace sequential_line_search
 

@@ -219,6 +219,23 @@ namespace Eigen
         Index            m_r, m_c;
         std::vector<int> m_v;
     };
+
+    /// Integer vector: indices that come back from the device (the per-draw incumbent's data point).
+    class VectorXi
+    {
+    public:
+        VectorXi() {}
+        explicit VectorXi(Index n) : m_v(static_cast<size_t>(n), 0) {}
+        static VectorXi Zero(Index n) { return VectorXi(n); }
+        Index      size() const { return static_cast<Index>(m_v.size()); }
+        int*       data() { return m_v.data(); }
+        const int* data() const { return m_v.data(); }
+        int&       operator()(Index i) { return m_v[static_cast<size_t>(i)]; }
+        int        operator()(Index i) const { return m_v[static_cast<size_t>(i)]; }
+
+    private:
+        std::vector<int> m_v;
+    };
 } // namespace Eigen
 
 #endif // !SLS_HAVE_REAL_EIGEN

@@ -66,6 +66,13 @@ namespace sequential_line_search
         /// any feedback it throws as DetermineNextQuery does; non-positive iteration counts select the same heuristic.
         void DetermineNextQueryByExpectedUtilityOfDraws(const unsigned long long seed, const int num_draws = 256,
                                                         const int num_global_search_iters = 0, const int num_local_search_iters = 0);
+        /// Opt-in alternative: option 0 as in DetermineNextQuery, the other m_num_options - 1 options the JOINT maximiser of noisy
+        /// expected improvement on num_draws posterior draws (acquisition_func::FindNextPointsByNoisyExpectedImprovement with draw
+        /// and start stream `seed`): improvement over the per-draw incumbent rather than over a known best value, which a
+        /// preference model does not have.  Before any feedback it throws as DetermineNextQuery does; non-positive iteration counts
+        /// select the same heuristic.
+        void DetermineNextQueryByNoisyExpectedImprovement(const unsigned long long seed, const int num_draws = 256,
+                                                          const int num_global_search_iters = 0, const int num_local_search_iters = 0);
 
         const std::vector<Eigen::VectorXd>& GetCurrentOptions() const { return m_current_options; }
         Eigen::VectorXd                     GetMaximizer() const;

@@ -105,8 +105,32 @@ namespace sequential_line_search
         /// the best end point split into its num_options options.  value (may be nullptr) receives the utility there.
         std::vector<Eigen::VectorXd> MaximizeExpectedUtilityOfBestOption(int num_options, const Eigen::MatrixXd& starts,
                                                                          unsigned num_local_search_iters, double* value = nullptr) const;
+        /// Per draw, the maximum over the columns of Xb (D x Mb, Mb >= 1; include/sls_hip.h sls_path_max_over_points): the draws'
+        /// incumbents when Xb is the data.  arg (may be nullptr) receives the lowest column that attains each maximum.
+        Eigen::VectorXd MaxOverPoints(const Eigen::MatrixXd& Xb, Eigen::VectorXi* arg = nullptr) const;
+        /// Noisy expected improvement of q = options.size() points on these draws over the per-draw baseline (qNEI, Letham et al.
+        /// 2019; include/sls_hip.h sls_qnei_*): (1 / num_draws) sum_s max(0, max_i f_s(x_i) - baseline_s), baseline of num_draws
+        /// finite values (MaxOverPoints at the data; a constant gives Monte-Carlo qEI).  Arguments and results as
+        /// CalcExpectedUtilitiesOfBestOption; a draw that nobody improves has no winner, so a column of win_counts sums to at most
+        /// num_draws.
+        Eigen::VectorXd CalcNoisyExpectedImprovements(const std::vector<Eigen::MatrixXd>& options, const Eigen::VectorXd& baseline,
+                                                      std::vector<Eigen::MatrixXd>* grads = nullptr,
+                                                      Eigen::MatrixXi* win_counts = nullptr) const;
+        /// Maximiser of that improvement over [0,1]^(num_points D): as MaximizeExpectedUtilityOfBestOption.  A start that no draw
+        /// improves is stationary (value 0, zero gradient) and does not move.
+        std::vector<Eigen::VectorXd> MaximizeNoisyExpectedImprovement(int num_points, const Eigen::VectorXd& baseline,
+                                                                      const Eigen::MatrixXd& starts, unsigned num_local_search_iters,
+                                                                      double* value = nullptr) const;
 
     private:
+        // the set criteria of both kinds: baseline == nullptr is the expected utility of the best option
+        Eigen::VectorXd              CalcSetCriterion(const char* who, const std::vector<Eigen::MatrixXd>& options,
+                                                      const Eigen::VectorXd* baseline, std::vector<Eigen::MatrixXd>* grads,
+                                                      Eigen::MatrixXi* win_counts) const;
+        std::vector<Eigen::VectorXd> MaximizeSetCriterion(const char* who, int num_options, const Eigen::VectorXd* baseline,
+                                                          const Eigen::MatrixXd& starts, unsigned num_local_search_iters,
+                                                          double* value) const;
+
         sls_path* m_path      = nullptr;
         int       m_num_draws = 0;
         int       m_num_dims  = 0;

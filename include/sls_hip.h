@@ -411,6 +411,48 @@ int sls_qeubo_eval(sls_path* p, int q, const double* sets, int M, double* val, d
 int sls_qeubo_maximize(sls_path* p, int q, const double* starts, int S_starts, int n_local, const sls_lbfgs_opts* opts,
                        long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars, double* y_stars);
 
+/* ---- noisy expected improvement on posterior draws (not in the reference) -------------------------------------------------
+ * qNEI (Letham et al., Bayesian Analysis 2019), the joint improvement of a batch of q points over an incumbent that is itself
+ * uncertain -- the targets of a PreferenceRegressor are MAP estimates of a latent function, so the best value seen so far is not a
+ * known number.  The estimator is a sample average over the FIXED draws of a path object p (n_draws = S draws f_s), with the incumbent
+ * taken per draw, from the same draw that evaluates the candidates:
+ *   t_s     = max_j f_s(X_j)                              (sls_path_max_over_points at the data, or any point set; any finite
+ *                                                          baseline may be passed: a constant one gives Monte-Carlo qEI)
+ *   v_{i,s} = f_s(x_i)                                    (formed as by sls_qeubo_eval: Phi^T W + K* V on the tile GEMM)
+ *   per draw, the scan  best = t_s, arg = none; for i = 0..q-1: if v_{i,s} > best then best = v_{i,s}, arg = i
+ *   wins_i  = #{ s : arg(s) = i }                         (sum_i wins_i <= S: a draw that nobody improves has no winner)
+ *   qNEI    = ( sum_s (best_s - t_s) ) / S                (one lane per set, from zero, increasing s, ONE division; a draw without
+ *                                                          a winner adds exactly +0)
+ *   m_i     = 0/1 indicator vector of { s : arg(s) = i }  (the column of a draw without a winner is all zero)
+ *   grad_{x_i} qNEI = ( grad fbar_i(x_i) ) / S,  fbar_i = the path function with weights (W m_i, V m_i), exactly as qEUBO forms it
+ * An option that wins no draw has an exactly zero gradient; a set that no draw improves has the value exactly 0 and the zero gradient.
+ * Guard: a NaN among the set's q S values or its qD gradient components gives the value 0 and the zero gradient (expected
+ * improvement's guard; the value is bounded below by 0, so no floor constant is needed).  The gradient is formed, and looked at by
+ * the guard, whether or not it is asked for.
+ * The pass, its route, the sets per pass and the bit contract are sls_qeubo_eval's (one pass function, the selection kernel apart): a
+ * set's bits depend on neither its column, the other sets of the call, the number of sets per pass nor SLS_COMPACT; permuting the
+ * options of a set permutes wins and the gradient blocks and leaves the value's bits unchanged.
+ * Known limitation: a start set that no draw improves is stationary (value 0, zero gradient) and leaves the maximiser's batch at
+ * once, as expected improvement's underflowed starts do.  A smoothed or log form (qLogNEI) is out of scope here.
+ * Locks are those of sls_path_eval / sls_path_maximize; a path whose handle was refitted, grown or switched in sigma mode is refused
+ * (SLS_ERR_INVALID), as by the other sls_path_* calls. */
+/* t_out[s] = max_j f_s(Xb[:, j]), arg_out[s] = the LOWEST j that attains it; s < n_draws, Xb is D x Mb (host), Mb >= 1.  The values
+ * are formed on the every-draw route of the qEUBO pass (Phi^T W + K* V on the tile GEMM), in passes of points bounded as that pass
+ * bounds the points of one-option sets (candidate chunk, 2^26 rule, whole 128-point tiles); a running (max, argmax) per draw is merged
+ * across the passes, and only the live rows of the last pass take part.  Either out pointer may be NULL.  A NaN among a draw's Mb
+ * values gives t_out[s] = NaN, arg_out[s] = -1.  Max and lowest-index argmax do not depend on order: the result's bits depend on
+ * neither the pass split, the launch geometry nor the position of a point among the others (beyond the index reported).  There is no
+ * NULL-means-data shortcut: the handle keeps only scaled data on the device, so the caller passes X.  Mb < 1, NULL p or NULL Xb is
+ * SLS_ERR_INVALID. */
+int sls_path_max_over_points(sls_path* p, const double* Xb, int Mb, double* t_out, int* arg_out);
+/* baseline: n_draws host doubles, uploaded once per call; all must be finite (else SLS_ERR_INVALID).  sets, val, grad, wins, q and M
+ * as sls_qeubo_eval. */
+int sls_qnei_eval(sls_path* p, int q, const double* baseline, const double* sets, int M, double* val, double* grad, int* wins);
+/* sls_qeubo_maximize with this objective; the baseline is validated and uploaded once, before the first round. */
+int sls_qnei_maximize(sls_path* p, int q, const double* baseline, const double* starts, int S_starts, int n_local,
+                      const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
+                      double* x_stars, double* y_stars);
+
 /* ---- multi-GPU maximisation ------------------------------------------------------------------------------
  * FindGlobalSolution's multi-start loop (src/acquisition-function.cpp:121-153) shards over its starts: the iterations share
  * only the const regressor (:125-141).  Every GPU holds a replica of the fitted state, runs a contiguous slice of the starts
@@ -540,6 +582,9 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
  * "qeubo_agg" (its two aggregation GEMMs Wbar = W mask, Vbar = V mask), "qeubo_data_gemm" (the data term K* V of the every-draw values
  * on the tile GEMM, where sls_path_eval runs path_data's gathered dot; the reused stages count under "cross_gram", "path_prior",
  * "path_data", "path_grad_gemm");
+ * "qnei" (the same two kernels with a per-draw baseline: two launches per pass of sls_qnei_eval / per pass and round of
+ * sls_qnei_maximize; every other stage counts as under qEUBO) and "path_max" (the column reduction of sls_path_max_over_points, one
+ * launch per pass; its values count under "cross_gram", "path_prior", "qeubo_data_gemm");
  * "potrf_fallbacks": launches = how often a single-launch factorisation gave up and was recomputed. */
 int sls_prof_enable(sls_ctx* ctx, int on);
 int sls_prof_reset(sls_ctx* ctx);

@@ -87,6 +87,24 @@ namespace pybind11
                 return a.release();
             }
         };
+        template <> struct type_caster<Eigen::VectorXi>
+        {
+            PYBIND11_TYPE_CASTER(Eigen::VectorXi, const_name("numpy.ndarray[int32[n]]"));
+            bool load(handle src, bool)
+            {
+                auto a = array_t<int, array::c_style | array::forcecast>::ensure(src);
+                if (!a || a.ndim() != 1) return false;
+                value = Eigen::VectorXi(a.shape(0));
+                for (ssize_t i = 0; i < a.shape(0); ++i) value(i) = a.at(i);
+                return true;
+            }
+            static handle cast(const Eigen::VectorXi& v, return_value_policy, handle)
+            {
+                array_t<int> a(v.size());
+                for (long i = 0; i < v.size(); ++i) a.mutable_at(i) = v(i);
+                return a.release();
+            }
+        };
     } // namespace detail
 } // namespace pybind11
 #else
@@ -189,7 +207,32 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
                  const auto q     = s.MaximizeExpectedUtilityOfBestOption(num_options, starts, num_local_search_iters, &value);
                  return std::make_pair(q, value);
              },
-             "num_options"_a, "starts"_a, "num_local_search_iters"_a = 50);
+             "num_options"_a, "starts"_a, "num_local_search_iters"_a = 50)
+        // noisy expected improvement on the draws: max_over_points returns (incumbents, argmax), calc_... (values, [gradient per
+        // point], win counts q x M), maximize_... (points, value)
+        .def("max_over_points",
+             [](const PosteriorFunctionSamples& s, const MatrixXd& points) {
+                 Eigen::VectorXi arg;
+                 const VectorXd  t = s.MaxOverPoints(points, &arg);
+                 return std::make_pair(t, arg);
+             },
+             "points"_a)
+        .def("calc_noisy_expected_improvements",
+             [](const PosteriorFunctionSamples& s, const std::vector<MatrixXd>& options, const VectorXd& baseline) {
+                 std::vector<MatrixXd> grads;
+                 Eigen::MatrixXi       wins;
+                 const VectorXd        v = s.CalcNoisyExpectedImprovements(options, baseline, &grads, &wins);
+                 return std::make_tuple(v, grads, wins);
+             },
+             "options"_a, "baseline"_a)
+        .def("maximize_noisy_expected_improvement",
+             [](const PosteriorFunctionSamples& s, int num_points, const VectorXd& baseline, const MatrixXd& starts,
+                unsigned num_local_search_iters) {
+                 double     value = 0.0;
+                 const auto q     = s.MaximizeNoisyExpectedImprovement(num_points, baseline, starts, num_local_search_iters, &value);
+                 return std::make_pair(q, value);
+             },
+             "num_points"_a, "baseline"_a, "starts"_a, "num_local_search_iters"_a = 50);
     m.def("sample_posterior_functions",
           [](const Regressor& r, int num_draws, unsigned long long seed, int num_frequencies) {
               return r.SamplePosteriorFunctions(num_draws, seed, num_frequencies);
@@ -214,6 +257,28 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
               return std::make_pair(q, value);
           },
           "regressor"_a, "num_options"_a, "starts"_a, "num_draws"_a = 256, "num_local_search_iters"_a = 50, "seed"_a = 0ULL,
+          "num_frequencies"_a = 2048);
+
+    // a batch of points chosen jointly by noisy expected improvement on posterior draws (acquisition-function.hpp): (points, value)
+    m.def("find_next_points_by_noisy_expected_improvement",
+          [](const Regressor& r, int num_points, unsigned num_draws, unsigned num_global_search_iters, unsigned num_local_search_iters,
+             unsigned long long seed, int num_frequencies) {
+              double     value = 0.0;
+              const auto q     = acquisition_func::FindNextPointsByNoisyExpectedImprovement(
+                  r, num_points, num_draws, num_global_search_iters, num_local_search_iters, seed, num_frequencies, &value);
+              return std::make_pair(q, value);
+          },
+          "regressor"_a, "num_points"_a, "num_draws"_a = 256, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50,
+          "seed"_a = 0ULL, "num_frequencies"_a = 2048);
+    m.def("find_next_points_by_noisy_expected_improvement_from_starts",
+          [](const Regressor& r, int num_points, const MatrixXd& starts, unsigned num_draws, unsigned num_local_search_iters,
+             unsigned long long seed, int num_frequencies) {
+              double     value = 0.0;
+              const auto q     = acquisition_func::FindNextPointsByNoisyExpectedImprovementFromStarts(
+                  r, num_points, starts, num_draws, num_local_search_iters, seed, num_frequencies, &value);
+              return std::make_pair(q, value);
+          },
+          "regressor"_a, "num_points"_a, "starts"_a, "num_draws"_a = 256, "num_local_search_iters"_a = 50, "seed"_a = 0ULL,
           "num_frequencies"_a = 2048);
 
     // DIRECT, then one L-BFGS from its result (acquisition_func::FindNextPointDirect) on such a regressor: (point, value)
@@ -284,6 +349,9 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
              "seed"_a, "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0)
         .def("determine_next_query_by_expected_utility_of_draws", &PreferentialBayesianOptimizer::DetermineNextQueryByExpectedUtilityOfDraws,
              "seed"_a, "num_draws"_a = 256, "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0)
+        .def("determine_next_query_by_noisy_expected_improvement",
+             &PreferentialBayesianOptimizer::DetermineNextQueryByNoisyExpectedImprovement, "seed"_a, "num_draws"_a = 256,
+             "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0)
         .def("get_current_options", &PreferentialBayesianOptimizer::GetCurrentOptions)
         .def("get_maximizer", &PreferentialBayesianOptimizer::GetMaximizer)
         .def("get_preference_value_mean", &PreferentialBayesianOptimizer::GetPreferenceValueMean, "point"_a)

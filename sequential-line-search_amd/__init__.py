@@ -65,6 +65,7 @@ EXPORTS = [
     "sls_path_create", "sls_path_destroy", "sls_path_eval", "sls_path_maximize",
     "sls_mes_terms", "sls_mes_eval", "sls_mes_maximize", "sls_logei_terms",
     "sls_eubo_eval", "sls_eubo_maximize", "sls_qeubo_eval", "sls_qeubo_maximize",
+    "sls_path_max_over_points", "sls_qnei_eval", "sls_qnei_maximize",
 ]
 
 
@@ -464,6 +465,63 @@ class PathSamples:
         _ck(lib().sls_qeubo_maximize(self.h, q, _p(starts), S, int(n_local), C.byref(opts) if opts is not None else None,
                                      C.c_long(offset), _p(x), C.byref(val), C.byref(idx), _p(xs) if want_all else None,
                                      _p(ys) if want_all else None))
+        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+
+    def max_over_points(self, Xb):
+        """Per draw, the maximum over the columns of Xb (D x Mb, Mb >= 1) and the lowest column that attains it
+        (sls_path_max_over_points): (t (n_draws,), arg (n_draws,) int32).  A NaN among a draw's values gives (NaN, -1)."""
+        Xb = _f(Xb)
+        if Xb.ndim != 2 or Xb.shape[0] != self.D or Xb.shape[1] < 1:
+            raise SlsError(f"max_over_points: Xb must be D x Mb = {self.D} x Mb with Mb >= 1, got {Xb.shape}")
+        t = np.empty(self.n_draws)
+        arg = np.empty(self.n_draws, dtype=np.int32)
+        _ck(lib().sls_path_max_over_points(self.h, _p(Xb), Xb.shape[1], _p(t), arg.ctypes.data_as(C.POINTER(C.c_int))))
+        return t, arg
+
+    def _baseline(self, who, baseline):
+        t = np.ascontiguousarray(np.asarray(baseline, dtype=np.float64))
+        if t.shape != (self.n_draws,):
+            raise SlsError(f"{who}: baseline must hold n_draws = {self.n_draws} values, got shape {t.shape}")
+        return t
+
+    def qnei_eval(self, sets, q, baseline, want_grad=True, want_wins=False):
+        """Noisy expected improvement of q points on the draws over the per-draw baseline (sls_qnei_eval) at the columns of sets (qD x
+        M: rows iD..iD+D-1 = point i): values (M,), then with want_grad the gradient (qD, M), then with want_wins the win counts
+        (q, M) int32."""
+        sets = _f(sets)
+        q = int(q)
+        if not 1 <= q <= QEUBO_MAX_OPTIONS:
+            raise SlsError(f"qnei_eval: q = {q} (1 .. {QEUBO_MAX_OPTIONS})")
+        if sets.ndim != 2 or sets.shape[0] != q * self.D:
+            raise SlsError(f"qnei_eval: sets must be qD x M = {q * self.D} x M, got {sets.shape}")
+        t = self._baseline("qnei_eval", baseline)
+        M = sets.shape[1]
+        val = np.empty(M)
+        grad = np.empty((q * self.D, M), order="F") if want_grad else None
+        wins = np.zeros((q, M), dtype=np.int32, order="F") if want_wins else None
+        _ck(lib().sls_qnei_eval(self.h, q, _p(t), _p(sets), M, _p(val), _p(grad) if want_grad else None,
+                                wins.ctypes.data_as(C.POINTER(C.c_int)) if want_wins else None))
+        out = (val,) + ((grad,) if want_grad else ()) + ((wins,) if want_wins else ())
+        return out if len(out) > 1 else val
+
+    def qnei_maximize(self, starts, q, n_local, baseline, offset=0, want_all=True, opts=None):
+        """acq_maximize over [0,1]^(qD) with the set objective of qnei_eval (sls_qnei_maximize): starts qD x S, x and x_stars have qD
+        rows.  GP.last_stats() of the path's handle reports the run."""
+        starts = _f(starts)
+        q = int(q)
+        if not 1 <= q <= QEUBO_MAX_OPTIONS:
+            raise SlsError(f"qnei_maximize: q = {q} (1 .. {QEUBO_MAX_OPTIONS})")
+        if starts.ndim != 2 or starts.shape[0] != q * self.D:
+            raise SlsError(f"qnei_maximize: starts must be qD x S = {q * self.D} x S, got {starts.shape}")
+        t = self._baseline("qnei_maximize", baseline)
+        S = starts.shape[1]
+        rows = starts.shape[0]
+        x, val, idx = np.empty(rows), C.c_double(), C.c_long()
+        xs = np.empty((rows, S), order="F") if want_all else None
+        ys = np.empty(S) if want_all else None
+        _ck(lib().sls_qnei_maximize(self.h, q, _p(t), _p(starts), S, int(n_local), C.byref(opts) if opts is not None else None,
+                                    C.c_long(offset), _p(x), C.byref(val), C.byref(idx), _p(xs) if want_all else None,
+                                    _p(ys) if want_all else None))
         return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
 
 

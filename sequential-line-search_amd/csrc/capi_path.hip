@@ -1,4 +1,4 @@
-// C-ABI of the pathwise posterior function draws (include/sls_hip.h: sls_path_*, and sls_qeubo_* on them): host orchestration of
+// C-ABI of the pathwise posterior function draws (include/sls_hip.h: sls_path_*, and sls_qeubo_* / sls_qnei_* on them): host orchestration of
 // kernels_path.hip and kernels_qeubo.hip, the cross Gram / gradient products of kernels_gram.hip / kernels_acq.hip, the tile GEMM
 // and block solve of kernels_tri.hip and the lock-step L-BFGS rounds of lbfgs_driver.hpp.  No CPU fallback.
 #include <algorithm>
@@ -294,17 +294,19 @@ struct QeuboWs {
     int* bad = nullptr;     // one flag per set of the pass
     int* ident = nullptr;   // ident[j] = j: point j is evaluated under aggregated column j
     int ident_n = 0;
-    void ensure(sls_ctx* c, const sls_path* p, const GpView& g, int Pp, int Sp) {
+    // values_only: the blocks of the every-draw values alone (sls_path_max_over_points)
+    void ensure(sls_ctx* c, const sls_path* p, const GpView& g, int Pp, int Sp, bool values_only = false) {
         const size_t P = Pp, Np = g.Np, Fp = p->Fp;
         XsT.ensure(P * g.Dcols);
         ns.ensure(P);
         Ks.ensure(P * Np);
         if (g.kernel == SLS_KERNEL_ARD_MATERN52) Cs.ensure(P * Np);
         PG.ensure(P * (Np + 2 * Fp));
+        VM.ensure(P * p->Rp);
+        if (values_only) return;
         csum.ensure(P);
         vpart.ensure(P * (Fp / 128));
         Gt.ensure(P * g.Dcols);
-        VM.ensure(P * p->Rp);
         Wbar.ensure(2 * Fp * P);
         Vbar.ensure(Np * P);
         sum.ensure(Sp);
@@ -319,16 +321,45 @@ struct QeuboWs {
     }
 };
 
+// Every draw at the Pp points of a pass into w.VM (Pp x Rp): `prep` fills XsT / ns, then cross_gram, Phi^T W and K* V accumulated onto
+// it, both on the tile GEMM.
+template <class Prep>
+void draw_values_device(sls_path* p, const GpView& g, QeuboWs& w, int Pp, Prep&& prep) {
+    sls_ctx* c = g.ctx;
+    const int Np = g.Np, Fp = p->Fp, Rp = p->Rp;
+    KernelSpec ks{g.kernel, g.a};
+    double* Cs = g.kernel == SLS_KERNEL_ARD_MATERN52 ? w.Cs.p : w.Ks.p;
+    double* G = w.PG.p + (size_t)Pp * Np;
+    {
+        ProfScope ps(c, "cross_gram");
+        prep();
+        launch_cross_gram(c->stream, w.XsT.p, Pp, w.ns.p, Pp, g.XT, g.Np, g.nx, Np, g.N, g.Dp, ks, nullptr, w.Ks.p, Cs, Pp, nullptr,
+                          nullptr);
+    }
+    {
+        ProfScope ps(c, "path_prior");
+        launch_path_feat(c->stream, w.XsT.p, Pp, g.Dp, Pp, p->Om.p, Fp, p->W.p, 2L * Fp, nullptr, Pp, G, Pp, nullptr, 0);
+        launch_gemm_plain(c->stream, G, Pp, false, p->W.p, 2L * Fp, true, w.VM.p, Pp, Pp / 128, Rp / 128, 2 * Fp, 1.0, 0.0);
+    }
+    {
+        ProfScope ps(c, "qeubo_data_gemm");
+        launch_gemm_plain(c->stream, w.Ks.p, Pp, false, p->V.p, Np, true, w.VM.p, Pp, Pp / 128, Rp / 128, Np, 1.0, 1.0);
+    }
+}
+
 // qEUBO (+ its qD gradient and the win counts; val, grad, wins may each be nullptr) at M sets, candidate-major raw coordinates
 // xr[n + r*ldr], rows iD..iD+D-1 the option i.  val[n], grad[n + r*ldo], wins[n + i*ldw].  The gradient is formed, and looked at by the
 // guard, whether or not it is asked for: a set's value does not depend on that.
-void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const double* xr, long ldr, int M, double* val, double* grad,
-                       long ldo, int* wins, long ldw) {
+// base != nullptr (device, n_draws doubles): qNEI -- the selection competes against the per-draw baseline, the guard value is 0 and
+// the two kernels count under "qnei".
+void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const double* base, const double* xr, long ldr, int M, double* val,
+                       double* grad, long ldo, int* wins, long ldw) {
     sls_ctx* c = g.ctx;
+    const char* scope = base ? "qnei" : "qeubo";
+    const double floor = base ? 0.0 : SLS_QEUBO_FLOOR;
     const int D = g.D, Np = g.Np, Fp = p->Fp, Rp = p->Rp, S = p->n_draws;
     const int pass_max = std::min(round_up(M, 128), qeubo_sets_per_pass(c, q, Np, Fp, Rp));
     w.ensure(c, p, g, q * pass_max, pass_max);
-    KernelSpec ks{g.kernel, g.a};
     double* Cs = g.kernel == SLS_KERNEL_ARD_MATERN52 ? w.Cs.p : w.Ks.p;
     const long Kc = (long)Np + Fp;
     if (!w.b2_ready) {
@@ -341,27 +372,14 @@ void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const do
         const int sc = std::min(pass_max, M - s0), Sp = round_up(sc, 128), Pp = q * Sp;
         double* Pm = w.PG.p;
         double* G = w.PG.p + (size_t)Pp * Np;
-        {
-            ProfScope ps(c, "cross_gram");
+        draw_values_device(p, g, w, Pp, [&] {
             for (int i = 0; i < q; ++i)
                 launch_prep_cands(c->stream, xr + (size_t)i * D * ldr + s0, ldr, D, sc, g.inv_ell, w.XsT.p + (size_t)i * Sp, Pp, Sp, g.Dcols,
                                   w.ns.p + (size_t)i * Sp);
-            launch_cross_gram(c->stream, w.XsT.p, Pp, w.ns.p, Pp, g.XT, g.Np, g.nx, Np, g.N, g.Dp, ks, nullptr, w.Ks.p, Cs, Pp, nullptr,
-                              nullptr);
-        }
+        });
         {
-            // every draw at every point: Phi^T W, then K* V accumulated onto it, both on the tile GEMM
-            ProfScope ps(c, "path_prior");
-            launch_path_feat(c->stream, w.XsT.p, Pp, g.Dp, Pp, p->Om.p, Fp, p->W.p, 2L * Fp, nullptr, Pp, G, Pp, nullptr, 0);
-            launch_gemm_plain(c->stream, G, Pp, false, p->W.p, 2L * Fp, true, w.VM.p, Pp, Pp / 128, Rp / 128, 2 * Fp, 1.0, 0.0);
-        }
-        {
-            ProfScope ps(c, "qeubo_data_gemm");
-            launch_gemm_plain(c->stream, w.Ks.p, Pp, false, p->V.p, Np, true, w.VM.p, Pp, Pp / 128, Rp / 128, Np, 1.0, 1.0);
-        }
-        {
-            ProfScope ps(c, "qeubo");
-            launch_qeubo_select(c->stream, sc, Sp, q, S, Rp, w.VM.p, Pp, w.sum.p, wins ? wins + s0 : nullptr, ldw, w.bad);
+            ProfScope ps(c, scope);
+            launch_qeubo_select(c->stream, sc, Sp, q, S, Rp, w.VM.p, Pp, base, w.sum.p, wins ? wins + s0 : nullptr, ldw, w.bad);
         }
         {
             // aggregated weights of every point: the sums of the columns of W / V over the draws its option wins
@@ -396,34 +414,46 @@ void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const do
             launch_path_grad(c->stream, Pp, D, Pp, w.Gt.p, w.XsT.p, w.csum.p, g.inv_ell, w.gpt.p, Pp);
         }
         {
-            ProfScope ps(c, "qeubo");
-            launch_qeubo_finish(c->stream, sc, Sp, q, D, S, w.sum.p, w.bad, w.gpt.p, Pp, val ? val + s0 : nullptr, grad ? grad + s0 : nullptr,
-                                ldo);
+            ProfScope ps(c, scope);
+            launch_qeubo_finish(c->stream, sc, Sp, q, D, S, w.sum.p, w.bad, w.gpt.p, Pp, floor, val ? val + s0 : nullptr,
+                                grad ? grad + s0 : nullptr, ldo);
         }
     }
 }
 
 }  // namespace
 
-extern "C" int sls_qeubo_eval(sls_path* p, int q, const double* sets, int M, double* val, double* grad, int* wins) {
+static void require_finite_baseline(const char* who, const sls_path* p, const double* baseline) {
+    SLS_REQUIRE(baseline != nullptr, "%s: baseline is NULL", who);
+    for (int s = 0; s < p->n_draws; ++s) SLS_REQUIRE(std::isfinite(baseline[s]), "%s: baseline[%d] is not finite", who, s);
+}
+
+// sls_qeubo_eval / sls_qnei_eval (want_base: competes against the per-draw baseline)
+static int set_eval(const char* who, sls_path* p, int q, const double* baseline, bool want_base, const double* sets, int M, double* val,
+                    double* grad, int* wins) {
     SLS_TRY
-    SLS_REQUIRE(p != nullptr, "sls_qeubo_eval: p is NULL");
-    SLS_REQUIRE(q >= 1 && q <= SLS_QEUBO_MAX_OPTIONS, "sls_qeubo_eval: q = %d (1 .. %d)", q, SLS_QEUBO_MAX_OPTIONS);
-    SLS_REQUIRE(M >= 0, "sls_qeubo_eval: M = %d", M);
-    SLS_REQUIRE(sets != nullptr, "sls_qeubo_eval: sets is NULL");
-    GpReadCall call(p->gp, p->generation, "sls_qeubo_eval");
+    SLS_REQUIRE(p != nullptr, "%s: p is NULL", who);
+    SLS_REQUIRE(q >= 1 && q <= SLS_QEUBO_MAX_OPTIONS, "%s: q = %d (1 .. %d)", who, q, SLS_QEUBO_MAX_OPTIONS);
+    SLS_REQUIRE(M >= 0, "%s: M = %d", who, M);
+    SLS_REQUIRE(sets != nullptr, "%s: sets is NULL", who);
+    if (want_base) require_finite_baseline(who, p, baseline);
+    GpReadCall call(p->gp, p->generation, who);
     if (M == 0) return SLS_OK;
     const GpView& g = call.g;
     sls_ctx* c = g.ctx;
     const int qD = q * g.D, Mp = round_up(M, 128);
     const std::vector<double> t = host_to_cm(sets, qD, M, Mp);   // alive until the synchronisation below
-    DBuf raw, out, wb;
+    DBuf raw, out, wb, tb;
     raw.ensure(t.size());
     h2d(c, raw.p, t.data(), t.size());
+    if (want_base) {
+        tb.ensure((size_t)p->n_draws);
+        h2d(c, tb.p, baseline, (size_t)p->n_draws);
+    }
     out.ensure((size_t)Mp * (1 + qD));
     int* d_wins = wins ? ints(wb, (size_t)Mp * q) : nullptr;
     QeuboWs ws;
-    qeubo_eval_device(p, g, ws, q, raw.p, Mp, M, out.p, grad ? out.p + Mp : nullptr, Mp, d_wins, Mp);
+    qeubo_eval_device(p, g, ws, q, tb.p, raw.p, Mp, M, out.p, grad ? out.p + Mp : nullptr, Mp, d_wins, Mp);
     std::vector<double> oh((size_t)Mp * (grad ? 1 + qD : 1));
     std::vector<int> wh(wins ? (size_t)Mp * q : 0);
     d2h(c, oh.data(), out.p, oh.size());
@@ -435,13 +465,19 @@ extern "C" int sls_qeubo_eval(sls_path* p, int q, const double* sets, int M, dou
     SLS_CATCH
 }
 
-extern "C" int sls_qeubo_maximize(sls_path* p, int q, const double* starts, int S_starts, int n_local, const sls_lbfgs_opts* opts,
-                                  long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars,
-                                  double* y_stars) {
+extern "C" int sls_qeubo_eval(sls_path* p, int q, const double* sets, int M, double* val, double* grad, int* wins) {
+    return set_eval("sls_qeubo_eval", p, q, nullptr, false, sets, M, val, grad, wins);
+}
+
+// sls_qeubo_maximize / sls_qnei_maximize
+static int set_maximize(const char* who, sls_path* p, int q, const double* baseline, bool want_base, const double* starts, int S_starts,
+                        int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
+                        double* x_stars, double* y_stars) {
     SLS_TRY
-    SLS_REQUIRE(p && starts, "sls_qeubo_maximize: NULL argument");
-    SLS_REQUIRE(q >= 1 && q <= SLS_QEUBO_MAX_OPTIONS, "sls_qeubo_maximize: q = %d (1 .. %d)", q, SLS_QEUBO_MAX_OPTIONS);
-    GpReadCall call(p->gp, p->generation, "sls_qeubo_maximize");
+    SLS_REQUIRE(p && starts, "%s: NULL argument", who);
+    SLS_REQUIRE(q >= 1 && q <= SLS_QEUBO_MAX_OPTIONS, "%s: q = %d (1 .. %d)", who, q, SLS_QEUBO_MAX_OPTIONS);
+    if (want_base) require_finite_baseline(who, p, baseline);
+    GpReadCall call(p->gp, p->generation, who);
     const GpView& g = call.g;
     sls_ctx* c = g.ctx;
     // the maximiser of sls_acq_maximize over [0,1]^(qD): one start = one set of q options.  Workspaces are per call; the best start
@@ -449,15 +485,19 @@ extern "C" int sls_qeubo_maximize(sls_path* p, int q, const double* starts, int 
     const int S = S_starts, qD = q * g.D;
     LbfgsWs lb;
     QeuboWs ws;
-    MultistartRun r = maximize_begin("sls_qeubo_maximize", p->gp, lb, opts, S, n_local, qD);
-    DBuf sd, best;
+    MultistartRun r = maximize_begin(who, p->gp, lb, opts, S, n_local, qD);
+    DBuf sd, best, tb;
     sd.ensure((size_t)qD * S);
     best.ensure((size_t)8 + qD);
     h2d(c, sd.p, starts, (size_t)qD * S);
+    if (want_base) {   // once, before the first round
+        tb.ensure((size_t)p->n_draws);
+        h2d(c, tb.p, baseline, (size_t)p->n_draws);
+    }
     LockstepStats ls;
     lockstep_rounds(c, r.st, lb, sd.p, S, n_local,
                     [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
-                        qeubo_eval_device(p, g, ws, q, trial, ld, nlive, val, grad, ld, nullptr, 0);
+                        qeubo_eval_device(p, g, ws, q, tb.p, trial, ld, nlive, val, grad, ld, nullptr, 0);
                     },
                     &ls);
     std::vector<double> bh((size_t)8 + qD), pageable;
@@ -469,4 +509,54 @@ extern "C" int sls_qeubo_maximize(sls_path* p, int q, const double* starts, int 
     };
     maximize_finish(c, r, ls, BestBlock{best.p, bh.data(), true}, fetch, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars);
     SLS_CATCH
+}
+
+extern "C" int sls_qeubo_maximize(sls_path* p, int q, const double* starts, int S_starts, int n_local, const sls_lbfgs_opts* opts,
+                                  long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars,
+                                  double* y_stars) {
+    return set_maximize("sls_qeubo_maximize", p, q, nullptr, false, starts, S_starts, n_local, opts, start_index_offset, x_out, val_out,
+                        idx_out, x_stars, y_stars);
+}
+
+// ---- noisy expected improvement on the draws (include/sls_hip.h) ---------------------------------------------------------------
+extern "C" int sls_path_max_over_points(sls_path* p, const double* Xb, int Mb, double* t_out, int* arg_out) {
+    SLS_TRY
+    SLS_REQUIRE(p && Xb, "sls_path_max_over_points: NULL argument");
+    SLS_REQUIRE(Mb >= 1, "sls_path_max_over_points: Mb = %d", Mb);
+    GpReadCall call(p->gp, p->generation, "sls_path_max_over_points");
+    const GpView& g = call.g;
+    sls_ctx* c = g.ctx;
+    const int D = g.D, nd = p->n_draws;
+    // passes of points bounded as a qEUBO pass of one-option sets bounds them; the running (max, argmax) per draw merges across passes
+    const int pass_max = std::min(round_up(Mb, 128), qeubo_sets_per_pass(c, 1, g.Np, p->Fp, p->Rp));
+    QeuboWs ws;
+    ws.ensure(c, p, g, pass_max, pass_max, true);
+    DBuf raw, tb, ab;
+    raw.ensure((size_t)D * Mb);
+    h2d(c, raw.p, Xb, (size_t)D * Mb);
+    tb.ensure((size_t)nd);
+    int* d_arg = ints(ab, (size_t)nd);
+    for (int p0 = 0; p0 < Mb; p0 += pass_max) {
+        const int pc = std::min(pass_max, Mb - p0), Pp = round_up(pc, 128);
+        draw_values_device(p, g, ws, Pp, [&] {
+            launch_prep_points(c->stream, raw.p + (size_t)p0 * D, D, pc, g.inv_ell, ws.XsT.p, Pp, Pp, g.Dcols, ws.ns.p);
+        });
+        ProfScope ps(c, "path_max");
+        launch_path_colmax(c->stream, ws.VM.p, Pp, pc, nd, p0, tb.p, d_arg);   // the pc live rows only
+    }
+    if (t_out) d2h(c, t_out, tb.p, (size_t)nd);
+    if (arg_out) SLS_HIP(hipMemcpyAsync(arg_out, d_arg, (size_t)nd * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    SLS_HIP(hipStreamSynchronize(c->stream));
+    SLS_CATCH
+}
+
+extern "C" int sls_qnei_eval(sls_path* p, int q, const double* baseline, const double* sets, int M, double* val, double* grad, int* wins) {
+    return set_eval("sls_qnei_eval", p, q, baseline, true, sets, M, val, grad, wins);
+}
+
+extern "C" int sls_qnei_maximize(sls_path* p, int q, const double* baseline, const double* starts, int S_starts, int n_local,
+                                 const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
+                                 double* x_stars, double* y_stars) {
+    return set_maximize("sls_qnei_maximize", p, q, baseline, true, starts, S_starts, n_local, opts, start_index_offset, x_out, val_out,
+                        idx_out, x_stars, y_stars);
 }

@@ -478,12 +478,18 @@ void launch_path_argmax(hipStream_t s, const double* f, int S, int n_draws, cons
 // V[i*Sp + n + s*ldv] = f_s(x_i) on entry (Rp rows s, the every-draw values).  One lane per set: sum[n] = sum over s < S (increasing) of
 // max_i, the lowest i winning ties; wins[n + i*ldw] = draws option i wins (wins may be NULL); bad[n] = 1 if any value is not a number.
 // V is overwritten in place by the 0/1 winner indicator, cleared for s >= S and for the padding sets n in [nsets, Sp).
-void launch_qeubo_select(hipStream_t s, int nsets, int Sp, int q, int S, int Rp, double* V, long ldv, double* sum, int* wins, long ldw,
-                         int* bad);
+// t != nullptr (qNEI: S device doubles, the per-draw baseline): the options compete against t[s] -- best = t[s] with no winner, every
+// option strictly-greater in increasing i --, sum[n] adds best - t[s], and a draw without a winner leaves its mask column zero.
+void launch_qeubo_select(hipStream_t s, int nsets, int Sp, int q, int S, int Rp, double* V, long ldv, const double* t, double* sum,
+                         int* wins, long ldw, int* bad);
 // val[n] = sum[n] / S, grad[n + (i*D + d)*ldo] = gpt[i*Sp + n + d*ldg] / S for n < nsets; bad[n] or a NaN among them: value
-// SLS_QEUBO_FLOOR and the zero gradient.  val / grad may be NULL.
+// `floor` (SLS_QEUBO_FLOOR; 0 for qNEI) and the zero gradient.  val / grad may be NULL.
 void launch_qeubo_finish(hipStream_t s, int nsets, int Sp, int q, int D, int S, const double* sum, const int* bad, const double* gpt,
-                         long ldg, double* val, double* grad, long ldo);
+                         long ldg, double floor, double* val, double* grad, long ldo);
+// Per draw s < n_draws (one workgroup each): the maximum over pt < rows of V[pt + s*ldv] and the lowest pt that attains it, merged into
+// the running record: base = 0 writes (t[s], arg[s]); base > 0 (a later pass, indices base + pt) replaces it only when strictly
+// greater.  A NaN in the column gives (NaN, -1), which later passes leave.
+void launch_path_colmax(hipStream_t s, const double* V, long ldv, int rows, int n_draws, int base, double* t, int* arg);
 
 // ---- kernels_map.hip -----------------------------------------------------------
 // MAP-gradient weights (replaces the (D+1) x N x N tensor of CalcLargeKYThetaDerivative, src/regressor.cpp:110-134):

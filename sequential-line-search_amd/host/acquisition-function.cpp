@@ -523,4 +523,29 @@ namespace sequential_line_search
             regressor, num_options, SeededStarts(num_options * regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed),
             num_draws, num_local_search_iters, seed, num_frequencies, value);
     }
+
+    // ---- noisy expected improvement of a batch on posterior draws (include/sls_hip.h sls_qnei_*; Letham et al. 2019) ----
+    std::vector<VectorXd> acquisition_func::FindNextPointsByNoisyExpectedImprovementFromStarts(
+        const Regressor& regressor, const int num_points, const MatrixXd& starts, const unsigned num_draws,
+        const unsigned num_local_search_iters, const unsigned long long seed, const int num_frequencies, double* value)
+    {
+        if (!regressor.GetDeviceHandle())
+            throw std::invalid_argument("acquisition_func: noisy expected improvement needs a device-resident regressor "
+                                        "(GaussianProcessRegressor / PreferenceRegressor); there is no host fallback");
+        const PosteriorFunctionSamples draws =
+            regressor.SamplePosteriorFunctions(static_cast<int>(std::max(1u, num_draws)), seed, num_frequencies);
+        const VectorXd incumbents = draws.MaxOverPoints(regressor.GetLargeX());   // per draw, from the draw that evaluates the candidates
+        return draws.MaximizeNoisyExpectedImprovement(num_points, incumbents, starts, num_local_search_iters, value);
+    }
+
+    std::vector<VectorXd> acquisition_func::FindNextPointsByNoisyExpectedImprovement(
+        const Regressor& regressor, const int num_points, const unsigned num_draws, const unsigned num_global_search_iters,
+        const unsigned num_local_search_iters, const unsigned long long seed, const int num_frequencies, double* value)
+    {
+        if (num_points < 1 || num_points > SLS_QEUBO_MAX_OPTIONS)
+            throw std::invalid_argument("FindNextPointsByNoisyExpectedImprovement: 1 .. 16 points");
+        return FindNextPointsByNoisyExpectedImprovementFromStarts(
+            regressor, num_points, SeededStarts(num_points * regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed),
+            num_draws, num_local_search_iters, seed, num_frequencies, value);
+    }
 } // namespace sequential_line_search

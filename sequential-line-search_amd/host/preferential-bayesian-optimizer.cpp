@@ -155,6 +155,17 @@ namespace sequential_line_search
         for (int i = 0; i < m_num_options; ++i) m_current_options[i] = q[i];
     }
 
+    void PreferentialBayesianOptimizer::DetermineNextQueryByNoisyExpectedImprovement(const unsigned long long seed, const int num_draws,
+                                                                                     const int num_global_search_iters,
+                                                                                     const int num_local_search_iters)
+    {
+        BuildNextQuery("DetermineNextQueryByNoisyExpectedImprovement", num_global_search_iters, num_local_search_iters,
+                       [&](int q, int n_global, int n_local) {
+                           return acquisition_func::FindNextPointsByNoisyExpectedImprovement(*m_regressor, q, std::max(1, num_draws),
+                                                                                             n_global, n_local, seed);
+                       });
+    }
+
     VectorXd PreferentialBayesianOptimizer::GetMaximizer() const { return m_current_options[0]; }
 
     double PreferentialBayesianOptimizer::GetPreferenceValueMean(const VectorXd& point) const

@@ -3,6 +3,7 @@
 #include <cmath>
 #include <sequential-line-search/regressor.hpp>
 #include <stdexcept>
+#include <string>
 
 #include "device.hpp"
 
@@ -230,16 +231,16 @@ namespace sequential_line_search
         return out;
     }
 
-    VectorXd PosteriorFunctionSamples::CalcExpectedUtilitiesOfBestOption(const std::vector<MatrixXd>& options, std::vector<MatrixXd>* grads,
-                                                                         Eigen::MatrixXi* win_counts) const
+    VectorXd PosteriorFunctionSamples::CalcSetCriterion(const char* who, const std::vector<MatrixXd>& options, const VectorXd* baseline,
+                                                        std::vector<MatrixXd>* grads, Eigen::MatrixXi* win_counts) const
     {
-        const long q = static_cast<long>(options.size());
-        if (q < 1 || q > SLS_QEUBO_MAX_OPTIONS)
-            throw std::invalid_argument("PosteriorFunctionSamples::CalcExpectedUtilitiesOfBestOption: 1 .. 16 options");
+        const std::string name = std::string("PosteriorFunctionSamples::") + who;
+        const long        q    = static_cast<long>(options.size());
+        if (q < 1 || q > SLS_QEUBO_MAX_OPTIONS) throw std::invalid_argument(name + ": 1 .. 16 options");
+        if (baseline && baseline->size() != m_num_draws) throw std::invalid_argument(name + ": the baseline must hold one value per draw");
         const long D = m_num_dims, M = options[0].cols();
         for (const MatrixXd& X : options)
-            if (X.rows() != D || X.cols() != M)
-                throw std::invalid_argument("PosteriorFunctionSamples::CalcExpectedUtilitiesOfBestOption: every option block must be D x M");
+            if (X.rows() != D || X.cols() != M) throw std::invalid_argument(name + ": every option block must be D x M");
         MatrixXd sets(q * D, M);
         for (long i = 0; i < q; ++i)
             for (long m = 0; m < M; ++m)
@@ -247,9 +248,13 @@ namespace sequential_line_search
         VectorXd v = VectorXd::Zero(M);
         MatrixXd g(grads ? q * D : 0, grads ? M : 0);
         if (win_counts) *win_counts = Eigen::MatrixXi::Zero(q, M);
-        device::Check(sls_qeubo_eval(m_path, static_cast<int>(q), sets.data(), static_cast<int>(M), v.data(), grads ? g.data() : nullptr,
-                                     win_counts ? win_counts->data() : nullptr),
-                      "sls_qeubo_eval");
+        double* gp = grads ? g.data() : nullptr;
+        int*    wp = win_counts ? win_counts->data() : nullptr;
+        if (baseline)
+            device::Check(sls_qnei_eval(m_path, static_cast<int>(q), baseline->data(), sets.data(), static_cast<int>(M), v.data(), gp, wp),
+                          "sls_qnei_eval");
+        else
+            device::Check(sls_qeubo_eval(m_path, static_cast<int>(q), sets.data(), static_cast<int>(M), v.data(), gp, wp), "sls_qeubo_eval");
         if (grads)
         {
             grads->assign(q, MatrixXd(D, M));
@@ -260,28 +265,70 @@ namespace sequential_line_search
         return v;
     }
 
-    std::vector<VectorXd> PosteriorFunctionSamples::MaximizeExpectedUtilityOfBestOption(int num_options, const MatrixXd& starts,
-                                                                                        unsigned num_local_search_iters, double* value) const
+    std::vector<VectorXd> PosteriorFunctionSamples::MaximizeSetCriterion(const char* who, int num_options, const VectorXd* baseline,
+                                                                         const MatrixXd& starts, unsigned num_local_search_iters,
+                                                                         double* value) const
     {
-        if (num_options < 1 || num_options > SLS_QEUBO_MAX_OPTIONS)
-            throw std::invalid_argument("PosteriorFunctionSamples::MaximizeExpectedUtilityOfBestOption: 1 .. 16 options");
+        const std::string name = std::string("PosteriorFunctionSamples::") + who;
+        if (num_options < 1 || num_options > SLS_QEUBO_MAX_OPTIONS) throw std::invalid_argument(name + ": 1 .. 16 options");
+        if (baseline && baseline->size() != m_num_draws) throw std::invalid_argument(name + ": the baseline must hold one value per draw");
         const long D = m_num_dims;
         if (starts.rows() != num_options * D || starts.cols() < 1)
-            throw std::invalid_argument("PosteriorFunctionSamples::MaximizeExpectedUtilityOfBestOption: starts must be (num_options D) x S "
-                                        "with S >= 1");
+            throw std::invalid_argument(name + ": starts must be (num_options D) x S with S >= 1");
         sls_lbfgs_opts o;
         sls_lbfgs_default_opts(&o);
         optim::SearchTolerances(&o.ftol_rel, &o.xtol_rel);   // the acquisition maximiser's local search tolerances
-        VectorXd x(num_options * D);
-        double   v   = 0.0;
-        long     idx = 0;
-        device::Check(sls_qeubo_maximize(m_path, num_options, starts.data(), static_cast<int>(starts.cols()),
-                                         std::max(1, static_cast<int>(num_local_search_iters)), &o, 0, x.data(), &v, &idx, nullptr, nullptr),
-                      "sls_qeubo_maximize");
+        VectorXd  x(num_options * D);
+        double    v   = 0.0;
+        long      idx = 0;
+        const int S = static_cast<int>(starts.cols()), n_local = std::max(1, static_cast<int>(num_local_search_iters));
+        if (baseline)
+            device::Check(sls_qnei_maximize(m_path, num_options, baseline->data(), starts.data(), S, n_local, &o, 0, x.data(), &v, &idx,
+                                            nullptr, nullptr),
+                          "sls_qnei_maximize");
+        else
+            device::Check(sls_qeubo_maximize(m_path, num_options, starts.data(), S, n_local, &o, 0, x.data(), &v, &idx, nullptr, nullptr),
+                          "sls_qeubo_maximize");
         if (value) *value = v;
         std::vector<VectorXd> out;
         for (int i = 0; i < num_options; ++i) out.push_back(x.segment(i * D, D));
         return out;
+    }
+
+    VectorXd PosteriorFunctionSamples::CalcExpectedUtilitiesOfBestOption(const std::vector<MatrixXd>& options, std::vector<MatrixXd>* grads,
+                                                                         Eigen::MatrixXi* win_counts) const
+    {
+        return CalcSetCriterion("CalcExpectedUtilitiesOfBestOption", options, nullptr, grads, win_counts);
+    }
+
+    std::vector<VectorXd> PosteriorFunctionSamples::MaximizeExpectedUtilityOfBestOption(int num_options, const MatrixXd& starts,
+                                                                                        unsigned num_local_search_iters, double* value) const
+    {
+        return MaximizeSetCriterion("MaximizeExpectedUtilityOfBestOption", num_options, nullptr, starts, num_local_search_iters, value);
+    }
+
+    VectorXd PosteriorFunctionSamples::MaxOverPoints(const MatrixXd& Xb, Eigen::VectorXi* arg) const
+    {
+        if (Xb.rows() != m_num_dims || Xb.cols() < 1)
+            throw std::invalid_argument("PosteriorFunctionSamples::MaxOverPoints: Xb must be D x Mb with Mb >= 1");
+        VectorXd t = VectorXd::Zero(m_num_draws);
+        if (arg) *arg = Eigen::VectorXi(m_num_draws);
+        device::Check(sls_path_max_over_points(m_path, Xb.data(), static_cast<int>(Xb.cols()), t.data(), arg ? arg->data() : nullptr),
+                      "sls_path_max_over_points");
+        return t;
+    }
+
+    VectorXd PosteriorFunctionSamples::CalcNoisyExpectedImprovements(const std::vector<MatrixXd>& options, const VectorXd& baseline,
+                                                                     std::vector<MatrixXd>* grads, Eigen::MatrixXi* win_counts) const
+    {
+        return CalcSetCriterion("CalcNoisyExpectedImprovements", options, &baseline, grads, win_counts);
+    }
+
+    std::vector<VectorXd> PosteriorFunctionSamples::MaximizeNoisyExpectedImprovement(int num_points, const VectorXd& baseline,
+                                                                                     const MatrixXd& starts,
+                                                                                     unsigned num_local_search_iters, double* value) const
+    {
+        return MaximizeSetCriterion("MaximizeNoisyExpectedImprovement", num_points, &baseline, starts, num_local_search_iters, value);
     }
 
     MatrixXd Regressor::SamplePosterior(const MatrixXd& Xs, int num_samples, unsigned long long seed, double* jitter_used) const
