@@ -1,0 +1,197 @@
+"""Cases and comparison rules shared by tests/test_gpu_maximize_restated.py (every *_maximize route of the device against
+tests/lbfgs_ref.py driven by the device's own *_eval) and tests/test_maximize_restated_seeds_cpu.py (the same cases on the CPU
+restatements of the objectives, to show that the INPUTS are not sensitive to the summation order).  numpy only at import.
+
+Starts: uniform in [-0.2, 1.2], every third column rounded to a corner of the box, so that the clamp, the projected gradient and the
+"cannot move" branches run.  N_LOCAL = 15 evaluations; four option sets per case (VARIANTS).
+
+Order sensitivity of the inputs, measured on the CPU (test_maximize_restated_seeds_cpu.py asserts it for every case and option set):
+the share of starts whose end values differ by more than 1e-6 of the largest one between lbfgs_ref.run(order="lanes") and
+order="sequential" on the CPU objective.  A case keeps its seed only if that share is at most 2 %; assert_starts_agree allows the
+device 5 %.  Share with the seeds below (start seed = SEED of the route + position in its table; the data seeds are in Case), for
+every shape and option set of every route -- harness, logei, mes, pair, eubo, qeubo, qnei, path, 108 runs: 0 of 129 (128, 150)
+starts, 0 %.  The first seeds tried were kept.  That test re-measures the share on every run and prints it per case."""
+import numpy as np
+
+import lbfgs_ref
+import util
+
+SE, MATERN52 = 0, 1
+EI, UCB, LOG_EI = 0, 1, 2
+N_LOCAL = 15
+UCB_H = 1.5
+FLOOR = -1.0e300
+# history 3: the ring wraps within 15 evaluations.  1e-6 is what the host layer passes on every route -- but a start that such a
+# tolerance stops has, by the test that stopped it, less than ~1e-6 of its value left to gain: options that never reach the kernel
+# would leave the end values within the comparison's 1e-6 (measured on the CPU objectives: unnoticed in 24 of 28 shapes).  At 1e-2
+# a stopped start keeps a visible distance from where it would have gone, so ignored tolerances show in the end values.
+VARIANTS = {"default": {}, "history3": dict(history=3), "tol1e-6": dict(ftol_rel=1e-6, xtol_rel=1e-6),
+            "tol1e-2": dict(ftol_rel=1e-2, xtol_rel=1e-2)}
+
+# route -> list of shapes.  S = 129 starts (one column into the second 128-wide tile) unless the shape says otherwise.
+HARNESS = [dict(acq=EI), dict(acq=UCB)]                                    # N = 600, D = 5, SLS_WAVE_PATH=0
+# Matern, eight starts on data points.  At b = 1e-8 sigma there is sqrt(b) = 1e-4 (measured on the device at all 200 / 90 data points:
+# 0.99999e-4 .. 1.00001e-4), far above the guard's 1e-10: those starts see a steep, finite LogEI and the floor is never taken.  It is
+# at b = 0: sigma^2 is rounding noise of either sign at the data, 119 of 200 and 58 of 90 data points are at the floor on the device.
+LOGEI = [dict(N=200, D=5, b=1e-8), dict(N=90, D=17, b=1e-8), dict(N=200, D=5, b=0.0), dict(N=90, D=17, b=0.0)]
+MES = [dict(N=90, D=2, mode=0), dict(N=90, D=2, mode=1), dict(N=200, D=20, mode=0), dict(N=200, D=20, mode=1)]
+PAIR = [dict(acq=EI, chol=False), dict(acq=UCB, chol=False), dict(acq=LOG_EI, chol=False), dict(acq=EI, chol=True)]   # N = 126 | 129, D = 4
+EUBO = [dict(D=8), dict(D=9), dict(D=32), dict(D=33)]                      # N = 90, S = 128: 2D = 16, 18, 64, 66
+QSETS = [dict(q=3, D=5), dict(q=2, D=9), dict(q=4, D=16), dict(q=16, D=5)]   # nvar = 15, 18, 64, 80; N = 60, F = 64, 8 draws
+PATH = [dict(D=6, kernel=SE), dict(D=6, kernel=MATERN52), dict(D=20, kernel=SE), dict(D=20, kernel=MATERN52)]   # 3 draws x 50 starts
+ROUTES = dict(harness=HARNESS, logei=LOGEI, mes=MES, pair=PAIR, eubo=EUBO, qeubo=QSETS, qnei=QSETS, path=PATH)
+SEED = dict(harness=100, logei=200, mes=300, pair=400, eubo=500, qeubo=600, qnei=700, path=800)
+PAIR_VARIANTS = ["default"]                                                # sls_acq_maximize_pair takes no options from Python
+
+
+def case_ids(route, variants=None):
+    return [(route, i, v) for i in range(len(ROUTES[route])) for v in (variants or VARIANTS)]
+
+
+def case_name(c):
+    route, i, v = c
+    return f"{route}-" + "-".join(f"{k}{val}" for k, val in ROUTES[route][i].items()) + f"-{v}"
+
+
+def problem(D, N, seed, ell=0.5, a=0.5, scale=1.0):
+    """The generator of the other acquisition tests."""
+    rng = np.random.default_rng(seed)
+    X = rng.uniform(0.0, 1.0, (D, N))
+    y = scale * (np.sin(2.0 * X.sum(axis=0) / np.sqrt(D)) + 0.05 * rng.standard_normal(N))
+    theta = np.concatenate([[a], np.full(D, ell) * rng.uniform(0.8, 1.25, D)])
+    return X, y, theta
+
+
+def box_starts(nvar, S, seed):
+    st = np.random.default_rng(seed).uniform(-0.2, 1.2, (nvar, S))
+    st[:, ::3] = np.round(st[:, ::3])
+    return st
+
+
+class Case:
+    """Inputs of one (route, shape): everything both sides are built from.  Attributes by route:
+    all: route, shape, nvar, S, starts, X, y, theta, b, kernel;  mes: y_star;  pair: X2, y2 are filled in by whoever grows the
+    sigma handle (grow[k] = the appended points);  qeubo / qnei / path: n_draws, F, path_seed;  qnei: dead (columns of starts made of
+    data points, where no draw can improve);  logei: at_data (columns of starts that are data points)."""
+
+    def __init__(self, route, i):
+        self.route, self.shape = route, dict(ROUTES[route][i])
+        sh, seed = self.shape, SEED[route] + i
+        self.S, self.kernel, self.b = 129, MATERN52, 0.05
+        if route == "harness":
+            D, N = 5, 600
+            self.X, self.y, self.theta = problem(D, N, seed=N + D)
+            self.nvar = D
+        elif route == "logei":
+            D, N = sh["D"], sh["N"]
+            self.X, self.y, self.theta = problem(D, N, seed=N + D, ell=0.3 * np.sqrt(D), scale=10.0)
+            self.b, self.nvar = sh["b"], D
+        elif route == "mes":
+            D, N = sh["D"], sh["N"]
+            self.X, self.y, self.theta = problem(D, N, seed=N + D, ell=0.3 * np.sqrt(D))
+            self.y_star = self.y.max() + np.array([0.1, 0.25, 0.6])
+            self.nvar = D
+        elif route == "pair":
+            D, N = 4, 126
+            self.X, self.y, self.theta = problem(D, N, seed=N + D)
+            self.grow = np.random.default_rng(seed + 50).uniform(0.0, 1.0, (D, 3))
+            self.nvar = D
+        elif route == "eubo":
+            D, N = sh["D"], 90
+            self.X, self.y, self.theta = problem(D, N, seed=60 + D, ell=0.3 * np.sqrt(D))
+            self.nvar, self.S = 2 * D, 128
+        elif route in ("qeubo", "qnei"):
+            D, N = sh["D"], 60
+            self.X, self.y, self.theta = problem(D, N, seed=N + D, ell=0.3 * np.sqrt(D))
+            self.n_draws, self.F, self.path_seed = 8, 64, 1234 + D
+            self.nvar = sh["q"] * D
+        elif route == "path":
+            D, N = sh["D"], 90
+            self.X, self.y, self.theta = problem(D, N, seed=N + D, ell=0.3 * np.sqrt(D))
+            self.kernel = sh["kernel"]
+            self.n_draws, self.F, self.path_seed, self.per_draw = 3, 256, 1234 + D, 50
+            self.nvar, self.S = D, 150
+        else:
+            raise KeyError(route)
+        self.D = self.X.shape[0]
+        self.starts = box_starts(self.nvar, self.S, seed)
+        if route == "logei":
+            self.at_data = np.arange(5, self.S, 16)
+            self.starts[:, self.at_data] = self.X[:, 3 * np.arange(self.at_data.size)]
+        if route == "qnei":
+            # a quarter of the sets: q of the 20 data points with the lowest y -- no draw's value there exceeds its maximum over the data
+            rng = np.random.default_rng(seed + 50)
+            low = np.argsort(self.y)[:20]
+            self.dead = np.arange(1, self.S, 4)
+            for j in self.dead:
+                self.starts[:, j] = self.X[:, rng.choice(low, sh["q"], replace=False)].T.ravel()
+
+
+# ---- comparison rules ------------------------------------------------------------------------------------------------------------------
+def restated(evaluate, case, kw, order="lanes", with_live=False):
+    return lbfgs_ref.run(evaluate, case.starts, N_LOCAL, order=order, with_live=with_live, **kw)
+
+
+def _bits(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).view(np.uint64)
+
+
+def hold_to_restatement(rg, rr, label, stats=None, n_local=N_LOCAL):
+    """rg: the device maximiser's result (x_stars, y_stars, index, value, x), rr: lbfgs_ref.run on the same evaluations.  Asserts
+    util.assert_starts_agree unchanged on every start whose reference end value is not the floor of LogEI (-1e300: it would become
+    the scale and make every other start agree); a start at the floor must have the device's floor and its clamped start, bit for
+    bit.  Records the measured figures (kind "maximize_restated"); asserts nothing on them."""
+    S = rr["y_stars"].size
+    assert rg["x_stars"].shape == rr["x_stars"].shape and rg["y_stars"].shape == (S,)
+    assert np.all((rg["x_stars"] >= 0.0) & (rg["x_stars"] <= 1.0))
+    floor = rr["y_stars"] <= 0.1 * FLOOR
+    assert np.array_equal(rg["y_stars"] <= 0.1 * FLOOR, floor), f"{label}: starts at the floor differ"
+    assert np.array_equal(_bits(rg["y_stars"][floor]), _bits(rr["y_stars"][floor]))
+    assert np.array_equal(_bits(rg["x_stars"][:, floor]), _bits(rr["x_stars"][:, floor]))
+    k = ~floor
+    scale = max(np.abs(rr["y_stars"][k]).max(), 1e-300)
+    gap = np.abs(rg["y_stars"][k] - rr["y_stars"][k]) / scale
+    close = np.isclose(rg["y_stars"][k], rr["y_stars"][k], rtol=1e-6, atol=1e-12 * scale)
+    xgap = np.abs(rg["x_stars"][:, k] - rr["x_stars"][:, k]).max(axis=0)
+    same = (_bits(rg["y_stars"]) == _bits(rr["y_stars"])) & (_bits(rg["x_stars"]) == _bits(rr["x_stars"])).all(axis=0)
+    util.record("maximize_restated", label=label, starts=int(S), at_floor=int(floor.sum()), divergent=int((~close).sum()),
+                divergent_armijo_margins=[float(v) for v in rr["armijo_margin"][k][~close][:32]],
+                largest_rel_gap=float(gap.max()), largest_rel_gap_agreeing=float(gap[close].max()) if close.any() else 0.0,
+                bit_equal=int(same.sum()), largest_x_gap_agreeing=float(xgap[close].max()) if close.any() else 0.0,
+                smallest_armijo_margin=float(rr["armijo_margin"].min()), evals_issued=rr["evals_issued"], rounds=rr["rounds"],
+                live_at_end=rr["live_at_end"], ring_max=int(rr["ring_max"].max()), accepted_max=int(rr["accepted"].max()),
+                device_stats=stats)
+    print(f"{label}: {S} starts, {int(floor.sum())} at the floor, {int((~close).sum())} divergent, largest gap {gap.max():.3e}, "
+          f"{int(same.sum())} bit-equal, largest |x - x_ref| over agreeing starts {xgap[close].max() if close.any() else 0.0:.3e}, "
+          f"smallest Armijo margin {rr['armijo_margin'].min():.3e}")
+    agree = util.assert_starts_agree(dict(y_stars=rg["y_stars"][k]), dict(y_stars=rr["y_stars"][k], armijo_margin=rr["armijo_margin"][k]),
+                                     label=label)
+    # the winner the device reports is one of the reference's best starts
+    i = rg["index"]
+    assert 0 <= i < S and rr["y_stars"][i] >= rr["value"] - 1e-6 * scale
+    assert abs(rg["value"] - rr["value"]) <= 1e-6 * scale
+    if stats is not None:
+        cap = S * n_local
+        if agree.all() and rr["armijo_margin"].min() > 1e-9:
+            got = {key: stats[key] for key in ("evals_issued", "rounds", "live_at_end")}
+            want = {key: rr[key] for key in ("evals_issued", "rounds", "live_at_end")}
+            assert got == want, f"{label}: statistics {got}, restated {want}"
+        assert stats["evals_cap"] == cap and S <= stats["evals_issued"] <= cap and 0 <= stats["live_at_end"] <= S, stats
+        assert 1 <= stats["rounds"] <= n_local, stats
+    return agree
+
+
+def hold_winner_to_restatement(value, index, y_ref, value_at_x, label):
+    """A route that returns its winner only.  y_ref: the reference's end values of the starts the winner was chosen among."""
+    scale = max(np.abs(y_ref).max(), 1e-300)
+    top, first = y_ref.max(), int(np.argmax(y_ref))
+    rest = np.delete(y_ref, first)
+    runner_up_far = rest.size == 0 or rest.max() < top - 1e-6 * scale
+    util.record("maximize_restated", label=label, starts=int(y_ref.size), winner_only=True, rel_gap=float(abs(value - top) / scale),
+                bit_equal=int((_bits(value) == _bits(top)).all()), index=int(index), reference_index=first, runner_up_far=bool(runner_up_far))
+    print(f"{label}: winner {value!r} (start {index}), restated {top!r} (start {first}), gap {abs(value - top) / scale:.3e}")
+    assert abs(value - top) <= 1e-6 * scale, f"{label}: winner {value!r}, restated {top!r}"
+    assert 0 <= index < y_ref.size and y_ref[index] >= top - 1e-6 * scale, f"{label}: start {index} is not among the restated best"
+    if runner_up_far:
+        assert index == first, f"{label}: winner is start {index}, restated {first}"
+    assert abs(value_at_x - value) <= 1e-12 * max(1.0, abs(value)), f"{label}: the objective at the returned point is {value_at_x!r}, returned {value!r}"

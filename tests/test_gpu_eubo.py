@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 import eubo_ref
+import lbfgs_ref
+import maximize_cases
 from util import sls
 
 pytestmark = pytest.mark.gpu
@@ -277,6 +279,10 @@ def test_maximiser_at_the_switch_points_of_the_step_kernel(m, ctx, D):
     assert np.all(r["y_stars"] >= at_start)
     assert r["value"] == r["y_stars"].max() and np.array_equal(r["x_stars"][:, r["index"]], r["x"])
     print(f"D {D}: rounds {st['rounds']}, best start value {at_start.max():.6g} -> {r['value']:.6g}")
+    # what depends on the DIRECTION: every start's trajectory against the restated L-BFGS on the device's own evaluations
+    # (tests/test_gpu_maximize_restated.py; these starts are vetted on the CPU by tests/test_maximize_restated_seeds_cpu.py)
+    rr = lbfgs_ref.run(gp.eubo_eval, starts, n_local, order="lanes")
+    maximize_cases.hold_to_restatement(r, rr, f"eubo switch points D={D} uniform starts", stats=st, n_local=n_local)
     gp.close()
 
 

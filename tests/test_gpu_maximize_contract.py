@@ -1,7 +1,7 @@
 """What every single-winner maximiser returns around its search (csrc/lbfgs_driver.hpp: maximize_begin / maximize_finish), pinned for
 each entry point that goes through it: sls_acq_maximize with the three acquisition types on the one-launch wave route and on the
-lock-step rounds, sls_mes_maximize, sls_eubo_maximize and sls_qeubo_maximize.  The winner is the first maximum of y_stars and its
-column of x_stars, bit for bit; the start index offset only shifts the index; leaving x_stars / y_stars out changes nothing else;
+lock-step rounds, sls_mes_maximize, sls_eubo_maximize, sls_qeubo_maximize and sls_qnei_maximize (baseline: every draw's maximum
+over the data, sls_path_max_over_points).  The winner is the first maximum of y_stars and its column of x_stars, bit for bit; the start index offset only shifts the index; leaving x_stars / y_stars out changes nothing else;
 sls_acq_last_stats describes the run; a history outside 1..8 is refused by name and leaves the handle usable.
 
 Shapes: N = 40, D = 3 takes the wave route for EI and UCB (LogEI has no wave objective and runs the rounds there); N = 200, D = 5 with
@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 SE, MATERN52 = 0, 1
 N_LOCAL = 12
 OFFSET = 12345
-CASES = ["ei_wave", "ucb_wave", "logei_small", "ei_rounds", "ucb_rounds", "logei_rounds", "mes", "eubo", "qeubo"]
+CASES = ["ei_wave", "ucb_wave", "logei_small", "ei_rounds", "ucb_rounds", "logei_rounds", "mes", "eubo", "qeubo", "qnei"]
 ACQ = {"ei": 0, "ucb": 1, "logei": 2}
 
 
@@ -49,7 +49,7 @@ class Route:
 
     def __init__(self, m, ctx, case, monkeypatch):
         name, _, shape = case.partition("_")
-        small = shape in ("wave", "small") or name == "qeubo"
+        small = shape in ("wave", "small") or name in ("qeubo", "qnei")
         N, D = (40, 3) if small else (200, 5)
         if shape == "rounds":
             monkeypatch.setenv("SLS_WAVE_PATH", "0")
@@ -69,7 +69,11 @@ class Route:
         else:
             self.nvar = 3 * D
             self.path = ps = m.PathSamples(gp, 8, 64, seed=7)
-            self.run = lambda starts, **kw: ps.qeubo_maximize(starts, 3, N_LOCAL, **kw)
+            if name == "qeubo":
+                self.run = lambda starts, **kw: ps.qeubo_maximize(starts, 3, N_LOCAL, **kw)
+            else:
+                t, _ = ps.max_over_points(X)
+                self.run = lambda starts, **kw: ps.qnei_maximize(starts, 3, N_LOCAL, t, **kw)
 
     def starts(self, S):
         return np.random.default_rng(100 + S).uniform(0.0, 1.0, (self.nvar, S))
