@@ -420,6 +420,9 @@ struct sls_gp {
     // changes whenever the predictor this handle stands for changes (fit, refit, appended point, sigma mode); process-wide unique, so
     // a new handle at a recycled address never repeats a number (sls_gp_generation: the host layer keys its replicas on it)
     long generation = 0;
+    // this fit is beyond the guard of the norm expansion (gram_direct_form, kernels.hpp): every Gram route of the handle forms q from
+    // the raw coordinate differences (set by gp_fit_device from the length scales)
+    bool gram_direct = false;
     // statistics of the last sls_acq_maximize* call on this handle (sls_acq_last_stats)
     long stat_issued = 0, stat_cap = 0;
     int stat_rounds = 0, stat_live_end = 0;
@@ -453,6 +456,7 @@ static void gp_fit_device(sls_gp* g) {
     g->generation = ++g_gp_generation;
     sls_ctx* c = g->ctx;
     const int N = g->N, Np = g->Np, D = g->D;
+    g->gram_direct = gram_direct_form(g->theta.data() + 1, D);
     if (gp_fit_small_ok(g)) {
         GpFitSmallArgs f;
         f.X = g->X.p; f.y = g->y.p; f.inv_ell = g->inv_ell.p;
@@ -470,7 +474,8 @@ static void gp_fit_device(sls_gp* g) {
     {
         ProfScope ps(c, "gram");
         launch_prep_points(c->stream, g->X.p, D, N, g->inv_ell.p, g->XT.p, Np, Np, g->Dcols, g->nx.p);
-        launch_gram_sym(c->stream, g->XT.p, Np, g->Dp, g->nx.p, Np, N, ks, g->b, g->L.p, true);
+        if (g->gram_direct) launch_gram_sym_direct(c->stream, g->X.p, D, g->inv_ell.p, Np, N, ks, g->b, g->L.p, true);
+        else launch_gram_sym(c->stream, g->XT.p, Np, g->Dp, g->nx.p, Np, N, ks, g->b, g->L.p, true);
     }
     SLS_HIP(hipMemsetAsync(c->d_info, 0, 64, c->stream));
     // L^-1 is read as a full matrix (gemv, the plain-product predict): its blocks above the diagonal must be zero.  Nothing ever
@@ -610,6 +615,7 @@ GpView gp_view(sls_gp* g) {
     v.a = g->a; v.b = g->b;
     v.XT = g->XT.p; v.nx = g->nx.p; v.inv_ell = g->inv_ell.p; v.alpha = g->alpha.p; v.Linv = g->Linv.p;
     v.y = g->y.p; v.L = g->L.p;
+    v.X = g->X.p; v.gram_direct = g->gram_direct;
     v.generation = g->generation;
     v.state = &g->state_mtx;
     return v;
@@ -694,7 +700,8 @@ extern "C" int sls_gp_get_matrix(sls_gp* g, int what, double* out) {
             // m_K_y is not kept resident (the Cholesky factor overwrites it): rebuild the full symmetric matrix
             DBuf K;
             K.ensure((size_t)Np * Np);
-            launch_gram_sym(c->stream, g->XT.p, Np, g->Dp, g->nx.p, Np, N, KernelSpec{g->kernel, g->a}, g->b, K.p, false);
+            if (g->gram_direct) launch_gram_sym_direct(c->stream, g->X.p, g->D, g->inv_ell.p, Np, N, KernelSpec{g->kernel, g->a}, g->b, K.p, false);
+            else launch_gram_sym(c->stream, g->XT.p, Np, g->Dp, g->nx.p, Np, N, KernelSpec{g->kernel, g->a}, g->b, K.p, false);
             if (staged) fetch_staged(K.p, false);
             else {
                 d2h_matrix(c, out, K.p, N, Np);
@@ -782,8 +789,12 @@ static void eval_candidates(sls_gp* g, const double* xr, long ldr, int S, const 
             ProfScope ps(c, "cross_gram");
             if (point_major) launch_prep_points(c->stream, xr + (size_t)s0 * D, D, sc, g->inv_ell.p, g->XsT.p, ldk, Sp, g->Dcols, g->ns.p);
             else launch_prep_cands(c->stream, xr + s0, ldr, D, sc, g->inv_ell.p, g->XsT.p, ldk, Sp, g->Dcols, g->ns.p);
-            launch_cross_gram(c->stream, g->XsT.p, ldk, g->ns.p, Sp, g->XT.p, Np, g->nx.p, Np, N, g->Dp, ks, g->alpha.p, g->Ks.p, Cs,
-                              ldk, mu_part, ca_part);
+            if (g->gram_direct)
+                launch_cross_gram_direct(c->stream, point_major ? xr + (size_t)s0 * D : xr + s0, point_major ? D : 1, point_major ? 1 : ldr, sc,
+                                         Sp, g->X.p, D, g->inv_ell.p, Np, N, ks, g->alpha.p, g->Ks.p, Cs, ldk, mu_part, ca_part);
+            else
+                launch_cross_gram(c->stream, g->XsT.p, ldk, g->ns.p, Sp, g->XT.p, Np, g->nx.p, Np, N, g->Dp, ks, g->alpha.p, g->Ks.p, Cs,
+                                  ldk, mu_part, ca_part);
         }
         int split_first = 0x7fffffff;
         const bool solve_grad = g->sigma_mode == 1 && (want_grad || !tri_predict());
@@ -808,7 +819,14 @@ static void eval_candidates(sls_gp* g, const double* xr, long ldr, int S, const 
             ProfScope ps(c, "var_gemm");
             launch_var_gemm(c->stream, g->Ks.p, ldk, Sp, g->Linv.p, Np, kw_solve, kw_solve + (size_t)2 * nbt * ldk);
         }
-        if (want_grad) {
+        if (want_grad && g->gram_direct) {
+            // beyond the guard: the contractions over raw coordinate differences; finalize's x~* ca and x~* cw terms are then zero
+            ProfScope ps(c, "grad_gemm");
+            launch_grad_direct(c->stream, g->P.p, Cs, ldk, Sp, point_major ? xr + (size_t)s0 * D : xr + s0, point_major ? D : 1,
+                               point_major ? 1 : ldr, sc, g->X.p, D, g->inv_ell.p, N, g->alpha.p, g->Gs.p, g->Gm.p);
+            SLS_HIP(hipMemsetAsync(ca_part, 0, (size_t)nbt * ldk * 8, c->stream));
+            SLS_HIP(hipMemsetAsync(cw_part, 0, (size_t)2 * nbt * ldk * 8, c->stream));
+        } else if (want_grad) {
             ProfScope ps(c, "grad_gemm");
             double* part = nullptr;
             if (D <= 64 && grad_gemm_wants_split(Sp)) {
@@ -842,7 +860,8 @@ static void eval_candidates(sls_gp* g, const double* xr, long ldr, int S, const 
 // only on the fitted state and the count, so repeated / sharded calls take the same path.  D never changes for a handle
 // (wave_path_dims); Np grows with appended points, so whoever works without the context's lock asks under the state lock.
 constexpr int WAVE_PATH_MAX_POINTS = 4096;   // query points / starts per launch
-static bool wave_path_dims(const sls_gp* g) { return tune_on(TUNE_WAVE_PATH) && g->D <= WAVE_PATH_MAX_D; }
+// A handle beyond the guard of the norm expansion (gram_direct) takes the tiled pipeline: the wavefront kernels difference scaled coordinates.
+static bool wave_path_dims(const sls_gp* g) { return tune_on(TUNE_WAVE_PATH) && g->D <= WAVE_PATH_MAX_D && !g->gram_direct; }
 static bool wave_path_applies(const sls_gp* g, int count) {
     return wave_path_dims(g) && g->Np <= WAVE_PATH_MAX_NP && count <= WAVE_PATH_MAX_POINTS;
 }
@@ -1434,8 +1453,12 @@ static void eval_pairs(sls_gp* g, const double* xr, long ldr, int S, double* val
         for (int o = 0; o < 2; ++o) {
             ProfScope ps(c, "cross_gram");
             launch_prep_cands(c->stream, xr + (size_t)o * D * ldr + s0, ldr, D, sc, g->inv_ell.p, XsT[o], ldk, Sp, g->Dcols, ns[o]);
-            launch_cross_gram(c->stream, XsT[o], ldk, ns[o], Sp, g->XT.p, Np, g->nx.p, Np, N, g->Dp, ks, g->alpha.p, Ks[o], Cs[o], ldk,
-                              mu_part[o], ca_part[o]);
+            if (g->gram_direct)
+                launch_cross_gram_direct(c->stream, xr + (size_t)o * D * ldr + s0, 1, ldr, sc, Sp, g->X.p, D, g->inv_ell.p, Np, N, ks,
+                                         g->alpha.p, Ks[o], Cs[o], ldk, mu_part[o], ca_part[o]);
+            else
+                launch_cross_gram(c->stream, XsT[o], ldk, ns[o], Sp, g->XT.p, Np, g->nx.p, Np, N, g->Dp, ks, g->alpha.p, Ks[o], Cs[o], ldk,
+                                  mu_part[o], ca_part[o]);
         }
         {
             ProfScope ps(c, "eubo");
@@ -1460,6 +1483,13 @@ static void eval_pairs(sls_gp* g, const double* xr, long ldr, int S, double* val
                                               g->P.p, kw_part[o], cw_part[o], c->d_info + 32);
             }
             ProfScope ps(c, "grad_gemm");
+            if (g->gram_direct) {   // as in eval_candidates
+                launch_grad_direct(c->stream, g->P.p, Cs[o], ldk, Sp, xr + (size_t)o * D * ldr + s0, 1, ldr, sc, g->X.p, D, g->inv_ell.p, N,
+                                   g->alpha.p, Gs[o], Gm[o]);
+                SLS_HIP(hipMemsetAsync(ca_part[o], 0, (size_t)nbt * ldk * 8, c->stream));
+                SLS_HIP(hipMemsetAsync(cw_part[o], 0, (size_t)2 * nbt * ldk * 8, c->stream));
+                continue;
+            }
             double* part = nullptr;
             if (D <= 64 && grad_gemm_wants_split(Sp)) {
                 g->Gpart.ensure((size_t)8 * Sp * 64);
@@ -1549,7 +1579,9 @@ extern "C" int sls_gram(sls_ctx* c, const double* X, int D, int N, const double*
     h2d(c, Xd.p, X, (size_t)D * N);
     h2d(c, il.p, ilh.data(), Dp);
     launch_prep_points(c->stream, Xd.p, D, N, il.p, XT.p, Np, Np, Dp, nx.p);
-    launch_gram_sym(c->stream, XT.p, Np, Dp, nx.p, Np, N, KernelSpec{kernel, theta[0]}, b, K.p, false);
+    // the entries themselves are the result here: the expansion serves them only while it is as good as the direct form (kernels.hpp)
+    if (gram_direct_form(theta + 1, D, gram_entry_bound(D))) launch_gram_sym_direct(c->stream, Xd.p, D, il.p, Np, N, KernelSpec{kernel, theta[0]}, b, K.p, false);
+    else launch_gram_sym(c->stream, XT.p, Np, Dp, nx.p, Np, N, KernelSpec{kernel, theta[0]}, b, K.p, false);
     d2h_matrix(c, K_out, K.p, N, Np);
     sync(c);
     SLS_CATCH
@@ -1576,8 +1608,12 @@ extern "C" int sls_gram_cross(sls_ctx* c, const double* X, int D, int N, const d
     h2d(c, il.p, ilh.data(), Dp);
     launch_prep_points(c->stream, Xd.p, D, N, il.p, XT.p, Np, Np, Dp, nx.p);
     launch_prep_points(c->stream, Xsd.p, D, M, il.p, XsT.p, Mp, Mp, Dp, ns.p);
-    launch_cross_gram(c->stream, XsT.p, Mp, ns.p, Mp, XT.p, Np, nx.p, Np, N, Dp, KernelSpec{kernel, theta[0]}, nullptr, Ks.p,
-                      matern ? Cs.p : Ks.p, Mp, nullptr, nullptr);
+    if (gram_direct_form(theta + 1, D, gram_entry_bound(D)))
+        launch_cross_gram_direct(c->stream, Xsd.p, D, 1, M, Mp, Xd.p, D, il.p, Np, N, KernelSpec{kernel, theta[0]}, nullptr, Ks.p,
+                                 matern ? Cs.p : Ks.p, Mp, nullptr, nullptr);
+    else
+        launch_cross_gram(c->stream, XsT.p, Mp, ns.p, Mp, XT.p, Np, nx.p, Np, N, Dp, KernelSpec{kernel, theta[0]}, nullptr, Ks.p,
+                          matern ? Cs.p : Ks.p, Mp, nullptr, nullptr);
     // device image is candidate-major [m + i*Mp]; the API returns N x M column-major (column m = k(xs_m, X))
     std::vector<double> t((size_t)Mp * Np);
     d2h(c, t.data(), Ks.p, (size_t)Mp * Np);
@@ -1705,8 +1741,12 @@ extern "C" int sls_gp_append_point(sls_gp* g, const double* x, double y_new) {
     KernelSpec ks{g->kernel, g->a};
     launch_prep_cands(c->stream, g->raw.p, 128, D, 1, g->inv_ell.p, g->XsT.p, 128, 128, g->Dcols, g->ns.p);
     double* Cs = (g->kernel == SLS_KERNEL_ARD_MATERN52) ? g->Cs.p : g->Ks.p;
-    launch_cross_gram(c->stream, g->XsT.p, 128, g->ns.p, 128, g->XT.p, Np, g->nx.p, Np, N, g->Dp, ks, nullptr, g->Ks.p, Cs, 128,
-                      nullptr, nullptr);
+    if (g->gram_direct)
+        launch_cross_gram_direct(c->stream, g->raw.p, 1, 128, 1, 128, g->X.p, D, g->inv_ell.p, Np, N, ks, nullptr, g->Ks.p, Cs, 128, nullptr,
+                                 nullptr);
+    else
+        launch_cross_gram(c->stream, g->XsT.p, 128, g->ns.p, 128, g->XT.p, Np, g->nx.p, Np, N, g->Dp, ks, nullptr, g->Ks.p, Cs, 128,
+                          nullptr, nullptr);
     // Ks[n + i*128], n = 0 -> stride-128 gather into a dense vector (padding rows i >= N are 0)
     SLS_HIP(hipMemcpy2DAsync(kvec, 8, g->Ks.p, 128 * 8, 8, Np, hipMemcpyDeviceToDevice, c->stream));
     launch_gemv_n(c->stream, g->Kinv.p, Np, kvec, uvec, g->gemv_part.p);     // u = K^-1 k   (padding: identity block x 0 = 0)

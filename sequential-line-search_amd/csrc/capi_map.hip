@@ -119,7 +119,9 @@ static bool nll_factor_enqueue(sls_nll* h, const double* theta, double b) {
     // no upload: the kernels read the mapped block (1 KB; the previous evaluation on this handle ended with a synchronisation)
     KernelSpec ks{h->kernel, theta[0]};
     launch_prep_points(c->stream, h->X.p, D, N, h->il_stage.dev, h->XT.p, Np, Np, h->Dcols, h->nx.p);
-    launch_gram_sym(c->stream, h->XT.p, Np, h->Dp, h->nx.p, Np, N, ks, b, h->L.p, true);
+    // beyond the guard of the norm expansion (kernels.hpp): K_y from the raw coordinate differences
+    if (gram_direct_form(theta + 1, D)) launch_gram_sym_direct(c->stream, h->X.p, D, h->il_stage.dev, Np, N, ks, b, h->L.p, true);
+    else launch_gram_sym(c->stream, h->XT.p, Np, h->Dp, h->nx.p, Np, N, ks, b, h->L.p, true);
     SLS_HIP(hipMemsetAsync(c->d_info, 0, 64, c->stream));
     c->potrf_tick_rearm();
     h->G.ensure((size_t)Np * Np);   // the gradient's weight matrix, written after the factorisation: holds (L^-1)^T until then
@@ -242,12 +244,17 @@ static void nll_eval_impl(sls_nll* h, const double* y, const double* theta, doub
         // alpha = K_y^-1 y from the explicit (symmetric, full) inverse the gradient's weights use anyway: one pass over one matrix
         // (it was L^-1 twice: 69 -> 25 us at N = 4096)
         launch_gemv_t(c->stream, h->Kinv.p, Np, h->y.p, h->alpha.p);
+        const bool direct = gram_direct_form(theta + 1, D);   // the guard of the norm expansion: the gradient's q and its contraction too
         if (want_grad) {
             h->G.ensure((size_t)Np * Np);
             h->Y.ensure((size_t)Np * h->Dcols * nll_y_chunks(nt, h->Dcols / 128));
             h->parts.ensure((size_t)nt * nt);
-            launch_nll_weight(c->stream, h->XT.p, Np, h->Dp, h->nx.p, Np, N, KernelSpec{h->kernel, theta[0]}, h->alpha.p, h->Kinv.p,
-                              h->G.p, h->parts.p, grad_theta ? h->gemv_part.p : nullptr);
+            if (direct)
+                launch_nll_weight_direct(c->stream, h->X.p, D, h->il_stage.dev, Np, N, KernelSpec{h->kernel, theta[0]}, h->alpha.p,
+                                         h->Kinv.p, h->G.p, h->parts.p);
+            else
+                launch_nll_weight(c->stream, h->XT.p, Np, h->Dp, h->nx.p, Np, N, KernelSpec{h->kernel, theta[0]}, h->alpha.p, h->Kinv.p,
+                                  h->G.p, h->parts.p, grad_theta ? h->gemv_part.p : nullptr);
         } else {
             h->parts.ensure(1);
         }
@@ -256,7 +263,10 @@ static void nll_eval_impl(sls_nll* h, const double* y, const double* theta, doub
         const double* Lf = fresh ? h->L.p : nullptr;
         const int* inf = fresh ? c->d_info : nullptr;
         const int nparts = want_grad ? nt * nt : 0;
-        if (grad_theta) {
+        if (grad_theta && direct) {
+            launch_lengthscale_grad_direct(c->stream, h->X.p, h->G.p, h->il_stage.dev, Np, N, D, h->res_dev() + 8, h->parts.p, nparts,
+                                           h->alpha.p, h->y.p, h->Kinv.p, h->res_dev(), Lf, inf);
+        } else if (grad_theta) {
             // Y = G X~ has only nt x Dcols/128 output tiles: split the contraction so that the launch fills the chip
             const int yc = nll_y_chunks(nt, h->Dcols / 128);
             launch_gemm_splitk_nt(c->stream, h->G.p, Np, h->XT.p, Np, h->Y.p, Np, (long)Np * h->Dcols, nt, h->Dcols / 128, Np, yc);
@@ -400,7 +410,11 @@ extern "C" int sls_gp_nll_batch(sls_nll* h, const double* y, const double* xs, i
                 double* XTq = h->bt_XT.p + (size_t)q * Np2 * Dcols;
                 double* nxq = h->bt_nx.p + (size_t)q * Np2;
                 launch_prep_points(c->stream, h->X.p, D, N, h->bt_il.p + (size_t)q * Dcols, XTq, Np2, Np2, Dcols, nxq);
-                launch_gram_sym(c->stream, XTq, Np2, Dp, nxq, Np2, N, KernelSpec{h->kernel, x[0]}, x[1], h->bt_L.p + q * mat, true);
+                if (gram_direct_form(x + 2, D))
+                    launch_gram_sym_direct(c->stream, h->X.p, D, h->bt_il.p + (size_t)q * Dcols, Np2, N, KernelSpec{h->kernel, x[0]}, x[1],
+                                           h->bt_L.p + q * mat, true);
+                else
+                    launch_gram_sym(c->stream, XTq, Np2, Dp, nxq, Np2, N, KernelSpec{h->kernel, x[0]}, x[1], h->bt_L.p + q * mat, true);
             }
             launch_border_row(c->stream, h->bt_L.p, (long)mat, P, Np2, N, h->y.p, 1e200);
             SLS_HIP(hipMemsetAsync(c->d_info, 0, 64, c->stream));

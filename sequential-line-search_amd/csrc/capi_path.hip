@@ -89,8 +89,12 @@ void path_eval_device(sls_path* p, const GpView& g, EvalWs& w, const double* xr,
             ProfScope ps(c, "cross_gram");
             if (point_major) launch_prep_points(c->stream, xr + (size_t)s0 * D, D, sc, g.inv_ell, w.XsT.p, Cp, Cp, g.Dcols, w.ns.p);
             else launch_prep_cands(c->stream, xr + s0, ldr, D, sc, g.inv_ell, w.XsT.p, Cp, Cp, g.Dcols, w.ns.p);
-            launch_cross_gram(c->stream, w.XsT.p, Cp, w.ns.p, Cp, g.XT, g.Np, g.nx, Np, g.N, g.Dp, ks, nullptr, w.Ks.p, Cs, Cp,
-                              nullptr, nullptr);
+            if (g.gram_direct)   // beyond the guard of the norm expansion (kernels.hpp): the data term from the raw coordinate differences
+                launch_cross_gram_direct(c->stream, point_major ? xr + (size_t)s0 * D : xr + s0, point_major ? D : 1, point_major ? 1 : ldr, sc,
+                                         Cp, g.X, D, g.inv_ell, Np, g.N, ks, nullptr, w.Ks.p, Cs, Cp, nullptr, nullptr);
+            else
+                launch_cross_gram(c->stream, w.XsT.p, Cp, w.ns.p, Cp, g.XT, g.Np, g.nx, Np, g.N, g.Dp, ks, nullptr, w.Ks.p, Cs, Cp,
+                                  nullptr, nullptr);
         }
         if (!draw) {
             {
@@ -322,9 +326,10 @@ struct QeuboWs {
 };
 
 // Every draw at the Pp points of a pass into w.VM (Pp x Rp): `prep` fills XsT / ns, then cross_gram, Phi^T W and K* V accumulated onto
-// it, both on the tile GEMM.
-template <class Prep>
-void draw_values_device(sls_path* p, const GpView& g, QeuboWs& w, int Pp, Prep&& prep) {
+// it, both on the tile GEMM.  `direct(ks, Cs)`: the cross Gram of the same points from their raw coordinates, for handles beyond the
+// guard of the norm expansion (kernels.hpp).
+template <class Prep, class Direct>
+void draw_values_device(sls_path* p, const GpView& g, QeuboWs& w, int Pp, Prep&& prep, Direct&& direct) {
     sls_ctx* c = g.ctx;
     const int Np = g.Np, Fp = p->Fp, Rp = p->Rp;
     KernelSpec ks{g.kernel, g.a};
@@ -333,8 +338,8 @@ void draw_values_device(sls_path* p, const GpView& g, QeuboWs& w, int Pp, Prep&&
     {
         ProfScope ps(c, "cross_gram");
         prep();
-        launch_cross_gram(c->stream, w.XsT.p, Pp, w.ns.p, Pp, g.XT, g.Np, g.nx, Np, g.N, g.Dp, ks, nullptr, w.Ks.p, Cs, Pp, nullptr,
-                          nullptr);
+        if (g.gram_direct) direct(ks, Cs);
+        else launch_cross_gram(c->stream, w.XsT.p, Pp, w.ns.p, Pp, g.XT, g.Np, g.nx, Np, g.N, g.Dp, ks, nullptr, w.Ks.p, Cs, Pp, nullptr, nullptr);
     }
     {
         ProfScope ps(c, "path_prior");
@@ -376,6 +381,10 @@ void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const do
             for (int i = 0; i < q; ++i)
                 launch_prep_cands(c->stream, xr + (size_t)i * D * ldr + s0, ldr, D, sc, g.inv_ell, w.XsT.p + (size_t)i * Sp, Pp, Sp, g.Dcols,
                                   w.ns.p + (size_t)i * Sp);
+        }, [&](KernelSpec ks, double* Cs) {
+            for (int i = 0; i < q; ++i)
+                launch_cross_gram_direct(c->stream, xr + (size_t)i * D * ldr + s0, 1, ldr, sc, Sp, g.X, D, g.inv_ell, g.Np, g.N, ks, nullptr,
+                                         w.Ks.p + (size_t)i * Sp, Cs + (size_t)i * Sp, Pp, nullptr, nullptr);
         });
         {
             ProfScope ps(c, scope);
@@ -540,6 +549,9 @@ extern "C" int sls_path_max_over_points(sls_path* p, const double* Xb, int Mb, d
         const int pc = std::min(pass_max, Mb - p0), Pp = round_up(pc, 128);
         draw_values_device(p, g, ws, Pp, [&] {
             launch_prep_points(c->stream, raw.p + (size_t)p0 * D, D, pc, g.inv_ell, ws.XsT.p, Pp, Pp, g.Dcols, ws.ns.p);
+        }, [&](KernelSpec ks, double* Cs) {
+            launch_cross_gram_direct(c->stream, raw.p + (size_t)p0 * D, D, 1, pc, Pp, g.X, D, g.inv_ell, g.Np, g.N, ks, nullptr, ws.Ks.p, Cs,
+                                     Pp, nullptr, nullptr);
         });
         ProfScope ps(c, "path_max");
         launch_path_colmax(c->stream, ws.VM.p, Pp, pc, nd, p0, tb.p, d_arg);   // the pc live rows only

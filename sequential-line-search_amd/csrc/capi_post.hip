@@ -48,8 +48,12 @@ void post_cov_device(const GpView& g, const double* Xs, int M, PostWs& w) {
         launch_prep_points(c->stream, w.raw.p, g.D, M, g.inv_ell, w.XsT.p, Mp, Mp, g.Dcols, w.ns.p);
         // Matern also writes the derivative weights C*: V's block is free until the triangular product overwrites it
         double* Cs = g.kernel == SLS_KERNEL_ARD_MATERN52 ? w.V.p : w.Ks.p;
-        launch_cross_gram(c->stream, w.XsT.p, Mp, w.ns.p, Mp, g.XT, g.Np, g.nx, Np, g.N, g.Dp, ks, g.alpha, w.Ks.p, Cs, Mp, mu_part,
-                          ca_part);
+        if (g.gram_direct)   // beyond the guard of the norm expansion (kernels.hpp): both Gram terms from the raw coordinate differences
+            launch_cross_gram_direct(c->stream, w.raw.p, g.D, 1, M, Mp, g.X, g.D, g.inv_ell, Np, g.N, ks, g.alpha, w.Ks.p, Cs, Mp, mu_part,
+                                     ca_part);
+        else
+            launch_cross_gram(c->stream, w.XsT.p, Mp, w.ns.p, Mp, g.XT, g.Np, g.nx, Np, g.N, g.Dp, ks, g.alpha, w.Ks.p, Cs, Mp, mu_part,
+                              ca_part);
     }
     {
         ProfScope ps(c, "finalize");
@@ -70,7 +74,8 @@ void post_cov_device(const GpView& g, const double* Xs, int M, PostWs& w) {
     }
     {
         ProfScope ps(c, "post_cov");
-        launch_post_cov(c->stream, w.XsT.p, Mp, g.Dp, w.ns.p, w.V.p, Mp, Np, Mp, M, ks, w.cov.p);
+        if (g.gram_direct) launch_post_cov_direct(c->stream, w.raw.p, g.D, g.inv_ell, w.V.p, Mp, Np, Mp, M, ks, w.cov.p);
+        else launch_post_cov(c->stream, w.XsT.p, Mp, g.Dp, w.ns.p, w.V.p, Mp, Np, Mp, M, ks, w.cov.p);
     }
 }
 

@@ -35,6 +35,8 @@ struct GpView {
     double a, b;
     const double *XT, *nx, *inv_ell, *alpha, *Linv;
     const double *y, *L;   // the data's targets (N, padded to Np) and the Cholesky factor of K_y (Np x Np)
+    const double* X;       // the raw design matrix (D x N): what the direct-difference Gram forms read
+    bool gram_direct;      // the fit is beyond the guard of the norm expansion (gram_direct_form, kernels.hpp)
     long generation;       // sls_gp_generation
     std::shared_mutex* state;
 };

@@ -81,6 +81,28 @@ struct KernelSpec {
     double a;     // signal variance theta[0]
 };
 
+// ---- the guard of the norm expansion ---------------------------------------------
+// The matrix-core Gram kernels take q_ij = |x~_i|^2 + |x~_j|^2 - 2 x~_i . x~_j, x~ = (x - 0.5) / l: a cancellation error of about
+// eps (|x~_i|^2 + |x~_j|^2) <= eps D / (2 l_min^2), ABSOLUTE in q, for points of the unit box.  May an evaluation with largest
+// inverse length scale `ilm` use it?  ONE criterion for the one-workgroup kernels (small_mc_form_ok, on the device) and the tiled
+// routes (gram_direct_form, on the host): beyond `bound` the evaluation forms q from the differences of the RAW coordinates, which are
+// exact for near-duplicate points.  A candidate outside the box needs no bound of its own: an entry matters only where k is not
+// negligible (q < ~500), i.e. within 23 scaled units of a training point, and there |x~*|^2 <= 2 |x~_i|^2 + 1e3.
+constexpr double GRAM_GUARD_BOUND = 1e-11;
+__host__ __device__ __forceinline__ bool gram_expansion_ok(double ilm, int D, double bound = GRAM_GUARD_BOUND) {
+    return ilm * ilm * (0.5 * D) * 2.3e-16 <= bound;
+}
+// Host side: ell = the D length scales of the evaluation.  SLS_GRAM_GUARD=0 switches the guard of the tiled routes off (A/B, tests).
+inline bool gram_direct_form(const double* ell, int D, double bound = GRAM_GUARD_BOUND) {
+    if (!tune_on(TUNE_GRAM_GUARD)) return false;
+    double ilm = 0.0;
+    for (int d = 0; d < D; ++d) ilm = 1.0 / ell[d] > ilm ? 1.0 / ell[d] : ilm;
+    return !gram_expansion_ok(ilm, D, bound);
+}
+// sls_gram / sls_gram_cross hand out the ENTRIES: held to the direct form's own error 4 (D + 8) eps a.  |dk/dq| <= a / 2, so the
+// expansion may serve them while its q is good to 8 (D + 8) eps.
+inline double gram_entry_bound(int D) { return 8.0 * (D + 8) * 2.2e-16; }
+
 // ---- kernels_gram.hip -------------------------------------------------------
 // X (D x M column-major, device) -> XT[i + d*ld] = (X[d,i]-0.5)*inv_ell[d] for i<M,d<D, 0 elsewhere (i<Mp, d<Dcols); norms[i].
 void launch_prep_points(hipStream_t s, const double* X, int D, int M, const double* inv_ell, double* XT, long ld, int Mp,
@@ -98,6 +120,19 @@ void launch_gram_sym(hipStream_t s, const double* XT, long ld, int Dp, const dou
 void launch_cross_gram(hipStream_t s, const double* XsT, long lds_, const double* ns, int Sp, const double* XT, long ld,
                        const double* nx, int Np, int N, int Dp, KernelSpec ks, const double* alpha, double* Ks, double* Cs,
                        long ldk, double* mu_part, double* ca_part);
+// The same two results from the direct differences ((x_id - x_jd) / l_d)^2 of the RAW coordinates, on the VALU (O(N^2 D); for the
+// evaluations gram_direct_form sends here).  X[d + i*D]: the N training points; inv_ell: D values.
+void launch_gram_sym_direct(hipStream_t s, const double* X, int D, const double* inv_ell, int Np, int N, KernelSpec ks, double b,
+                            double* K, bool lower_only);
+// xr[n*sn + d*sd]: the M raw candidates (rows M .. Sp-1 are padding: 0.5 in every dimension, as launch_prep_* leave them)
+void launch_cross_gram_direct(hipStream_t s, const double* xr, long sn, long sd, int M, int Sp, const double* X, int D,
+                              const double* inv_ell, int Np, int N, KernelSpec ks, const double* alpha, double* Ks, double* Cs,
+                              long ldk, double* mu_part, double* ca_part);
+
+// gram_direct_form: the gradient contractions Gs / Gm of launch_grad_gemm (kernels_acq.hip) over the differences (x_i - x*_n) / l of the
+// raw coordinates instead of x~_i alone; the finalize kernels are then given ca_part = cw_part = 0 (their x~* ca, x~* cw terms vanish).
+void launch_grad_direct(hipStream_t s, const double* P, const double* Cs, long ldk, int Sp, const double* xr, long sn, long sd, int M,
+                        const double* X, int D, const double* inv_ell, int N, const double* alpha, double* Gs, double* Gm);
 
 // ---- kernels_small.hip ---------------------------------------------------------
 // Whole MAP-objective evaluation for N <= 128, D <= 128 in one single-workgroup launch.  Inputs a, b, l_1..l_D, y_1..y_N travel
@@ -428,6 +463,9 @@ void launch_gemm_lhs_lower(hipStream_t s, const double* L, long ldl, const doubl
 // multiples of 16.
 void launch_post_cov(hipStream_t s, const double* XsT, long ldx, int Dp, const double* ns, const double* V, long ldv, int Kv, int Mp,
                      int M, KernelSpec ks, double* C);
+// the same with the prior term k(Xs, Xs) from the raw query points Xs[d + i*D] (gram_direct_form)
+void launch_post_cov_direct(hipStream_t s, const double* Xs, int D, const double* inv_ell, const double* V, long ldv, int Kv, int Mp,
+                            int M, KernelSpec ks, double* C);
 // Standard normal number t of stream `seed`: Philox4x64-10 with key (seed, 0) on block counter (t / 4, 0, 0, 0); each 64-bit
 // output x becomes u = ((x >> 11) + 0.5) 2^-53; Box-Muller on the output pairs (0, 1) and (2, 3) gives r01 cos, r01 sin, r23 cos,
 // r23 sin for t mod 4 = 0 .. 3.
@@ -507,6 +545,13 @@ void launch_nll_scalars(hipStream_t s, const double* part, int nparts, const dou
 void launch_lengthscale_grad(hipStream_t s, const double* XT, const double* Y, const double* svec, const double* inv_ell,
                              long ld, int N, int D, double* gl, const double* part, int nparts, const double* alpha, const double* y,
                              const double* Kinv, int Np, double* out, const double* Lfac, const int* info);
+// gram_direct_form: G and the per-tile sums wk_part from the raw coordinate differences (X[d + i*D]), and the length-scale gradient
+// as the unexpanded contraction sum_ij G_ij (x~_ip - x~_jp)^2 / l_p (no Y, no row sums); the last block leaves the evaluation's sums.
+void launch_nll_weight_direct(hipStream_t s, const double* X, int D, const double* inv_ell, int Np, int N, KernelSpec ks,
+                              const double* alpha, const double* Kinv, double* G, double* wk_part);
+void launch_lengthscale_grad_direct(hipStream_t s, const double* X, const double* G, const double* inv_ell, int Np, int N, int D,
+                                    double* gl, const double* part, int nparts, const double* alpha, const double* y, const double* Kinv,
+                                    double* out, const double* Lfac, const int* info);
 // Y = sum of `chunks` partial products `stride` apart (in place in the first), and svec = sum of `row_chunks` slices of row_part
 void launch_sum_chunks(hipStream_t s, double* Y, long n, int chunks, long stride, const double* row_part, int Np, int row_chunks,
                        double* svec);

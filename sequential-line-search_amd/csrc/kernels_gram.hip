@@ -233,4 +233,110 @@ void launch_cross_gram(hipStream_t s, const double* XsT, long lds_, const double
                            Np, N, Dp, ks.a, alpha, Ks, Cs, ldk, mu_part, ca_part);
 }
 
+// ---- the direct-difference forms (gram_direct_form, kernels.hpp) -----------------------------------------------------------
+// q = sum_d ((xa_d - xb_d) / l_d)^2 in dimension order from the raw coordinates: the difference of two near-duplicate points is exact,
+// so q keeps a RELATIVE error of (D + O(1)) eps at any length scale.  One thread per element, no tiles: these serve the evaluations
+// the expansion gets wrong, not the benchmark.
+__device__ __forceinline__ double direct_q(const double* __restrict__ xa, long sa, bool pad_a, const double* __restrict__ xb,
+                                           const double* __restrict__ inv_ell, int D) {
+    double q = 0.0;
+    for (int d = 0; d < D; ++d) {
+        const double t = ((pad_a ? 0.5 : xa[d * sa]) - xb[d]) * inv_ell[d];
+        q = fma(t, t, q);
+    }
+    return q;
+}
+
+// grid (ceil(Np / 256), Np): thread = row i of column j.  The results gram_sym_kernel defines: a + b on the diagonal, identity in the
+// padding, tiles above the diagonal untouched when lower_only; K_ij and K_ji have the same bits ((x_i - x_j)^2 == (x_j - x_i)^2).
+__global__ __launch_bounds__(256) void gram_sym_direct_kernel(const double* __restrict__ X, int D, const double* __restrict__ inv_ell,
+                                                              int Np, int N, int kernel, double a, double b, double* __restrict__ K,
+                                                              int lower_only) {
+    extern __shared__ double ils[];   // the D inverse length scales, read once per workgroup (they may sit in mapped host memory)
+    for (int d = threadIdx.x; d < D; d += 256) ils[d] = inv_ell[d];
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (i >= Np || (lower_only && (i >> 7) < (j >> 7))) return;
+    double k, c;
+    if (i >= N || j >= N) {
+        k = (i == j) ? 1.0 : 0.0;
+    } else {
+        const double q = (i == j) ? 0.0 : direct_q(X + (long)i * D, 1, false, X + (long)j * D, ils, D);
+        kernel_kc(kernel, a, q, k, c);
+        if (i == j) k += b;
+    }
+    K[(long)i + (long)j * Np] = k;
+}
+
+void launch_gram_sym_direct(hipStream_t s, const double* X, int D, const double* inv_ell, int Np, int N, KernelSpec ks, double b,
+                            double* K, bool lower_only) {
+    hipLaunchKernelGGL(gram_sym_direct_kernel, dim3((Np + 255) / 256, Np), dim3(256), (size_t)D * 8, s, X, D, inv_ell, Np, N, ks.kernel, ks.a, b, K,
+                       (int)lower_only);
+}
+
+// grid (Sp / 128, Np / 128): thread = candidate m over the 128 training points of tile column tn, ascending; its two sums are the
+// tile's entries of mu_part / ca_part (the layout cross_gram_kernel leaves for the finalize kernel).
+template <bool MATERN>
+__global__ __launch_bounds__(128) void cross_gram_direct_kernel(const double* __restrict__ xr, long sn, long sd, int M,
+                                                                const double* __restrict__ X, int D, const double* __restrict__ inv_ell,
+                                                                int N, double a, const double* __restrict__ alpha,
+                                                                double* __restrict__ Ks, double* __restrict__ Cs, long ldk,
+                                                                double* __restrict__ mu_part, double* __restrict__ ca_part) {
+    const int m = blockIdx.x * 128 + threadIdx.x, tn = blockIdx.y;
+    double smu = 0.0, sca = 0.0;
+    for (int gi = tn * 128; gi < tn * 128 + 128; ++gi) {
+        double k = 0.0, c = 0.0;
+        if (gi < N) {
+            const double q = direct_q(xr + (long)m * sn, sd, m >= M, X + (long)gi * D, inv_ell, D);
+            kernel_kc(MATERN ? SLS_KERNEL_ARD_MATERN52 : SLS_KERNEL_ARD_SQUARED_EXPONENTIAL, a, q, k, c);
+        }
+        Ks[(long)m + (long)gi * ldk] = k;
+        if (MATERN) Cs[(long)m + (long)gi * ldk] = c;
+        const double al = alpha ? alpha[gi] : 0.0;
+        smu += al * k;
+        sca += al * c;
+    }
+    if (alpha) {
+        mu_part[(long)tn * ldk + m] = smu;
+        ca_part[(long)tn * ldk + m] = sca;
+    }
+}
+
+void launch_cross_gram_direct(hipStream_t s, const double* xr, long sn, long sd, int M, int Sp, const double* X, int D,
+                              const double* inv_ell, int Np, int N, KernelSpec ks, const double* alpha, double* Ks, double* Cs,
+                              long ldk, double* mu_part, double* ca_part) {
+    const dim3 grid(Sp / 128, Np / 128);
+    if (ks.kernel == SLS_KERNEL_ARD_MATERN52)
+        hipLaunchKernelGGL(cross_gram_direct_kernel<true>, grid, dim3(128), 0, s, xr, sn, sd, M, X, D, inv_ell, N, ks.a, alpha, Ks, Cs,
+                           ldk, mu_part, ca_part);
+    else
+        hipLaunchKernelGGL(cross_gram_direct_kernel<false>, grid, dim3(128), 0, s, xr, sn, sd, M, X, D, inv_ell, N, ks.a, alpha, Ks, Cs,
+                           ldk, mu_part, ca_part);
+}
+
+// The two gradient contractions of the tiled evaluation with the coordinate differences taken first, from the raw coordinates:
+//   Gs[n + d*ldk] = sum_i P[n + i*ldk] t_id,  Gm[n + d*ldk] = sum_i Cs[n + i*ldk] alpha_i t_id,  t_id = (x_id - x*_nd) / l_d,  i < N, d < D.
+// The matrix-core form (grad_gemm) contracts x~_i alone and the finalize kernels subtract x~* times the sums ca / cw afterwards, which
+// leaves eps |x~| / l in every entry; with these sums the caller hands the finalize kernel ca = cw = 0.  grid (Sp / 128, D).
+__global__ __launch_bounds__(128) void grad_direct_kernel(const double* __restrict__ P, const double* __restrict__ Cs, long ldk,
+                                                          const double* __restrict__ xr, long sn, long sd, int M,
+                                                          const double* __restrict__ X, int D, const double* __restrict__ inv_ell, int N,
+                                                          const double* __restrict__ alpha, double* __restrict__ Gs,
+                                                          double* __restrict__ Gm) {
+    const int n = blockIdx.x * 128 + threadIdx.x, d = blockIdx.y;
+    const double xs = n < M ? xr[(long)n * sn + (long)d * sd] : 0.5, il = inv_ell[d];
+    double gs = 0.0, gm = 0.0;
+    for (int i = 0; i < N; ++i) {
+        const double t = (X[d + (long)i * D] - xs) * il;
+        gs = fma(P[(long)n + (long)i * ldk], t, gs);
+        gm = fma(Cs[(long)n + (long)i * ldk] * alpha[i], t, gm);
+    }
+    Gs[(long)n + (long)d * ldk] = gs;
+    Gm[(long)n + (long)d * ldk] = gm;
+}
+void launch_grad_direct(hipStream_t s, const double* P, const double* Cs, long ldk, int Sp, const double* xr, long sn, long sd, int M,
+                        const double* X, int D, const double* inv_ell, int N, const double* alpha, double* Gs, double* Gm) {
+    hipLaunchKernelGGL(grad_direct_kernel, dim3(Sp / 128, D), dim3(128), 0, s, P, Cs, ldk, xr, sn, sd, M, X, D, inv_ell, N, alpha, Gs, Gm);
+}
+
 }  // namespace slsk

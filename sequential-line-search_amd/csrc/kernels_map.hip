@@ -201,4 +201,90 @@ void launch_lengthscale_grad(hipStream_t s, const double* XT, const double* Y, c
                        NllScalarArgs{part, nparts, alpha, y, Kinv, Np, N, out, Lfac, info});
 }
 
+// ---- the direct-difference forms of the gradient (gram_direct_form, kernels.hpp) ---------------------------------------------
+// What nll_weight_kernel leaves, with q from the raw coordinate differences: G = 1/2 W .* c and the per-tile sums of 1/2 W .* k
+// (wk_part[tm + tn nt], the order nll_scalars_block adds them in).  One workgroup per 128 x 128 tile, a thread = one row over 64 columns.
+template <bool MATERN>
+__global__ __launch_bounds__(256) void nll_weight_direct_kernel(const double* __restrict__ X, int D, const double* __restrict__ inv_ell,
+                                                                int Np, int N, double a, const double* __restrict__ alpha,
+                                                                const double* __restrict__ Kinv, double* __restrict__ G,
+                                                                double* __restrict__ wk_part) {
+    __shared__ double red[4];
+    extern __shared__ double ils[];   // the D inverse length scales, read once per workgroup (they sit in mapped host memory)
+    for (int d = threadIdx.x; d < D; d += 256) ils[d] = inv_ell[d];
+    __syncthreads();
+    const int nt = Np / 128;
+    const int m0 = (blockIdx.x % nt) * 128, n0 = (blockIdx.x / nt) * 128;
+    const int gi = m0 + (threadIdx.x & 127), c0 = n0 + 64 * (threadIdx.x >> 7);
+    const double ai = alpha[gi];
+    double part = 0.0;
+    for (int gj = c0; gj < c0 + 64; ++gj) {
+        const long off = (long)gi + (long)gj * Np;
+        double g = 0.0;
+        if (gi < N && gj < N) {
+            double q = 0.0;
+            if (gi != gj)
+                for (int d = 0; d < D; ++d) {
+                    const double t = (X[d + (long)gi * D] - X[d + (long)gj * D]) * ils[d];
+                    q = fma(t, t, q);
+                }
+            double k, c;
+            if (!MATERN) {
+                k = a * exp(-0.5 * q);
+                c = k;
+            } else {
+                const double s = sqrt(5.0 * q), ex = exp(-s);
+                k = a * (1.0 + s + (5.0 / 3.0) * q) * ex;
+                c = a * (5.0 / 3.0) * (1.0 + s) * ex;
+            }
+            const double w = 0.5 * (ai * alpha[gj] - Kinv[off]);
+            g = w * c;
+            part += w * k;
+        }
+        G[off] = g;
+    }
+    const double t = block_sum_256(part, red);
+    if (threadIdx.x == 0) wk_part[blockIdx.x] = t;
+}
+
+void launch_nll_weight_direct(hipStream_t s, const double* X, int D, const double* inv_ell, int Np, int N, KernelSpec ks,
+                              const double* alpha, const double* Kinv, double* G, double* wk_part) {
+    const int nt = Np / 128;
+    if (ks.kernel == SLS_KERNEL_ARD_MATERN52)
+        hipLaunchKernelGGL(nll_weight_direct_kernel<true>, dim3(nt * nt), dim3(256), (size_t)D * 8, s, X, D, inv_ell, Np, N, ks.a, alpha, Kinv, G, wk_part);
+    else
+        hipLaunchKernelGGL(nll_weight_direct_kernel<false>, dim3(nt * nt), dim3(256), (size_t)D * 8, s, X, D, inv_ell, Np, N, ks.a, alpha, Kinv, G, wk_part);
+}
+
+// blocks [0, D): gl[p] = inv_ell[p] sum_ij G_ij ((x_ip - x_jp) inv_ell[p])^2 -- the contraction 2 inv_ell[p] sum_j x~_jp (x~_jp s_j - Y_jp)
+// of lengthscale_grad_kernel before it is expanded into Y = G X~ (which cancels like the Gram expansion does);  block D: the sums
+__global__ __launch_bounds__(256) void lengthscale_grad_direct_kernel(const double* __restrict__ X, const double* __restrict__ G,
+                                                                      const double* __restrict__ inv_ell, int Np, int N, int D,
+                                                                      double* __restrict__ gl, NllScalarArgs sa) {
+    __shared__ double red[4];
+    __shared__ double red256[256];
+    const int p = blockIdx.x;
+    if (p == D) {
+        nll_scalars_block(sa, red, red256);
+        return;
+    }
+    const double il = inv_ell[p];
+    double acc = 0.0;
+    for (int j = 0; j < N; ++j) {
+        const double xj = X[p + (long)j * D];
+        for (int i = threadIdx.x; i < N; i += 256) {
+            const double t = (X[p + (long)i * D] - xj) * il;
+            acc = fma(G[(long)i + (long)j * Np], t * t, acc);
+        }
+    }
+    const double t = block_sum_256(acc, red);
+    if (threadIdx.x == 0) gl[p] = il * t;
+}
+void launch_lengthscale_grad_direct(hipStream_t s, const double* X, const double* G, const double* inv_ell, int Np, int N, int D,
+                                    double* gl, const double* part, int nparts, const double* alpha, const double* y, const double* Kinv,
+                                    double* out, const double* Lfac, const int* info) {
+    hipLaunchKernelGGL(lengthscale_grad_direct_kernel, dim3(D + 1), dim3(256), 0, s, X, G, inv_ell, Np, N, D, gl,
+                       NllScalarArgs{part, nparts, alpha, y, Kinv, Np, N, out, Lfac, info});
+}
+
 }  // namespace slsk

@@ -75,6 +75,38 @@ void launch_post_cov(hipStream_t s, const double* XsT, long ldx, int Dp, const d
         hipLaunchKernelGGL(post_cov_kernel<false>, grid, dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, XsT, ldx, Dp, ns, V, ldv, Kv, Mp, M, ks.a, C);
 }
 
+// The same Sigma with the prior term from the raw coordinate differences (gram_direct_form, kernels.hpp): thread = entry (i, j) of the
+// lower triangle, written with its mirror.  Xs[d + i*D]: the M raw query points.
+__global__ __launch_bounds__(256) void post_cov_direct_kernel(const double* __restrict__ Xs, int D, const double* __restrict__ inv_ell,
+                                                              const double* __restrict__ V, long ldv, int Kv, int Mp, int M, int kernel,
+                                                              double a, double* __restrict__ C) {
+    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (i >= Mp || i < j) return;
+    double v;
+    if (i >= M || j >= M) {
+        v = i == j ? 1.0 : 0.0;
+    } else {
+        double q = 0.0;
+        if (i != j)
+            for (int d = 0; d < D; ++d) {
+                const double t = (Xs[d + (long)i * D] - Xs[d + (long)j * D]) * inv_ell[d];
+                q = fma(t, t, q);
+            }
+        double k, c;
+        kernel_kc(kernel, a, q, k, c);
+        double vv = 0.0;
+        for (int kk = 0; kk < Kv; ++kk) vv = fma(V[i + (long)kk * ldv], V[j + (long)kk * ldv], vv);
+        v = k - vv;
+    }
+    C[(long)i + (long)j * Mp] = v;
+    if (i != j) C[(long)j + (long)i * Mp] = v;
+}
+void launch_post_cov_direct(hipStream_t s, const double* Xs, int D, const double* inv_ell, const double* V, long ldv, int Kv, int Mp,
+                            int M, KernelSpec ks, double* C) {
+    hipLaunchKernelGGL(post_cov_direct_kernel, dim3((Mp + 255) / 256, Mp), dim3(256), 0, s, Xs, D, inv_ell, V, ldv, Kv, Mp, M, ks.kernel,
+                       ks.a, C);
+}
+
 // ---- Philox4x64-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC 2011) ----
 __device__ __forceinline__ void philox4x64_10(unsigned long long (&x)[4], unsigned long long k0, unsigned long long k1) {
     constexpr unsigned long long M0 = 0xD2E7470EE14C6C93ull, M1 = 0xCA5A826395121157ull;

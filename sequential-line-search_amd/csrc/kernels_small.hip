@@ -220,7 +220,7 @@ __device__ __forceinline__ SmallPts small_pts_stage(double* As, const double* __
 __device__ __forceinline__ bool small_mc_form_ok(double* As, int D) {
     const int l64 = threadIdx.x & 63;
     const double ilm = wave_max(fmax(small_scratch(As, SC_INVL + l64), small_scratch(As, SC_INVL + 64 + l64)));
-    return ilm * ilm * (0.5 * D) * 2.3e-16 <= 1e-11;
+    return gram_expansion_ok(ilm, D);   // kernels.hpp: the criterion the tiled routes share
 }
 
 // q_ij = sum_d ((x_id - x_jd) / l_d)^2 in dimension order, B dimensions' operands in flight at a time

@@ -128,13 +128,15 @@ def test_matrix_core_form_and_direct_difference_form_agree(ctx, oracle, kernel, 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kernel", [0, 1])
 @pytest.mark.parametrize("ell", [3e-3, 1e-5, 1e-8])
-def test_small_length_scales_with_near_duplicates_take_the_direct_form(ctx, oracle, kernel, ell):
+@pytest.mark.parametrize("M,D", [(40, 6), (200, 6), (300, 64)])
+def test_small_length_scales_with_near_duplicates_take_the_direct_form(ctx, oracle, kernel, ell, M, D):
     """ADVICE (round 5): the matrix-core Gram pass expands q_ij = |x~_i|^2 + |x~_j|^2 - 2 x~_i . x~_j, whose cancellation error is
     eps D / (2 l^2) absolute -- O(1) at the l = 1e-8 the DIRECT phase of the GP MAP fit visits, exactly where near-duplicate points
     (late in a line search) have a small TRUE q.  Such evaluations must take the direct differences: the marginal likelihood and its
-    gradient with near-duplicates at small l agree with the oracle (which forms differences) and with SLS_SMALL_XLDS=0."""
+    gradient with near-duplicates at small l agree with the oracle (which forms differences) and with SLS_SMALL_XLDS=0.
+    M = 200 and 300 take the tiled route (N > 128), which carries the same guard; SLS_SMALL_XLDS belongs to the one-workgroup
+    kernels, so the bit comparison with it applies at M = 40 only."""
     rng = np.random.default_rng(11 + kernel)
-    M, D = 40, 6
     X = rng.uniform(0, 1, (D, M))
     X[:, 1] = X[:, 0] + ell * 0.3 * rng.normal(size=D)        # q ~ 0.5 at this length scale: the kernel value is O(1), not 0 or 1
     X[:, 7] = X[:, 6] + ell * 1.0 * rng.normal(size=D)
@@ -153,8 +155,9 @@ def test_small_length_scales_with_near_duplicates_take_the_direct_form(ctx, orac
     for vg, gg in (fast, direct):
         assert abs(vg - vgo) <= 1e-8 * max(1.0, abs(vgo)), (vg, vgo)
         np.testing.assert_allclose(gg, ggo, rtol=1e-6, atol=1e-8 * max(1.0, np.abs(ggo).max()))
-    assert fast[0] == direct[0]                                # the same arithmetic: the guard sent both down the direct path
-    np.testing.assert_array_equal(fast[1], direct[1])
+    if M <= 128:
+        assert fast[0] == direct[0]                            # the same arithmetic: the guard sent both down the direct path
+        np.testing.assert_array_equal(fast[1], direct[1])
 
 
 def test_device_btl_overflows_like_the_reference(ctx, oracle):

@@ -103,3 +103,36 @@ def test_device_memory_pool_limit(oracle, monkeypatch):
     for (m1, s1), (m0, s0) in zip(out["16384"], out["0"]):
         assert np.array_equal(m1, m0) and np.array_equal(s1, s0)
     assert np.array_equal(out["0"][0][0], out["0"][2][0])
+
+
+@pytest.mark.parametrize("kernel", [0, 1])
+def test_gram_guard_switch(kernel, monkeypatch):
+    """SLS_GRAM_GUARD: the guard of the norm expansion on the tiled Gram routes (csrc/kernels.hpp).  At l = 0.3 the guard does not
+    trip: with and without it sls_gram, sls_gram_cross, a fit and the MAP objective come from the same kernels, bit for bit.  At
+    l = 1e-5 it is what keeps sls_gram within 4 (D + 8) eps a of the direct differences: switched off, the matrix-core expansion
+    misses that by orders of magnitude on near-duplicate points (the defect tests/test_gpu_short_length_scales.py is there for)."""
+    import gram_ref as gr
+    m = sls()
+    N, D = 200, 6
+    res = {}
+    for v in ("1", "0"):
+        monkeypatch.setenv("SLS_GRAM_GUARD", v)
+        c = m.Context(0)
+        out = []
+        for case in (0.3, 1e-5):
+            r = gr.reference(N, D, case, kernel)
+            K, Ks = c.gram(r["X"], r["theta"], r["b"], kernel), c.gram_cross(r["X"], r["Xs"], r["theta"], kernel)
+            g = m.GP(c, r["X"], r["y"], r["theta"], r["b"], kernel)
+            h = m.Nll(c, r["X"], kernel)
+            out.append((K, Ks, g.matrix(m.GP_ALPHA), *g.predict(r["Xs"]), *h.gp_objective(r["y"], r["hyp"])))
+            g.close(); h.close()
+        res[v] = out
+        c.close()
+    monkeypatch.delenv("SLS_GRAM_GUARD")
+    for on, off in zip(res["1"][0], res["0"][0]):                      # l = 0.3: identical bits
+        assert np.array_equal(np.asarray(on), np.asarray(off))
+    ref = gr.quantities(gr.reference(N, D, 1e-5, kernel))
+    tol = gr.gram_tolerance(D)
+    assert np.abs(res["1"][1][0] - ref["K"]).max() <= tol and np.abs(res["1"][1][1] - ref["Ks"]).max() <= tol
+    assert np.abs(res["0"][1][0] - ref["K"]).max() > 1e4 * tol         # measured 1e-6 a against 9e-15 a
+    assert np.abs(res["0"][1][1] - ref["Ks"]).max() > 1e4 * tol
