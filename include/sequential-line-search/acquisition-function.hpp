@@ -204,6 +204,29 @@ namespace sequential_line_search
                                                                                         const unsigned long long seed = 0,
                                                                                         const int num_frequencies = 2048,
                                                                                         double* value = nullptr);
+
+        /// The next slider by the expected utility of the best position on it (not in the reference; line EUBO, include/sls_hip.h
+        /// sls_line_*): the query of SequentialLineSearchOptimizer is a line and the user picks the best point on it, so the
+        /// criterion is E[max_t f((1 - t) a + t b)], estimated on num_positions grid positions (2 .. 16) over num_draws pathwise
+        /// posterior draws (stream `seed`, num_frequencies random features) and maximised over the ends: with `anchor` (D values,
+        /// e.g. the current best point) the first end is fixed there and the second is searched over [0,1]^D; with an empty anchor
+        /// both ends are free ([0,1]^(2D)).  One L-BFGS of num_local_search_iters evaluations (the tolerances of
+        /// GetLocalSearchTolerances) from each of num_global_search_iters uniform starts of the generator
+        /// FindNextQueryByExpectedUtility uses, seeded with `seed`, all in lock step on the device.  The same seed gives the same
+        /// slider.  value (may be nullptr) receives the utility there.  Device-resident regressors only (std::invalid_argument
+        /// otherwise).
+        std::pair<Eigen::VectorXd, Eigen::VectorXd> FindNextSliderByExpectedUtility(const Regressor& regressor, const Eigen::VectorXd& anchor,
+                                                                                    const int      num_positions = 9,
+                                                                                    const unsigned num_draws = 256,
+                                                                                    const unsigned num_global_search_iters = 100,
+                                                                                    const unsigned num_local_search_iters = 50,
+                                                                                    const unsigned long long seed = 0,
+                                                                                    const int num_frequencies = 2048, double* value = nullptr);
+        /// The same from an explicit start set (2D x S: rows 0..D-1 start the first end; D x S with an anchor).
+        std::pair<Eigen::VectorXd, Eigen::VectorXd> FindNextSliderByExpectedUtilityFromStarts(
+            const Regressor& regressor, const Eigen::VectorXd& anchor, const Eigen::MatrixXd& starts, const int num_positions = 9,
+            const unsigned num_draws = 256, const unsigned num_local_search_iters = 50, const unsigned long long seed = 0,
+            const int num_frequencies = 2048, double* value = nullptr);
     } // namespace acquisition_func
 } // namespace sequential_line_search
 

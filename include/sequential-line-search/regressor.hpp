@@ -5,6 +5,7 @@
 
 #include <sequential-line-search/eigen-lite.hpp>
 #include <sequential-line-search/kernel-type.hpp>
+#include <utility>
 #include <vector>
 
 struct sls_gp;
@@ -121,6 +122,25 @@ namespace sequential_line_search
         std::vector<Eigen::VectorXd> MaximizeNoisyExpectedImprovement(int num_points, const Eigen::VectorXd& baseline,
                                                                       const Eigen::MatrixXd& starts, unsigned num_local_search_iters,
                                                                       double* value = nullptr) const;
+        /// Expected utility of the best of num_positions grid positions on the slider from ends_a.col(m) to ends_b.col(m) (line EUBO;
+        /// include/sls_hip.h sls_line_*): CalcExpectedUtilitiesOfBestOption at the positions (1 - t_i) a + t_i b, t_i = i /
+        /// (num_positions - 1), 2 <= num_positions <= 16 -- Slider::GetValue on the grid.  ends_a, ends_b D x M.  Returns the M values;
+        /// grad_a, grad_b (may be nullptr) receive the gradients with respect to the two ends (D x M each, the chain rule on the
+        /// positions' gradients), win_counts (may be nullptr) num_positions x M, the number of draws each position wins (win_counts
+        /// / GetNumDraws() estimates the probability that the user stops there).  With baseline (num_draws finite values) the
+        /// criterion is CalcNoisyExpectedImprovements at the same positions.
+        Eigen::VectorXd CalcExpectedUtilitiesOfBestSliderPosition(const Eigen::MatrixXd& ends_a, const Eigen::MatrixXd& ends_b,
+                                                                  int num_positions, Eigen::MatrixXd* grad_a = nullptr,
+                                                                  Eigen::MatrixXd* grad_b = nullptr, Eigen::MatrixXi* win_counts = nullptr,
+                                                                  const Eigen::VectorXd* baseline = nullptr) const;
+        /// Maximiser of that utility over the ends: starts is 2D x S (rows 0..D-1 start the first end), or with `anchor` (D values;
+        /// the first end of every slider, e.g. the current best point) D x S, the second end alone -- 2D or D variables whatever
+        /// num_positions is.  One lock-step bounded L-BFGS of num_local_search_iters evaluations per start (the acquisition
+        /// maximiser's local search tolerances); returns the best slider's two ends (the first is the anchor when there is one).
+        /// value (may be nullptr) receives the utility there.
+        std::pair<Eigen::VectorXd, Eigen::VectorXd> MaximizeExpectedUtilityOfBestSliderPosition(
+            int num_positions, const Eigen::MatrixXd& starts, unsigned num_local_search_iters, const Eigen::VectorXd* anchor = nullptr,
+            const Eigen::VectorXd* baseline = nullptr, double* value = nullptr) const;
 
     private:
         // the set criteria of both kinds: baseline == nullptr is the expected utility of the best option

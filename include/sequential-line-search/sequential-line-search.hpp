@@ -42,6 +42,16 @@ namespace sequential_line_search
         void SubmitFeedbackData(const double slider_position, const int num_map_estimation_iters, const int num_global_search_iters,
                                 const int num_local_search_iters);
 
+        /// SubmitFeedbackData with the next slider chosen by the criterion of the query that is actually asked (an addition of this
+        /// build): identical up to and including the current best point x+, then the far end is the maximiser of the expected
+        /// utility of the best of num_positions grid positions on the slider from x+ (acquisition_func::FindNextSliderByExpectedUtility
+        /// anchored at x+, num_draws posterior draws of num_frequencies random features, draw and start stream `seed`) instead of
+        /// the maximiser of the pointwise acquisition function.  The pair goes through the same Slider (enlargement as configured).
+        void SubmitFeedbackDataByExpectedUtility(const double slider_position, const int num_positions = 9, const int num_draws = 256,
+                                                 const int num_map_estimation_iters = 100, const int num_global_search_iters = 100,
+                                                 const int num_local_search_iters = 50, const unsigned long long seed = 0,
+                                                 const int num_frequencies = 2048);
+
         std::pair<Eigen::VectorXd, Eigen::VectorXd> GetSliderEnds() const;
         Eigen::VectorXd                             CalcPointFromSliderPosition(const double slider_position) const;
         Eigen::VectorXd                             GetMaximizer() const;

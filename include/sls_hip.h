@@ -453,6 +453,52 @@ int sls_qnei_maximize(sls_path* p, int q, const double* baseline, const double* 
                       const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
                       double* x_stars, double* y_stars);
 
+/* ---- expected utility of the best slider position on posterior draws (not in the reference) --------------------------------
+ * Line EUBO: the query of SequentialLineSearchOptimizer is a slider from a to b, and the user picks the best point anywhere on it.
+ * The one-step criterion of that query is E[ max_t f((1-t) a + t b) ], estimated on a grid of q positions over the FIXED draws of a
+ * path object p.  A line is its ends (a, b), each in [0,1]^D, with SLS_LINE_MIN_POSITIONS <= q <= SLS_QEUBO_MAX_OPTIONS:
+ *   u_i = (q-1-i)/(q-1),  t_i = i/(q-1)             (each ONE double division of two exact integers, on the device)
+ *   x_i = u_i a + t_i b,  i = 0..q-1                (two products and one sum per coordinate, separate roundings, NO fused
+ *                                                    multiply-add, no clamp: Slider::GetValue on the grid; x_0 = a, x_{q-1} = b)
+ *   value  = sls_qeubo_eval at the set (x_0..x_{q-1}); with a per-draw baseline (n_draws finite doubles) sls_qnei_eval at it
+ *   wins_i = as there: wins_i / n_draws estimates the probability that the user stops at position i
+ *   grad_a = sum_i u_i g_i,  grad_b = sum_i t_i g_i  (g_i = the set gradient's block of option i; product and sum separate roundings;
+ *                                                    grad_a from zero in INCREASING i, grad_b from zero in DECREASING i -- the
+ *                                                    mirror image of grad_a's order, which is what makes the mirror contract below
+ *                                                    hold to the bit: one order for both cannot, a sum of q > 3 terms depends on it)
+ * Guard: the set's guard passes through -- a guarded set gives SLS_QEUBO_FLOOR (0 with a baseline) and an exactly zero line gradient.
+ * Anchored form: with `anchor` (D host doubles, all finite, else SLS_ERR_INVALID; uploaded once per call) a = anchor for every line of
+ * the call, a line is b alone (D variables) and only grad_b is returned.  This is the slider through x+.
+ * Contract:
+ *   - A line's value and wins are bit for bit those of sls_qeubo_eval / sls_qnei_eval at the expanded set, and its gradient is bit for
+ *     bit the fold above of that call's gradient.
+ *   - A line's bits depend on neither its column, the other lines of the call, the lines per pass nor SLS_COMPACT.
+ *   - Mirror symmetry: swapping a and b leaves the value's bits unchanged, reverses wins and swaps the two gradient blocks, with or
+ *     without a baseline: u_i = t_{q-1-i} to the bit and the sum of two products commutes, so the expanded set is the reversed set bit
+ *     for bit, and the permutation contract of sls_qeubo_eval gives the reversed set gradient bit for bit; the swapped line's grad_b
+ *     then adds, in decreasing i, exactly the products this line's grad_a adds in increasing i (and the other way round), so the
+ *     blocks swap bit for bit for every q.
+ *   - Degenerate line a = b: wherever the expansion reproduces a at every position (always for q = 2 and q = 3, where the weights are
+ *     0, 1/2, 1; for other q whenever u_i a + t_i a rounds back to a in every coordinate, e.g. coordinates with few mantissa bits and
+ *     q - 1 a power of two) all options tie, position 0 wins every draw, grad_b is exactly zero and grad_a = g_0.  Elsewhere the
+ *     positions differ from a by a rounding and an inner position may win a draw by that much.
+ * Route per pass: line_expand (lines -> the candidate-major set block), ONE pass of the qEUBO evaluation unchanged, line_fold (set
+ * gradient -> line gradient).  Lines per pass are the sets per pass of sls_qeubo_eval, and the expanded sets and their gradient are
+ * held for one pass only (qD x pass doubles each, never qD x M).  The maximiser runs L-BFGS over 2D variables (D anchored) whatever q.
+ * Locks and the staleness rule are those of sls_qeubo_eval. */
+#define SLS_LINE_MIN_POSITIONS 2
+/* lines: (anchor ? D : 2D) x M column-major, rows 0..D-1 = a (free form), last D rows = b.  baseline NULL: EUBO form; else n_draws
+ * finite doubles.  val (M), grad ((anchor ? D : 2D) x M), wins (q x M ints): each may be NULL.  M = 0 is a no-op; q outside
+ * SLS_LINE_MIN_POSITIONS..SLS_QEUBO_MAX_OPTIONS, M < 0, NULL p, NULL lines, a non-finite anchor or baseline is SLS_ERR_INVALID. */
+int sls_line_eval(sls_path* p, int q, const double* baseline, const double* anchor, const double* lines, int M,
+                  double* val, double* grad, int* wins);
+/* sls_qeubo_maximize over [0,1]^(2D) (or [0,1]^D anchored) with this objective: starts, x_out, x_stars have 2D (D) rows; the other
+ * outputs and sls_acq_last_stats as there.  Anchor and baseline are validated and uploaded once, before the first round.  S_starts < 1
+ * or n_local < 1 is SLS_ERR_INVALID. */
+int sls_line_maximize(sls_path* p, int q, const double* baseline, const double* anchor, const double* starts, int S_starts,
+                      int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out,
+                      long* idx_out, double* x_stars, double* y_stars);
+
 /* ---- multi-GPU maximisation ------------------------------------------------------------------------------
  * FindGlobalSolution's multi-start loop (src/acquisition-function.cpp:121-153) shards over its starts: the iterations share
  * only the const regressor (:125-141).  Every GPU holds a replica of the fitted state, runs a contiguous slice of the starts
@@ -585,6 +631,8 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
  * "qnei" (the same two kernels with a per-draw baseline: two launches per pass of sls_qnei_eval / per pass and round of
  * sls_qnei_maximize; every other stage counts as under qEUBO) and "path_max" (the column reduction of sls_path_max_over_points, one
  * launch per pass; its values count under "cross_gram", "path_prior", "qeubo_data_gemm");
+ * "line" (line_expand and line_fold: two launches per pass of sls_line_eval -- one without a gradient -- / per pass and round of
+ * sls_line_maximize; the pass between them counts as under qEUBO / qNEI);
  * "potrf_fallbacks": launches = how often a single-launch factorisation gave up and was recomputed. */
 int sls_prof_enable(sls_ctx* ctx, int on);
 int sls_prof_reset(sls_ctx* ctx);

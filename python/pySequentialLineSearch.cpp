@@ -232,7 +232,26 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
                  const auto q     = s.MaximizeNoisyExpectedImprovement(num_points, baseline, starts, num_local_search_iters, &value);
                  return std::make_pair(q, value);
              },
-             "num_points"_a, "baseline"_a, "starts"_a, "num_local_search_iters"_a = 50);
+             "num_points"_a, "baseline"_a, "starts"_a, "num_local_search_iters"_a = 50)
+        // the expected utility of the best slider position on the draws: (values, gradient for the first end, for the second, win
+        // counts num_positions x M); maximize_... ((end_0, end_1), value)
+        .def("calc_expected_utilities_of_best_slider_position",
+             [](const PosteriorFunctionSamples& s, const MatrixXd& ends_a, const MatrixXd& ends_b, int num_positions) {
+                 MatrixXd        ga, gb;
+                 Eigen::MatrixXi wins;
+                 const VectorXd  v = s.CalcExpectedUtilitiesOfBestSliderPosition(ends_a, ends_b, num_positions, &ga, &gb, &wins);
+                 return std::make_tuple(v, ga, gb, wins);
+             },
+             "ends_a"_a, "ends_b"_a, "num_positions"_a = 9)
+        .def("maximize_expected_utility_of_best_slider_position",
+             [](const PosteriorFunctionSamples& s, int num_positions, const MatrixXd& starts, unsigned num_local_search_iters,
+                const VectorXd& anchor) {
+                 double     value = 0.0;
+                 const auto ends  = s.MaximizeExpectedUtilityOfBestSliderPosition(num_positions, starts, num_local_search_iters,
+                                                                                 anchor.size() != 0 ? &anchor : nullptr, nullptr, &value);
+                 return std::make_pair(ends, value);
+             },
+             "num_positions"_a, "starts"_a, "num_local_search_iters"_a = 50, "anchor"_a = VectorXd());
     m.def("sample_posterior_functions",
           [](const Regressor& r, int num_draws, unsigned long long seed, int num_frequencies) {
               return r.SamplePosteriorFunctions(num_draws, seed, num_frequencies);
@@ -281,6 +300,29 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
           "regressor"_a, "num_points"_a, "starts"_a, "num_draws"_a = 256, "num_local_search_iters"_a = 50, "seed"_a = 0ULL,
           "num_frequencies"_a = 2048);
 
+    // the next slider by the expected utility of its best position (acquisition-function.hpp): ((end_0, end_1), value); an empty anchor
+    // leaves both ends free
+    m.def("find_next_slider_by_expected_utility",
+          [](const Regressor& r, const VectorXd& anchor, int num_positions, unsigned num_draws, unsigned num_global_search_iters,
+             unsigned num_local_search_iters, unsigned long long seed, int num_frequencies) {
+              double     value = 0.0;
+              const auto ends  = acquisition_func::FindNextSliderByExpectedUtility(
+                  r, anchor, num_positions, num_draws, num_global_search_iters, num_local_search_iters, seed, num_frequencies, &value);
+              return std::make_pair(ends, value);
+          },
+          "regressor"_a, "anchor"_a = VectorXd(), "num_positions"_a = 9, "num_draws"_a = 256, "num_global_search_iters"_a = 100,
+          "num_local_search_iters"_a = 50, "seed"_a = 0ULL, "num_frequencies"_a = 2048);
+    m.def("find_next_slider_by_expected_utility_from_starts",
+          [](const Regressor& r, const VectorXd& anchor, const MatrixXd& starts, int num_positions, unsigned num_draws,
+             unsigned num_local_search_iters, unsigned long long seed, int num_frequencies) {
+              double     value = 0.0;
+              const auto ends  = acquisition_func::FindNextSliderByExpectedUtilityFromStarts(
+                  r, anchor, starts, num_positions, num_draws, num_local_search_iters, seed, num_frequencies, &value);
+              return std::make_pair(ends, value);
+          },
+          "regressor"_a, "anchor"_a, "starts"_a, "num_positions"_a = 9, "num_draws"_a = 256, "num_local_search_iters"_a = 50,
+          "seed"_a = 0ULL, "num_frequencies"_a = 2048);
+
     // DIRECT, then one L-BFGS from its result (acquisition_func::FindNextPointDirect) on such a regressor: (point, value)
     m.def("find_next_point_direct",
           [](const Regressor& r, unsigned num_global_search_iters, unsigned num_local_search_iters, AcquisitionFuncType func_type,
@@ -313,6 +355,9 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
              static_cast<void (SequentialLineSearchOptimizer::*)(const double, const int, const int, const int)>(
                  &SequentialLineSearchOptimizer::SubmitFeedbackData),
              "slider_position"_a, "num_map_estimation_iters"_a, "num_global_search_iters"_a, "num_local_search_iters"_a)
+        .def("submit_feedback_data_by_expected_utility", &SequentialLineSearchOptimizer::SubmitFeedbackDataByExpectedUtility,
+             "slider_position"_a, "num_positions"_a = 9, "num_draws"_a = 256, "num_map_estimation_iters"_a = 100,
+             "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50, "seed"_a = 0ULL, "num_frequencies"_a = 2048)
         .def("get_slider_ends", &SequentialLineSearchOptimizer::GetSliderEnds)
         .def("calc_point_from_slider_position", &SequentialLineSearchOptimizer::CalcPointFromSliderPosition, "slider_position"_a)
         .def("get_maximizer", &SequentialLineSearchOptimizer::GetMaximizer)

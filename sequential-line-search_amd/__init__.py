@@ -66,6 +66,7 @@ EXPORTS = [
     "sls_mes_terms", "sls_mes_eval", "sls_mes_maximize", "sls_logei_terms",
     "sls_eubo_eval", "sls_eubo_maximize", "sls_qeubo_eval", "sls_qeubo_maximize",
     "sls_path_max_over_points", "sls_qnei_eval", "sls_qnei_maximize",
+    "sls_line_eval", "sls_line_maximize",
 ]
 
 
@@ -375,6 +376,7 @@ class GP:
 
 
 QEUBO_MAX_OPTIONS = 16   # SLS_QEUBO_MAX_OPTIONS
+LINE_MIN_POSITIONS = 2   # SLS_LINE_MIN_POSITIONS
 
 
 class PathSamples:
@@ -522,6 +524,50 @@ class PathSamples:
         _ck(lib().sls_qnei_maximize(self.h, q, _p(t), _p(starts), S, int(n_local), C.byref(opts) if opts is not None else None,
                                     C.c_long(offset), _p(x), C.byref(val), C.byref(idx), _p(xs) if want_all else None,
                                     _p(ys) if want_all else None))
+        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+
+    def _line_args(self, who, q, anchor, baseline, block, what):
+        q = int(q)
+        if not LINE_MIN_POSITIONS <= q <= QEUBO_MAX_OPTIONS:
+            raise SlsError(f"{who}: q = {q} ({LINE_MIN_POSITIONS} .. {QEUBO_MAX_OPTIONS})")
+        a = None
+        if anchor is not None:
+            a = np.ascontiguousarray(np.asarray(anchor, dtype=np.float64))
+            if a.shape != (self.D,):
+                raise SlsError(f"{who}: anchor must hold D = {self.D} values, got shape {a.shape}")
+        rows = self.D if a is not None else 2 * self.D
+        if block.ndim != 2 or block.shape[0] != rows:
+            raise SlsError(f"{who}: {what} must be {'D' if a is not None else '2D'} x M = {rows} x M, got {block.shape}")
+        t = self._baseline(who, baseline) if baseline is not None else None
+        return q, a, t, rows
+
+    def line_eval(self, lines, q, anchor=None, baseline=None, want_grad=True, want_wins=False):
+        """Expected utility of the best of q grid positions on the slider from a to b (sls_line_eval) at the columns of lines (2D x M:
+        rows 0..D-1 = a, D..2D-1 = b; with anchor (D,) every line starts there and lines is D x M = b).  With baseline (n_draws,) the
+        qNEI form.  Values (M,), then with want_grad the gradient (2D or D, M), then with want_wins the win counts (q, M) int32."""
+        lines = _f(lines)
+        q, a, t, rows = self._line_args("line_eval", q, anchor, baseline, lines, "lines")
+        M = lines.shape[1]
+        val = np.empty(M)
+        grad = np.empty((rows, M), order="F") if want_grad else None
+        wins = np.zeros((q, M), dtype=np.int32, order="F") if want_wins else None
+        _ck(lib().sls_line_eval(self.h, q, _p(t) if t is not None else None, _p(a) if a is not None else None, _p(lines), M, _p(val),
+                                _p(grad) if want_grad else None, wins.ctypes.data_as(C.POINTER(C.c_int)) if want_wins else None))
+        out = (val,) + ((grad,) if want_grad else ()) + ((wins,) if want_wins else ())
+        return out if len(out) > 1 else val
+
+    def line_maximize(self, starts, q, n_local, anchor=None, baseline=None, offset=0, want_all=True, opts=None):
+        """acq_maximize over the ends of a slider with the objective of line_eval (sls_line_maximize): starts 2D x S (D x S with
+        anchor), x and x_stars have as many rows.  GP.last_stats() of the path's handle reports the run."""
+        starts = _f(starts)
+        q, a, t, rows = self._line_args("line_maximize", q, anchor, baseline, starts, "starts")
+        S = starts.shape[1]
+        x, val, idx = np.empty(rows), C.c_double(), C.c_long()
+        xs = np.empty((rows, S), order="F") if want_all else None
+        ys = np.empty(S) if want_all else None
+        _ck(lib().sls_line_maximize(self.h, q, _p(t) if t is not None else None, _p(a) if a is not None else None, _p(starts), S,
+                                    int(n_local), C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val),
+                                    C.byref(idx), _p(xs) if want_all else None, _p(ys) if want_all else None))
         return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
 
 

@@ -572,3 +572,130 @@ extern "C" int sls_qnei_maximize(sls_path* p, int q, const double* baseline, con
     return set_maximize("sls_qnei_maximize", p, q, baseline, true, starts, S_starts, n_local, opts, start_index_offset, x_out, val_out,
                         idx_out, x_stars, y_stars);
 }
+
+// ---- expected utility of the best slider position on the draws (include/sls_hip.h) ------------------------------------------
+namespace {
+
+struct LineWs {
+    QeuboWs q;
+    DBuf sets, sgrad;   // the expanded sets and their gradient of ONE pass (qD x pass), never of the whole call
+};
+
+// Line EUBO (qNEI form with base) at M lines, candidate-major lines[n + r*ld] (2D rows, or D rows with the device D-vector anchor).
+// val[n], grad[n + r*ldo] (2D / D rows), wins[n + i*ldw]; each may be nullptr.  Per pass of the qEUBO sizing: expand, ONE pass of
+// qeubo_eval_device, fold.  A pass's bits do not depend on the split, so driving the chunks here only bounds the two workspaces.
+void line_eval_device(sls_path* p, const GpView& g, LineWs& w, int q, const double* base, const double* anchor, const double* lines,
+                      long ld, int M, double* val, double* grad, long ldo, int* wins, long ldw) {
+    sls_ctx* c = g.ctx;
+    const int D = g.D;
+    const int pass_max = std::min(round_up(M, 128), qeubo_sets_per_pass(c, q, g.Np, p->Fp, p->Rp));
+    w.sets.ensure((size_t)q * D * pass_max);
+    if (grad) w.sgrad.ensure((size_t)q * D * pass_max);
+    for (int s0 = 0; s0 < M; s0 += pass_max) {
+        const int sc = std::min(pass_max, M - s0);
+        {
+            ProfScope ps(c, "line");
+            launch_line_expand(c->stream, sc, D, q, lines + s0, ld, anchor, w.sets.p, pass_max);
+        }
+        qeubo_eval_device(p, g, w.q, q, base, w.sets.p, pass_max, sc, val ? val + s0 : nullptr, grad ? w.sgrad.p : nullptr, pass_max,
+                          wins ? wins + s0 : nullptr, ldw);
+        if (grad) {
+            ProfScope ps(c, "line");
+            launch_line_fold(c->stream, sc, D, q, anchor != nullptr, w.sgrad.p, pass_max, grad + s0, ldo);
+        }
+    }
+}
+
+void require_line_args(const char* who, const sls_path* p, int q, const double* baseline, const double* anchor) {
+    SLS_REQUIRE(p != nullptr, "%s: p is NULL", who);
+    SLS_REQUIRE(q >= SLS_LINE_MIN_POSITIONS && q <= SLS_QEUBO_MAX_OPTIONS, "%s: q = %d (%d .. %d)", who, q, SLS_LINE_MIN_POSITIONS,
+                SLS_QEUBO_MAX_OPTIONS);
+    if (baseline) require_finite_baseline(who, p, baseline);
+    if (anchor)
+        for (int d = 0; d < p->D; ++d) SLS_REQUIRE(std::isfinite(anchor[d]), "%s: anchor[%d] is not finite", who, d);
+}
+
+}  // namespace
+
+extern "C" int sls_line_eval(sls_path* p, int q, const double* baseline, const double* anchor, const double* lines, int M, double* val,
+                             double* grad, int* wins) {
+    SLS_TRY
+    const char* who = "sls_line_eval";
+    require_line_args(who, p, q, baseline, anchor);
+    SLS_REQUIRE(M >= 0, "%s: M = %d", who, M);
+    SLS_REQUIRE(lines != nullptr, "%s: lines is NULL", who);
+    GpReadCall call(p->gp, p->generation, who);
+    if (M == 0) return SLS_OK;
+    const GpView& g = call.g;
+    sls_ctx* c = g.ctx;
+    const int D = g.D, nvar = anchor ? D : 2 * D, Mp = round_up(M, 128);
+    const std::vector<double> t = host_to_cm(lines, nvar, M, Mp);   // alive until the synchronisation below
+    DBuf raw, out, wb, tb, ab;
+    raw.ensure(t.size());
+    h2d(c, raw.p, t.data(), t.size());
+    if (baseline) {
+        tb.ensure((size_t)p->n_draws);
+        h2d(c, tb.p, baseline, (size_t)p->n_draws);
+    }
+    if (anchor) {
+        ab.ensure((size_t)D);
+        h2d(c, ab.p, anchor, (size_t)D);
+    }
+    out.ensure((size_t)Mp * (1 + nvar));
+    int* d_wins = wins ? ints(wb, (size_t)Mp * q) : nullptr;
+    LineWs ws;
+    line_eval_device(p, g, ws, q, tb.p, ab.p, raw.p, Mp, M, out.p, grad ? out.p + Mp : nullptr, Mp, d_wins, Mp);
+    std::vector<double> oh((size_t)Mp * (grad ? 1 + nvar : 1));
+    std::vector<int> wh(wins ? (size_t)Mp * q : 0);
+    d2h(c, oh.data(), out.p, oh.size());
+    if (wins) SLS_HIP(hipMemcpyAsync(wh.data(), d_wins, wh.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    SLS_HIP(hipStreamSynchronize(c->stream));
+    cm_to_host(oh.data(), Mp, 1, M, val);
+    cm_to_host(oh.data() + Mp, Mp, nvar, M, grad);
+    cm_to_host(wh.data(), Mp, q, M, wins);
+    SLS_CATCH
+}
+
+extern "C" int sls_line_maximize(sls_path* p, int q, const double* baseline, const double* anchor, const double* starts, int S_starts,
+                                 int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out,
+                                 long* idx_out, double* x_stars, double* y_stars) {
+    SLS_TRY
+    const char* who = "sls_line_maximize";
+    SLS_REQUIRE(p && starts, "%s: NULL argument", who);
+    require_line_args(who, p, q, baseline, anchor);
+    GpReadCall call(p->gp, p->generation, who);
+    const GpView& g = call.g;
+    sls_ctx* c = g.ctx;
+    // the maximiser of sls_qeubo_maximize over the ENDS: one start = one line, 2D variables (D with the anchor) whatever q is
+    const int S = S_starts, D = g.D, nvar = anchor ? D : 2 * D;
+    LbfgsWs lb;
+    LineWs ws;
+    MultistartRun r = maximize_begin(who, p->gp, lb, opts, S, n_local, nvar);
+    DBuf sd, best, tb, ab;
+    sd.ensure((size_t)nvar * S);
+    best.ensure((size_t)8 + nvar);
+    h2d(c, sd.p, starts, (size_t)nvar * S);
+    if (baseline) {   // both once, before the first round
+        tb.ensure((size_t)p->n_draws);
+        h2d(c, tb.p, baseline, (size_t)p->n_draws);
+    }
+    if (anchor) {
+        ab.ensure((size_t)D);
+        h2d(c, ab.p, anchor, (size_t)D);
+    }
+    LockstepStats ls;
+    lockstep_rounds(c, r.st, lb, sd.p, S, n_local,
+                    [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
+                        line_eval_device(p, g, ws, q, tb.p, ab.p, trial, ld, nlive, val, grad, ld, nullptr, 0);
+                    },
+                    &ls);
+    std::vector<double> bh((size_t)8 + nvar), pageable;
+    auto fetch = [&](const double* dev, size_t n) {
+        pageable.resize(n);
+        d2h(c, pageable.data(), dev, n);
+        SLS_HIP(hipStreamSynchronize(c->stream));
+        return pageable.data();
+    };
+    maximize_finish(c, r, ls, BestBlock{best.p, bh.data(), true}, fetch, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars);
+    SLS_CATCH
+}

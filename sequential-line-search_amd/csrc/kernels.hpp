@@ -529,6 +529,18 @@ void launch_qeubo_finish(hipStream_t s, int nsets, int Sp, int q, int D, int S, 
 // greater.  A NaN in the column gives (NaN, -1), which later passes leave.
 void launch_path_colmax(hipStream_t s, const double* V, long ldv, int rows, int n_draws, int base, double* t, int* arg);
 
+// ---- kernels_line.hip: expected utility of the best slider position (sls_line_*) ------------------------------------------
+// A line is its ends (a, b); position i of q is x_i = u_i a + t_i b with u_i = (q-1-i)/(q-1), t_i = i/(q-1) computed on the device (one
+// division each; two products and one sum per coordinate, never fused).  trial[n + r*ld] is the candidate-major line block: rows
+// 0..D-1 = a and D..2D-1 = b (anchor == nullptr), or D rows = b with a = anchor[d] (device, D doubles).
+// sets[n + (i*D + d)*lds] = x_i[d] for n < nlines: the block qeubo_eval_device reads.
+void launch_line_expand(hipStream_t s, int nlines, int D, int q, const double* trial, long ld, const double* anchor, double* sets,
+                        long lds);
+// grad_a = sum_i u_i g_i (from zero, increasing i), grad_b = sum_i t_i g_i (from zero, DECREASING i: the mirror image of grad_a's order)
+// of the set gradient sgrad[n + (i*D + d)*lds], product and sum never fused.  grad[n + d*ldo] = grad_a and grad[n + (D + d)*ldo] =
+// grad_b; anchored: grad[n + d*ldo] = grad_b alone.
+void launch_line_fold(hipStream_t s, int nlines, int D, int q, bool anchored, const double* sgrad, long lds, double* grad, long ldo);
+
 // ---- kernels_map.hip -----------------------------------------------------------
 // MAP-gradient weights (replaces the (D+1) x N x N tensor of CalcLargeKYThetaDerivative, src/regressor.cpp:110-134):
 // G[j + k*Np] = 1/2 (alpha_j alpha_k - Kinv_jk) c_jk  (0 in the padding);  wk_part[tile] = sum over the tile of

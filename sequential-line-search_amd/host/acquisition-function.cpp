@@ -548,4 +548,30 @@ namespace sequential_line_search
             regressor, num_points, SeededStarts(num_points * regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed),
             num_draws, num_local_search_iters, seed, num_frequencies, value);
     }
+    // ---- the next slider by the expected utility of its best position (include/sls_hip.h sls_line_*) ----
+    std::pair<VectorXd, VectorXd> acquisition_func::FindNextSliderByExpectedUtilityFromStarts(
+        const Regressor& regressor, const VectorXd& anchor, const MatrixXd& starts, const int num_positions, const unsigned num_draws,
+        const unsigned num_local_search_iters, const unsigned long long seed, const int num_frequencies, double* value)
+    {
+        RequireDeviceHandleForExpectedUtility(regressor);
+        if (anchor.size() != 0 && anchor.size() != static_cast<long>(regressor.GetNumDims()))
+            throw std::invalid_argument("FindNextSliderByExpectedUtilityFromStarts: the anchor must be empty or hold D values");
+        const PosteriorFunctionSamples draws =
+            regressor.SamplePosteriorFunctions(static_cast<int>(std::max(1u, num_draws)), seed, num_frequencies);
+        return draws.MaximizeExpectedUtilityOfBestSliderPosition(num_positions, starts, num_local_search_iters,
+                                                                 anchor.size() != 0 ? &anchor : nullptr, nullptr, value);
+    }
+
+    std::pair<VectorXd, VectorXd> acquisition_func::FindNextSliderByExpectedUtility(
+        const Regressor& regressor, const VectorXd& anchor, const int num_positions, const unsigned num_draws,
+        const unsigned num_global_search_iters, const unsigned num_local_search_iters, const unsigned long long seed,
+        const int num_frequencies, double* value)
+    {
+        RequireDeviceHandleForExpectedUtility(regressor);
+        if (num_positions < SLS_LINE_MIN_POSITIONS || num_positions > SLS_QEUBO_MAX_OPTIONS)
+            throw std::invalid_argument("FindNextSliderByExpectedUtility: 2 .. 16 positions");
+        const unsigned nvar = (anchor.size() != 0 ? 1u : 2u) * regressor.GetNumDims();
+        return FindNextSliderByExpectedUtilityFromStarts(regressor, anchor, SeededStarts(nvar, std::max(1u, num_global_search_iters), seed),
+                                                         num_positions, num_draws, num_local_search_iters, seed, num_frequencies, value);
+    }
 } // namespace sequential_line_search

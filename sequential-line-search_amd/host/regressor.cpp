@@ -331,6 +331,70 @@ namespace sequential_line_search
         return MaximizeSetCriterion("MaximizeNoisyExpectedImprovement", num_points, &baseline, starts, num_local_search_iters, value);
     }
 
+    VectorXd PosteriorFunctionSamples::CalcExpectedUtilitiesOfBestSliderPosition(const MatrixXd& ends_a, const MatrixXd& ends_b,
+                                                                                 int num_positions, MatrixXd* grad_a, MatrixXd* grad_b,
+                                                                                 Eigen::MatrixXi* win_counts, const VectorXd* baseline) const
+    {
+        const std::string name = "PosteriorFunctionSamples::CalcExpectedUtilitiesOfBestSliderPosition";
+        if (num_positions < SLS_LINE_MIN_POSITIONS || num_positions > SLS_QEUBO_MAX_OPTIONS)
+            throw std::invalid_argument(name + ": 2 .. 16 positions");
+        if (baseline && baseline->size() != m_num_draws) throw std::invalid_argument(name + ": the baseline must hold one value per draw");
+        const long D = m_num_dims, M = ends_a.cols();
+        if (ends_a.rows() != D || ends_b.rows() != D || ends_b.cols() != M)
+            throw std::invalid_argument(name + ": ends_a and ends_b must both be D x M");
+        MatrixXd lines(2 * D, M);
+        for (long m = 0; m < M; ++m)
+            for (long d = 0; d < D; ++d)
+            {
+                lines(d, m)     = ends_a(d, m);
+                lines(D + d, m) = ends_b(d, m);
+            }
+        VectorXd   v         = VectorXd::Zero(M);
+        const bool want_grad = grad_a || grad_b;
+        MatrixXd   g(want_grad ? 2 * D : 0, want_grad ? M : 0);
+        if (win_counts) *win_counts = Eigen::MatrixXi::Zero(num_positions, M);
+        device::Check(sls_line_eval(m_path, num_positions, baseline ? baseline->data() : nullptr, nullptr, lines.data(),
+                                    static_cast<int>(M), v.data(), want_grad ? g.data() : nullptr,
+                                    win_counts ? win_counts->data() : nullptr),
+                      "sls_line_eval");
+        for (int o = 0; o < 2; ++o)
+        {
+            MatrixXd* out = o == 0 ? grad_a : grad_b;
+            if (!out) continue;
+            *out = MatrixXd(D, M);
+            for (long m = 0; m < M; ++m)
+                for (long d = 0; d < D; ++d) (*out)(d, m) = g(o * D + d, m);
+        }
+        return v;
+    }
+
+    std::pair<VectorXd, VectorXd> PosteriorFunctionSamples::MaximizeExpectedUtilityOfBestSliderPosition(
+        int num_positions, const MatrixXd& starts, unsigned num_local_search_iters, const VectorXd* anchor, const VectorXd* baseline,
+        double* value) const
+    {
+        const std::string name = "PosteriorFunctionSamples::MaximizeExpectedUtilityOfBestSliderPosition";
+        if (num_positions < SLS_LINE_MIN_POSITIONS || num_positions > SLS_QEUBO_MAX_OPTIONS)
+            throw std::invalid_argument(name + ": 2 .. 16 positions");
+        if (baseline && baseline->size() != m_num_draws) throw std::invalid_argument(name + ": the baseline must hold one value per draw");
+        const long D = m_num_dims, nvar = anchor ? D : 2 * D;
+        if (anchor && anchor->size() != D) throw std::invalid_argument(name + ": the anchor must hold D values");
+        if (starts.rows() != nvar || starts.cols() < 1)
+            throw std::invalid_argument(name + ": starts must be 2D x S (D x S with an anchor) with S >= 1");
+        sls_lbfgs_opts o;
+        sls_lbfgs_default_opts(&o);
+        optim::SearchTolerances(&o.ftol_rel, &o.xtol_rel);   // the acquisition maximiser's local search tolerances
+        VectorXd x(nvar);
+        double   v   = 0.0;
+        long     idx = 0;
+        device::Check(sls_line_maximize(m_path, num_positions, baseline ? baseline->data() : nullptr, anchor ? anchor->data() : nullptr,
+                                        starts.data(), static_cast<int>(starts.cols()),
+                                        std::max(1, static_cast<int>(num_local_search_iters)), &o, 0, x.data(), &v, &idx, nullptr, nullptr),
+                      "sls_line_maximize");
+        if (value) *value = v;
+        if (anchor) return std::make_pair(*anchor, x);
+        return std::make_pair(VectorXd(x.segment(0, D)), VectorXd(x.segment(D, D)));
+    }
+
     MatrixXd Regressor::SamplePosterior(const MatrixXd& Xs, int num_samples, unsigned long long seed, double* jitter_used) const
     {
         sls_gp* h = GetDeviceHandle();

@@ -2,6 +2,7 @@
 #include <sequential-line-search/acquisition-function.hpp>
 #include <sequential-line-search/preference-data-manager.hpp>
 #include <sequential-line-search/preference-regressor.hpp>
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -101,6 +102,34 @@ namespace sequential_line_search
                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
 
         m_slider = std::make_shared<Slider>(x_plus, x_acquisition, m_use_slider_enlargement);
+    }
+
+    // SubmitFeedbackData up to and including x_plus; the far end by the expected utility of the best slider position
+    void SequentialLineSearchOptimizer::SubmitFeedbackDataByExpectedUtility(const double slider_position, const int num_positions,
+                                                                            const int num_draws, const int num_map_estimation_iters,
+                                                                            const int num_global_search_iters,
+                                                                            const int num_local_search_iters,
+                                                                            const unsigned long long seed, const int num_frequencies)
+    {
+        const VectorXd x_chosen   = CalcPointFromSliderPosition(slider_position);
+        const VectorXd x_prev_max = m_slider->original_end_0;
+        const VectorXd x_prev_ei  = m_slider->original_end_1;
+
+        m_data->AddNewPoints(x_chosen, {x_prev_max, x_prev_ei}, true);
+
+        m_regressor = std::make_shared<PreferenceRegressor>(m_data->GetX(), m_data->GetD(), m_use_map_hyperparams, m_kernel_signal_var,
+                                                            m_kernel_length_scale, m_noise_level, m_kernel_hyperparams_prior_var,
+                                                            m_btl_scale, num_map_estimation_iters, m_kernel_type);
+
+        const VectorXd x_plus = (m_current_best_selection_strategy == CurrentBestSelectionStrategy::LargestExpectValue)
+                                    ? m_regressor->FindArgMax()
+                                    : x_chosen;
+        const std::pair<VectorXd, VectorXd> ends = acquisition_func::FindNextSliderByExpectedUtility(
+            *m_regressor, x_plus, num_positions, static_cast<unsigned>(std::max(1, num_draws)),
+            static_cast<unsigned>(std::max(1, num_global_search_iters)), static_cast<unsigned>(std::max(1, num_local_search_iters)), seed,
+            num_frequencies);
+
+        m_slider = std::make_shared<Slider>(x_plus, ends.second, m_use_slider_enlargement);
     }
 
     std::pair<VectorXd, VectorXd> SequentialLineSearchOptimizer::GetSliderEnds() const { return {m_slider->end_0, m_slider->end_1}; }
