@@ -1506,6 +1506,10 @@ static void eval_pairs(sls_gp* g, const double* xr, long ldr, int S, double* val
                 f.Gs[o] = Gs[o]; f.Gm[o] = Gm[o]; f.XsT[o] = XsT[o];
             }
             f.kw_part = kw_part[0]; f.kw_solve_part = kw_solve; f.inv_ell = g->inv_ell.p; f.a = g->a;
+            if (g->gram_direct) {   // the pair's own prior covariance from the raw coordinate differences as well
+                for (int o = 0; o < 2; ++o) f.xr[o] = xr + (size_t)o * D * ldr + s0;
+                f.ldr = ldr;
+            }
             f.ldo = ldo;
             f.val = val ? val + s0 : nullptr;
             f.grad = grad ? grad + s0 : nullptr;

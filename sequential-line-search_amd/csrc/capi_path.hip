@@ -45,10 +45,12 @@ int chunk_of(int Np, int Fp) { return std::max(128, std::min(16384, ((1 << 26) /
 struct EvalWs {
     // Pm and G share one block: G = Pm + Cp Np (same leading dimension), so that [Pm | G] is ONE operand of the gradient contraction
     // against B2 = [X~ ; Om] (k-stacked, built once per call)
-    DBuf XsT, ns, Ks, Cs, PG, csum, vpart, Gt, B2, Gpart;
+    // Gd: the data term's gradient contraction over raw coordinate differences, for handles beyond the guard of the norm expansion
+    DBuf XsT, ns, Ks, Cs, PG, csum, vpart, Gt, B2, Gpart, Gd;
     bool b2_ready = false;
     void ensure(const sls_path* p, const GpView& g, int chunk) {
         const size_t C = chunk, Np = g.Np;
+        if (g.gram_direct) Gd.ensure(C * g.Dcols);
         XsT.ensure(C * g.Dcols);
         ns.ensure(C);
         Ks.ensure(C * Np);
@@ -75,7 +77,7 @@ void path_eval_device(sls_path* p, const GpView& g, EvalWs& w, const double* xr,
     KernelSpec ks{g.kernel, g.a};
     double* Cs = g.kernel == SLS_KERNEL_ARD_MATERN52 ? w.Cs.p : w.Ks.p;
     const long Kc = (long)Np + Fp;   // depth of the gradient contraction [Pm | G] [X~ ; Om]
-    if (grad && !w.b2_ready) {
+    if (grad && !g.gram_direct && !w.b2_ready) {
         w.B2.ensure((size_t)Kc * g.Dcols);
         SLS_HIP(hipMemcpy2DAsync(w.B2.p, Kc * 8, g.XT, (size_t)Np * 8, (size_t)Np * 8, g.Dcols, hipMemcpyDeviceToDevice, c->stream));
         SLS_HIP(hipMemcpy2DAsync(w.B2.p + Np, Kc * 8, p->Om.p, (size_t)Fp * 8, (size_t)Fp * 8, g.Dcols, hipMemcpyDeviceToDevice, c->stream));
@@ -118,7 +120,25 @@ void path_eval_device(sls_path* p, const GpView& g, EvalWs& w, const double* xr,
             launch_path_data(c->stream, w.Ks.p, Cs, Cp, g.N, Np, p->V.p, Np, draw + s0, 0, 0, sc, val + s0, grad ? Pm : nullptr,
                              w.csum.p);
         }
-        if (grad) {
+        if (grad && g.gram_direct) {
+            // Beyond the guard: Gt = G Om alone (Fp deep) and the data term over raw coordinate differences (grad_direct).  In the one
+            // contraction below the accumulator carries x~* sum_i c_i (|x~| ~ 1 / (2 l)) through the Fp additions of the prior and
+            // loses it again only in path_grad: eps |x~| |csum| sqrt(Fp) / l, 20 times the rounding of the terms themselves at
+            // F = 16384, l = 3e-3.
+            {
+                ProfScope ps(c, "path_grad_gemm");
+                double* part = nullptr;
+                if (D <= 64 && grad_gemm_wants_split(Cp)) {
+                    w.Gpart.ensure((size_t)8 * Cp * 64);
+                    part = w.Gpart.p;
+                }
+                launch_grad_gemm(c->stream, G, nullptr, Cp, Cp, p->Om.p, nullptr, Fp, Fp, D <= 64 ? -g.Dcols : g.Dcols, w.Gt.p, nullptr, part, 1);
+                launch_grad_direct(c->stream, Pm, nullptr, Cp, Cp, point_major ? xr + (size_t)s0 * D : xr + s0, point_major ? D : 1,
+                                   point_major ? 1 : ldr, sc, g.X, D, g.inv_ell, g.N, nullptr, w.Gd.p, nullptr);
+            }
+            ProfScope ps(c, "path_data");
+            launch_path_grad_direct(c->stream, sc, D, Cp, w.Gt.p, w.Gd.p, g.inv_ell, grad + s0, ldgrad);
+        } else if (grad) {
             {
                 // Gt = [Pm | G] [X~ ; Om]: X~^T c of the data term plus the prior's gradient in scaled coordinates, ONE MFMA contraction
                 // (Np + Fp deep) on grad_gemm's P-pass alone (fixed quarter order: a candidate's bits do not depend on the launch)
@@ -293,7 +313,7 @@ int qeubo_sets_per_pass(const sls_ctx* c, int q, int Np, int Fp, int Rp) {
 }
 
 struct QeuboWs {
-    DBuf XsT, ns, Ks, Cs, PG, csum, vpart, Gt, B2, Gpart, VM, Wbar, Vbar, sum, fbar, gpt, badb, identb;
+    DBuf XsT, ns, Ks, Cs, PG, csum, vpart, Gt, B2, Gpart, Gd, VM, Wbar, Vbar, sum, fbar, gpt, badb, identb;
     bool b2_ready = false;
     int* bad = nullptr;     // one flag per set of the pass
     int* ident = nullptr;   // ident[j] = j: point j is evaluated under aggregated column j
@@ -311,6 +331,7 @@ struct QeuboWs {
         csum.ensure(P);
         vpart.ensure(P * (Fp / 128));
         Gt.ensure(P * g.Dcols);
+        if (g.gram_direct) Gd.ensure(P * g.Dcols);
         Wbar.ensure(2 * Fp * P);
         Vbar.ensure(Np * P);
         sum.ensure(Sp);
@@ -367,7 +388,7 @@ void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const do
     w.ensure(c, p, g, q * pass_max, pass_max);
     double* Cs = g.kernel == SLS_KERNEL_ARD_MATERN52 ? w.Cs.p : w.Ks.p;
     const long Kc = (long)Np + Fp;
-    if (!w.b2_ready) {
+    if (!g.gram_direct && !w.b2_ready) {
         w.B2.ensure((size_t)Kc * g.Dcols);
         SLS_HIP(hipMemcpy2DAsync(w.B2.p, Kc * 8, g.XT, (size_t)Np * 8, (size_t)Np * 8, g.Dcols, hipMemcpyDeviceToDevice, c->stream));
         SLS_HIP(hipMemcpy2DAsync(w.B2.p + Np, Kc * 8, p->Om.p, (size_t)Fp * 8, (size_t)Fp * 8, g.Dcols, hipMemcpyDeviceToDevice, c->stream));
@@ -415,12 +436,20 @@ void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const do
                 w.Gpart.ensure((size_t)8 * Pp * 64);
                 part = w.Gpart.p;
             }
-            launch_grad_gemm(c->stream, Pm, nullptr, Pp, Pp, w.B2.p, nullptr, Kc, (int)Kc, D <= 64 ? -g.Dcols : g.Dcols, w.Gt.p, nullptr, part,
-                             1);
+            if (g.gram_direct) {   // as in path_eval_device: G Om alone, the data term over raw coordinate differences per option
+                launch_grad_gemm(c->stream, G, nullptr, Pp, Pp, p->Om.p, nullptr, Fp, Fp, D <= 64 ? -g.Dcols : g.Dcols, w.Gt.p, nullptr, part, 1);
+                for (int i = 0; i < q; ++i)
+                    launch_grad_direct(c->stream, Pm + (size_t)i * Sp, nullptr, Pp, Sp, xr + (size_t)i * D * ldr + s0, 1, ldr, sc, g.X, D,
+                                       g.inv_ell, g.N, nullptr, w.Gd.p + (size_t)i * Sp, nullptr);
+            } else {
+                launch_grad_gemm(c->stream, Pm, nullptr, Pp, Pp, w.B2.p, nullptr, Kc, (int)Kc, D <= 64 ? -g.Dcols : g.Dcols, w.Gt.p, nullptr,
+                                 part, 1);
+            }
         }
         {
             ProfScope ps(c, "path_data");
-            launch_path_grad(c->stream, Pp, D, Pp, w.Gt.p, w.XsT.p, w.csum.p, g.inv_ell, w.gpt.p, Pp);
+            if (g.gram_direct) launch_path_grad_direct(c->stream, Pp, D, Pp, w.Gt.p, w.Gd.p, g.inv_ell, w.gpt.p, Pp);
+            else launch_path_grad(c->stream, Pp, D, Pp, w.Gt.p, w.XsT.p, w.csum.p, g.inv_ell, w.gpt.p, Pp);
         }
         {
             ProfScope ps(c, scope);

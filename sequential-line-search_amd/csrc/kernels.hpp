@@ -131,6 +131,7 @@ void launch_cross_gram_direct(hipStream_t s, const double* xr, long sn, long sd,
 
 // gram_direct_form: the gradient contractions Gs / Gm of launch_grad_gemm (kernels_acq.hip) over the differences (x_i - x*_n) / l of the
 // raw coordinates instead of x~_i alone; the finalize kernels are then given ca_part = cw_part = 0 (their x~* ca, x~* cw terms vanish).
+// Gm == nullptr: Gs alone (Cs and alpha are not read).
 void launch_grad_direct(hipStream_t s, const double* P, const double* Cs, long ldk, int Sp, const double* xr, long sn, long sd, int M,
                         const double* X, int D, const double* inv_ell, int N, const double* alpha, double* Gs, double* Gm);
 
@@ -296,6 +297,10 @@ struct EuboFinalizeArgs {
     const double *mu_part[2], *ca_part[2], *cw_part[2], *Gs[2], *Gm[2], *XsT[2];
     const double *kw_part, *inv_ell;
     const double* kw_solve_part = nullptr;
+    // beyond the guard of the norm expansion (gram_direct_form): the two options' RAW coordinates, candidate-major xr[o][n + d*ldr];
+    // k(x, x') and e_d then come from (x_d - x'_d) / l_d, differenced first (XsT's scaled coordinates leave eps / l).  nullptr: XsT.
+    const double* xr[2] = {nullptr, nullptr};
+    long ldr = 0;
     double a;
     // outputs, candidate-major with leading dimension ldo, offset already applied: val (may be NULL), grad (may be NULL): rows
     // 0..D-1 the gradient in x, rows D..2D-1 the gradient in x'
@@ -506,6 +511,9 @@ void launch_path_data(hipStream_t s, const double* Ks, const double* Cs, long ld
 // grad[n + d*ldo] = inv_ell_d (Gt[n + d*ldk] - XsT[n + d*ldk] csum[n])
 void launch_path_grad(hipStream_t s, int S, int D, long ldk, const double* Gt, const double* XsT, const double* csum, const double* inv_ell,
                       double* grad, long ldo);
+// grad[n + d*ldo] = inv_ell_d (Gt[n + d*ldk] + Gd[n + d*ldk]): Gt = G Om alone, Gd = launch_grad_direct's Gs with P = Pm (gram_direct_form)
+void launch_path_grad_direct(hipStream_t s, int S, int D, long ldk, const double* Gt, const double* Gd, const double* inv_ell, double* grad,
+                             long ldo);
 // draw[j] = (live ? live[j] : j) / S, j < n
 void launch_path_draw_of_live(hipStream_t s, const int* live, int n, int S, int* draw);
 // per draw s (starts [s S, (s+1) S)): first maximum of -f; out[s (D + 2) + 0] = value, [+1] = index within the draw, [+2 ..] = x

@@ -37,6 +37,10 @@ __device__ __forceinline__ double eubo_value(double mu0, double Phi0, double mu1
 
 // ONE lane per pair, whatever the grid: the partial sums of both options are added in increasing t in the pair's own lane, so its
 // bits depend on neither its column, the other pairs nor the launch shape.  Option 0 is x, option 1 is x'.
+// RAW (a handle beyond the guard of the norm expansion): the pair's own scaled difference (x_d - x'_d) / l_d is taken from the raw
+// coordinates, differenced first -- a near-duplicate pair's difference is then exact, where x~_d - x~'_d carries eps |x~| = eps / (2 l)
+// absolute (at l = 1e-8: 5e-9 in a difference of 0.3, 3e-9 a in k(x, x') and so in s^2).  RAW = false is the kernel as it was.
+template <bool RAW>
 __global__ __launch_bounds__(256) void eubo_finalize_kernel(EuboFinalizeArgs p) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= p.S) return;
@@ -67,7 +71,9 @@ __global__ __launch_bounds__(256) void eubo_finalize_kernel(EuboFinalizeArgs p) 
     // k(x, x') and its derivative weight from the scaled coordinates of the two options
     double q = 0.0;
     for (int d = 0; d < p.D; ++d) {
-        const double df = p.XsT[0][n + (long)d * p.ldk] - p.XsT[1][n + (long)d * p.ldk];
+        double df;
+        if constexpr (RAW) df = (p.xr[0][n + (long)d * p.ldr] - p.xr[1][n + (long)d * p.ldr]) * p.inv_ell[d];
+        else df = p.XsT[0][n + (long)d * p.ldk] - p.XsT[1][n + (long)d * p.ldk];
         q = fma(df, df, q);
     }
     double k12, c12;
@@ -90,7 +96,9 @@ __global__ __launch_bounds__(256) void eubo_finalize_kernel(EuboFinalizeArgs p) 
             const double il = p.inv_ell[d];
             const double dm = -il * (xo * ca[o] - p.Gm[o][n + (long)d * p.ldk]);
             const double T = il * (xo * cw[o] - p.Gs[o][n + (long)d * p.ldk]);
-            const double e = c12 * (x0 - x1) * il;
+            double e;
+            if constexpr (RAW) e = c12 * ((p.xr[0][n + (long)d * p.ldr] - p.xr[1][n + (long)d * p.ldr]) * il) * il;
+            else e = c12 * (x0 - x1) * il;
             if (isnan(Phi[o] * dm + h * (sg * (e + T)))) bad = true;
         }
     }
@@ -105,14 +113,17 @@ __global__ __launch_bounds__(256) void eubo_finalize_kernel(EuboFinalizeArgs p) 
             const double il = p.inv_ell[d];
             const double dm = -il * (xo * ca[o] - p.Gm[o][n + (long)d * p.ldk]);     // grad mu of this option
             const double T = il * (xo * cw[o] - p.Gs[o][n + (long)d * p.ldk]);       // T_x,d / T_x',d
-            const double e = c12 * (x0 - x1) * il;                                   // e_d
+            double e;                                                                // e_d
+            if constexpr (RAW) e = c12 * ((p.xr[0][n + (long)d * p.ldr] - p.xr[1][n + (long)d * p.ldr]) * il) * il;
+            else e = c12 * (x0 - x1) * il;
             p.grad[n + (long)(o * p.D + d) * p.ldo] = bad ? 0.0 : Phi[o] * dm + h * (sg * (e + T));
         }
     }
 }
 void launch_eubo_finalize(hipStream_t s, const EuboFinalizeArgs& a) {
     if (a.S <= 0) return;
-    hipLaunchKernelGGL(eubo_finalize_kernel, dim3((a.S + 255) / 256), dim3(256), 0, s, a);
+    if (a.xr[0]) hipLaunchKernelGGL(eubo_finalize_kernel<true>, dim3((a.S + 255) / 256), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(eubo_finalize_kernel<false>, dim3((a.S + 255) / 256), dim3(256), 0, s, a);
 }
 
 }  // namespace slsk

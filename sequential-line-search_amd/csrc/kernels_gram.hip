@@ -318,6 +318,8 @@ void launch_cross_gram_direct(hipStream_t s, const double* xr, long sn, long sd,
 //   Gs[n + d*ldk] = sum_i P[n + i*ldk] t_id,  Gm[n + d*ldk] = sum_i Cs[n + i*ldk] alpha_i t_id,  t_id = (x_id - x*_nd) / l_d,  i < N, d < D.
 // The matrix-core form (grad_gemm) contracts x~_i alone and the finalize kernels subtract x~* times the sums ca / cw afterwards, which
 // leaves eps |x~| / l in every entry; with these sums the caller hands the finalize kernel ca = cw = 0.  grid (Sp / 128, D).
+// MEAN = false: Gs alone (Cs, alpha and Gm are not touched): the data term of a path gradient, whose weights are P = C* o v.
+template <bool MEAN>
 __global__ __launch_bounds__(128) void grad_direct_kernel(const double* __restrict__ P, const double* __restrict__ Cs, long ldk,
                                                           const double* __restrict__ xr, long sn, long sd, int M,
                                                           const double* __restrict__ X, int D, const double* __restrict__ inv_ell, int N,
@@ -329,14 +331,15 @@ __global__ __launch_bounds__(128) void grad_direct_kernel(const double* __restri
     for (int i = 0; i < N; ++i) {
         const double t = (X[d + (long)i * D] - xs) * il;
         gs = fma(P[(long)n + (long)i * ldk], t, gs);
-        gm = fma(Cs[(long)n + (long)i * ldk] * alpha[i], t, gm);
+        if constexpr (MEAN) gm = fma(Cs[(long)n + (long)i * ldk] * alpha[i], t, gm);
     }
     Gs[(long)n + (long)d * ldk] = gs;
-    Gm[(long)n + (long)d * ldk] = gm;
+    if constexpr (MEAN) Gm[(long)n + (long)d * ldk] = gm;
 }
 void launch_grad_direct(hipStream_t s, const double* P, const double* Cs, long ldk, int Sp, const double* xr, long sn, long sd, int M,
                         const double* X, int D, const double* inv_ell, int N, const double* alpha, double* Gs, double* Gm) {
-    hipLaunchKernelGGL(grad_direct_kernel, dim3(Sp / 128, D), dim3(128), 0, s, P, Cs, ldk, xr, sn, sd, M, X, D, inv_ell, N, alpha, Gs, Gm);
+    if (Gm) hipLaunchKernelGGL(grad_direct_kernel<true>, dim3(Sp / 128, D), dim3(128), 0, s, P, Cs, ldk, xr, sn, sd, M, X, D, inv_ell, N, alpha, Gs, Gm);
+    else hipLaunchKernelGGL(grad_direct_kernel<false>, dim3(Sp / 128, D), dim3(128), 0, s, P, Cs, ldk, xr, sn, sd, M, X, D, inv_ell, N, alpha, Gs, Gm);
 }
 
 }  // namespace slsk

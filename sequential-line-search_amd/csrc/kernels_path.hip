@@ -243,6 +243,23 @@ void launch_path_grad(hipStream_t s, int S, int D, long ldk, const double* Gt, c
     hipLaunchKernelGGL(path_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, S, D, ldk, Gt, XsT, csum, inv_ell, grad, ldo);
 }
 
+// grad[n + d*ldo] = inv_ell_d (Gt[n + d*ldk] + Gd[n + d*ldk])  for n < S, d < D: the prior's gradient in scaled coordinates (Gt = G Om) plus
+// the data term's contraction over raw coordinate differences (grad_direct: Gd = sum_i c_i (x_id - x_d) / l_d), beyond the guard
+__global__ __launch_bounds__(256) void path_grad_direct_kernel(int S, int D, long ldk, const double* __restrict__ Gt, const double* __restrict__ Gd,
+                                                               const double* __restrict__ inv_ell, double* __restrict__ grad, long ldo) {
+    const long idx = blockIdx.x * 256L + threadIdx.x;
+    if (idx >= (long)S * D) return;
+    const int n = (int)(idx % S), d = (int)(idx / S);
+    const long e = n + (long)d * ldk;
+    grad[n + (long)d * ldo] = inv_ell[d] * (Gt[e] + Gd[e]);
+}
+void launch_path_grad_direct(hipStream_t s, int S, int D, long ldk, const double* Gt, const double* Gd, const double* inv_ell, double* grad,
+                             long ldo) {
+    const long n = (long)S * D;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(path_grad_direct_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, S, D, ldk, Gt, Gd, inv_ell, grad, ldo);
+}
+
 // draw[j] = (live ? live[j] : j) / S  for j < n
 __global__ __launch_bounds__(256) void path_draw_of_live_kernel(const int* __restrict__ live, int n, int S, int* __restrict__ draw) {
     const int j = blockIdx.x * 256 + threadIdx.x;

@@ -29,6 +29,22 @@ def scaled_sqdist(A, B):
     return q
 
 
+def closed_form(mu, s2, dmu, ds2):
+    """The pair's value and gradient from its posterior: mu (2, M), s2 = Var[f(x) - f(x')] (M,), dmu and ds2 (2, D, M) the gradients
+    of mu_o and of s2 in option o.  Returns (val (M,), grad (2D, M), s, u, Phi (2, M), phi, bad), the guard applied."""
+    with np.errstate(all="ignore"):
+        s = np.sqrt(s2)
+        u = (mu[0] - mu[1]) / s
+        Phi = np.stack([0.5 * erfc(-u * RSQRT2), 0.5 * erfc(u * RSQRT2)])
+        phi = np.exp(-0.5 * u * u) * RSQRT_2PI
+        val = (mu[0] * Phi[0] + mu[1] * Phi[1]) + s * phi
+        grad = np.concatenate([Phi[o][None, :] * dmu[o] + (phi / (2.0 * s))[None, :] * ds2[o] for o in range(2)], axis=0)
+        bad = ~(s2 > 0.0) | (s < 1e-10) | np.isnan(val) | np.isnan(grad).any(axis=0)
+        val = np.where(bad, np.fmax(mu[0], mu[1]), val)
+        grad = np.where(bad[None, :], 0.0, grad)
+    return val, grad, s, u, Phi, phi, bad
+
+
 def eubo(X, y, theta, b, kernel, pairs, s2=None):
     """X (D, N), y (N,), theta = (a, l_1..l_D), noise b, pairs (2D, M): rows 0..D-1 = x, D..2D-1 = x'.
     Returns (val (M,), grad (2D, M), info).  s2 (M,), if given, replaces the reference's own Var[f(x) - f(x')] (the value and the
@@ -57,11 +73,6 @@ def eubo(X, y, theta, b, kernel, pairs, s2=None):
         k12, c12 = kernel_kc(kernel, a, q12)
         own_s2 = (2.0 * a - 2.0 * k12) - np.sum(dvec * w, axis=0)
         s2v = own_s2 if s2 is None else np.asarray(s2, dtype=np.float64)
-        s = np.sqrt(s2v)
-        u = (mu[0] - mu[1]) / s
-        Phi = np.stack([0.5 * erfc(-u * RSQRT2), 0.5 * erfc(u * RSQRT2)])
-        phi = np.exp(-0.5 * u * u) * RSQRT_2PI
-        val = (mu[0] * Phi[0] + mu[1] * Phi[1]) + s * phi
         e = c12[None, :] * (xt[0] - xt[1]) * il[:, None]
         dmu, ds2 = [], []
         for o in range(2):
@@ -72,9 +83,6 @@ def eubo(X, y, theta, b, kernel, pairs, s2=None):
             T = il[:, None] * (xt[o] * cw[None, :] - Xt @ (c * w))
             ds2.append((2.0 if o == 0 else -2.0) * (e + T))
         dmu, ds2 = np.stack(dmu), np.stack(ds2)
-        grad = np.concatenate([Phi[o][None, :] * dmu[o] + (phi / (2.0 * s))[None, :] * ds2[o] for o in range(2)], axis=0)
-        bad = ~(s2v > 0.0) | (s < 1e-10) | np.isnan(val) | np.isnan(grad).any(axis=0)
-        val = np.where(bad, np.fmax(mu[0], mu[1]), val)
-        grad = np.where(bad[None, :], 0.0, grad)
+        val, grad, s, u, Phi, phi, bad = closed_form(mu, s2v, dmu, ds2)
     return val, grad, dict(mu=mu, s2=s2v, own_s2=own_s2, s=s, u=u, Phi=Phi, phi=phi, dmu=dmu, ds2=ds2, cond=ev[-1] / ev[0],
                            alpha=alpha, bad=bad)

@@ -10,7 +10,10 @@ the share of starts whose end values differ by more than 1e-6 of the largest one
 order="sequential" on the CPU objective.  A case keeps its seed only if that share is at most 2 %; assert_starts_agree allows the
 device 5 %.  Share with the seeds below (start seed = SEED of the route + position in its table; the data seeds are in Case), for
 every shape and option set of every route -- harness, logei, mes, pair, eubo, qeubo, qnei, path, 108 runs: 0 of 129 (128, 150)
-starts, 0 %.  The first seeds tried were kept.  That test re-measures the share on every run and prints it per case."""
+starts, 0 %.  The first seeds tried were kept.  That test re-measures the share on every run and prints it per case.
+The three shapes beyond the Gram guard (GUARD, 12 runs more): eubo and qeubo 0 of 128 / 129; path 2 of 150 (1.3 %) in three of its
+four option sets, starts 18 and 72, neither a draw's winner nor its runner-up (each winner reproduces to 2e-12 between the orders
+and leads by 0.4 or more)."""
 import numpy as np
 
 import lbfgs_ref
@@ -39,7 +42,13 @@ PAIR = [dict(acq=EI, chol=False), dict(acq=UCB, chol=False), dict(acq=LOG_EI, ch
 EUBO = [dict(D=8), dict(D=9), dict(D=32), dict(D=33)]                      # N = 90, S = 128: 2D = 16, 18, 64, 66
 QSETS = [dict(q=3, D=5), dict(q=2, D=9), dict(q=4, D=16), dict(q=16, D=5)]   # nvar = 15, 18, 64, 80; N = 60, F = 64, 8 draws
 PATH = [dict(D=6, kernel=SE), dict(D=6, kernel=MATERN52), dict(D=20, kernel=SE), dict(D=20, kernel=MATERN52)]   # 3 draws x 50 starts
-ROUTES = dict(harness=HARNESS, logei=LOGEI, mes=MES, pair=PAIR, eubo=EUBO, qeubo=QSETS, qnei=QSETS, path=PATH)
+# One shape per route whose handle lies beyond the guard of the norm expansion (at D = 65 and l = 0.02 [0.016 .. 0.025]
+# ilm^2 (D/2) 2.3e-16 is 1.2e-11 .. 2.9e-11 > 1e-11): the maximiser's trial blocks go through the direct-difference cross Gram and,
+# for the pairs, the raw-difference gradient contraction.  At that length scale a uniform start is ~50 scaled units from every data
+# point, where the data term is exactly 0: two of three columns start 1.5 scaled units from a data point instead (near_data_starts).
+GUARD = dict(D=65, N=200, ell=0.02)
+ROUTES = dict(harness=HARNESS, logei=LOGEI, mes=MES, pair=PAIR, eubo=EUBO + [GUARD], qeubo=QSETS + [dict(q=2, **GUARD)], qnei=QSETS,
+              path=PATH + [dict(kernel=MATERN52, **GUARD)])
 SEED = dict(harness=100, logei=200, mes=300, pair=400, eubo=500, qeubo=600, qnei=700, path=800)
 PAIR_VARIANTS = ["default"]                                                # sls_acq_maximize_pair takes no options from Python
 
@@ -65,6 +74,19 @@ def problem(D, N, seed, ell=0.5, a=0.5, scale=1.0):
 def box_starts(nvar, S, seed):
     st = np.random.default_rng(seed).uniform(-0.2, 1.2, (nvar, S))
     st[:, ::3] = np.round(st[:, ::3])
+    return st
+
+
+def near_data_starts(st, X, ell, seed, dist=1.5):
+    """Columns 1, 2 mod 3 of the start block st (k D x S, k points of D coordinates each): every point becomes a data point plus
+    dist l g / sqrt(D), g standard normal -- about `dist` scaled units away, not clamped (a data point next to a face leaves the box).
+    Columns 0 mod 3 keep their corners."""
+    rng = np.random.default_rng(seed + 70)
+    D, N = X.shape
+    for j in range(st.shape[1]):
+        if j % 3:
+            for k in range(st.shape[0] // D):
+                st[k * D:(k + 1) * D, j] = X[:, rng.integers(0, N)] + dist * ell * rng.standard_normal(D) / np.sqrt(D)
     return st
 
 
@@ -97,17 +119,17 @@ class Case:
             self.grow = np.random.default_rng(seed + 50).uniform(0.0, 1.0, (D, 3))
             self.nvar = D
         elif route == "eubo":
-            D, N = sh["D"], 90
-            self.X, self.y, self.theta = problem(D, N, seed=60 + D, ell=0.3 * np.sqrt(D))
+            D, N = sh["D"], sh.get("N", 90)
+            self.X, self.y, self.theta = problem(D, N, seed=60 + D, ell=sh.get("ell", 0.3 * np.sqrt(D)))
             self.nvar, self.S = 2 * D, 128
         elif route in ("qeubo", "qnei"):
-            D, N = sh["D"], 60
-            self.X, self.y, self.theta = problem(D, N, seed=N + D, ell=0.3 * np.sqrt(D))
+            D, N = sh["D"], sh.get("N", 60)
+            self.X, self.y, self.theta = problem(D, N, seed=N + D, ell=sh.get("ell", 0.3 * np.sqrt(D)))
             self.n_draws, self.F, self.path_seed = 8, 64, 1234 + D
             self.nvar = sh["q"] * D
         elif route == "path":
-            D, N = sh["D"], 90
-            self.X, self.y, self.theta = problem(D, N, seed=N + D, ell=0.3 * np.sqrt(D))
+            D, N = sh["D"], sh.get("N", 90)
+            self.X, self.y, self.theta = problem(D, N, seed=N + D, ell=sh.get("ell", 0.3 * np.sqrt(D)))
             self.kernel = sh["kernel"]
             self.n_draws, self.F, self.path_seed, self.per_draw = 3, 256, 1234 + D, 50
             self.nvar, self.S = D, 150
@@ -115,6 +137,8 @@ class Case:
             raise KeyError(route)
         self.D = self.X.shape[0]
         self.starts = box_starts(self.nvar, self.S, seed)
+        if "ell" in sh:
+            self.starts = near_data_starts(self.starts, self.X, self.theta[1:], seed)
         if route == "logei":
             self.at_data = np.arange(5, self.S, 16)
             self.starts[:, self.at_data] = self.X[:, 3 * np.arange(self.at_data.size)]

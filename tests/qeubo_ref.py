@@ -10,7 +10,10 @@ FLOOR = -1.0e300
 
 
 def grad_with_weights(ref, Xs, Wb, Vb):
-    """Gradient (D x M) at Xs[:, m] of the path function with weights (Wb[:, m] (2F), Vb[:, m] (N)): PathRef.eval's formulas."""
+    """Gradient (D x M) at Xs[:, m] of the path function with weights (Wb[:, m] (2F), Vb[:, m] (N)): PathRef.eval's formulas, or the
+    reference's own where it has them (path_short_ref: raw coordinate differences, in its own number type)."""
+    if hasattr(ref, "grad_with_weights"):
+        return ref.grad_with_weights(Xs, Wb, Vb)
     Xs = np.asarray(Xs, float)
     T = ref.om @ ((Xs - 0.5) / ref.ell[:, None])                    # F x M
     wc, ws = Wb[:ref.F], Wb[ref.F:]
