@@ -205,6 +205,23 @@ namespace sequential_line_search
                                                                                         const int num_frequencies = 2048,
                                                                                         double* value = nullptr);
 
+        /// The same batch by the log form of that criterion (not in the reference; qLogNEI after Ament et al. 2023, include/sls_hip.h
+        /// sls_qlognei_*): a softplus of temperature tau_relu for max(0, .), a log-sum-exp of temperature tau_max for the max over
+        /// the points and a log-sum-exp over the draws make the objective smooth, and a start that no draw improves -- stationary
+        /// under FindNextPointsByNoisyExpectedImprovement -- has a gradient and moves.  value receives the LOG criterion.
+        std::vector<Eigen::VectorXd> FindNextPointsByLogNoisyExpectedImprovement(const Regressor& regressor, const int num_points,
+                                                                                 const unsigned num_draws = 256,
+                                                                                 const unsigned num_global_search_iters = 100,
+                                                                                 const unsigned num_local_search_iters = 50,
+                                                                                 const unsigned long long seed = 0,
+                                                                                 const int num_frequencies = 2048, double* value = nullptr,
+                                                                                 const double tau_relu = 1e-6, const double tau_max = 1e-2);
+        /// The same from an explicit start set ((num_points D) x S: rows iD..iD+D-1 start point i).
+        std::vector<Eigen::VectorXd> FindNextPointsByLogNoisyExpectedImprovementFromStarts(
+            const Regressor& regressor, const int num_points, const Eigen::MatrixXd& starts, const unsigned num_draws = 256,
+            const unsigned num_local_search_iters = 50, const unsigned long long seed = 0, const int num_frequencies = 2048,
+            double* value = nullptr, const double tau_relu = 1e-6, const double tau_max = 1e-2);
+
         /// The next slider by the expected utility of the best position on it (not in the reference; line EUBO, include/sls_hip.h
         /// sls_line_*): the query of SequentialLineSearchOptimizer is a line and the user picks the best point on it, so the
         /// criterion is E[max_t f((1 - t) a + t b)], estimated on num_positions grid positions (2 .. 16) over num_draws pathwise

@@ -73,6 +73,11 @@ namespace sequential_line_search
         /// select the same heuristic.
         void DetermineNextQueryByNoisyExpectedImprovement(const unsigned long long seed, const int num_draws = 256,
                                                           const int num_global_search_iters = 0, const int num_local_search_iters = 0);
+        /// The same with the log form of the criterion (acquisition_func::FindNextPointsByLogNoisyExpectedImprovement): starts that
+        /// no draw improves still move.
+        void DetermineNextQueryByLogNoisyExpectedImprovement(const unsigned long long seed, const int num_draws = 256,
+                                                             const int num_global_search_iters = 0, const int num_local_search_iters = 0,
+                                                             const double tau_relu = 1e-6, const double tau_max = 1e-2);
 
         const std::vector<Eigen::VectorXd>& GetCurrentOptions() const { return m_current_options; }
         Eigen::VectorXd                     GetMaximizer() const;

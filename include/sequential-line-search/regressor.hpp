@@ -122,6 +122,21 @@ namespace sequential_line_search
         std::vector<Eigen::VectorXd> MaximizeNoisyExpectedImprovement(int num_points, const Eigen::VectorXd& baseline,
                                                                       const Eigen::MatrixXd& starts, unsigned num_local_search_iters,
                                                                       double* value = nullptr) const;
+        /// Log-space noisy expected improvement (qLogNEI after Ament et al. 2023; include/sls_hip.h sls_qlognei_*): the smooth log
+        /// form of CalcNoisyExpectedImprovements -- a softplus of temperature tau_relu for max(0, .), a log-sum-exp of temperature
+        /// tau_max for the max over the points, a log-sum-exp over the draws.  Arguments and results as
+        /// CalcNoisyExpectedImprovements (win_counts are its hard counts); a set that no draw improves has a finite value and a
+        /// nonzero gradient.
+        Eigen::VectorXd CalcLogNoisyExpectedImprovements(const std::vector<Eigen::MatrixXd>& options, const Eigen::VectorXd& baseline,
+                                                         std::vector<Eigen::MatrixXd>* grads = nullptr,
+                                                         Eigen::MatrixXi* win_counts = nullptr, double tau_relu = 1e-6,
+                                                         double tau_max = 1e-2) const;
+        /// Maximiser of that criterion over [0,1]^(num_points D): as MaximizeNoisyExpectedImprovement, but a start that no draw
+        /// improves moves.
+        std::vector<Eigen::VectorXd> MaximizeLogNoisyExpectedImprovement(int num_points, const Eigen::VectorXd& baseline,
+                                                                         const Eigen::MatrixXd& starts, unsigned num_local_search_iters,
+                                                                         double* value = nullptr, double tau_relu = 1e-6,
+                                                                         double tau_max = 1e-2) const;
         /// Expected utility of the best of num_positions grid positions on the slider from ends_a.col(m) to ends_b.col(m) (line EUBO;
         /// include/sls_hip.h sls_line_*): CalcExpectedUtilitiesOfBestOption at the positions (1 - t_i) a + t_i b, t_i = i /
         /// (num_positions - 1), 2 <= num_positions <= 16 -- Slider::GetValue on the grid.  ends_a, ends_b D x M.  Returns the M values;
@@ -143,13 +158,14 @@ namespace sequential_line_search
             const Eigen::VectorXd* baseline = nullptr, double* value = nullptr) const;
 
     private:
-        // the set criteria of both kinds: baseline == nullptr is the expected utility of the best option
+        // the set criteria of every kind: baseline == nullptr is the expected utility of the best option, taus != nullptr
+        // (tau_relu, tau_max) the log form of the noisy expected improvement
         Eigen::VectorXd              CalcSetCriterion(const char* who, const std::vector<Eigen::MatrixXd>& options,
                                                       const Eigen::VectorXd* baseline, std::vector<Eigen::MatrixXd>* grads,
-                                                      Eigen::MatrixXi* win_counts) const;
+                                                      Eigen::MatrixXi* win_counts, const double* taus = nullptr) const;
         std::vector<Eigen::VectorXd> MaximizeSetCriterion(const char* who, int num_options, const Eigen::VectorXd* baseline,
                                                           const Eigen::MatrixXd& starts, unsigned num_local_search_iters,
-                                                          double* value) const;
+                                                          double* value, const double* taus = nullptr) const;
 
         sls_path* m_path      = nullptr;
         int       m_num_draws = 0;

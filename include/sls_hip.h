@@ -432,8 +432,8 @@ int sls_qeubo_maximize(sls_path* p, int q, const double* starts, int S_starts, i
  * The pass, its route, the sets per pass and the bit contract are sls_qeubo_eval's (one pass function, the selection kernel apart): a
  * set's bits depend on neither its column, the other sets of the call, the number of sets per pass nor SLS_COMPACT; permuting the
  * options of a set permutes wins and the gradient blocks and leaves the value's bits unchanged.
- * Known limitation: a start set that no draw improves is stationary (value 0, zero gradient) and leaves the maximiser's batch at
- * once, as expected improvement's underflowed starts do.  A smoothed or log form (qLogNEI) is out of scope here.
+ * A start set that no draw improves is stationary (value 0, zero gradient) and leaves the maximiser's batch at once, as expected
+ * improvement's underflowed starts do; sls_qlognei_eval / sls_qlognei_maximize below are the log form, which has a gradient there.
  * Locks are those of sls_path_eval / sls_path_maximize; a path whose handle was refitted, grown or switched in sigma mode is refused
  * (SLS_ERR_INVALID), as by the other sls_path_* calls. */
 /* t_out[s] = max_j f_s(Xb[:, j]), arg_out[s] = the LOWEST j that attains it; s < n_draws, Xb is D x Mb (host), Mb >= 1.  The values
@@ -452,6 +452,48 @@ int sls_qnei_eval(sls_path* p, int q, const double* baseline, const double* sets
 int sls_qnei_maximize(sls_path* p, int q, const double* baseline, const double* starts, int S_starts, int n_local,
                       const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
                       double* x_stars, double* y_stars);
+
+/* ---- log-space noisy expected improvement on posterior draws (not in the reference) -----------------------------------------
+ * qLogNEI: the log form of the criterion above after Ament et al. (NeurIPS 2023, qLogEI) -- a softplus for the ReLU, a temperature
+ * log-sum-exp for the max over the q points, a log-sum-exp over the draws.  It is smooth, and a set that no draw improves keeps a
+ * finite value and a nonzero gradient.  For a path object p (S = n_draws draws), a per-draw baseline t_s, temperatures
+ * tau_relu = T0 > 0 and tau_max = Tm > 0, and a set of q points:
+ *   a_{i,s} = (v_{i,s} - t_s) / T0                        v_{i,s} = f_s(x_i), formed exactly as sls_qnei_eval forms it
+ *   L(a)    = log softplus(a):   a >= 0       : log(a + log1p(exp(-a)))
+ *                                -36 <= a < 0 : log(log1p(exp(a)))
+ *                                a < -36      : a                      (the neglected term is < exp(-36)/2)
+ *   R(a)    = dL/da:             a >= 0       : 1 / ((1 + exp(-a)) (a + log1p(exp(-a))))
+ *                                -36 <= a < 0 : exp(a) / ((1 + exp(a)) log1p(exp(a)))
+ *                                a < -36      : 1
+ *   l_{i,s} = log T0 + L(a_{i,s}),   rho_{i,s} = R(a_{i,s}) / T0
+ *   m_s     = Mq_s + Tm log sum_i exp((l_{i,s} - Mq_s)/Tm),  Mq_s = max_i l_{i,s};   pi_{i,s} = exp((l_{i,s} - Mq_s)/Tm) / (that sum)
+ *   value   = Mx + log sum_s exp(m_s - Mx) - log S,  Mx = max_s m_s;   omega_s = exp(m_s - Mx) / (that sum)
+ *   c_{i,s} = omega_s pi_{i,s} rho_{i,s}                  (= d value / d v_{i,s}; all > 0 before rounding: a factor pi or omega more
+ *                                                          than 745 below its maximum underflows to 0)
+ *   grad_{x_i} value = grad fbar_i(x_i),  fbar_i = the path function with weights (W c_i, V c_i)      -- no division by S
+ *   wins_i  = sls_qnei_eval's wins (hard, strictly-greater against t_s), bit for bit
+ * The sum over i does not depend on the order of the options: Mq_s is taken at the largest v_{i,s}, every term lies in [0, 1] and is
+ * rounded to a multiple of 2^-58, and the terms are added as 64-bit integers (q <= 16 of them stay below 2^62; the sum is >= 1, so this
+ * rounding moves it by less than eps / 4 relative).  The log-sum-exp over the draws is accumulated online (a running maximum, the sum
+ * rescaled when the maximum moves), over s increasing inside slices of 16 draws, over the slices increasing.
+ * Bounds: qNEI <= exp(value) <= q^Tm (qNEI + T0 ln 2), from softplus in [relu, relu + T0 ln 2] and log-sum-exp in [max, max + Tm ln q].
+ * Guard: a NaN among the set's q S values or its qD gradient components gives the value SLS_QEUBO_FLOOR and the zero gradient; the
+ * scan runs before any write and whether or not the gradient is asked for.
+ * Bits: a set's value, gradient and wins depend on neither its column, the other sets of the call, the number of sets per pass nor
+ * SLS_COMPACT.  Permuting the options of a set permutes wins and the gradient blocks exactly, because the sum over i above has no order and
+ * the draws keep theirs; for the value, rely on no more than unchanged to rounding.
+ * tau_relu or tau_max not finite or <= 0, and a non-finite baseline, are SLS_ERR_INVALID (checked once per call, before any upload);
+ * q, M, NULL arguments, locks and the staleness rule are as sls_qnei_eval.  The slider form (sls_line_*) has no log variant. */
+#define SLS_QLOGNEI_TAU_RELU 1e-6
+#define SLS_QLOGNEI_TAU_MAX 1e-2
+/* L[i] = L(a[i]), R[i] = R(a[i]) for i < n on the device of ctx (a test hook, as sls_logei_terms is); either output may be NULL. */
+int sls_qlognei_terms(sls_ctx* ctx, const double* a, long n, double* L, double* R);
+int sls_qlognei_eval(sls_path* p, int q, const double* baseline, double tau_relu, double tau_max, const double* sets, int M,
+                     double* val, double* grad, int* wins);
+/* sls_qnei_maximize with this objective; temperatures and baseline are validated once, before the first round. */
+int sls_qlognei_maximize(sls_path* p, int q, const double* baseline, double tau_relu, double tau_max, const double* starts,
+                         int S_starts, int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out,
+                         double* val_out, long* idx_out, double* x_stars, double* y_stars);
 
 /* ---- expected utility of the best slider position on posterior draws (not in the reference) --------------------------------
  * Line EUBO: the query of SequentialLineSearchOptimizer is a slider from a to b, and the user picks the best point anywhere on it.
@@ -631,6 +673,8 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
  * "qnei" (the same two kernels with a per-draw baseline: two launches per pass of sls_qnei_eval / per pass and round of
  * sls_qnei_maximize; every other stage counts as under qEUBO) and "path_max" (the column reduction of sls_path_max_over_points, one
  * launch per pass; its values count under "cross_gram", "path_prior", "qeubo_data_gemm");
+ * "qlognei" (the selection of the log form, two kernels under one entry, and the finish under another: two entries per pass of
+ * sls_qlognei_eval / per pass and round of sls_qlognei_maximize; every other stage counts as under qEUBO);
  * "line" (line_expand and line_fold: two launches per pass of sls_line_eval -- one without a gradient -- / per pass and round of
  * sls_line_maximize; the pass between them counts as under qEUBO / qNEI);
  * "potrf_fallbacks": launches = how often a single-launch factorisation gave up and was recomputed. */

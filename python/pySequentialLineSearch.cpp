@@ -233,6 +233,25 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
                  return std::make_pair(q, value);
              },
              "num_points"_a, "baseline"_a, "starts"_a, "num_local_search_iters"_a = 50)
+        // the log form of the two above (temperatures trailing)
+        .def("calc_log_noisy_expected_improvements",
+             [](const PosteriorFunctionSamples& s, const std::vector<MatrixXd>& options, const VectorXd& baseline, double tau_relu,
+                double tau_max) {
+                 std::vector<MatrixXd> grads;
+                 Eigen::MatrixXi       wins;
+                 const VectorXd        v = s.CalcLogNoisyExpectedImprovements(options, baseline, &grads, &wins, tau_relu, tau_max);
+                 return std::make_tuple(v, grads, wins);
+             },
+             "options"_a, "baseline"_a, "tau_relu"_a = 1e-6, "tau_max"_a = 1e-2)
+        .def("maximize_log_noisy_expected_improvement",
+             [](const PosteriorFunctionSamples& s, int num_points, const VectorXd& baseline, const MatrixXd& starts,
+                unsigned num_local_search_iters, double tau_relu, double tau_max) {
+                 double     value = 0.0;
+                 const auto q =
+                     s.MaximizeLogNoisyExpectedImprovement(num_points, baseline, starts, num_local_search_iters, &value, tau_relu, tau_max);
+                 return std::make_pair(q, value);
+             },
+             "num_points"_a, "baseline"_a, "starts"_a, "num_local_search_iters"_a = 50, "tau_relu"_a = 1e-6, "tau_max"_a = 1e-2)
         // the expected utility of the best slider position on the draws: (values, gradient for the first end, for the second, win
         // counts num_positions x M); maximize_... ((end_0, end_1), value)
         .def("calc_expected_utilities_of_best_slider_position",
@@ -299,6 +318,26 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
           },
           "regressor"_a, "num_points"_a, "starts"_a, "num_draws"_a = 256, "num_local_search_iters"_a = 50, "seed"_a = 0ULL,
           "num_frequencies"_a = 2048);
+    m.def("find_next_points_by_log_noisy_expected_improvement",
+          [](const Regressor& r, int num_points, unsigned num_draws, unsigned num_global_search_iters, unsigned num_local_search_iters,
+             unsigned long long seed, int num_frequencies, double tau_relu, double tau_max) {
+              double     value = 0.0;
+              const auto q     = acquisition_func::FindNextPointsByLogNoisyExpectedImprovement(
+                  r, num_points, num_draws, num_global_search_iters, num_local_search_iters, seed, num_frequencies, &value, tau_relu, tau_max);
+              return std::make_pair(q, value);
+          },
+          "regressor"_a, "num_points"_a, "num_draws"_a = 256, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50,
+          "seed"_a = 0ULL, "num_frequencies"_a = 2048, "tau_relu"_a = 1e-6, "tau_max"_a = 1e-2);
+    m.def("find_next_points_by_log_noisy_expected_improvement_from_starts",
+          [](const Regressor& r, int num_points, const MatrixXd& starts, unsigned num_draws, unsigned num_local_search_iters,
+             unsigned long long seed, int num_frequencies, double tau_relu, double tau_max) {
+              double     value = 0.0;
+              const auto q     = acquisition_func::FindNextPointsByLogNoisyExpectedImprovementFromStarts(
+                  r, num_points, starts, num_draws, num_local_search_iters, seed, num_frequencies, &value, tau_relu, tau_max);
+              return std::make_pair(q, value);
+          },
+          "regressor"_a, "num_points"_a, "starts"_a, "num_draws"_a = 256, "num_local_search_iters"_a = 50, "seed"_a = 0ULL,
+          "num_frequencies"_a = 2048, "tau_relu"_a = 1e-6, "tau_max"_a = 1e-2);
 
     // the next slider by the expected utility of its best position (acquisition-function.hpp): ((end_0, end_1), value); an empty anchor
     // leaves both ends free
@@ -397,6 +436,9 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
         .def("determine_next_query_by_noisy_expected_improvement",
              &PreferentialBayesianOptimizer::DetermineNextQueryByNoisyExpectedImprovement, "seed"_a, "num_draws"_a = 256,
              "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0)
+        .def("determine_next_query_by_log_noisy_expected_improvement",
+             &PreferentialBayesianOptimizer::DetermineNextQueryByLogNoisyExpectedImprovement, "seed"_a, "num_draws"_a = 256,
+             "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0, "tau_relu"_a = 1e-6, "tau_max"_a = 1e-2)
         .def("get_current_options", &PreferentialBayesianOptimizer::GetCurrentOptions)
         .def("get_maximizer", &PreferentialBayesianOptimizer::GetMaximizer)
         .def("get_preference_value_mean", &PreferentialBayesianOptimizer::GetPreferenceValueMean, "point"_a)

@@ -67,6 +67,7 @@ EXPORTS = [
     "sls_eubo_eval", "sls_eubo_maximize", "sls_qeubo_eval", "sls_qeubo_maximize",
     "sls_path_max_over_points", "sls_qnei_eval", "sls_qnei_maximize",
     "sls_line_eval", "sls_line_maximize",
+    "sls_qlognei_terms", "sls_qlognei_eval", "sls_qlognei_maximize",
 ]
 
 
@@ -158,6 +159,14 @@ class Context:
         log_h, b1, b2 = np.empty(u.size), np.empty(u.size), np.empty(u.size)
         _ck(lib().sls_logei_terms(self.h, _p(u), C.c_long(u.size), _p(log_h), _p(b1), _p(b2)))
         return log_h, b1, b2
+
+    def qlognei_terms(self, a):
+        """(L(a), R(a)) = (log softplus(a), its derivative) of log-space noisy expected improvement for an array of a
+        (sls_qlognei_terms)."""
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).ravel())
+        L, R = np.empty(a.size), np.empty(a.size)
+        _ck(lib().sls_qlognei_terms(self.h, _p(a), C.c_long(a.size), _p(L), _p(R)))
+        return L, R
 
     # ---- free functions (src/regressor.cpp) ----
     def gram(self, X, theta, b, kernel):
@@ -377,6 +386,8 @@ class GP:
 
 QEUBO_MAX_OPTIONS = 16   # SLS_QEUBO_MAX_OPTIONS
 LINE_MIN_POSITIONS = 2   # SLS_LINE_MIN_POSITIONS
+QEUBO_FLOOR = -1.0e300   # SLS_QEUBO_FLOOR
+QLOGNEI_TAU_RELU, QLOGNEI_TAU_MAX = 1e-6, 1e-2   # SLS_QLOGNEI_TAU_RELU, SLS_QLOGNEI_TAU_MAX
 
 
 class PathSamples:
@@ -524,6 +535,58 @@ class PathSamples:
         _ck(lib().sls_qnei_maximize(self.h, q, _p(t), _p(starts), S, int(n_local), C.byref(opts) if opts is not None else None,
                                     C.c_long(offset), _p(x), C.byref(val), C.byref(idx), _p(xs) if want_all else None,
                                     _p(ys) if want_all else None))
+        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+
+    @staticmethod
+    def _temperatures(who, tau_relu, tau_max):
+        t0, tm = float(tau_relu), float(tau_max)
+        if not (np.isfinite(t0) and t0 > 0.0):
+            raise SlsError(f"{who}: tau_relu = {t0} (finite, > 0)")
+        if not (np.isfinite(tm) and tm > 0.0):
+            raise SlsError(f"{who}: tau_max = {tm} (finite, > 0)")
+        return C.c_double(t0), C.c_double(tm)
+
+    def qlognei_eval(self, sets, q, baseline, tau_relu=QLOGNEI_TAU_RELU, tau_max=QLOGNEI_TAU_MAX, want_grad=True, want_wins=False):
+        """Log-space noisy expected improvement of q points on the draws over the per-draw baseline (sls_qlognei_eval) at the columns
+        of sets (qD x M: rows iD..iD+D-1 = point i): values (M,), then with want_grad the gradient (qD, M), then with want_wins the
+        hard win counts of qnei_eval (q, M) int32."""
+        sets = _f(sets)
+        q = int(q)
+        if not 1 <= q <= QEUBO_MAX_OPTIONS:
+            raise SlsError(f"qlognei_eval: q = {q} (1 .. {QEUBO_MAX_OPTIONS})")
+        if sets.ndim != 2 or sets.shape[0] != q * self.D:
+            raise SlsError(f"qlognei_eval: sets must be qD x M = {q * self.D} x M, got {sets.shape}")
+        t = self._baseline("qlognei_eval", baseline)
+        t0, tm = self._temperatures("qlognei_eval", tau_relu, tau_max)
+        M = sets.shape[1]
+        val = np.empty(M)
+        grad = np.empty((q * self.D, M), order="F") if want_grad else None
+        wins = np.zeros((q, M), dtype=np.int32, order="F") if want_wins else None
+        _ck(lib().sls_qlognei_eval(self.h, q, _p(t), t0, tm, _p(sets), M, _p(val), _p(grad) if want_grad else None,
+                                   wins.ctypes.data_as(C.POINTER(C.c_int)) if want_wins else None))
+        out = (val,) + ((grad,) if want_grad else ()) + ((wins,) if want_wins else ())
+        return out if len(out) > 1 else val
+
+    def qlognei_maximize(self, starts, q, n_local, baseline, tau_relu=QLOGNEI_TAU_RELU, tau_max=QLOGNEI_TAU_MAX, offset=0,
+                         want_all=True, opts=None):
+        """acq_maximize over [0,1]^(qD) with the set objective of qlognei_eval (sls_qlognei_maximize): starts qD x S, x and x_stars
+        have qD rows.  GP.last_stats() of the path's handle reports the run."""
+        starts = _f(starts)
+        q = int(q)
+        if not 1 <= q <= QEUBO_MAX_OPTIONS:
+            raise SlsError(f"qlognei_maximize: q = {q} (1 .. {QEUBO_MAX_OPTIONS})")
+        if starts.ndim != 2 or starts.shape[0] != q * self.D:
+            raise SlsError(f"qlognei_maximize: starts must be qD x S = {q * self.D} x S, got {starts.shape}")
+        t = self._baseline("qlognei_maximize", baseline)
+        t0, tm = self._temperatures("qlognei_maximize", tau_relu, tau_max)
+        S = starts.shape[1]
+        rows = starts.shape[0]
+        x, val, idx = np.empty(rows), C.c_double(), C.c_long()
+        xs = np.empty((rows, S), order="F") if want_all else None
+        ys = np.empty(S) if want_all else None
+        _ck(lib().sls_qlognei_maximize(self.h, q, _p(t), t0, tm, _p(starts), S, int(n_local),
+                                       C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val),
+                                       C.byref(idx), _p(xs) if want_all else None, _p(ys) if want_all else None))
         return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
 
     def _line_args(self, who, q, anchor, baseline, block, what):

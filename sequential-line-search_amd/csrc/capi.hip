@@ -207,7 +207,7 @@ bool potrf_gave_up(sls_ctx* c, int abort_flag, int attempt) {
 }  // namespace slsk
 
 extern "C" const char* sls_last_error(void) { return slsk::g_err; }
-extern "C" int sls_version(void) { return 100; }
+extern "C" int sls_version(void) { return 101; }
 
 extern "C" int sls_ctx_create(int device, sls_ctx** out) {
     SLS_TRY
@@ -1362,6 +1362,11 @@ extern "C" int sls_logei_terms(sls_ctx* ctx, const double* u, long n, double* lo
     return scalar_terms("sls_logei_terms", ctx, u, n, 3, host, [&](const double* in, long m, double* const* out) {
         launch_logei_terms(ctx->stream, in, m, out[0], out[1], out[2]);
     });
+}
+extern "C" int sls_qlognei_terms(sls_ctx* ctx, const double* a, long n, double* L, double* R) {
+    double* const host[2] = {L, R};
+    return scalar_terms("sls_qlognei_terms", ctx, a, n, 2, host,
+                        [&](const double* in, long m, double* const* out) { launch_qlognei_terms(ctx->stream, in, m, out[0], out[1]); });
 }
 
 extern "C" int sls_mes_eval(sls_gp* g, const double* y_star, int K, const double* Xs, int M, double* val, double* grad) {

@@ -312,8 +312,27 @@ int qeubo_sets_per_pass(const sls_ctx* c, int q, int Np, int Fp, int Rp) {
     return std::max(128, points / q / 128 * 128);
 }
 
+// What the selection of a pass computes: qEUBO (base == nullptr), qNEI (base: n_draws device doubles, the per-draw baseline) or
+// qLogNEI (log_form, with base and the two temperatures).
+struct SetMode {
+    const double* base = nullptr;
+    bool log_form = false;
+    double tau_relu = 0.0, tau_max = 0.0;
+};
+
 struct QeuboWs {
     DBuf XsT, ns, Ks, Cs, PG, csum, vpart, Gt, B2, Gpart, Gd, VM, Wbar, Vbar, sum, fbar, gpt, badb, identb;
+    DBuf lmq, lzq, lpmx, lpsm, lpbadb, lpwinb;   // the scratch of the log-form selection (launch_qlognei_select)
+    int *lpbad = nullptr, *lpwin = nullptr;
+    void ensure_log(const sls_path* p, int q, int Sp) {
+        const size_t nsl = (size_t)qlognei_slices(p->n_draws);
+        lmq.ensure((size_t)Sp * p->Rp);
+        lzq.ensure((size_t)Sp * p->Rp);
+        lpmx.ensure((size_t)Sp * nsl);
+        lpsm.ensure((size_t)Sp * nsl);
+        lpbad = ints(lpbadb, (size_t)Sp * nsl);
+        lpwin = ints(lpwinb, (size_t)Sp * nsl * q);
+    }
     bool b2_ready = false;
     int* bad = nullptr;     // one flag per set of the pass
     int* ident = nullptr;   // ident[j] = j: point j is evaluated under aggregated column j
@@ -377,15 +396,18 @@ void draw_values_device(sls_path* p, const GpView& g, QeuboWs& w, int Pp, Prep&&
 // xr[n + r*ldr], rows iD..iD+D-1 the option i.  val[n], grad[n + r*ldo], wins[n + i*ldw].  The gradient is formed, and looked at by the
 // guard, whether or not it is asked for: a set's value does not depend on that.
 // base != nullptr (device, n_draws doubles): qNEI -- the selection competes against the per-draw baseline, the guard value is 0 and
-// the two kernels count under "qnei".
-void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const double* base, const double* xr, long ldr, int M, double* val,
-                       double* grad, long ldo, int* wins, long ldw) {
+// the two kernels count under "qnei".  mode.log_form: qLogNEI -- the selection is launch_qlognei_select (real weights in place of the
+// mask), the finish divides nothing, the guard value is SLS_QEUBO_FLOOR and the launches count under "qlognei".
+void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const SetMode& mode, const double* xr, long ldr, int M,
+                       double* val, double* grad, long ldo, int* wins, long ldw) {
     sls_ctx* c = g.ctx;
-    const char* scope = base ? "qnei" : "qeubo";
-    const double floor = base ? 0.0 : SLS_QEUBO_FLOOR;
+    const double* base = mode.base;
+    const char* scope = mode.log_form ? "qlognei" : base ? "qnei" : "qeubo";
+    const double floor = base && !mode.log_form ? 0.0 : SLS_QEUBO_FLOOR;
     const int D = g.D, Np = g.Np, Fp = p->Fp, Rp = p->Rp, S = p->n_draws;
     const int pass_max = std::min(round_up(M, 128), qeubo_sets_per_pass(c, q, Np, Fp, Rp));
     w.ensure(c, p, g, q * pass_max, pass_max);
+    if (mode.log_form) w.ensure_log(p, q, pass_max);
     double* Cs = g.kernel == SLS_KERNEL_ARD_MATERN52 ? w.Cs.p : w.Ks.p;
     const long Kc = (long)Np + Fp;
     if (!g.gram_direct && !w.b2_ready) {
@@ -409,7 +431,11 @@ void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const do
         });
         {
             ProfScope ps(c, scope);
-            launch_qeubo_select(c->stream, sc, Sp, q, S, Rp, w.VM.p, Pp, base, w.sum.p, wins ? wins + s0 : nullptr, ldw, w.bad);
+            if (mode.log_form)
+                launch_qlognei_select(c->stream, sc, Sp, q, S, Rp, w.VM.p, Pp, base, mode.tau_relu, mode.tau_max, w.lmq.p, w.lzq.p, w.lpmx.p,
+                                      w.lpsm.p, w.lpbad, w.lpwin, w.sum.p, wins ? wins + s0 : nullptr, ldw, w.bad);
+            else
+                launch_qeubo_select(c->stream, sc, Sp, q, S, Rp, w.VM.p, Pp, base, w.sum.p, wins ? wins + s0 : nullptr, ldw, w.bad);
         }
         {
             // aggregated weights of every point: the sums of the columns of W / V over the draws its option wins
@@ -454,12 +480,28 @@ void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const do
         {
             ProfScope ps(c, scope);
             launch_qeubo_finish(c->stream, sc, Sp, q, D, S, w.sum.p, w.bad, w.gpt.p, Pp, floor, val ? val + s0 : nullptr,
-                                grad ? grad + s0 : nullptr, ldo);
+                                grad ? grad + s0 : nullptr, ldo, mode.log_form);
         }
     }
 }
 
 }  // namespace
+
+// taus = (tau_relu, tau_max) of the log form, checked once per call before anything is uploaded
+static void require_temperatures(const char* who, const double* taus) {
+    SLS_REQUIRE(std::isfinite(taus[0]) && taus[0] > 0.0, "%s: tau_relu = %g (finite, > 0)", who, taus[0]);
+    SLS_REQUIRE(std::isfinite(taus[1]) && taus[1] > 0.0, "%s: tau_max = %g (finite, > 0)", who, taus[1]);
+}
+static SetMode set_mode(const double* device_base, const double* taus) {
+    SetMode m;
+    m.base = device_base;
+    if (taus) {
+        m.log_form = true;
+        m.tau_relu = taus[0];
+        m.tau_max = taus[1];
+    }
+    return m;
+}
 
 static void require_finite_baseline(const char* who, const sls_path* p, const double* baseline) {
     SLS_REQUIRE(baseline != nullptr, "%s: baseline is NULL", who);
@@ -468,12 +510,13 @@ static void require_finite_baseline(const char* who, const sls_path* p, const do
 
 // sls_qeubo_eval / sls_qnei_eval (want_base: competes against the per-draw baseline)
 static int set_eval(const char* who, sls_path* p, int q, const double* baseline, bool want_base, const double* sets, int M, double* val,
-                    double* grad, int* wins) {
+                    double* grad, int* wins, const double* taus = nullptr) {
     SLS_TRY
     SLS_REQUIRE(p != nullptr, "%s: p is NULL", who);
     SLS_REQUIRE(q >= 1 && q <= SLS_QEUBO_MAX_OPTIONS, "%s: q = %d (1 .. %d)", who, q, SLS_QEUBO_MAX_OPTIONS);
     SLS_REQUIRE(M >= 0, "%s: M = %d", who, M);
     SLS_REQUIRE(sets != nullptr, "%s: sets is NULL", who);
+    if (taus) require_temperatures(who, taus);
     if (want_base) require_finite_baseline(who, p, baseline);
     GpReadCall call(p->gp, p->generation, who);
     if (M == 0) return SLS_OK;
@@ -491,7 +534,7 @@ static int set_eval(const char* who, sls_path* p, int q, const double* baseline,
     out.ensure((size_t)Mp * (1 + qD));
     int* d_wins = wins ? ints(wb, (size_t)Mp * q) : nullptr;
     QeuboWs ws;
-    qeubo_eval_device(p, g, ws, q, tb.p, raw.p, Mp, M, out.p, grad ? out.p + Mp : nullptr, Mp, d_wins, Mp);
+    qeubo_eval_device(p, g, ws, q, set_mode(tb.p, taus), raw.p, Mp, M, out.p, grad ? out.p + Mp : nullptr, Mp, d_wins, Mp);
     std::vector<double> oh((size_t)Mp * (grad ? 1 + qD : 1));
     std::vector<int> wh(wins ? (size_t)Mp * q : 0);
     d2h(c, oh.data(), out.p, oh.size());
@@ -510,10 +553,11 @@ extern "C" int sls_qeubo_eval(sls_path* p, int q, const double* sets, int M, dou
 // sls_qeubo_maximize / sls_qnei_maximize
 static int set_maximize(const char* who, sls_path* p, int q, const double* baseline, bool want_base, const double* starts, int S_starts,
                         int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
-                        double* x_stars, double* y_stars) {
+                        double* x_stars, double* y_stars, const double* taus = nullptr) {
     SLS_TRY
     SLS_REQUIRE(p && starts, "%s: NULL argument", who);
     SLS_REQUIRE(q >= 1 && q <= SLS_QEUBO_MAX_OPTIONS, "%s: q = %d (1 .. %d)", who, q, SLS_QEUBO_MAX_OPTIONS);
+    if (taus) require_temperatures(who, taus);
     if (want_base) require_finite_baseline(who, p, baseline);
     GpReadCall call(p->gp, p->generation, who);
     const GpView& g = call.g;
@@ -532,10 +576,11 @@ static int set_maximize(const char* who, sls_path* p, int q, const double* basel
         tb.ensure((size_t)p->n_draws);
         h2d(c, tb.p, baseline, (size_t)p->n_draws);
     }
+    const SetMode mode = set_mode(tb.p, taus);
     LockstepStats ls;
     lockstep_rounds(c, r.st, lb, sd.p, S, n_local,
                     [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
-                        qeubo_eval_device(p, g, ws, q, tb.p, trial, ld, nlive, val, grad, ld, nullptr, 0);
+                        qeubo_eval_device(p, g, ws, q, mode, trial, ld, nlive, val, grad, ld, nullptr, 0);
                     },
                     &ls);
     std::vector<double> bh((size_t)8 + qD), pageable;
@@ -602,6 +647,21 @@ extern "C" int sls_qnei_maximize(sls_path* p, int q, const double* baseline, con
                         idx_out, x_stars, y_stars);
 }
 
+// ---- log-space noisy expected improvement on the draws (include/sls_hip.h) --------------------------------------------------
+extern "C" int sls_qlognei_eval(sls_path* p, int q, const double* baseline, double tau_relu, double tau_max, const double* sets, int M,
+                                double* val, double* grad, int* wins) {
+    const double taus[2] = {tau_relu, tau_max};
+    return set_eval("sls_qlognei_eval", p, q, baseline, true, sets, M, val, grad, wins, taus);
+}
+
+extern "C" int sls_qlognei_maximize(sls_path* p, int q, const double* baseline, double tau_relu, double tau_max, const double* starts,
+                                    int S_starts, int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out,
+                                    double* val_out, long* idx_out, double* x_stars, double* y_stars) {
+    const double taus[2] = {tau_relu, tau_max};
+    return set_maximize("sls_qlognei_maximize", p, q, baseline, true, starts, S_starts, n_local, opts, start_index_offset, x_out, val_out,
+                        idx_out, x_stars, y_stars, taus);
+}
+
 // ---- expected utility of the best slider position on the draws (include/sls_hip.h) ------------------------------------------
 namespace {
 
@@ -626,8 +686,8 @@ void line_eval_device(sls_path* p, const GpView& g, LineWs& w, int q, const doub
             ProfScope ps(c, "line");
             launch_line_expand(c->stream, sc, D, q, lines + s0, ld, anchor, w.sets.p, pass_max);
         }
-        qeubo_eval_device(p, g, w.q, q, base, w.sets.p, pass_max, sc, val ? val + s0 : nullptr, grad ? w.sgrad.p : nullptr, pass_max,
-                          wins ? wins + s0 : nullptr, ldw);
+        qeubo_eval_device(p, g, w.q, q, set_mode(base, nullptr), w.sets.p, pass_max, sc, val ? val + s0 : nullptr,
+                          grad ? w.sgrad.p : nullptr, pass_max, wins ? wins + s0 : nullptr, ldw);
         if (grad) {
             ProfScope ps(c, "line");
             launch_line_fold(c->stream, sc, D, q, anchor != nullptr, w.sgrad.p, pass_max, grad + s0, ldo);

@@ -530,12 +530,26 @@ void launch_qeubo_select(hipStream_t s, int nsets, int Sp, int q, int S, int Rp,
                          int* wins, long ldw, int* bad);
 // val[n] = sum[n] / S, grad[n + (i*D + d)*ldo] = gpt[i*Sp + n + d*ldg] / S for n < nsets; bad[n] or a NaN among them: value
 // `floor` (SLS_QEUBO_FLOOR; 0 for qNEI) and the zero gradient.  val / grad may be NULL.
+// precomputed (qLogNEI): val[n] = sum[n] and the gradient as it stands, nothing divided.
 void launch_qeubo_finish(hipStream_t s, int nsets, int Sp, int q, int D, int S, const double* sum, const int* bad, const double* gpt,
-                         long ldg, double floor, double* val, double* grad, long ldo);
+                         long ldg, double floor, double* val, double* grad, long ldo, bool precomputed = false);
 // Per draw s < n_draws (one workgroup each): the maximum over pt < rows of V[pt + s*ldv] and the lowest pt that attains it, merged into
 // the running record: base = 0 writes (t[s], arg[s]); base > 0 (a later pass, indices base + pt) replaces it only when strictly
 // greater.  A NaN in the column gives (NaN, -1), which later passes leave.
 void launch_path_colmax(hipStream_t s, const double* V, long ldv, int rows, int n_draws, int base, double* t, int* arg);
+
+// ---- kernels_qlognei.hip: log-space noisy expected improvement on posterior draws (sls_qlognei_*) -------------------------
+// L[i] = log softplus(a[i]), R[i] = L'(a[i]), i < n (the branches of include/sls_hip.h); either output may be NULL
+void launch_qlognei_terms(hipStream_t s, const double* a, long n, double* L, double* R);
+// The slices the S draws are cut into (a fixed slice length, whatever S and the pass are)
+int qlognei_slices(int S);
+// The selection of the qEUBO pass in log space, two launches.  V[i*Sp + n + s*ldv] = f_s(x_i) on entry, c_{i,s} = d value / d v_{i,s}
+// on exit (rows S <= s < Rp, the lanes n >= nsets and sets with a NaN: exactly 0); t = S device doubles.  sum[n] = the value (nothing
+// is left to divide), wins[n + i*ldw] = the hard wins of launch_qeubo_select with the same t, bad[n] = a NaN among the q S values.
+// Scratch: mq, zq (Sp x Rp doubles), pmx, psm (Sp x qlognei_slices(S) doubles), pbad (as many ints), pwin (q times as many ints).
+void launch_qlognei_select(hipStream_t s, int nsets, int Sp, int q, int S, int Rp, double* V, long ldv, const double* t, double tau0,
+                           double taum, double* mq, double* zq, double* pmx, double* psm, int* pbad, int* pwin, double* sum, int* wins,
+                           long ldw, int* bad);
 
 // ---- kernels_line.hip: expected utility of the best slider position (sls_line_*) ------------------------------------------
 // A line is its ends (a, b); position i of q is x_i = u_i a + t_i b with u_i = (q-1-i)/(q-1), t_i = i/(q-1) computed on the device (one

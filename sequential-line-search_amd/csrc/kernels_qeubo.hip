@@ -85,16 +85,18 @@ void launch_qeubo_select(hipStream_t s, int nsets, int Sp, int q, int S, int Rp,
 // to the candidate-major block grad[n + (i D + d) ldo] the lock-step rounds read.  Guard: bad[n], or a NaN in the value or in any of
 // the q D gradient components, gives `floor` (SLS_QEUBO_FLOOR; 0 for qNEI) and the zero gradient; the scan runs before any write and
 // whether or not the gradient is asked for.  val / grad may be NULL.
+// PRE (qLogNEI): sum[n] is the value and gpt the gradient as they stand -- nothing is divided.
+template <bool PRE>
 __global__ __launch_bounds__(256) void qeubo_finish_kernel(int nsets, int Sp, int q, int D, int S, const double* __restrict__ sum,
                                                            const int* __restrict__ bad, const double* __restrict__ gpt, long ldg,
                                                            double floor, double* __restrict__ val, double* __restrict__ grad, long ldo) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= nsets) return;
-    const double v = sum[n] / (double)S;
+    const double v = PRE ? sum[n] : sum[n] / (double)S;
     bool guard = bad[n] != 0 || v != v;
     for (int i = 0; i < q && !guard; ++i)
         for (int d = 0; d < D; ++d) {
-            const double g = gpt[(long)i * Sp + n + (long)d * ldg] / (double)S;
+            const double g = PRE ? gpt[(long)i * Sp + n + (long)d * ldg] : gpt[(long)i * Sp + n + (long)d * ldg] / (double)S;
             if (g != g) {
                 guard = true;
                 break;
@@ -104,13 +106,18 @@ __global__ __launch_bounds__(256) void qeubo_finish_kernel(int nsets, int Sp, in
     if (!grad) return;
     for (int i = 0; i < q; ++i)
         for (int d = 0; d < D; ++d)
-            grad[n + (long)(i * D + d) * ldo] = guard ? 0.0 : gpt[(long)i * Sp + n + (long)d * ldg] / (double)S;
+            grad[n + (long)(i * D + d) * ldo] =
+                guard ? 0.0 : (PRE ? gpt[(long)i * Sp + n + (long)d * ldg] : gpt[(long)i * Sp + n + (long)d * ldg] / (double)S);
 }
 void launch_qeubo_finish(hipStream_t s, int nsets, int Sp, int q, int D, int S, const double* sum, const int* bad, const double* gpt,
-                         long ldg, double floor, double* val, double* grad, long ldo) {
+                         long ldg, double floor, double* val, double* grad, long ldo, bool precomputed) {
     if (nsets <= 0) return;
-    hipLaunchKernelGGL(qeubo_finish_kernel, dim3((nsets + 255) / 256), dim3(256), 0, s, nsets, Sp, q, D, S, sum, bad, gpt, ldg, floor, val,
-                       grad, ldo);
+    if (precomputed)
+        hipLaunchKernelGGL(qeubo_finish_kernel<true>, dim3((nsets + 255) / 256), dim3(256), 0, s, nsets, Sp, q, D, S, sum, bad, gpt, ldg,
+                           floor, val, grad, ldo);
+    else
+        hipLaunchKernelGGL(qeubo_finish_kernel<false>, dim3((nsets + 255) / 256), dim3(256), 0, s, nsets, Sp, q, D, S, sum, bad, gpt, ldg,
+                           floor, val, grad, ldo);
 }
 
 // Column maximum with its lowest argmax: ONE workgroup per draw s over the rows pt < rows of V[pt + s ldv] (a draw's column is

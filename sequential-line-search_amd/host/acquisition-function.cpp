@@ -548,6 +548,33 @@ namespace sequential_line_search
             regressor, num_points, SeededStarts(num_points * regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed),
             num_draws, num_local_search_iters, seed, num_frequencies, value);
     }
+
+    // ---- its log form (include/sls_hip.h sls_qlognei_*; Ament et al. 2023) ----
+    std::vector<VectorXd> acquisition_func::FindNextPointsByLogNoisyExpectedImprovementFromStarts(
+        const Regressor& regressor, const int num_points, const MatrixXd& starts, const unsigned num_draws,
+        const unsigned num_local_search_iters, const unsigned long long seed, const int num_frequencies, double* value,
+        const double tau_relu, const double tau_max)
+    {
+        if (!regressor.GetDeviceHandle())
+            throw std::invalid_argument("acquisition_func: log noisy expected improvement needs a device-resident regressor "
+                                        "(GaussianProcessRegressor / PreferenceRegressor); there is no host fallback");
+        const PosteriorFunctionSamples draws =
+            regressor.SamplePosteriorFunctions(static_cast<int>(std::max(1u, num_draws)), seed, num_frequencies);
+        const VectorXd incumbents = draws.MaxOverPoints(regressor.GetLargeX());
+        return draws.MaximizeLogNoisyExpectedImprovement(num_points, incumbents, starts, num_local_search_iters, value, tau_relu, tau_max);
+    }
+
+    std::vector<VectorXd> acquisition_func::FindNextPointsByLogNoisyExpectedImprovement(
+        const Regressor& regressor, const int num_points, const unsigned num_draws, const unsigned num_global_search_iters,
+        const unsigned num_local_search_iters, const unsigned long long seed, const int num_frequencies, double* value,
+        const double tau_relu, const double tau_max)
+    {
+        if (num_points < 1 || num_points > SLS_QEUBO_MAX_OPTIONS)
+            throw std::invalid_argument("FindNextPointsByLogNoisyExpectedImprovement: 1 .. 16 points");
+        return FindNextPointsByLogNoisyExpectedImprovementFromStarts(
+            regressor, num_points, SeededStarts(num_points * regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed),
+            num_draws, num_local_search_iters, seed, num_frequencies, value, tau_relu, tau_max);
+    }
     // ---- the next slider by the expected utility of its best position (include/sls_hip.h sls_line_*) ----
     std::pair<VectorXd, VectorXd> acquisition_func::FindNextSliderByExpectedUtilityFromStarts(
         const Regressor& regressor, const VectorXd& anchor, const MatrixXd& starts, const int num_positions, const unsigned num_draws,

@@ -166,6 +166,18 @@ namespace sequential_line_search
                        });
     }
 
+    void PreferentialBayesianOptimizer::DetermineNextQueryByLogNoisyExpectedImprovement(const unsigned long long seed, const int num_draws,
+                                                                                        const int num_global_search_iters,
+                                                                                        const int num_local_search_iters,
+                                                                                        const double tau_relu, const double tau_max)
+    {
+        BuildNextQuery("DetermineNextQueryByLogNoisyExpectedImprovement", num_global_search_iters, num_local_search_iters,
+                       [&](int q, int n_global, int n_local) {
+                           return acquisition_func::FindNextPointsByLogNoisyExpectedImprovement(
+                               *m_regressor, q, std::max(1, num_draws), n_global, n_local, seed, 2048, nullptr, tau_relu, tau_max);
+                       });
+    }
+
     VectorXd PreferentialBayesianOptimizer::GetMaximizer() const { return m_current_options[0]; }
 
     double PreferentialBayesianOptimizer::GetPreferenceValueMean(const VectorXd& point) const

@@ -232,7 +232,8 @@ namespace sequential_line_search
     }
 
     VectorXd PosteriorFunctionSamples::CalcSetCriterion(const char* who, const std::vector<MatrixXd>& options, const VectorXd* baseline,
-                                                        std::vector<MatrixXd>* grads, Eigen::MatrixXi* win_counts) const
+                                                        std::vector<MatrixXd>* grads, Eigen::MatrixXi* win_counts,
+                                                        const double* taus) const
     {
         const std::string name = std::string("PosteriorFunctionSamples::") + who;
         const long        q    = static_cast<long>(options.size());
@@ -250,7 +251,11 @@ namespace sequential_line_search
         if (win_counts) *win_counts = Eigen::MatrixXi::Zero(q, M);
         double* gp = grads ? g.data() : nullptr;
         int*    wp = win_counts ? win_counts->data() : nullptr;
-        if (baseline)
+        if (baseline && taus)
+            device::Check(sls_qlognei_eval(m_path, static_cast<int>(q), baseline->data(), taus[0], taus[1], sets.data(),
+                                           static_cast<int>(M), v.data(), gp, wp),
+                          "sls_qlognei_eval");
+        else if (baseline)
             device::Check(sls_qnei_eval(m_path, static_cast<int>(q), baseline->data(), sets.data(), static_cast<int>(M), v.data(), gp, wp),
                           "sls_qnei_eval");
         else
@@ -267,7 +272,7 @@ namespace sequential_line_search
 
     std::vector<VectorXd> PosteriorFunctionSamples::MaximizeSetCriterion(const char* who, int num_options, const VectorXd* baseline,
                                                                          const MatrixXd& starts, unsigned num_local_search_iters,
-                                                                         double* value) const
+                                                                         double* value, const double* taus) const
     {
         const std::string name = std::string("PosteriorFunctionSamples::") + who;
         if (num_options < 1 || num_options > SLS_QEUBO_MAX_OPTIONS) throw std::invalid_argument(name + ": 1 .. 16 options");
@@ -282,7 +287,11 @@ namespace sequential_line_search
         double    v   = 0.0;
         long      idx = 0;
         const int S = static_cast<int>(starts.cols()), n_local = std::max(1, static_cast<int>(num_local_search_iters));
-        if (baseline)
+        if (baseline && taus)
+            device::Check(sls_qlognei_maximize(m_path, num_options, baseline->data(), taus[0], taus[1], starts.data(), S, n_local, &o, 0,
+                                               x.data(), &v, &idx, nullptr, nullptr),
+                          "sls_qlognei_maximize");
+        else if (baseline)
             device::Check(sls_qnei_maximize(m_path, num_options, baseline->data(), starts.data(), S, n_local, &o, 0, x.data(), &v, &idx,
                                             nullptr, nullptr),
                           "sls_qnei_maximize");
@@ -329,6 +338,24 @@ namespace sequential_line_search
                                                                                      unsigned num_local_search_iters, double* value) const
     {
         return MaximizeSetCriterion("MaximizeNoisyExpectedImprovement", num_points, &baseline, starts, num_local_search_iters, value);
+    }
+
+    VectorXd PosteriorFunctionSamples::CalcLogNoisyExpectedImprovements(const std::vector<MatrixXd>& options, const VectorXd& baseline,
+                                                                        std::vector<MatrixXd>* grads, Eigen::MatrixXi* win_counts,
+                                                                        double tau_relu, double tau_max) const
+    {
+        const double taus[2] = {tau_relu, tau_max};
+        return CalcSetCriterion("CalcLogNoisyExpectedImprovements", options, &baseline, grads, win_counts, taus);
+    }
+
+    std::vector<VectorXd> PosteriorFunctionSamples::MaximizeLogNoisyExpectedImprovement(int num_points, const VectorXd& baseline,
+                                                                                        const MatrixXd& starts,
+                                                                                        unsigned num_local_search_iters, double* value,
+                                                                                        double tau_relu, double tau_max) const
+    {
+        const double taus[2] = {tau_relu, tau_max};
+        return MaximizeSetCriterion("MaximizeLogNoisyExpectedImprovement", num_points, &baseline, starts, num_local_search_iters, value,
+                                    taus);
     }
 
     VectorXd PosteriorFunctionSamples::CalcExpectedUtilitiesOfBestSliderPosition(const MatrixXd& ends_a, const MatrixXd& ends_b,
