@@ -15,6 +15,12 @@ A, B = 0.7, 5e-3                                       # signal variance and noi
 EPS = float(np.finfo(np.float64).eps)
 ELL_CASES = (0.3, 3e-2, 3e-3, 1e-5, 1e-8, "ard")       # isotropic l, and one ARD case: one l = 1e-5 among 0.3s
 SIZES = ((100, 6), (129, 6), (300, 6), (300, 33), (300, 64), (200, 65))   # both sides of N = 128, D = 32 / 64, D % 16
+# D > 128 (a second and a third 128-column tile of the gradient contraction, no one-wavefront route, no single-launch fit): the
+# smallest shapes with two row tiles or two / three column tiles.  l = 0.3 sqrt(D) keeps the problem dense (every gradient row is
+# non-trivial); the last two lie beyond the guard of the norm expansion.
+WIDE_DENSE = ((130, 129, 3.4), (90, 257, 4.8), (200, 192, 4.2))
+WIDE_CASES = WIDE_DENSE + ((130, 129, 3e-3), (90, 257, "ard"))
+WIDE_SIZES = tuple((N, D) for (N, D, _) in WIDE_DENSE)
 N_PAIRS = 20
 N_CAND = 40                                            # 0..15 ordinary, 16..27 outside the box, 28..37 against training points, 38/39 a pair
 CAND_NEAR = range(28, 38)
@@ -245,7 +251,7 @@ def check(got, ref, D, y_max):
     """Hold `got` to `ref` at the tolerances of the issue, key by key (only the keys present in `got`):
     K, Ks: 4 (D + 8) eps a per entry.  alpha: rtol 1e-6, atol 1e-7 |y|max.  Kinv: 1e-9 of its largest entry.  logdet: rtol 1e-10.
     mean / cov: rtol 1e-8, atol 1e-10.  dev: rtol 1e-7, atol 1e-10.  acquisition values and gradients: rtol 1e-6, atol 1e-9 of the
-    largest.  MAP value 1e-8 max(1, |v|); MAP gradient rtol 1e-6, atol 1e-8 max(1, |g|max)."""
+    largest (so too the gradients of mean and deviation).  MAP value 1e-8 max(1, |v|); MAP gradient rtol 1e-6, atol 1e-8 max(1, |g|max)."""
     def close(k, rtol, atol):
         g, r = np.asarray(got[k], dtype=np.longdouble), np.asarray(ref[k], dtype=np.longdouble)
         bad = np.abs(g - r) > atol + rtol * np.abs(r)
@@ -264,7 +270,7 @@ def check(got, ref, D, y_max):
             close(k, 1e-8, 1e-10)
         elif k == "dev":
             close(k, 1e-7, 1e-10)
-        elif k in ("ei", "ei_grad", "ucb", "ucb_grad"):
+        elif k in ("ei", "ei_grad", "ucb", "ucb_grad", "dmean", "ddev"):    # UCB's gradient is dmean + h ddev: its tolerance
             close(k, 1e-6, 1e-9 * max(rmax, 1e-30))
         elif k == "map_value":
             close(k, 0.0, 1e-8 * max(1.0, rmax))
@@ -278,7 +284,7 @@ def quantities(r):
     """The comparable quantities of a reference() record, under the keys of check()."""
     out = dict(K=r["fit"]["K"], Ks=r["Ks"], alpha=r["fit"]["alpha"], Kinv=r["fit"]["Kinv"], logdet=r["fit"]["logdet"],
                mean=r["pred"]["mean"], dev=r["pred"]["dev"], cov=r["pred"]["cov"], ei=r["ei"][0], ei_grad=r["ei"][1],
-               ucb=r["ucb"][0], ucb_grad=r["ucb"][1])
+               ucb=r["ucb"][0], ucb_grad=r["ucb"][1], dmean=r["pred"]["dmean"], ddev=r["pred"]["ddev"])
     if "map" in r:
         out.update(map_value=r["map"][0], map_grad=r["map"][1])
     return out

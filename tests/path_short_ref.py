@@ -28,6 +28,10 @@ F, SEED = 200, 4321                                    # Fp = 256
 SIZES = ((129, 6), (300, 33), (200, 65))               # both sides of one 128-row tile, of D = 32 / 64; a second dimension chunk
 ELL_CASES = (0.3, 3e-3, 1e-5, 1e-8, "ard")
 CASES = [(N, D, case, 5) for (N, D) in SIZES for case in ELL_CASES] + [(200, 65, 0.02, 5), (129, 6, 1e-5, 130)]
+# D > 128 (gram_ref.WIDE_CASES): Dcols = 256 / 384 and Dp = 144 / 208 / 272 in the feature and gradient kernels, tiled routes only
+WIDE_CASES = [(N, D, case, 5) for (N, D, case) in gr.WIDE_CASES]
+CASES += WIDE_CASES
+INSIDE = [(N, D, 0.3) for (N, D) in SIZES] + list(gr.WIDE_DENSE)            # the cases inside the guard of the norm expansion
 QS = (2, 5, 16)
 LINE_Q = 4
 BAND_FACTOR = 16.0                                     # device and restatement: two fp64 evaluations in different summation orders

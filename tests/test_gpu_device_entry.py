@@ -153,9 +153,10 @@ def test_library_calls_leave_no_hip_error_for_the_caller(ctx, oracle):
 
 # ---- 1. a refit in place equals a fresh fit, on every fit route ---------------------------------------------------------------------
 # (D, N): smallest fit; single-workgroup fit at its limit; first tiled fit (Np = 256, separate launches); Np = 384, first fused
-# factor-and-inverse launch; last / first size on / past the one-wavefront evaluation path; claimed tile pools (N >= 2432)
+# factor-and-inverse launch; last / first size on / past the one-wavefront evaluation path; claimed tile pools (N >= 2432);
+# D = 129: two 128-column tiles in every gradient behind the snapshot, no one-wavefront route
 FIT_SHAPES = [(1, 1), (3, 128), (3, 129), (5, 300), (4, 512), (6, 640)]
-FIT_CASES = [(D, N, k, mode) for D, N in FIT_SHAPES for k in (0, 1) for mode in (0, 1)] + [(6, 2560, 1, 0)]
+FIT_CASES = [(D, N, k, mode) for D, N in FIT_SHAPES for k in (0, 1) for mode in (0, 1)] + [(6, 2560, 1, 0), (129, 130, 1, 0)]
 
 
 @pytest.mark.parametrize("D,N,kernel,mode", FIT_CASES, ids=[f"D{D}-N{N}-{'matern' if k else 'se'}-{'solve' if mode else 'inverse'}"

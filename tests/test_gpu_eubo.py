@@ -77,7 +77,7 @@ def tolerances(info, theta, N, alpha_max):
     return tol_v, np.stack(tol_g)
 
 
-SHAPES = [(1, 1), (90, 2), (129, 8), (300, 33), (300, 96)]
+SHAPES = [(1, 1), (90, 2), (129, 8), (300, 33), (300, 96), (90, 129), (130, 257)]     # the last two: 2 and 3 column tiles per option
 
 
 @pytest.mark.parametrize("mode", [0, 1])

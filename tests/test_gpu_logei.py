@@ -111,7 +111,7 @@ def test_scalar_terms_against_60_digit_values(ctx):
 
 
 # ---- 2. combiner on the device's own predictions -----------------------------------------------------------------------------------
-CASES = [(SE, 90, 1), (MATERN52, 700, 16), (SE, 300, 96)]
+CASES = [(SE, 90, 1), (MATERN52, 700, 16), (SE, 300, 96), (SE, 90, 129), (MATERN52, 130, 257)]     # the last two: D > 128
 
 
 @pytest.mark.parametrize("mode", [0, 1])

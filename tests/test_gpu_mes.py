@@ -78,7 +78,7 @@ def test_scalar_terms_against_60_digit_values(ctx):
     assert lib.sls_mes_terms(ctx.h, t.ctypes.data_as(dp), C.c_long(-1), only.ctypes.data_as(dp), None) == -1
 
 
-CASES = [(SE, 90, 2), (MATERN52, 700, 16), (SE, 300, 96), (MATERN52, 300, 300)]
+CASES = [(SE, 90, 2), (MATERN52, 700, 16), (SE, 300, 96), (MATERN52, 300, 300), (SE, 90, 129), (MATERN52, 130, 257)]
 
 
 @pytest.mark.parametrize("mode", [0, 1])

@@ -887,7 +887,18 @@ def test_lbfgs_options_and_single_evaluation(ctx, oracle):
 def test_append_point_equals_refit(ctx, oracle, kernel, N0):
     """sls_gp_append_point (rank-1 growth, used by FindNextPoints) against a fresh fit on the extended data; N0 = 126 / 128
     cross the 128-padding boundary (in-place update vs buffer growth)."""
-    D, extra = 3, 4
+    append_point_equals_refit(ctx, oracle, kernel, N0, 3)
+
+
+@pytest.mark.parametrize("kernel", [0, 1])
+def test_append_point_equals_refit_above_128_dimensions(ctx, oracle, kernel):
+    """The same at D = 129, N0 = 126 -> 130 across the padding: the appended row's cross Gram and the evaluations behind it run over
+    two 128-column tiles, and no route of the handle is a one-wavefront one."""
+    append_point_equals_refit(ctx, oracle, kernel, 126, 129)
+
+
+def append_point_equals_refit(ctx, oracle, kernel, N0, D):
+    extra = 4
     X, y, theta, b = synth_problem(oracle, D, N0 + extra)
     gp = sls().GP(ctx, X[:, :N0], y[:N0], theta, b, kernel)
     for i in range(N0, N0 + extra):

@@ -44,7 +44,9 @@ def problem(D, N, seed, ell=0.5, a=0.5):
 CASES = [(ph.SE, 90, 2, 100), (ph.MATERN52, 90, 16, 1024), (ph.SE, 700, 16, 4096), (ph.MATERN52, 700, 64, 100),
          (ph.SE, 2048, 64, 1024), (ph.MATERN52, 2048, 2, 4096),
          # D > 64 (the gradient GEMMs at D > 64 columns) and D > 128 (more than one 128-column output tile of the gradient GEMMs)
-         (ph.SE, 300, 96, 700), (ph.MATERN52, 300, 300, 300)]
+         (ph.SE, 300, 96, 700), (ph.MATERN52, 300, 300, 300),
+         # D = 129: ONE live column in the second tile; D = 257: one in the third, with N just past one 128-row tile
+         (ph.SE, 90, 129, 100), (ph.MATERN52, 130, 257, 300)]
 
 
 @pytest.mark.parametrize("kernel,N,D,F", CASES)

@@ -68,6 +68,8 @@ def setup(m, ctx, kernel, N, D, F, nd, b=0.05):
 # (SE, 300, 96, ..): D > 64, and 37 draws: the padding up to 128 must neither win nor contribute; (MATERN52, 700, 7, .., 130): a
 # second 128-deep k-tile of the aggregation GEMM
 CASES = [(ph.SE, 90, 2, 100, 3, 64), (ph.MATERN52, 90, 16, 1024, 4, 64), (ph.SE, 300, 96, 700, 2, 37), (ph.MATERN52, 700, 7, 300, 5, 130)]
+# D > 128: two (D = 129) and three (D = 257) 128-column tiles in the gradient contractions, tiled routes only
+CASES += [(ph.SE, 90, 129, 100, 2, 37), (ph.MATERN52, 130, 257, 300, 4, 37)]
 
 
 @pytest.mark.parametrize("kernel,N,D,F,q,nd", CASES)

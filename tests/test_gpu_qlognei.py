@@ -98,7 +98,9 @@ def test_scalar_terms_against_50_digit_values(ctx):
 
 # tests/test_gpu_qeubo.py's four cases, then 16 points on one draw and one point on 130 draws
 CASES = [(ph.SE, 90, 2, 100, 3, 64), (ph.MATERN52, 90, 16, 1024, 4, 64), (ph.SE, 300, 96, 700, 2, 37), (ph.MATERN52, 700, 7, 300, 5, 130),
-         (ph.SE, 90, 2, 100, 16, 1), (ph.MATERN52, 90, 2, 100, 16, 1), (ph.SE, 90, 2, 100, 1, 130), (ph.MATERN52, 90, 2, 100, 1, 130)]
+         (ph.SE, 90, 2, 100, 16, 1), (ph.MATERN52, 90, 2, 100, 16, 1), (ph.SE, 90, 2, 100, 1, 130), (ph.MATERN52, 90, 2, 100, 1, 130),
+         # D > 128 (tests/test_gpu_qeubo.py's two): the only check of this criterion's gradient above 128 columns
+         (ph.SE, 90, 129, 100, 2, 37), (ph.MATERN52, 130, 257, 300, 4, 37)]
 
 
 @pytest.mark.parametrize("kernel,N,D,F,q,nd", CASES)

@@ -8,6 +8,10 @@ and walk l over {0.3, 3e-2, 3e-3, 1e-5, 1e-8} plus one ARD case, at sizes on bot
 kernels / tiles; D = 32, 64: the staging limits; D = 65: a second dimension chunk).  tests/test_gram_ref_cpu.py shows that the
 reference is good to 1e-13 on these cases and that the expansion, emulated in fp64, fails them at l <= 1e-5.
 
+The same bodies run gram_ref.WIDE_CASES: D = 129, 192 and 257 at l = 0.3 sqrt(D) (dense: every gradient row is live) and two cases
+beyond the guard.  Above D = 128 the gradient contraction has a second and a third 128-column tile, no handle takes the one-wavefront
+kernels, and N <= 128 runs the tiled fit and the tiled MAP objective (the single-launch forms stop at D = 128).
+
 Tolerances (gram_ref.check): Gram entries 4 (D + 8) eps a, derived from the direct form; everything else the suite's own
 (test_append_point_equals_refit, test_matrix_core_form_and_direct_difference_form_agree, the short-l MAP test).  Every case leaves
 its measured errors in the session's evidence file (kind "short_length_scales")."""
@@ -19,7 +23,7 @@ from util import env_switch, record, sls
 
 pytestmark = pytest.mark.gpu
 
-CASES = [(N, D, case) for (N, D) in gr.SIZES for case in gr.ELL_CASES]
+CASES = [(N, D, case) for (N, D) in gr.SIZES for case in gr.ELL_CASES] + list(gr.WIDE_CASES)
 EI, UCB = 0, 1
 
 
@@ -70,6 +74,26 @@ def test_fit_predict_and_acquisition(ctx, N, D, case, kernel, wave):
             got["ucb"], got["ucb_grad"] = gp.acq_eval(r["Xs"], UCB, 2.0)
             gp.close()
             hold("gp", got, ref, y_max, N=N, D=D, ell=case, kernel=kernel, wave=wave, sigma_mode=sigma_mode)
+
+
+@pytest.mark.parametrize("wave", [0, 1])
+@pytest.mark.parametrize("kernel", [0, 1])
+@pytest.mark.parametrize("N,D,case", gr.WIDE_CASES)
+def test_predict_grad_above_128_dimensions(ctx, N, D, case, kernel, wave):
+    """sls_gp_predict_grad in both sigma modes: the gradients of mean and deviation at the tolerance of UCB's gradient, which is
+    their sum with h = 2.  Rows 128 and up come from the second and third column tile of the contraction."""
+    m = sls()
+    r = gr.reference(N, D, case, kernel)
+    ref = gr.quantities(r)
+    with env_switch("SLS_WAVE_PATH", wave):
+        for sigma_mode in (0, 1):
+            gp = m.GP(ctx, r["X"], r["y"], r["theta"], r["b"], kernel)
+            if sigma_mode:
+                gp.set_sigma_mode(sigma_mode)
+            got = {}
+            got["dmean"], got["ddev"] = gp.predict_grad(r["Xs"])
+            gp.close()
+            hold("predict_grad", got, ref, 1.0, N=N, D=D, ell=case, kernel=kernel, wave=wave, sigma_mode=sigma_mode)
 
 
 @pytest.mark.parametrize("kernel", [0, 1])
@@ -142,7 +166,7 @@ def test_gp_map_objective_and_gradient(ctx, oracle, N, D, case, kernel):
 
 
 @pytest.mark.parametrize("kernel", [0, 1])
-@pytest.mark.parametrize("N,D", gr.SIZES)
+@pytest.mark.parametrize("N,D", gr.SIZES + gr.WIDE_SIZES)
 def test_gp_map_objective_batch_mixing_ordinary_and_short_length_scales(ctx, N, D, kernel):
     """sls_gp_nll_batch over rows that alternate l = 0.3 and l = 1e-8 (and one ARD row) on data whose near-duplicates are O(1) apart
     at 1e-8: equal to the single evaluations the way test_gp_map_objective_batch_matches_single_evaluations asserts it, and every
@@ -159,7 +183,7 @@ def test_gp_map_objective_batch_mixing_ordinary_and_short_length_scales(ctx, N, 
     h.close()
     record("short_length_scales", route="map_batch", N=N, D=D, kernel=kernel,
            errors=dict(batch=[float(e) for e in np.abs(vb - ref)], single=[float(e) for e in np.abs(single - ref)]), values=[float(v) for v in ref])
-    if N <= 128:
+    if N <= 128 and D <= 128:                            # the single-launch objective: one route for batch and single
         np.testing.assert_array_equal(vb, single)
     else:
         np.testing.assert_array_equal(vb, one)

@@ -9,7 +9,9 @@ of these calls is an O(1) error that no test at ordinary length scales sees.
 
 Cases (path_short_ref.CASES): gram_ref.problem at (N, D) in {(129, 6), (300, 33), (200, 65)}, l in {0.3 (inside the guard), 3e-3,
 1e-5, 1e-8, one ARD case}, l = 0.02 at D = 65 (just beyond the guard), both kernels, F = 200, 5 draws and one case of 130; the points
-are gram_ref's 40 candidates (ordinary, outside the box, 0.7 scaled units from a training point, a near-duplicate pair).
+are gram_ref's 40 candidates (ordinary, outside the box, 0.7 scaled units from a training point, a near-duplicate pair).  And
+gram_ref.WIDE_CASES: D = 129, 192, 257 on both sides of the guard, where the feature and gradient kernels run over two and three
+128-column tiles and every route is the tiled one.
 
 Tolerances, one scheme (path_short_ref.reference): the tolerance the entry point's ordinary restatement test uses (tol_v / tol_g of
 test_eval_agrees_with_the_restatement, the tolerances() of test_gpu_eubo.py) with this case's cond(K_y), |v| and shortest length
@@ -94,7 +96,7 @@ def test_path_eval_and_the_identity_at_the_data(m, ctx, N, D, case, nd, kernel):
     """sls_path_eval, gathered (value, gradient) and every-draw, against the reference and against each other; and
     f_s(x_i) = y_i - sqrt(b) eps_{s,i} - b v_{s,i} at the training points with v from the longdouble reference."""
     r = sr.reference(N, D, case, kernel, nd)
-    assert sr.beyond_guard(r["ell"], D) == (case != 0.3)
+    assert sr.beyond_guard(r["ell"], D) == ((N, D, case) not in sr.INSIDE)
     gp, ps = handles(m, ctx, r)
     dr = sr.draws_of_points(gr.N_CAND, nd)
     val, grad = ps.eval(r["Xs"], dr)
@@ -280,7 +282,7 @@ def test_maximize_across_a_chunk_boundary_in_the_direct_form(m, ctx, kernel):
 
 # ---- h: posterior samples ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kernel", [0, 1])
-@pytest.mark.parametrize("N,D", sr.SIZES)
+@pytest.mark.parametrize("N,D", sr.SIZES + gr.WIDE_SIZES)
 def test_posterior_samples_are_mu_plus_cholesky_times_z(m, ctx, N, D, kernel):
     """The assertion of test_samples_are_mu_plus_cholesky_times_z at l = 1e-5 with mean and covariance from gram_ref (longdouble), the
     near-duplicate candidate pair among the points: its prior covariance is neither 0 nor a."""

@@ -31,3 +31,26 @@ def test_fp64_direct_differences_agree_with_longdouble_and_the_expansion_does_no
         for key in ("K", "Ks", "alpha", "logdet"):
             with pytest.raises(AssertionError):
                 gr.check({key: qex[key]}, qld, D, y_max)
+
+
+@pytest.mark.parametrize("kernel", [0, 1])
+@pytest.mark.parametrize("N,D,case", gr.WIDE_CASES)
+def test_wide_cases_fp64_agrees_with_longdouble(oracle, N, D, case, kernel):
+    """D > 128 (gram_ref.WIDE_CASES): the fp64 form within every tolerance of check() of its longdouble form, the gradients of mean
+    and deviation included, and the oracle's MAP objective with it; beyond the guard the emulated expansion fails on K_y."""
+    r64 = gr.reference(N, D, case, kernel)
+    y_max = float(np.abs(r64["y"]).max())
+    q64 = gr.quantities(r64)
+    qld = gr.quantities(gr.reference(N, D, case, kernel, np.longdouble))
+    gr.check(q64, qld, D, y_max)
+    for k in ("dmean", "ddev", "ucb_grad", "ei_grad"):           # every gradient row, 128 and up included, is live at some candidate
+        rows = np.abs(qld[k]).max(axis=1)
+        assert rows.min() > (1e-3 * rows.max() if (N, D, case) in gr.WIDE_DENSE else 0.0), k
+    assert np.abs(qld["map_grad"][2:]).min() > 0
+    vo, go = oracle.gp_map_objective(kernel, r64["X"], r64["y"], r64["hyp"])
+    gr.check(dict(map_value=vo, map_grad=go), qld, D, y_max)
+    if (N, D, case) not in gr.WIDE_DENSE:
+        qex = gr.quantities(gr.reference(N, D, case, kernel, expansion=True))
+        gr._CACHE.pop((N, D, case, kernel, np.float64, True))
+        with pytest.raises(AssertionError):
+            gr.check(dict(K=qex["K"]), qld, D, y_max)

@@ -19,9 +19,20 @@ KERNELS = [0, 1]
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("N,D", sr.SIZES)
 def test_inside_the_guard_it_is_the_restatement_of_the_path_tests(N, D, kernel):
-    """l = 0.3: values to the 1e-8 and gradients to the 1e-6 (1 + |g|max) of tests/test_path_sample_cpu.py, against
+    inside_the_guard(N, D, 0.3, kernel)
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("N,D,case", gr.WIDE_DENSE)
+def test_wide_dense_cases_are_the_restatement_of_the_path_tests(N, D, case, kernel):
+    """D = 129, 192, 257 at l = 0.3 sqrt(D): inside the guard, the same assertions."""
+    inside_the_guard(N, D, case, kernel)
+
+
+def inside_the_guard(N, D, case, kernel):
+    """l = 0.3 (0.3 sqrt(D) at D > 128): values to the 1e-8 and gradients to the 1e-6 (1 + |g|max) of tests/test_path_sample_cpu.py, against
     path_ref.PathRef; qEUBO, a line and the EUBO pairs against qeubo_ref / line_ref on that PathRef and eubo_ref.eubo."""
-    r = sr.reference(N, D, 0.3, kernel)
+    r = sr.reference(N, D, case, kernel)
     assert not sr.beyond_guard(r["ell"], D)
     ref, q64, Xs = r["ref64"], r["q64"], r["Xs"]
     old = ph.PathRef(r["X"], r["y"], r["theta"], r["b"], kernel, r["nd"], sr.F, seed=r["seed"])
@@ -40,7 +51,7 @@ def test_inside_the_guard_it_is_the_restatement_of_the_path_tests(N, D, kernel):
         new_l, old_l = lr.line(ref, lines, sr.LINE_Q, anchor), lr.line(old, lines, sr.LINE_Q, anchor)
         assert np.abs(new_l[0] - old_l[0]).max() <= 1e-8 and np.array_equal(new_l[2], old_l[2])
         assert np.abs(new_l[1] - old_l[1]).max() <= 1e-6 * (1 + np.abs(old_l[1]).max())
-    e = sr.eubo_reference(N, D, 0.3, kernel)
+    e = sr.eubo_reference(N, D, case, kernel)
     rv, rg, info = eubo_ref.eubo(r["X"], r["y"], r["theta"], r["b"], kernel, e["pairs"])
     assert not info["bad"].any() and not e["e64"][2]["bad"].any()
     assert np.abs(e["e64"][0] - rv).max() <= 1e-8 and np.abs(e["e64"][1] - rg).max() <= 1e-6 * (1 + np.abs(rg).max())
