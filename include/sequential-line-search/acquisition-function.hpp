@@ -36,6 +36,27 @@ namespace sequential_line_search
         ParallelMultiStart,
     };
 
+    /// The affine image x = offset + basis z of the box z in [0,1]^d, 1 <= d <= D, that a search is restricted to (not in the
+    /// reference; include/sls_hip.h "maximisation over affine subspaces"): a trust region, a line or plane, a random embedding.
+    /// offset has D entries, basis is D x d.  The constructors only produce maps whose image lies inside [0,1]^D (a coordinate may
+    /// touch a face to within rounding); a hand-made one may leave it: the evaluations are defined on all of R^D.
+    struct SearchSubspace
+    {
+        Eigen::VectorXd offset;
+        Eigen::MatrixXd basis;
+
+        /// The box [lower, upper] (a trust region): offset = lower, basis = diag(upper - lower).  Throws std::invalid_argument
+        /// unless 0 <= lower <= upper <= 1 in every coordinate.
+        static SearchSubspace Box(const Eigen::VectorXd& lower, const Eigen::VectorXd& upper);
+        /// The segment from a (z = 0) to b (z = 1), d = 1: a slider.  Throws unless both ends lie in [0,1]^D.
+        static SearchSubspace Segment(const Eigen::VectorXd& a, const Eigen::VectorXd& b);
+        /// The image of [0,1]^d under `directions` (D x d), centred at `center` (in [0,1]^D): every row of `directions` that would
+        /// carry the image across a face is scaled down so that it just reaches it (0.5 sum_j |B_rj| <= min(center_r, 1 - center_r)).
+        static SearchSubspace Centered(const Eigen::VectorXd& center, const Eigen::MatrixXd& directions);
+        /// offset + basis z, in the device's arithmetic (from offset, one product and one sum per column of the basis).
+        Eigen::VectorXd Point(const Eigen::VectorXd& z) const;
+    };
+
     namespace acquisition_func
     {
         void                 SetGlobalSearchStrategy(GlobalSearchStrategy strategy);
@@ -244,6 +265,52 @@ namespace sequential_line_search
             const Regressor& regressor, const Eigen::VectorXd& anchor, const Eigen::MatrixXd& starts, const int num_positions = 9,
             const unsigned num_draws = 256, const unsigned num_local_search_iters = 50, const unsigned long long seed = 0,
             const int num_frequencies = 2048, double* value = nullptr);
+
+        /// The starts of every seeded search above and below (FindNextPointsByThompsonSampling, FindNextPointByMaxValueEntropySearch,
+        /// FindNextPointInSubspace, ...): num_dims x count numbers uniform in [0,1), column after column from one std::mt19937_64
+        /// seeded with `seed`.  With them and the tolerances of GetLocalSearchTolerances the ...FromStarts forms -- and the C ABI --
+        /// reproduce a seeded call.
+        Eigen::MatrixXd SeededUniformStarts(const unsigned num_dims, const long count, const unsigned long long seed);
+
+        /// Search restricted to affine subspaces (not in the reference; include/sls_hip.h sls_acq_*_sub, sls_path_*_sub).  Device-
+        /// resident regressors only (std::invalid_argument otherwise).
+        /// Acquisition values at subspace.Point(Z.col(m)) (Z is d x M) and their gradient in z (d x M) if grad_z != nullptr.
+        Eigen::VectorXd CalcAcquisitionValuesInSubspace(const Regressor& regressor, const SearchSubspace& subspace, const Eigen::MatrixXd& Z,
+                                                        const AcquisitionFuncType func_type = AcquisitionFuncType::ExpectedImprovement,
+                                                        const double gaussian_process_upper_confidence_bound_hyperparam = 1.0,
+                                                        Eigen::MatrixXd* grad_z = nullptr);
+        /// Maximiser of the acquisition function over the subspace: always the multi-start search, whatever the
+        /// GlobalSearchStrategy -- one L-BFGS of num_local_search_iters evaluations (the tolerances of GetLocalSearchTolerances) in
+        /// the d variables from each of num_global_search_iters uniform starts in [0,1]^d of the generator
+        /// FindNextPointByMaxValueEntropySearch uses, seeded with `seed`.  The same seed gives the same point.  Returns the point
+        /// x in R^D; value (may be nullptr) receives the acquisition value there.
+        Eigen::VectorXd FindNextPointInSubspace(const Regressor& regressor, const SearchSubspace& subspace,
+                                                const unsigned num_global_search_iters = 100, const unsigned num_local_search_iters = 50,
+                                                const AcquisitionFuncType func_type = AcquisitionFuncType::ExpectedImprovement,
+                                                const double gaussian_process_upper_confidence_bound_hyperparam = 1.0,
+                                                const unsigned long long seed = 0, double* value = nullptr);
+        /// Several subspaces of the same d in ONE lock-step search (several trust regions at once): start j (starts_z.col(j), d x S)
+        /// searches subspaces[subspace_of_start[j]].  Returns the best end point over all of them; winner_subspace (may be nullptr)
+        /// receives the subspace it lies in.
+        Eigen::VectorXd FindNextPointInSubspacesFromStarts(const Regressor& regressor, const std::vector<SearchSubspace>& subspaces,
+                                                           const std::vector<int>& subspace_of_start, const Eigen::MatrixXd& starts_z,
+                                                           const unsigned num_local_search_iters, const AcquisitionFuncType func_type,
+                                                           const double gaussian_process_upper_confidence_bound_hyperparam,
+                                                           double* value = nullptr, int* winner_subspace = nullptr);
+        /// FindNextPointInSubspace over SearchSubspace::Box(lower, upper).
+        Eigen::VectorXd FindNextPointInBox(const Regressor& regressor, const Eigen::VectorXd& lower, const Eigen::VectorXd& upper,
+                                           const unsigned num_global_search_iters = 100, const unsigned num_local_search_iters = 50,
+                                           const AcquisitionFuncType func_type = AcquisitionFuncType::ExpectedImprovement,
+                                           const double gaussian_process_upper_confidence_bound_hyperparam = 1.0,
+                                           const unsigned long long seed = 0, double* value = nullptr);
+        /// FindNextPointsByThompsonSampling with every draw maximised over the box [lower, upper] instead of the cube: the
+        /// candidate step of a trust-region method (TuRBO).  The same seed gives the same points.
+        std::vector<Eigen::VectorXd> FindNextPointsByThompsonSamplingInBox(const Regressor& regressor, const unsigned num_points,
+                                                                           const Eigen::VectorXd& lower, const Eigen::VectorXd& upper,
+                                                                           const unsigned num_global_search_iters = 100,
+                                                                           const unsigned num_local_search_iters  = 50,
+                                                                           const unsigned long long seed = 0,
+                                                                           const int num_frequencies = 2048);
     } // namespace acquisition_func
 } // namespace sequential_line_search
 

@@ -13,6 +13,8 @@ struct sls_path;
 
 namespace sequential_line_search
 {
+    struct SearchSubspace;   // acquisition-function.hpp
+
     class Regressor
     {
     public:
@@ -93,6 +95,11 @@ namespace sequential_line_search
         /// best end point.  values (may be nullptr) receives the draws' maxima.
         std::vector<Eigen::VectorXd> Maximize(const Eigen::MatrixXd& starts, unsigned num_local_search_iters,
                                               Eigen::VectorXd* values = nullptr) const;
+        /// Maximize with every draw searched over the affine subspace x = offset + basis z, z in [0,1]^d (SearchSubspace,
+        /// acquisition-function.hpp; include/sls_hip.h sls_path_maximize_sub): starts_z is d x (num_draws S).  Returns the draws'
+        /// best points x (D each); values (may be nullptr) receives their maxima over the subspace.
+        std::vector<Eigen::VectorXd> MaximizeInSubspace(const SearchSubspace& subspace, const Eigen::MatrixXd& starts_z,
+                                                        unsigned num_local_search_iters, Eigen::VectorXd* values = nullptr) const;
         /// Expected utility of the best of q = options.size() options on these draws (qEUBO, Astudillo et al. 2023; include/sls_hip.h
         /// sls_qeubo_*): set m is (options[0].col(m), .., options[q-1].col(m)), every options[i] D x M, 1 <= q <= 16.  Returns the M
         /// values; grads (may be nullptr) receives q matrices D x M, the gradient with respect to each option; win_counts (may be

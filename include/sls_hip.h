@@ -541,6 +541,67 @@ int sls_line_maximize(sls_path* p, int q, const double* baseline, const double* 
                       int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out,
                       long* idx_out, double* x_stars, double* y_stars);
 
+/* ---- maximisation over affine subspaces: boxes, lines, embeddings (not in the reference) ---------------------------------
+ * Every maximiser above searches [0,1]^D.  Trust regions (x = lo + diag(hi - lo) z), line and plane searches (x = a + (b - a) z)
+ * and random embeddings (x = c + A z, d << D) all search the affine image of a small box instead.  The *_sub entry points take the
+ * VARIABLES z in [0,1]^d, 1 <= d <= D, and a set of maps; a column (a query point, a start) with map k stands for the point
+ *   x = c_k + A_k z.
+ * Arithmetic (part of the contract: numpy restates it to the bit):
+ *   expand  x_r = c_r, then for j = 0..d-1 in increasing order  x_r = x_r + (A_rj z_j);    no clamp
+ *   fold    gz_j = 0,  then for r = 0..D-1 in increasing order  gz_j = gz_j + (A_rj gx_r)
+ * the product and the sum of every step rounded separately (never fused).  Between the two, the evaluation of the corresponding
+ * plain call runs unchanged on the expanded points: val is bit for bit what sls_acq_eval / sls_mes_eval / sls_path_eval return at
+ * X_out, grad_z the fold of their gradient.  A column's bits depend only on its own z and its own map -- not on the column it sits
+ * in, the tile, the compaction of the maximiser or the other maps.
+ * The maximisers clamp z to [0,1]^d exactly as the plain ones clamp x (the step kernels are the same); nothing requires the image
+ * to lie in [0,1]^D: the evaluations are defined on all of R^D and do not clamp.  (The host layer's constructors, SearchSubspace::Box /
+ * Segment / Centered, only produce maps whose image is inside the cube.)
+ * SLS_ERR_INVALID, checked on the host before any launch: a struct_size other than sizeof(sls_submaps), d < 1 or d > D, n_maps < 1,
+ * a NULL A or c, a non-finite entry of A or c, a map_of_column entry outside [0, n_maps).  M = 0 is a no-op.  Locks, generation
+ * checks (sls_path) and sls_acq_last_stats behave exactly as in the corresponding plain call.
+ * These routes NEVER take the one-wavefront kernel of small problems, the evaluation slots or the zero-copy path: always the tiled
+ * evaluation, as LogEI does (compare against plain calls under SLS_WAVE_PATH=0 when bits matter).
+ * Memory: A, c and map_of_column are uploaded once per call into one device block (8 n_maps D (d + 1) + 4 columns bytes); the expanded
+ * points and their gradient are two blocks of D x round_up(columns, 128) doubles, kept with the handle (sls_acq_*_sub, sls_mes_*_sub)
+ * or taken from the device pool for the call (sls_path_*_sub).
+ * Profiler scopes: "sub_expand" and "sub_fold", one launch each per evaluation / per round of a maximiser (plus one "sub_expand" for
+ * x_out / x_stars); everything between them counts as in the plain call.
+ * Out of scope: the pair and set criteria (sls_eubo_*, sls_qeubo_*, sls_qnei_*, sls_qlognei_*, sls_line_*), sls_acq_maximize_pair,
+ * sls_acq_maximize_dev and sls_multi_* have no _sub form. */
+typedef struct sls_submaps {
+    int struct_size;            /* sizeof(sls_submaps) as the caller's header declares it, as sls_lbfgs_opts */
+    int d;                      /* variables per column, 1 <= d <= D */
+    int n_maps;                 /* >= 1 */
+    const double* A;            /* n_maps blocks of D x d, column-major: A_k[r + j*D] */
+    const double* c;            /* n_maps blocks of D */
+    const int* map_of_column;   /* one entry per point / start, in [0, n_maps); NULL: every column uses map 0 */
+} sls_submaps;
+/* sls_acq_eval at x = c + A z: Z is d x M; val (M); grad_z (d x M, may be NULL); X_out (D x M, may be NULL) = the expanded points.
+ * All three acquisition types. */
+int sls_acq_eval_sub(sls_gp* gp, int acq_type, double ucb_h, const sls_submaps* maps, const double* Z, int M, double* val,
+                     double* grad_z, double* X_out);
+/* sls_acq_maximize over z in [0,1]^d: starts_z is d x S, map_of_column has S entries.  z_out (d) / x_out (D) are the winner's variables
+ * and point, z_stars (d x S) / x_stars (D x S) every start's; x is the expansion of z (one more expand launch: x_stars is bit for
+ * bit the contract's expand of z_stars).  Any out pointer may be NULL.  val_out, idx_out, y_stars, start_index_offset and
+ * sls_acq_last_stats as in sls_acq_maximize. */
+int sls_acq_maximize_sub(sls_gp* gp, int acq_type, double ucb_h, const sls_submaps* maps, const double* starts_z, int S, int n_local,
+                         const sls_lbfgs_opts* opts, long start_index_offset, double* z_out, double* x_out, double* val_out,
+                         long* idx_out, double* z_stars, double* x_stars, double* y_stars);
+/* The same pair for max-value entropy search: y_star, K as in sls_mes_eval / sls_mes_maximize. */
+int sls_mes_eval_sub(sls_gp* gp, const double* y_star, int K, const sls_submaps* maps, const double* Z, int M, double* val,
+                     double* grad_z, double* X_out);
+int sls_mes_maximize_sub(sls_gp* gp, const double* y_star, int K, const sls_submaps* maps, const double* starts_z, int S, int n_local,
+                         const sls_lbfgs_opts* opts, long start_index_offset, double* z_out, double* x_out, double* val_out,
+                         long* idx_out, double* z_stars, double* x_stars, double* y_stars);
+/* The same pair for the path draws.  sls_path_eval_sub: the gathered form only -- draw_of_point must not be NULL;
+ * val[m] = f_{draw_of_point[m]}(c + A Z[:,m]).  sls_path_maximize_sub: starts_z is d x (n_draws S), columns [s S, (s+1) S) belong to
+ * draw s and map_of_column is indexed by that column (n_draws S entries); per draw, as sls_path_maximize returns them, z_out
+ * (d x n_draws), x_out (D x n_draws), val_out and idx_out (n_draws each; the start index within the draw). */
+int sls_path_eval_sub(sls_path* p, const sls_submaps* maps, const double* Z, int M, const int* draw_of_point, double* val,
+                      double* grad_z, double* X_out);
+int sls_path_maximize_sub(sls_path* p, const sls_submaps* maps, const double* starts_z, int S, int n_local, const sls_lbfgs_opts* opts,
+                          double* z_out, double* x_out, double* val_out, long* idx_out);
+
 /* ---- multi-GPU maximisation ------------------------------------------------------------------------------
  * FindGlobalSolution's multi-start loop (src/acquisition-function.cpp:121-153) shards over its starts: the iterations share
  * only the const regressor (:125-141).  Every GPU holds a replica of the fitted state, runs a contiguous slice of the starts
@@ -677,6 +738,8 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
  * sls_qlognei_eval / per pass and round of sls_qlognei_maximize; every other stage counts as under qEUBO);
  * "line" (line_expand and line_fold: two launches per pass of sls_line_eval -- one without a gradient -- / per pass and round of
  * sls_line_maximize; the pass between them counts as under qEUBO / qNEI);
+ * "sub_expand" and "sub_fold" (the two kernels of the *_sub calls: one launch each per evaluation / per round of a maximiser, one more
+ * "sub_expand" for x_out / x_stars; the evaluation between them counts as in the plain call);
  * "potrf_fallbacks": launches = how often a single-launch factorisation gave up and was recomputed. */
 int sls_prof_enable(sls_ctx* ctx, int on);
 int sls_prof_reset(sls_ctx* ctx);

@@ -339,6 +339,38 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
           "regressor"_a, "num_points"_a, "starts"_a, "num_draws"_a = 256, "num_local_search_iters"_a = 50, "seed"_a = 0ULL,
           "num_frequencies"_a = 2048, "tau_relu"_a = 1e-6, "tau_max"_a = 1e-2);
 
+    // the starts of the seeded searches (acquisition-function.hpp): num_dims x count
+    m.def("seeded_uniform_starts", &acquisition_func::SeededUniformStarts, "num_dims"_a, "count"_a, "seed"_a = 0ULL);
+    // search restricted to a box / an affine subspace x = offset + basis z, z in [0,1]^d (acquisition-function.hpp): (x, value)
+    m.def("find_next_point_in_box",
+          [](const Regressor& r, const VectorXd& lower, const VectorXd& upper, unsigned num_global_search_iters,
+             unsigned num_local_search_iters, AcquisitionFuncType func_type, double hyperparam, unsigned long long seed) {
+              double         value = 0.0;
+              const VectorXd x     = acquisition_func::FindNextPointInBox(r, lower, upper, num_global_search_iters, num_local_search_iters,
+                                                                      func_type, hyperparam, seed, &value);
+              return std::make_pair(x, value);
+          },
+          "regressor"_a, "lower"_a, "upper"_a, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50,
+          "func_type"_a = AcquisitionFuncType::ExpectedImprovement, "gaussian_process_upper_confidence_bound_hyperparam"_a = 1.0,
+          "seed"_a = 0ULL);
+    m.def("find_next_point_in_subspace",
+          [](const Regressor& r, const VectorXd& offset, const MatrixXd& basis, unsigned num_global_search_iters,
+             unsigned num_local_search_iters, AcquisitionFuncType func_type, double hyperparam, unsigned long long seed) {
+              SearchSubspace s;
+              s.offset             = offset;
+              s.basis              = basis;
+              double         value = 0.0;
+              const VectorXd x     = acquisition_func::FindNextPointInSubspace(r, s, num_global_search_iters, num_local_search_iters,
+                                                                           func_type, hyperparam, seed, &value);
+              return std::make_pair(x, value);
+          },
+          "regressor"_a, "offset"_a, "basis"_a, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50,
+          "func_type"_a = AcquisitionFuncType::ExpectedImprovement, "gaussian_process_upper_confidence_bound_hyperparam"_a = 1.0,
+          "seed"_a = 0ULL);
+    m.def("find_next_points_by_thompson_sampling_in_box", &acquisition_func::FindNextPointsByThompsonSamplingInBox, "regressor"_a,
+          "num_points"_a, "lower"_a, "upper"_a, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50, "seed"_a = 0ULL,
+          "num_frequencies"_a = 2048);
+
     // the next slider by the expected utility of its best position (acquisition-function.hpp): ((end_0, end_1), value); an empty anchor
     // leaves both ends free
     m.def("find_next_slider_by_expected_utility",

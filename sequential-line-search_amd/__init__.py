@@ -38,6 +38,46 @@ class LbfgsOpts(C.Structure):
         super().__init__(C.sizeof(LbfgsOpts), history, c1, shrink, gtol, max_backtracks, ftol_rel, xtol_rel)
 
 
+class _SubMapsStruct(C.Structure):
+    """sls_submaps (include/sls_hip.h)."""
+    _fields_ = [("struct_size", C.c_int), ("d", C.c_int), ("n_maps", C.c_int), ("A", _dp), ("c", _dp), ("map_of_column", C.POINTER(C.c_int))]
+
+
+class SubMaps:
+    """The maps of a *_sub call (sls_submaps): a column with map k stands for the point x = c[k] + A[k] @ z.  A is (n_maps, D, d) or
+    (D, d), c is (n_maps, D) or (D,); map_of_column (one entry per point / start, None: every column uses map 0).  Nothing is
+    checked here: the library refuses what the contract refuses."""
+
+    def __init__(self, A, c, map_of_column=None):
+        A, c = np.asarray(A, dtype=np.float64), np.asarray(c, dtype=np.float64)
+        if A.ndim == 2:
+            A, c = A[None], c.reshape(1, -1)
+        assert A.ndim == 3 and c.shape == A.shape[:2], (A.shape, c.shape)
+        self.n_maps, self.D, self.d = A.shape
+        self.A, self.c = A, c
+        # n_maps blocks of D x d, column-major: A_k[r + j*D]
+        self._A = np.ascontiguousarray(A.transpose(0, 2, 1)).ravel()
+        self._c = np.ascontiguousarray(c).ravel()
+        self.map_of_column = None if map_of_column is None else np.ascontiguousarray(np.asarray(map_of_column, dtype=np.int32).ravel())
+
+    def struct(self, **override):
+        """The C struct (keeps this object's arrays alive only as long as this object lives); override: members for refusal tests."""
+        moc = self.map_of_column
+        s = _SubMapsStruct(C.sizeof(_SubMapsStruct), self.d, self.n_maps, _p(self._A), _p(self._c),
+                           moc.ctypes.data_as(C.POINTER(C.c_int)) if moc is not None else None)
+        for k, v in override.items():
+            setattr(s, k, v)
+        return s
+
+    def subset(self, columns):
+        """The same maps for a subset (or reordering) of the columns."""
+        return SubMaps(self.A, self.c, None if self.map_of_column is None else self.map_of_column[np.asarray(columns)])
+
+
+def _sub_struct(maps):
+    return maps if isinstance(maps, _SubMapsStruct) else maps.struct()
+
+
 def lib():
     """Load libsls_hip.so (raises if it has not been built -- see __graft_entry__.build())."""
     global _lib
@@ -68,6 +108,7 @@ EXPORTS = [
     "sls_path_max_over_points", "sls_qnei_eval", "sls_qnei_maximize",
     "sls_line_eval", "sls_line_maximize",
     "sls_qlognei_terms", "sls_qlognei_eval", "sls_qlognei_maximize",
+    "sls_acq_eval_sub", "sls_acq_maximize_sub", "sls_mes_eval_sub", "sls_mes_maximize_sub", "sls_path_eval_sub", "sls_path_maximize_sub",
 ]
 
 
@@ -374,6 +415,52 @@ class GP:
                                     _p(ys) if want_all else None))
         return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
 
+    # ---- maximisation over affine subspaces (sls_*_sub): maps is a SubMaps (or its C struct), Z / starts_z are d x M / d x S
+    def _eval_sub(self, call, maps, Z, want_grad, want_x):
+        s = _sub_struct(maps)
+        Z = _f(Z)
+        rows, M = max(1, s.d), Z.shape[1]
+        val = np.empty(M)
+        grad = np.empty((rows, M), order="F") if want_grad else None
+        X = np.empty((self.D, M), order="F") if want_x else None
+        _ck(call(C.byref(s), _p(Z), M, _p(val), _p(grad) if want_grad else None, _p(X) if want_x else None))
+        out = (val,) + ((grad,) if want_grad else ()) + ((X,) if want_x else ())
+        return out if len(out) > 1 else val
+
+    def _maximize_sub(self, call, maps, starts_z, n_local, offset, want_all, opts):
+        s = _sub_struct(maps)
+        starts_z = _f(starts_z)
+        rows, S = max(1, s.d), starts_z.shape[1]
+        z, x, val, idx = np.empty(rows), np.empty(self.D), C.c_double(), C.c_long()
+        zs = np.empty((rows, S), order="F") if want_all else None
+        xs = np.empty((self.D, S), order="F") if want_all else None
+        ys = np.empty(S) if want_all else None
+        _ck(call(C.byref(s), _p(starts_z), S, int(n_local), C.byref(opts) if opts is not None else None, C.c_long(offset), _p(z), _p(x),
+                 C.byref(val), C.byref(idx), _p(zs) if want_all else None, _p(xs) if want_all else None, _p(ys) if want_all else None))
+        return dict(index=idx.value, z=z, x=x, value=val.value, z_stars=zs, x_stars=xs, y_stars=ys)
+
+    def acq_eval_sub(self, maps, Z, acq=ACQ_EI, ucb_h=1.0, want_grad=True, want_x=False):
+        """acq_eval at x = c + A z (sls_acq_eval_sub): values (M,), then with want_grad the gradient in z (d, M), then with want_x the
+        expanded points (D, M)."""
+        return self._eval_sub(lambda *a: lib().sls_acq_eval_sub(self.h, int(acq), C.c_double(ucb_h), *a), maps, Z, want_grad, want_x)
+
+    def acq_maximize_sub(self, maps, starts_z, n_local, acq=ACQ_EI, ucb_h=1.0, offset=0, want_all=True, opts=None):
+        """acq_maximize over z in [0,1]^d with x = c + A z (sls_acq_maximize_sub): z / x of the winner, z_stars (d, S) / x_stars (D, S) /
+        y_stars of every start."""
+        return self._maximize_sub(lambda *a: lib().sls_acq_maximize_sub(self.h, int(acq), C.c_double(ucb_h), *a), maps, starts_z, n_local,
+                                  offset, want_all, opts)
+
+    def mes_eval_sub(self, y_star, maps, Z, want_grad=True, want_x=False):
+        """mes_eval at x = c + A z (sls_mes_eval_sub)."""
+        y_star = _f(y_star).ravel()
+        return self._eval_sub(lambda *a: lib().sls_mes_eval_sub(self.h, _p(y_star), y_star.size, *a), maps, Z, want_grad, want_x)
+
+    def mes_maximize_sub(self, y_star, maps, starts_z, n_local, offset=0, want_all=True, opts=None):
+        """mes_maximize over z in [0,1]^d with x = c + A z (sls_mes_maximize_sub)."""
+        y_star = _f(y_star).ravel()
+        return self._maximize_sub(lambda *a: lib().sls_mes_maximize_sub(self.h, _p(y_star), y_star.size, *a), maps, starts_z, n_local,
+                                  offset, want_all, opts)
+
     def last_stats(self):
         """Evaluation counts of the last acq_maximize* call (sls_acq_last_stats)."""
         issued, cap, rounds, live = C.c_long(), C.c_long(), C.c_int(), C.c_int()
@@ -442,6 +529,39 @@ class PathSamples:
         _ck(lib().sls_path_maximize(self.h, _p(starts), S, int(n_local), C.byref(opts) if opts is not None else None, _p(x), _p(val),
                                     idx.ctypes.data_as(C.POINTER(C.c_long))))
         return dict(x=x, value=val, index=idx)
+
+    def eval_sub(self, maps, Z, draw_of_point, want_grad=True, want_x=False):
+        """eval at x = c + A z (sls_path_eval_sub): values (M,), then with want_grad the gradient in z (d, M), then with want_x the
+        expanded points (D, M)."""
+        s = _sub_struct(maps)
+        Z = _f(Z)
+        rows, M = max(1, s.d), Z.shape[1]
+        dr = None if draw_of_point is None else np.ascontiguousarray(np.asarray(draw_of_point, dtype=np.int32))
+        assert dr is None or dr.shape == (M,)
+        val = np.empty(M)
+        grad = np.empty((rows, M), order="F") if want_grad else None
+        X = np.empty((self.D, M), order="F") if want_x else None
+        _ck(lib().sls_path_eval_sub(self.h, C.byref(s), _p(Z), M, dr.ctypes.data_as(C.POINTER(C.c_int)) if dr is not None else None,
+                                    _p(val), _p(grad) if want_grad else None, _p(X) if want_x else None))
+        out = (val,) + ((grad,) if want_grad else ()) + ((X,) if want_x else ())
+        return out if len(out) > 1 else val
+
+    def maximize_sub(self, maps, starts_z, n_local, opts=None):
+        """maximize over z in [0,1]^d with x = c + A z (sls_path_maximize_sub): starts_z (d, n_draws * S), columns [s S, (s + 1) S) for
+        draw s; per draw z (d, n_draws), x (D, n_draws), value and the start index within the draw."""
+        s = _sub_struct(maps)
+        starts_z = _f(starts_z)
+        T = starts_z.shape[1]
+        assert T % self.n_draws == 0
+        rows = max(1, s.d)
+        z = np.empty((rows, self.n_draws), order="F")
+        x = np.empty((self.D, self.n_draws), order="F")
+        val = np.empty(self.n_draws)
+        idx = np.empty(self.n_draws, dtype=np.int64)
+        _ck(lib().sls_path_maximize_sub(self.h, C.byref(s), _p(starts_z), T // self.n_draws, int(n_local),
+                                        C.byref(opts) if opts is not None else None, _p(z), _p(x), _p(val),
+                                        idx.ctypes.data_as(C.POINTER(C.c_long))))
+        return dict(z=z, x=x, value=val, index=idx)
 
     def qeubo_eval(self, sets, q, want_grad=True, want_wins=False):
         """Expected utility of the best of q options on the draws (sls_qeubo_eval) at the columns of sets (qD x M: rows iD..iD+D-1 =

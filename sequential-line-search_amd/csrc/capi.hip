@@ -15,6 +15,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "lbfgs_driver.hpp"
+#include "sub_maps.hpp"
 
 using namespace slsk;
 
@@ -414,6 +415,8 @@ struct sls_gp {
     DBuf eubo_Ks, eubo_Cs, eubo_XsT, eubo_ns, eubo_parts, eubo_Gs, eubo_Gm, eubo_Kd;
     int eubo_chunk = 0, eubo_np = 0;
     HostBuf eubo_best;   // mapped: the pair maximiser's best start (8 + 2D doubles; `sum` holds 8 + D)
+    // the *_sub entry points: the expanded points x = c + A z and their gradient, D x round_up(columns, 128) doubles each, grown on demand
+    DBuf sub_x, sub_gx;
     // 0: sigma^2 = a - k^T K^-1 k with the explicit inverse (GaussianProcessRegressor); 1: a - |L^-1 k|^2, the Cholesky solve of
     // PreferenceRegressor (sls_gp_set_sigma_mode)
     int sigma_mode = 0;
@@ -1399,6 +1402,133 @@ extern "C" int sls_mes_maximize(sls_gp* g, const double* y_star, int K, const do
     const MesSamples mes{ys.p, K};
     maximize_impl("sls_mes_maximize", g, nullptr, 0, 0.0, starts, true, S, n_local, opts, start_index_offset, x_out, val_out, idx_out,
                   x_stars, y_stars, &mes);
+    SLS_CATCH
+}
+
+// ---- maximisation over affine subspaces (include/sls_hip.h) --------------------------------------------------------------
+// eval_acq at x = c + A z: expand the candidate-major variables z[n + j*ld] (n < count; column n is start live[n], nullptr: identity)
+// into the handle's block of points, the unchanged evaluation there, then the fold of its gradient onto z.  Always the tiled evaluation.
+// The expand pads the last 128-wide tile of the points with 0.5; the gradient block is written by the evaluation for n < count and
+// read by the fold for n < count only.
+static void sub_eval_device(sls_gp* g, const SubMaps& m, const double* z, long ld, int count, const int* live, int acq_type, double ucb_h,
+                            double* val, double* grad_z, const MesSamples* mes) {
+    sls_ctx* c = g->ctx;
+    g->sub_x.ensure((size_t)g->D * ld);
+    if (grad_z) g->sub_gx.ensure((size_t)g->D * ld);
+    sub_expand(c, m, count, live, z, ld, g->sub_x.p, ld);
+    eval_acq(g, nullptr, g->sub_x.p, ld, count, acq_type, ucb_h, val, grad_z ? g->sub_gx.p : nullptr, ld, mes);
+    if (grad_z) sub_fold(c, m, count, live, g->sub_gx.p, ld, grad_z, ld);
+}
+
+// The body of sls_acq_eval_sub and sls_mes_eval_sub (M >= 1): Z is d x M on the host; results to the caller's arrays.
+static void eval_sub_points(const char* who, sls_gp* g, int acq_type, double ucb_h, const sls_submaps* maps, const double* Z, int M,
+                            double* val, double* grad_z, double* X_out, const MesSamples* mes) {
+    SubMapsDev up;
+    upload_sub_maps(who, g->ctx, maps, g->D, M, up);
+    const int Mp = round_up(M, 128), d = up.m.d;
+    upload_candidates(g, Z, d, M, Mp);
+    std::vector<double> unused;   // the combiners always write the values
+    if (!val) unused.resize(M);
+    EvalOut want;
+    want.val = val ? val : unused.data(); want.grad = grad_z;
+    g->outv.ensure(eval_block_doubles(want, d, Mp));
+    const EvalOut o = eval_block(want, g->outv.p, d, Mp);
+    sub_eval_device(g, up.m, g->raw.p, Mp, M, nullptr, acq_type, ucb_h, o.val, o.grad, mes);
+    download_block(g, want, g->outv.p, d, M, Mp);
+    if (X_out) {
+        std::vector<double> pageable;
+        cm_to_host(fetch(g, g->sub_x.p, (size_t)g->D * Mp, pageable), Mp, g->D, M, X_out);
+    }
+}
+
+// The body of sls_acq_maximize_sub and sls_mes_maximize_sub: the shared maximiser in the d variables with sub_eval_device as its
+// objective -- the step kernels see z in [0,1]^d and nothing else --, then one more expand launch for the points of the end variables.
+static void maximize_sub_impl(const char* who, sls_gp* g, int acq_type, double ucb_h, const sls_submaps* maps, const double* starts_z, int S,
+                              int n_local, const sls_lbfgs_opts* opts_in, long off, double* z_out, double* x_out, double* val_out,
+                              long* idx_out, double* z_stars, double* x_stars, double* y_stars, const MesSamples* mes = nullptr) {
+    sls_ctx* c = g->ctx;
+    SLS_REQUIRE(mes || known_acq(acq_type), "unknown acquisition type %d", acq_type);
+    SLS_REQUIRE(S >= 1, "%s: need S >= 1 (S = %d)", who, S);
+    SubMapsDev up;
+    upload_sub_maps(who, c, maps, g->D, S, up);
+    const int D = g->D, d = up.m.d;
+    MultistartRun r = maximize_begin(who, g, g->lb, opts_in, S, n_local, d);
+    DBuf sd;
+    sd.ensure((size_t)d * S);
+    h2d(c, sd.p, starts_z, (size_t)d * S);
+    LockstepStats ls;
+    lockstep_rounds(c, r.st, g->lb, sd.p, S, n_local,
+                    [&](const double* trial, long ld, int nlive, const int* live, double* val, double* grad) {
+                        sub_eval_device(g, up.m, trial, ld, nlive, live, acq_type, ucb_h, val, grad, mes);
+                    },
+                    &ls);
+    std::vector<double> pageable;
+    const long winner = maximize_finish(c, r, ls, BestBlock{g->sum.dev + 8, g->sum.host + 8, false}, staged_fetch(g, pageable), off, z_out,
+                                        val_out, idx_out, z_stars, y_stars);
+    if (!x_out && !x_stars) return;
+    const long ld = r.st.ld;
+    g->sub_x.ensure((size_t)D * ld);
+    sub_expand(c, up.m, S, nullptr, r.st.x, ld, g->sub_x.p, ld);
+    const double* xs = fetch(g, g->sub_x.p, (size_t)D * ld, pageable);
+    if (x_out)
+        for (int rr = 0; rr < D; ++rr) x_out[rr] = xs[(size_t)winner + (size_t)rr * ld];
+    cm_to_host(xs, ld, D, S, x_stars);
+}
+
+extern "C" int sls_acq_eval_sub(sls_gp* g, int acq_type, double ucb_h, const sls_submaps* maps, const double* Z, int M, double* val,
+                                double* grad_z, double* X_out) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g && M >= 0, "sls_acq_eval_sub: bad argument");
+    SLS_REQUIRE(known_acq(acq_type), "unknown acquisition type %d", acq_type);
+    if (M == 0) return SLS_OK;
+    SLS_REQUIRE(Z != nullptr, "sls_acq_eval_sub: Z is NULL");
+    eval_sub_points("sls_acq_eval_sub", g, acq_type, ucb_h, maps, Z, M, val, grad_z, X_out, nullptr);
+    SLS_CATCH
+}
+
+extern "C" int sls_acq_maximize_sub(sls_gp* g, int acq_type, double ucb_h, const sls_submaps* maps, const double* starts_z, int S,
+                                    int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* z_out, double* x_out,
+                                    double* val_out, long* idx_out, double* z_stars, double* x_stars, double* y_stars) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g && starts_z, "sls_acq_maximize_sub: NULL argument");
+    maximize_sub_impl("sls_acq_maximize_sub", g, acq_type, ucb_h, maps, starts_z, S, n_local, opts, start_index_offset, z_out, x_out,
+                      val_out, idx_out, z_stars, x_stars, y_stars);
+    SLS_CATCH
+}
+
+extern "C" int sls_mes_eval_sub(sls_gp* g, const double* y_star, int K, const sls_submaps* maps, const double* Z, int M, double* val,
+                                double* grad_z, double* X_out) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g != nullptr, "sls_mes_eval_sub: gp is NULL");
+    SLS_REQUIRE(M >= 0, "sls_mes_eval_sub: M = %d", M);
+    DBuf ys;
+    upload_max_values("sls_mes_eval_sub", g, y_star, K, ys);
+    if (M == 0) {
+        sync(g->ctx);
+        return SLS_OK;
+    }
+    SLS_REQUIRE(Z != nullptr, "sls_mes_eval_sub: Z is NULL");
+    SLS_REQUIRE(val != nullptr, "sls_mes_eval_sub: val is NULL");
+    const MesSamples mes{ys.p, K};
+    eval_sub_points("sls_mes_eval_sub", g, 0, 0.0, maps, Z, M, val, grad_z, X_out, &mes);
+    SLS_CATCH
+}
+
+extern "C" int sls_mes_maximize_sub(sls_gp* g, const double* y_star, int K, const sls_submaps* maps, const double* starts_z, int S,
+                                    int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* z_out, double* x_out,
+                                    double* val_out, long* idx_out, double* z_stars, double* x_stars, double* y_stars) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g != nullptr, "sls_mes_maximize_sub: gp is NULL");
+    SLS_REQUIRE(starts_z != nullptr, "sls_mes_maximize_sub: starts_z is NULL");
+    DBuf ys;
+    upload_max_values("sls_mes_maximize_sub", g, y_star, K, ys);
+    const MesSamples mes{ys.p, K};
+    maximize_sub_impl("sls_mes_maximize_sub", g, 0, 0.0, maps, starts_z, S, n_local, opts, start_index_offset, z_out, x_out, val_out,
+                      idx_out, z_stars, x_stars, y_stars, &mes);
     SLS_CATCH
 }
 

@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "lbfgs_driver.hpp"
+#include "sub_maps.hpp"
 
 using namespace slsk;
 
@@ -293,6 +294,116 @@ extern "C" int sls_path_maximize(sls_path* p, const double* starts, int S, int n
         if (val_out) val_out[s] = b[0];
         if (idx_out) idx_out[s] = (long)b[1];
         if (x_out) std::copy(b + 2, b + 2 + D, x_out + (size_t)s * D);
+    }
+    SLS_CATCH
+}
+
+// ---- the draws over affine subspaces (include/sls_hip.h "maximisation over affine subspaces") ------------------------------------
+namespace {
+
+// The two blocks of a call: the expanded points x = c + A z and their gradient, D x ld doubles each, from the device pool
+struct SubWs {
+    DBuf x, gx;
+};
+
+// path_eval_device (gathered form) at x = c + A z: z[n + j*ld] candidate-major, n < count, column n is start live[n] (nullptr:
+// identity) under draw[n]; the fold of the gradient onto z goes to grad_z[n + j*ld] (may be nullptr).
+void path_sub_eval_device(sls_path* p, const GpView& g, EvalWs& ws, SubWs& sw, const SubMaps& m, const double* z, long ld, int count,
+                          const int* live, const int* draw, double* val, double* grad_z) {
+    sls_ctx* c = g.ctx;
+    sw.x.ensure((size_t)g.D * ld);
+    if (grad_z) sw.gx.ensure((size_t)g.D * ld);
+    sub_expand(c, m, count, live, z, ld, sw.x.p, ld);
+    path_eval_device(p, g, ws, sw.x.p, ld, false, count, draw, val, 0, grad_z ? sw.gx.p : nullptr, ld);
+    if (grad_z) sub_fold(c, m, count, live, sw.gx.p, ld, grad_z, ld);
+}
+
+}  // namespace
+
+extern "C" int sls_path_eval_sub(sls_path* p, const sls_submaps* maps, const double* Z, int M, const int* draw_of_point, double* val,
+                                 double* grad_z, double* X_out) {
+    SLS_TRY
+    SLS_REQUIRE(p != nullptr, "sls_path_eval_sub: p is NULL");
+    SLS_REQUIRE(M >= 0, "sls_path_eval_sub: M = %d", M);
+    if (M == 0) return SLS_OK;
+    SLS_REQUIRE(draw_of_point != nullptr, "sls_path_eval_sub: draw_of_point is NULL (the every-draw form has no _sub call)");
+    SLS_REQUIRE(Z && val, "sls_path_eval_sub: Z / val is NULL");
+    for (int m = 0; m < M; ++m)
+        SLS_REQUIRE(draw_of_point[m] >= 0 && draw_of_point[m] < p->n_draws, "sls_path_eval_sub: draw_of_point[%d] = %d (n_draws = %d)", m,
+                    draw_of_point[m], p->n_draws);
+    GpReadCall call(p->gp, p->generation, "sls_path_eval_sub");
+    const GpView& g = call.g;
+    sls_ctx* c = g.ctx;
+    SubMapsDev up;
+    upload_sub_maps("sls_path_eval_sub", c, maps, g.D, M, up);
+    const int D = g.D, d = up.m.d, Mp = round_up(M, 128);
+    const std::vector<double> zh = host_to_cm(Z, d, M, Mp);
+    DBuf zd, vout, gout, dbuf;
+    zd.ensure(zh.size());
+    h2d(c, zd.p, zh.data(), zh.size());
+    int* d_draw = ints(dbuf, (size_t)M);
+    SLS_HIP(hipMemcpyAsync(d_draw, draw_of_point, (size_t)M * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    vout.ensure(Mp);
+    if (grad_z) gout.ensure((size_t)Mp * d);
+    EvalWs ws;
+    SubWs sw;
+    path_sub_eval_device(p, g, ws, sw, up.m, zd.p, Mp, M, nullptr, d_draw, vout.p, grad_z ? gout.p : nullptr);
+    d2h(c, val, vout.p, (size_t)M);
+    std::vector<double> gh(grad_z ? (size_t)Mp * d : 0), xh(X_out ? (size_t)Mp * D : 0);
+    if (grad_z) d2h(c, gh.data(), gout.p, gh.size());
+    if (X_out) d2h(c, xh.data(), sw.x.p, xh.size());
+    SLS_HIP(hipStreamSynchronize(c->stream));
+    cm_to_host(gh.data(), Mp, d, M, grad_z);
+    cm_to_host(xh.data(), Mp, D, M, X_out);
+    SLS_CATCH
+}
+
+extern "C" int sls_path_maximize_sub(sls_path* p, const sls_submaps* maps, const double* starts_z, int S, int n_local,
+                                     const sls_lbfgs_opts* opts, double* z_out, double* x_out, double* val_out, long* idx_out) {
+    SLS_TRY
+    SLS_REQUIRE(p && starts_z, "sls_path_maximize_sub: NULL argument");
+    SLS_REQUIRE(S >= 1 && (long)S * p->n_draws <= (1L << 26), "sls_path_maximize_sub: S = %d starts per draw (1 .. 2^26 / n_draws)", S);
+    GpReadCall call(p->gp, p->generation, "sls_path_maximize_sub");
+    const GpView& g = call.g;
+    sls_ctx* c = g.ctx;
+    const int D = g.D, nd = p->n_draws, T = S * nd, Sp = round_up(T, 128);
+    SubMapsDev up;
+    upload_sub_maps("sls_path_maximize_sub", c, maps, D, T, up);
+    const int d = up.m.d;
+    // sls_path_maximize in the d variables: all T = n_draws S starts in one search, the winner per draw
+    LbfgsWs lb;
+    EvalWs ws;
+    SubWs sw;
+    MultistartRun r = maximize_begin("sls_path_maximize_sub", nullptr, lb, opts, T, n_local, d, Sp);
+    const LbfgsState& st = r.st;
+    int* d_draw = lb.tail();   // the draw of every live column
+    DBuf sd;
+    sd.ensure((size_t)d * T);
+    h2d(c, sd.p, starts_z, (size_t)d * T);
+    lockstep_rounds(c, r.st, lb, sd.p, T, n_local,
+                    [&](const double* trial, long ld, int nlive, const int* live, double* val, double* grad) {
+                        launch_path_draw_of_live(c->stream, live, nlive, S, d_draw);
+                        path_sub_eval_device(p, g, ws, sw, up.m, trial, ld, nlive, live, d_draw, val, grad);
+                    },
+                    nullptr);
+    // the points of the end variables (one more expand launch), then the per-draw first maximum once with z and once with x
+    sw.x.ensure((size_t)D * Sp);
+    sub_expand(c, up.m, T, nullptr, st.x, Sp, sw.x.p, Sp);
+    DBuf best;
+    const size_t nz = (size_t)nd * (d + 2), nx = (size_t)nd * (D + 2);
+    best.ensure(nz + nx);
+    launch_path_argmax(c->stream, st.f, S, nd, st.x, Sp, d, best.p);
+    launch_path_argmax(c->stream, st.f, S, nd, sw.x.p, Sp, D, best.p + nz);
+    std::vector<double> bh(nz + nx);
+    d2h(c, bh.data(), best.p, bh.size());
+    SLS_HIP(hipStreamSynchronize(c->stream));
+    for (int s = 0; s < nd; ++s) {
+        const double* bz = bh.data() + (size_t)s * (d + 2);
+        const double* bx = bh.data() + nz + (size_t)s * (D + 2);
+        if (val_out) val_out[s] = bz[0];
+        if (idx_out) idx_out[s] = (long)bz[1];
+        if (z_out) std::copy(bz + 2, bz + 2 + d, z_out + (size_t)s * d);
+        if (x_out) std::copy(bx + 2, bx + 2 + D, x_out + (size_t)s * D);
     }
     SLS_CATCH
 }

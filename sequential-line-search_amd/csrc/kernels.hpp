@@ -563,6 +563,22 @@ void launch_line_expand(hipStream_t s, int nlines, int D, int q, const double* t
 // grad_b; anchored: grad[n + d*ldo] = grad_b alone.
 void launch_line_fold(hipStream_t s, int nlines, int D, int q, bool anchored, const double* sgrad, long lds, double* grad, long ldo);
 
+// ---- kernels_sub.hip: search over affine subspaces (the *_sub entry points) ------------------------------------------------
+// The maps of one call as the kernels read them (device pointers into ONE block, uploaded once per call): n_maps blocks A_k of D x d,
+// column-major A_k[r + j*D], n_maps blocks c_k of D, and the map of every column of the call (nullptr: every column uses map 0).
+struct SubMaps {
+    int D, d, n_maps;
+    const double* A;
+    const double* c;
+    const int* map_of_column;
+};
+// X[n + r*ldx] = c_r + sum_j A_rj z[n + j*ld] for n < ncols, r < D, with the map of column (live ? live[n] : n): from c_r, one product
+// and one sum per j in increasing j, never fused.  No clamp.  A column's bits depend on its own z and its own map alone.
+// The columns ncols <= n < min(round_up(ncols, 128), ldx) are set to 0.5 (the padding of the last tile the evaluation reads).
+void launch_sub_expand(hipStream_t s, const SubMaps& m, int ncols, const int* live, const double* z, long ld, double* X, long ldx);
+// gz[n + j*ldo] = sum_r A_rj gx[n + r*ldx] for n < ncols, j < d: from zero, one product and one sum per r in increasing r, never fused.
+void launch_sub_fold(hipStream_t s, const SubMaps& m, int ncols, const int* live, const double* gx, long ldx, double* gz, long ldo);
+
 // ---- kernels_map.hip -----------------------------------------------------------
 // MAP-gradient weights (replaces the (D+1) x N x N tensor of CalcLargeKYThetaDerivative, src/regressor.cpp:110-134):
 // G[j + k*Np] = 1/2 (alpha_j alpha_k - Kinv_jk) c_jk  (0 in the padding);  wk_part[tile] = sum over the tile of

@@ -143,8 +143,9 @@ struct BestBlock {
 // Epilogue of a maximiser with ONE winner: first maximum of -f and its point in one launch, ONE synchronisation, the statistics, then
 // what the caller asked for -- value, index (+ off) and point of the winner; every start's end point (x_stars, nvar x S column-major)
 // and value (y_stars).  fetch(dev, n): n doubles of device memory where the host can read them on return (one synchronisation each).
+// Returns the winner's index among the S starts (without `off`).
 template <class Fetch>
-void maximize_finish(sls_ctx* c, const MultistartRun& r, const LockstepStats& ls, BestBlock best, Fetch&& fetch, long off,
+long maximize_finish(sls_ctx* c, const MultistartRun& r, const LockstepStats& ls, BestBlock best, Fetch&& fetch, long off,
                      double* x_out, double* val_out, long* idx_out, double* x_stars, double* y_stars) {
     const LbfgsState& st = r.st;
     const int S = st.S, nvar = st.D;
@@ -152,15 +153,17 @@ void maximize_finish(sls_ctx* c, const MultistartRun& r, const LockstepStats& ls
     if (best.copy) d2h(c, best.host, best.dev, (size_t)8 + nvar);
     SLS_HIP(hipStreamSynchronize(c->stream));
     const double* b = best.host;
+    const long winner = (long)b[1];   // taken here, once: callers need not read the best block again behind the fetches below
     if (r.stats_of) gp_set_acq_stats(r.stats_of, ls.issued_dev ? (long)b[2] : ls.issued, (long)S * r.n_local, ls.rounds, ls.live_end);
     if (val_out) *val_out = b[0];
-    if (idx_out) *idx_out = (long)b[1] + off;
+    if (idx_out) *idx_out = winner + off;
     if (x_out) std::copy(b + 8, b + 8 + nvar, x_out);
     if (x_stars) cm_to_host(fetch(st.x, (size_t)st.ld * nvar), st.ld, nvar, S, x_stars);
     if (y_stars) {
         const double* f = fetch(st.f, (size_t)st.ld);
         for (int i = 0; i < S; ++i) y_stars[i] = -f[i];
     }
+    return winner;
 }
 
 }  // namespace slsk

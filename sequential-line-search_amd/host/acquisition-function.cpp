@@ -601,4 +601,212 @@ namespace sequential_line_search
         return FindNextSliderByExpectedUtilityFromStarts(regressor, anchor, SeededStarts(nvar, std::max(1u, num_global_search_iters), seed),
                                                          num_positions, num_draws, num_local_search_iters, seed, num_frequencies, value);
     }
+
+    MatrixXd acquisition_func::SeededUniformStarts(const unsigned num_dims, const long count, const unsigned long long seed)
+    {
+        return SeededStarts(num_dims, count, seed);
+    }
+
+    // ---- search restricted to affine subspaces (include/sls_hip.h sls_acq_*_sub, sls_path_*_sub) ----
+    namespace
+    {
+        void RequireInCube(const char* who, const VectorXd& v)
+        {
+            for (long i = 0; i < v.size(); ++i)
+                if (!(v(i) >= 0.0 && v(i) <= 1.0)) throw std::invalid_argument(std::string(who) + ": a coordinate lies outside [0,1]");
+        }
+
+        // sls_submaps over subspaces of one shape: the blocks A_k (D x d, column-major: MatrixXd's own layout) and c_k one behind the other
+        struct PackedSubspaces
+        {
+            std::vector<double> A, c;
+            sls_submaps         maps;
+        };
+        void Pack(const char* who, const std::vector<SearchSubspace>& subspaces, long num_dims, const int* subspace_of_start,
+                  PackedSubspaces& p)
+        {
+            if (subspaces.empty()) throw std::invalid_argument(std::string(who) + ": no subspace");
+            const long D = subspaces[0].basis.rows(), d = subspaces[0].basis.cols();
+            if (D != num_dims || d < 1 || d > D)
+                throw std::invalid_argument(std::string(who) + ": the basis must be D x d with 1 <= d <= D, D the regressor's dimensionality");
+            for (const SearchSubspace& s : subspaces)
+            {
+                if (s.basis.rows() != D || s.basis.cols() != d || s.offset.size() != D)
+                    throw std::invalid_argument(std::string(who) + ": every subspace needs a D x d basis and an offset of D values");
+                p.A.insert(p.A.end(), s.basis.data(), s.basis.data() + D * d);
+                p.c.insert(p.c.end(), s.offset.data(), s.offset.data() + D);
+            }
+            p.maps.struct_size   = static_cast<int>(sizeof(sls_submaps));
+            p.maps.d             = static_cast<int>(d);
+            p.maps.n_maps        = static_cast<int>(subspaces.size());
+            p.maps.A             = p.A.data();
+            p.maps.c             = p.c.data();
+            p.maps.map_of_column = subspace_of_start;
+        }
+    } // namespace
+
+    SearchSubspace SearchSubspace::Box(const VectorXd& lower, const VectorXd& upper)
+    {
+        const long D = lower.size();
+        if (D < 1 || upper.size() != D) throw std::invalid_argument("SearchSubspace::Box: lower and upper must hold D >= 1 values each");
+        for (long r = 0; r < D; ++r)
+            if (!(0.0 <= lower(r) && lower(r) <= upper(r) && upper(r) <= 1.0))
+                throw std::invalid_argument("SearchSubspace::Box: need 0 <= lower <= upper <= 1 in every coordinate");
+        SearchSubspace s;
+        s.offset = lower;
+        s.basis  = MatrixXd::Zero(D, D);
+        for (long r = 0; r < D; ++r) s.basis(r, r) = upper(r) - lower(r);
+        return s;
+    }
+
+    SearchSubspace SearchSubspace::Segment(const VectorXd& a, const VectorXd& b)
+    {
+        const long D = a.size();
+        if (D < 1 || b.size() != D) throw std::invalid_argument("SearchSubspace::Segment: the ends must hold D >= 1 values each");
+        RequireInCube("SearchSubspace::Segment", a);
+        RequireInCube("SearchSubspace::Segment", b);
+        SearchSubspace s;
+        s.offset = a;
+        s.basis  = MatrixXd(D, 1);
+        for (long r = 0; r < D; ++r) s.basis(r, 0) = b(r) - a(r);
+        return s;
+    }
+
+    SearchSubspace SearchSubspace::Centered(const VectorXd& center, const MatrixXd& directions)
+    {
+        const long D = center.size(), d = directions.cols();
+        if (D < 1 || directions.rows() != D || d < 1 || d > D)
+            throw std::invalid_argument("SearchSubspace::Centered: directions must be D x d with 1 <= d <= D");
+        RequireInCube("SearchSubspace::Centered", center);
+        SearchSubspace s;
+        s.offset = VectorXd(D);
+        s.basis  = directions;
+        for (long r = 0; r < D; ++r)
+        {
+            double half = 0.0;
+            for (long j = 0; j < d; ++j)
+            {
+                if (!std::isfinite(directions(r, j))) throw std::invalid_argument("SearchSubspace::Centered: a direction is not finite");
+                half += 0.5 * std::fabs(directions(r, j));
+            }
+            const double room = std::min(center(r), 1.0 - center(r));
+            if (half > room)
+                for (long j = 0; j < d; ++j) s.basis(r, j) *= room / half;
+            double sum = 0.0;
+            for (long j = 0; j < d; ++j) sum += s.basis(r, j);
+            s.offset(r) = center(r) - 0.5 * sum;
+        }
+        return s;
+    }
+
+    VectorXd SearchSubspace::Point(const VectorXd& z) const
+    {
+        if (z.size() != basis.cols() || offset.size() != basis.rows())
+            throw std::invalid_argument("SearchSubspace::Point: z must hold d values (basis D x d, offset D)");
+        VectorXd x = offset;
+        for (long j = 0; j < basis.cols(); ++j)
+            for (long r = 0; r < basis.rows(); ++r)
+            {
+                const volatile double product = basis(r, j) * z(j);   // rounded before it is added, as on the device
+                x(r) = x(r) + product;
+            }
+        return x;
+    }
+
+    VectorXd acquisition_func::CalcAcquisitionValuesInSubspace(const Regressor& regressor, const SearchSubspace& subspace, const MatrixXd& Z,
+                                                               const AcquisitionFuncType func_type, const double hyperparam,
+                                                               MatrixXd* grad_z)
+    {
+        sls_gp*         h = RequireHandle(regressor);
+        PackedSubspaces p;
+        Pack("CalcAcquisitionValuesInSubspace", {subspace}, regressor.GetNumDims(), nullptr, p);
+        if (Z.rows() != p.maps.d) throw std::invalid_argument("CalcAcquisitionValuesInSubspace: Z must be d x M");
+        const long M = Z.cols();
+        VectorXd   v = VectorXd::Zero(M);
+        if (grad_z) *grad_z = MatrixXd::Zero(Z.rows(), M);
+        device::Check(sls_acq_eval_sub(h, AcqId(func_type), hyperparam, &p.maps, Z.data(), static_cast<int>(M), v.data(),
+                                       grad_z ? grad_z->data() : nullptr, nullptr),
+                      "sls_acq_eval_sub");
+        return v;
+    }
+
+    VectorXd acquisition_func::FindNextPointInSubspacesFromStarts(const Regressor& regressor, const std::vector<SearchSubspace>& subspaces,
+                                                                  const std::vector<int>& subspace_of_start, const MatrixXd& starts_z,
+                                                                  const unsigned num_local_search_iters, const AcquisitionFuncType func_type,
+                                                                  const double hyperparam, double* value, int* winner_subspace)
+    {
+        sls_gp*         h = RequireHandle(regressor);
+        PackedSubspaces p;
+        const long      S = starts_z.cols();
+        if (!subspace_of_start.empty() && static_cast<long>(subspace_of_start.size()) != S)
+            throw std::invalid_argument("FindNextPointInSubspacesFromStarts: subspace_of_start must be empty or hold one entry per start");
+        Pack("FindNextPointInSubspacesFromStarts", subspaces, regressor.GetNumDims(), subspace_of_start.empty() ? nullptr : subspace_of_start.data(), p);
+        if (starts_z.rows() != p.maps.d || S < 1) throw std::invalid_argument("FindNextPointInSubspacesFromStarts: starts_z must be d x S, S >= 1");
+        VectorXd             x(regressor.GetNumDims());
+        double               v     = 0.0;
+        long                 idx   = 0;
+        const sls_lbfgs_opts lopts = LocalSearchOpts();   // GetLocalSearchTolerances
+        device::Check(sls_acq_maximize_sub(h, AcqId(func_type), hyperparam, &p.maps, starts_z.data(), static_cast<int>(S),
+                                           std::max(1, static_cast<int>(num_local_search_iters)), &lopts, 0, nullptr, x.data(), &v, &idx,
+                                           nullptr, nullptr, nullptr),
+                      "sls_acq_maximize_sub");
+        if (value) *value = v;
+        if (winner_subspace) *winner_subspace = subspace_of_start.empty() ? 0 : subspace_of_start[static_cast<size_t>(idx)];
+        return x;
+    }
+
+    VectorXd acquisition_func::FindNextPointInSubspace(const Regressor& regressor, const SearchSubspace& subspace,
+                                                       const unsigned num_global_search_iters, const unsigned num_local_search_iters,
+                                                       const AcquisitionFuncType func_type, const double hyperparam,
+                                                       const unsigned long long seed, double* value)
+    {
+        RequireHandle(regressor);
+        const MatrixXd starts = SeededStarts(static_cast<unsigned>(std::max<long>(1, subspace.basis.cols())), std::max(1u, num_global_search_iters), seed);
+        return FindNextPointInSubspacesFromStarts(regressor, {subspace}, {}, starts, num_local_search_iters, func_type, hyperparam, value);
+    }
+
+    VectorXd acquisition_func::FindNextPointInBox(const Regressor& regressor, const VectorXd& lower, const VectorXd& upper,
+                                                  const unsigned num_global_search_iters, const unsigned num_local_search_iters,
+                                                  const AcquisitionFuncType func_type, const double hyperparam, const unsigned long long seed,
+                                                  double* value)
+    {
+        return FindNextPointInSubspace(regressor, SearchSubspace::Box(lower, upper), num_global_search_iters, num_local_search_iters,
+                                       func_type, hyperparam, seed, value);
+    }
+
+    std::vector<VectorXd> acquisition_func::FindNextPointsByThompsonSamplingInBox(const Regressor& regressor, const unsigned num_points,
+                                                                                  const VectorXd& lower, const VectorXd& upper,
+                                                                                  const unsigned num_global_search_iters,
+                                                                                  const unsigned num_local_search_iters,
+                                                                                  const unsigned long long seed, const int num_frequencies)
+    {
+        if (num_points == 0) return {};
+        RequireHandle(regressor);
+        const SearchSubspace box = SearchSubspace::Box(lower, upper);
+        const unsigned       S   = std::max(1u, num_global_search_iters);
+        const PosteriorFunctionSamples draws = regressor.SamplePosteriorFunctions(static_cast<int>(num_points), seed, num_frequencies);
+        return draws.MaximizeInSubspace(box, SeededStarts(regressor.GetNumDims(), static_cast<long>(num_points) * S, seed),
+                                        num_local_search_iters);
+    }
+
+    std::vector<VectorXd> PosteriorFunctionSamples::MaximizeInSubspace(const SearchSubspace& subspace, const MatrixXd& starts_z,
+                                                                       unsigned num_local_search_iters, VectorXd* values) const
+    {
+        const long T = starts_z.cols();
+        if (T < m_num_draws || T % m_num_draws != 0)
+            throw std::invalid_argument("PosteriorFunctionSamples::MaximizeInSubspace: the start count must be a positive multiple of the draw count");
+        PackedSubspaces p;
+        Pack("PosteriorFunctionSamples::MaximizeInSubspace", {subspace}, m_num_dims, nullptr, p);
+        if (starts_z.rows() != p.maps.d) throw std::invalid_argument("PosteriorFunctionSamples::MaximizeInSubspace: starts_z must be d x (num_draws S)");
+        const sls_lbfgs_opts o = LocalSearchOpts();   // the acquisition maximiser's local search tolerances
+        MatrixXd             X(m_num_dims, m_num_draws);
+        VectorXd             v(m_num_draws);
+        device::Check(sls_path_maximize_sub(m_path, &p.maps, starts_z.data(), static_cast<int>(T / m_num_draws),
+                                            std::max(1, static_cast<int>(num_local_search_iters)), &o, nullptr, X.data(), v.data(), nullptr),
+                      "sls_path_maximize_sub");
+        if (values) *values = v;
+        std::vector<VectorXd> out;
+        for (int s = 0; s < m_num_draws; ++s) out.push_back(X.col(s));
+        return out;
+    }
 } // namespace sequential_line_search
