@@ -14,12 +14,22 @@ namespace sequential_line_search
         struct GpHandle;
     }
 
+    /// Extension: the criterion the estimating constructor maximises (both with the same log-normal priors): the log marginal
+    /// likelihood (the reference), or the leave-one-out log pseudo-likelihood (GPML 5.4.2), which is more robust when the kernel
+    /// is misspecified.
+    enum class HyperparamCriterion
+    {
+        MarginalLikelihood,
+        LeaveOneOut
+    };
+
     class GaussianProcessRegressor : public Regressor
     {
     public:
-        /// Hyper-parameters (a, b, r) come from MAP estimation of the log marginal likelihood with log-normal priors.
+        /// Hyper-parameters (a, b, r) come from MAP estimation of `criterion` with log-normal priors.
         GaussianProcessRegressor(const Eigen::MatrixXd& X, const Eigen::VectorXd& y,
-                                 const KernelType kernel_type = KernelType::ArdMatern52Kernel);
+                                 const KernelType kernel_type = KernelType::ArdMatern52Kernel,
+                                 HyperparamCriterion criterion = HyperparamCriterion::MarginalLikelihood);
 
         /// Specified hyper-parameters are used as they are.  `materialize_matrices = false` (extension) skips the
         /// 2 x N^2 device->host copies of m_K_y / m_K_y_inv for THIS object (large N, or internal helper regressors).
@@ -61,6 +71,10 @@ namespace sequential_line_search
         };
         const MapFitStats& GetMapFitStats() const { return m_map_stats; }
 
+        /// Extension: leave-one-out cross-validation at this object's hyper-parameters (sls_gp_loo): the predictive mean and
+        /// variance (noise included) of y_i from the other N - 1 observations, and the log density of y_i under that prediction.
+        void CalcLeaveOneOutPredictions(Eigen::VectorXd& mu, Eigen::VectorXd& variance, Eigen::VectorXd& log_density) const;
+
         /// Extension: add one observation without refitting (O(N^2) update on the device; hyper-parameters unchanged).
         /// m_K_y / m_K_y_inv are refreshed only if this object materialises them.
         void AppendPoint(const Eigen::VectorXd& x, double y);
@@ -74,6 +88,7 @@ namespace sequential_line_search
         Eigen::VectorXd m_kernel_hyperparams;
         double          m_noise_hyperparam;
         bool            m_materialize = true;
+        HyperparamCriterion m_criterion = HyperparamCriterion::MarginalLikelihood;
         MapFitStats     m_map_stats;
 
         std::shared_ptr<device::GpHandle> m_handle;

@@ -678,6 +678,29 @@ int sls_nll_eval(sls_nll* h, const double* y, const double* theta, double b, dou
 /* objective(x, grad) of src/gaussian-process-regressor.cpp:141-193 with x = (a, b, r_1..r_D) and the file's fixed
  * log-normal priors (:18-24).  grad (D + 2) may be NULL. */
 int sls_gp_nll_grad(sls_nll* h, const double* y, const double* x, double* value, double* grad);
+/* ---- leave-one-out cross-validation (Rasmussen & Williams, GPML 5.4.2) ---------------------------------------------------------
+ * For K_y = K_f(theta) + b I, Kinv = K_y^-1, alpha = Kinv y and d_i = Kinv_ii, the prediction of y_i from the other N - 1 points:
+ *   loo_mu[i]   = y_i - alpha_i / d_i            loo_var[i] = 1 / d_i  (the variance of y_i: noise included)
+ *   loo_logp[i] = 1/2 log d_i - alpha_i^2 / (2 d_i) - 1/2 log 2 pi                     *value = L = sum_i loo_logp[i]
+ * and the gradient of the LOO log pseudo-likelihood L as one weight matrix against dK/dtheta_p (no N^3 product per parameter):
+ *   u = Kinv (alpha ./ d),  c_i = 1/2 (1 + alpha_i^2 / d_i) / d_i,  M = Kinv diag(c) Kinv,  W = 1/2 (u alpha^T + alpha u^T) - M
+ *   grad_theta[p] = sum_ij W_ij dK_ij/dtheta_p, p = 0..D (theta as in sls_nll_eval),   *grad_b = sum_i (u_i alpha_i - M_ii).
+ * N = 1 gives the prior: mean 0, variance a + b.  Every output may be NULL.  Always the tiled pipeline (also N <= 128), through the
+ * same cached factorisation as sls_nll_eval (a repeated (theta, b) re-uses it; a call of either function leaves the other's results
+ * unchanged).  A call without a gradient launches neither the symmetric product M nor the weight kernel.  M costs Np^2 doubles of
+ * device memory per handle from the first gradient call on.  Errors as sls_nll_eval (SLS_ERR_NOT_SPD, SLS_ERR_INVALID).
+ * Contract: equal inputs give equal bits; a call on a fresh factor and a call on the cached one give equal bits; the value of a
+ * value-only call equals the value of a gradient call (L is summed in one fixed order: 256 partial sums over i mod 256, then a
+ * binary tree). */
+int sls_nll_loo(sls_nll* h, const double* y, const double* theta, double b, double* loo_mu, double* loo_var, double* loo_logp,
+                double* value, double* grad_theta, double* grad_b);
+/* sls_gp_nll_grad with the log marginal likelihood replaced by L: the same x = (a, b, r_1..r_D), the same log-normal prior terms,
+ * the same sign (to be maximised).  grad (D + 2) may be NULL.  An invalid x (a <= 0, b < 0, r <= 0) is refused before any launch. */
+int sls_gp_loo_grad(sls_nll* h, const double* y, const double* x, double* value, double* grad);
+/* The three vectors (N each, any may be NULL) for a fitted handle's own hyper-parameters and data, in either sigma mode (explicit
+ * inverse: diag(Kinv); Cholesky solve: d_i = sum_k (L^-1)_ki^2) and after sls_gp_append_point.  Takes the state lock shared, as the
+ * predictions do. */
+int sls_gp_loo(sls_gp* gp, double* loo_mu, double* loo_var, double* loo_logp);
 /* values[k] = the same objective at xs[k] = (a, b, r_1..r_D), k < B, no gradients: the B independent evaluations of one DIRECT
    iteration of PerformMapEstimation (src/gaussian-process-regressor.cpp:294 evaluates them one by one).
      N <= 128: ONE launch, one workgroup per parameter set (bit-identical to B single evaluations).
@@ -740,6 +763,8 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
  * sls_line_maximize; the pass between them counts as under qEUBO / qNEI);
  * "sub_expand" and "sub_fold" (the two kernels of the *_sub calls: one launch each per evaluation / per round of a maximiser, one more
  * "sub_expand" for x_out / x_stars; the evaluation between them counts as in the plain call);
+ * "loo_terms" (the per-point terms and L: one launch per sls_nll_loo / sls_gp_loo_grad / sls_gp_loo call, two in the Cholesky-solve
+ * sigma mode), "loo_syrk" (the scaled copy R and M = R R^T) and "loo_weight" (the LOO weights), one entry each per gradient call;
  * "potrf_fallbacks": launches = how often a single-launch factorisation gave up and was recomputed. */
 int sls_prof_enable(sls_ctx* ctx, int on);
 int sls_prof_reset(sls_ctx* ctx);

@@ -148,11 +148,38 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
         .value("ArdMatern52Kernel", KernelType::ArdMatern52Kernel);
 
     // max-value entropy search on a regressor with fixed hyper-parameters (acquisition-function.hpp)
+    py::enum_<HyperparamCriterion>(m, "HyperparamCriterion", py::arithmetic())
+        .value("MarginalLikelihood", HyperparamCriterion::MarginalLikelihood)
+        .value("LeaveOneOut", HyperparamCriterion::LeaveOneOut);
     py::class_<Regressor>(m, "Regressor");
     py::class_<GaussianProcessRegressor, Regressor>(m, "GaussianProcessRegressor")
         .def(py::init<const MatrixXd&, const VectorXd&, const VectorXd&, double, const KernelType, bool>(), "X"_a, "y"_a,
              "kernel_hyperparams"_a, "noise_hyperparam"_a, "kernel_type"_a = KernelType::ArdMatern52Kernel,
-             "materialize_matrices"_a = false);
+             "materialize_matrices"_a = false)
+        // hyper-parameters estimated from the data: MAP of the log marginal likelihood, or of the leave-one-out pseudo-likelihood
+        .def(py::init([](const MatrixXd& X, const VectorXd& y, const KernelType kernel_type, HyperparamCriterion criterion) {
+                 const bool prev = GaussianProcessRegressor::s_materialize_matrices.exchange(false);
+                 try
+                 {
+                     auto* gp = new GaussianProcessRegressor(X, y, kernel_type, criterion);
+                     GaussianProcessRegressor::s_materialize_matrices.store(prev);
+                     return gp;
+                 }
+                 catch (...)
+                 {
+                     GaussianProcessRegressor::s_materialize_matrices.store(prev);
+                     throw;
+                 }
+             }),
+             "X"_a, "y"_a, "kernel_type"_a = KernelType::ArdMatern52Kernel, "criterion"_a = HyperparamCriterion::MarginalLikelihood)
+        .def("kernel_hyperparams", [](const GaussianProcessRegressor& r) { return r.GetKernelHyperparams(); })
+        .def("noise_hyperparam", &GaussianProcessRegressor::GetNoiseHyperparam)
+        // leave-one-out cross-validation at the object's hyper-parameters: (mean, variance, log density), N each
+        .def("leave_one_out", [](const GaussianProcessRegressor& r) {
+            VectorXd mu, var, logp;
+            r.CalcLeaveOneOutPredictions(mu, var, logp);
+            return std::make_tuple(mu, var, logp);
+        });
     m.def("sample_max_values", &acquisition_func::SampleMaxValues, "regressor"_a, "num_samples"_a = 64,
           "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50, "seed"_a = 0ULL, "num_frequencies"_a = 2048);
     m.def("calc_max_value_entropies",

@@ -109,6 +109,7 @@ EXPORTS = [
     "sls_line_eval", "sls_line_maximize",
     "sls_qlognei_terms", "sls_qlognei_eval", "sls_qlognei_maximize",
     "sls_acq_eval_sub", "sls_acq_maximize_sub", "sls_mes_eval_sub", "sls_mes_maximize_sub", "sls_path_eval_sub", "sls_path_maximize_sub",
+    "sls_nll_loo", "sls_gp_loo_grad", "sls_gp_loo",
 ]
 
 
@@ -282,6 +283,12 @@ class GP:
         assert x.shape == (self.D,)
         _ck(lib().sls_gp_append_point(self.h, _p(x), C.c_double(y)))
         self.N += 1
+
+    def loo(self):
+        """Leave-one-out predictions (mu, variance, log density; N each) at the handle's own hyper-parameters and data (sls_gp_loo)."""
+        mu, var, logp = np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        _ck(lib().sls_gp_loo(self.h, _p(mu), _p(var), _p(logp)))
+        return mu, var, logp
 
     def matrix(self, what):
         out = np.empty((self.N, self.N), order="F") if what in (GP_K_Y, GP_K_Y_INV, GP_CHOL_L) else np.empty(self.N)
@@ -796,6 +803,26 @@ class Nll:
         val = C.c_double()
         g = np.empty(self.D + 2) if want_grad else None
         _ck(lib().sls_gp_nll_grad(self.h, _p(y), _p(x), C.byref(val), _p(g) if want_grad else None))
+        return (val.value, g) if want_grad else val.value
+
+    def loo(self, y, theta, b, want_grad=True):
+        """Leave-one-out cross-validation at (theta, b) (sls_nll_loo): per-point mean, variance and log density, their sum
+        `value`, and (want_grad) its gradient in theta = (a, r_1..r_D) and b."""
+        y, theta = _f(y), _f(theta)
+        val, gb = C.c_double(), C.c_double()
+        mu, var, logp = np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        gth = np.empty(self.D + 1)
+        _ck(lib().sls_nll_loo(self.h, _p(y), _p(theta), C.c_double(b), _p(mu), _p(var), _p(logp), C.byref(val),
+                              _p(gth) if want_grad else None, C.byref(gb) if want_grad else None))
+        return dict(mu=mu, var=var, logp=logp, value=val.value, grad_theta=gth if want_grad else None,
+                    grad_b=gb.value if want_grad else None)
+
+    def gp_loo_objective(self, y, x, want_grad=True):
+        """The LOO log pseudo-likelihood plus the log-normal priors at x = (a, b, r_1..r_D) (sls_gp_loo_grad)."""
+        y, x = _f(y), _f(x)
+        val = C.c_double()
+        g = np.empty(self.D + 2) if want_grad else None
+        _ck(lib().sls_gp_loo_grad(self.h, _p(y), _p(x), C.byref(val), _p(g) if want_grad else None))
         return (val.value, g) if want_grad else val.value
 
     def gp_objective_batch(self, y, xs):

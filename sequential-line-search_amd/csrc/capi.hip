@@ -1845,6 +1845,38 @@ extern "C" int sls_potri(sls_ctx* c, const double* L, int N, double* Ainv) {
     SLS_CATCH
 }
 
+// Leave-one-out predictions of the fitted handle at its own hyper-parameters and data (kernels_loo.hip): closed forms in
+// diag(K_y^-1) and alpha, both part of the fitted state.  Explicit-inverse mode: the diagonal of Kinv; Cholesky-solve mode:
+// d_i = sum_k (L^-1)_ki^2 from the factor's inverse, the matrix that mode predicts with.
+extern "C" int sls_gp_loo(sls_gp* g, double* loo_mu, double* loo_var, double* loo_logp) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g, "sls_gp_loo: NULL handle");
+    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
+    sls_ctx* c = g->ctx;
+    const int N = g->N, Np = g->Np;
+    DBuf ws;   // pooled: five vectors of the terms, d, and the sum
+    ws.ensure((size_t)6 * Np + 8);
+    double* v = ws.p;
+    double* dvec = v + (size_t)5 * Np;
+    {
+        ProfScope ps(c, "loo_terms");
+        if (g->sigma_mode == 1) {
+            launch_loo_diag_linv(c->stream, g->Linv.p, Np, N, dvec);
+            launch_loo_terms(c->stream, dvec, 1, g->alpha.p, g->y.p, Np, N, v, v + Np, v + 2 * (size_t)Np, v + 3 * (size_t)Np,
+                             v + 4 * (size_t)Np, dvec + Np);
+        } else {
+            launch_loo_terms(c->stream, g->Kinv.p, (long)Np + 1, g->alpha.p, g->y.p, Np, N, v, v + Np, v + 2 * (size_t)Np,
+                             v + 3 * (size_t)Np, v + 4 * (size_t)Np, dvec + Np);
+        }
+    }
+    if (loo_mu) d2h(c, loo_mu, v, N);
+    if (loo_var) d2h(c, loo_var, v + Np, N);
+    if (loo_logp) d2h(c, loo_logp, v + 2 * (size_t)Np, N);
+    sync(c);
+    SLS_CATCH
+}
+
 // Grow the fitted state by one observation in O(N^2): Schur-complement update of K^-1, one new row of L and L^-1,
 // alpha, mu at the data points, arg max and log-determinant.  Replaces the full refit of the dummy regressor in
 // FindNextPoints (src/acquisition-function.cpp:280-293).  When N is a multiple of 128 the padded buffers are full and

@@ -15,6 +15,9 @@ struct sls_nll {
     sls_ctx* ctx = nullptr;
     int D = 0, N = 0, Np = 0, Dp = 0, Dcols = 0, kernel = 0;
     DBuf X, y, XT, nx, L, Linv, Kinv, alpha, G, Y, svec, parts, gemv_part, small_in, small_out, small_info;
+    // leave-one-out cross-validation (sls_nll_loo): six vectors of Np (mu, var, logp, alpha ./ d, sqrt c, u) and M = Kinv diag(c) Kinv
+    // (Np x Np, lower tiles; the gradient only), grown on first use
+    DBuf loo_vec, loo_M;
     DBuf XTr, small_kc;   // one-workgroup path (N <= 128): the raw design matrix transposed [i + d * 128]; pair scratch of the gradient
     std::vector<double> cached_theta;
     double cached_b = -1.0;
@@ -332,6 +335,133 @@ extern "C" int sls_gp_nll_grad(sls_nll* h, const double* y, const double* x, dou
     if (value) *value = -0.5 * quad - 0.5 * logdet - 0.5 * N * std::log(2.0 * M_PI) + reg;   // :174-192
     if (grad) {
         grad[0] = gth[0] + log_lognormal_d(a, a_mu, a_s2);                                   // calc_grad :120-124
+        grad[1] = gb + log_lognormal_d(b, b_mu, b_s2);
+        for (int d = 0; d < D; ++d) grad[2 + d] = gth[1 + d] + log_lognormal_d(x[2 + d], r_mu, r_s2);
+    }
+    SLS_CATCH
+}
+
+// ---- leave-one-out cross-validation (kernels_loo.hip) ---------------------------------------------------------------------------
+// The tiled pipeline of nll_eval_impl with the LOO terms behind alpha and, for a gradient, the LOO weights in place of the marginal
+// likelihood's: always tiled (also N <= 128), through nll_factor_enqueue / nll_factor_accept.  Result words: [3] = L (loo_terms),
+// [0] = sum W .* K_f and [1] = dL/db (loo_scalars, launched behind the evaluation's own sums), [4..6] log|K_y| and the info words.
+static void nll_loo_impl(sls_nll* h, const double* y, const double* theta, double b, double* loo_mu, double* loo_var, double* loo_logp,
+                         double* value, double* grad_theta, double* grad_b) {
+    sls_ctx* c = h->ctx;
+    const int D = h->D, N = h->N, Np = h->Np;
+    SLS_REQUIRE(y && theta, "sls_nll_loo: NULL argument");
+    SLS_REQUIRE(b >= 0.0, "noise level must be >= 0");
+    SLS_REQUIRE(theta[0] > 0.0, "signal variance must be positive");
+    for (int d = 0; d < D; ++d) SLS_REQUIRE(theta[1 + d] > 0.0, "length scale %d must be positive", d);
+    const bool want_grad = grad_theta || grad_b;
+    const int nt = Np / 128;
+    nll_stage_ensure(h);
+    const double* res = h->res_stage();
+    h->loo_vec.ensure((size_t)6 * Np);
+    double* v_mu = h->loo_vec.p;
+    double* v_var = v_mu + Np;
+    double* v_logp = v_var + Np;
+    double* v_ad = v_logp + Np;
+    double* v_sc = v_ad + Np;
+    double* v_u = v_sc + Np;
+    for (int attempt = 0;; ++attempt) {
+        if (!h->y_on_device || std::memcmp(h->y_stage(), y, sizeof(double) * N) != 0) {
+            std::memcpy(h->y_stage(), y, sizeof(double) * N);
+            SLS_HIP(hipMemcpyAsync(h->y.p, h->y_stage(), (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
+            h->y_on_device = true;
+        }
+        const bool fresh = nll_factor_enqueue(h, theta, b);
+        launch_gemv_t(c->stream, h->Kinv.p, Np, h->y.p, h->alpha.p);
+        {
+            ProfScope ps(c, "loo_terms");
+            launch_loo_terms(c->stream, h->Kinv.p, (long)Np + 1, h->alpha.p, h->y.p, Np, N, v_mu, v_var, v_logp, v_ad, v_sc, h->res_dev() + 3);
+        }
+        const bool direct = gram_direct_form(theta + 1, D);
+        if (want_grad) {
+            h->G.ensure((size_t)Np * Np);
+            h->loo_M.ensure((size_t)Np * Np);
+            h->Y.ensure((size_t)Np * h->Dcols * nll_y_chunks(nt, h->Dcols / 128));
+            h->parts.ensure((size_t)nt * nt);
+            launch_gemv_t(c->stream, h->Kinv.p, Np, v_ad, v_u);   // u = Kinv (alpha ./ d)
+            {
+                ProfScope ps(c, "loo_syrk");   // R = Kinv diag(sqrt c) passes through G, which the weights overwrite next
+                launch_loo_syrk(c->stream, h->Kinv.p, v_sc, Np, h->G.p, h->loo_M.p);
+            }
+            ProfScope ps(c, "loo_weight");
+            if (direct)
+                launch_loo_weight_direct(c->stream, h->X.p, D, h->il_stage.dev, Np, N, KernelSpec{h->kernel, theta[0]}, h->alpha.p, v_u,
+                                         h->loo_M.p, h->G.p, h->parts.p);
+            else
+                launch_loo_weight(c->stream, h->XT.p, Np, h->Dp, h->nx.p, Np, N, KernelSpec{h->kernel, theta[0]}, h->alpha.p, v_u, h->loo_M.p,
+                                  h->G.p, h->parts.p, grad_theta ? h->gemv_part.p : nullptr);
+        } else {
+            h->parts.ensure(1);
+        }
+        const double* Lf = fresh ? h->L.p : nullptr;
+        const int* inf = fresh ? c->d_info : nullptr;
+        const int nparts = want_grad ? nt * nt : 0;
+        if (grad_theta && direct) {
+            launch_lengthscale_grad_direct(c->stream, h->X.p, h->G.p, h->il_stage.dev, Np, N, D, h->res_dev() + 8, h->parts.p, nparts,
+                                           h->alpha.p, h->y.p, h->Kinv.p, h->res_dev(), Lf, inf);
+        } else if (grad_theta) {
+            const int yc = nll_y_chunks(nt, h->Dcols / 128);
+            launch_gemm_splitk_nt(c->stream, h->G.p, Np, h->XT.p, Np, h->Y.p, Np, (long)Np * h->Dcols, nt, h->Dcols / 128, Np, yc);
+            launch_sum_chunks(c->stream, h->Y.p, (long)Np * h->Dcols, yc, (long)Np * h->Dcols, h->gemv_part.p, Np, nt, h->svec.p);
+            launch_lengthscale_grad(c->stream, h->XT.p, h->Y.p, h->svec.p, h->il_stage.dev, Np, N, D, h->res_dev() + 8, h->parts.p, nparts,
+                                    h->alpha.p, h->y.p, h->Kinv.p, Np, h->res_dev(), Lf, inf);
+        } else {
+            launch_nll_scalars(c->stream, h->parts.p, nparts, h->alpha.p, h->y.p, h->Kinv.p, Np, N, h->res_dev(), Lf, inf);
+        }
+        // behind the evaluation's own sums (which leave log|K_y| and the info words): words 0 and 1 are the LOO gradient's from here on
+        if (want_grad) launch_loo_scalars(c->stream, h->parts.p, nparts, h->alpha.p, v_u, h->loo_M.p, Np, N, h->res_dev());
+        if (loo_mu) SLS_HIP(hipMemcpyAsync(loo_mu, v_mu, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
+        if (loo_var) SLS_HIP(hipMemcpyAsync(loo_var, v_var, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
+        if (loo_logp) SLS_HIP(hipMemcpyAsync(loo_logp, v_logp, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
+        SLS_HIP(hipStreamSynchronize(c->stream));
+        if (!fresh) break;
+        const int info2[2] = {(int)res[5], (int)res[6]};
+        if (nll_factor_accept(h, theta, b, info2, attempt)) {
+            h->logdet = res[4];
+            break;
+        }
+    }
+    if (value) *value = res[3];
+    if (grad_b) *grad_b = res[1];
+    if (grad_theta) {
+        grad_theta[0] = res[0] / theta[0];
+        for (int d = 0; d < D; ++d) grad_theta[1 + d] = res[8 + d];
+    }
+}
+
+extern "C" int sls_nll_loo(sls_nll* h, const double* y, const double* theta, double b, double* loo_mu, double* loo_var,
+                           double* loo_logp, double* value, double* grad_theta, double* grad_b) {
+    SLS_TRY
+    CtxCall call_(h);
+    SLS_REQUIRE(h, "sls_nll_loo: NULL handle");
+    nll_loo_impl(h, y, theta, b, loo_mu, loo_var, loo_logp, value, grad_theta, grad_b);
+    SLS_CATCH
+}
+
+extern "C" int sls_gp_loo_grad(sls_nll* h, const double* y, const double* x, double* value, double* grad) {
+    SLS_TRY
+    CtxCall call_(h);
+    SLS_REQUIRE(h && y && x, "sls_gp_loo_grad: NULL argument");
+    const int D = h->D;
+    // the priors of sls_gp_nll_grad
+    const double a_mu = std::log(0.5), a_s2 = 0.5, b_mu = std::log(1e-4), b_s2 = 0.5, r_mu = std::log(0.5), r_s2 = 0.5;
+    const double a = x[0], b = x[1];
+    SLS_REQUIRE(a > 0.0 && b >= 0.0, "sls_gp_loo_grad: signal variance must be positive, noise level >= 0");
+    for (int d = 0; d < D; ++d) SLS_REQUIRE(x[2 + d] > 0.0, "length scale %d must be positive", d);
+    std::vector<double> theta(D + 1), gth(D + 1);
+    theta[0] = a;
+    for (int d = 0; d < D; ++d) theta[1 + d] = x[2 + d];
+    double L = 0, gb = 0;
+    nll_loo_impl(h, y, theta.data(), b, nullptr, nullptr, nullptr, &L, grad ? gth.data() : nullptr, grad ? &gb : nullptr);
+    double reg = log_lognormal(a, a_mu, a_s2) + log_lognormal(b, b_mu, b_s2);
+    for (int d = 0; d < D; ++d) reg += log_lognormal(x[2 + d], r_mu, r_s2);
+    if (value) *value = L + reg;
+    if (grad) {
+        grad[0] = gth[0] + log_lognormal_d(a, a_mu, a_s2);
         grad[1] = gb + log_lognormal_d(b, b_mu, b_s2);
         for (int d = 0; d < D; ++d) grad[2 + d] = gth[1 + d] + log_lognormal_d(x[2 + d], r_mu, r_s2);
     }

@@ -606,4 +606,26 @@ void launch_lengthscale_grad_direct(hipStream_t s, const double* X, const double
 void launch_sum_chunks(hipStream_t s, double* Y, long n, int chunks, long stride, const double* row_part, int Np, int row_chunks,
                        double* svec);
 
+// ---- kernels_loo.hip: leave-one-out cross-validation (sls_nll_loo, sls_gp_loo_grad, sls_gp_loo) ---------------------------------
+// With d_i = (K_y^-1)_ii = dvec[i*dstride] (Kinv with stride Np + 1, or a vector), one workgroup writes, for i < N (exactly 0 for
+// N <= i < Np): mu[i] = y_i - alpha_i / d_i, var[i] = 1 / d_i, logp[i] = 1/2 log d_i - alpha_i^2 / (2 d_i) - 1/2 log 2 pi,
+// ad[i] = alpha_i / d_i, sc[i] = sqrt(c_i), c_i = 1/2 (1 + alpha_i^2 / d_i) / d_i; and Lsum[0] = sum_i logp[i]: 256 partial sums over
+// i mod 256 in increasing i, then the binary tree.
+void launch_loo_terms(hipStream_t s, const double* dvec, long dstride, const double* alpha, const double* y, int Np, int N, double* mu,
+                      double* var, double* logp, double* ad, double* sc, double* Lsum);
+// d[i] = sum_k (L^-1)_ki^2, i < N: diag(K_y^-1) from L^-1 alone (lower triangular, [k + i*Np])
+void launch_loo_diag_linv(hipStream_t s, const double* Linv, int Np, int N, double* d);
+// R = Kinv diag(sc) (one N^2 pass, Np x Np), then M = R R^T = Kinv diag(c) Kinv on the fp64 matrix cores: only the nt (nt + 1) / 2
+// tiles with tm >= tn are computed and written (N^3 flop); the tiles of M above the diagonal keep whatever they held.
+void launch_loo_syrk(hipStream_t s, const double* Kinv, const double* sc, int Np, double* R, double* M);
+// launch_nll_weight / launch_nll_weight_direct with the LOO weights w_ij = 1/2 (u_i alpha_j + alpha_i u_j) - M_ij (0 for a padded
+// index), M read from its lower triangle only (entry (i, j), i < j, reads M_ji): the same G, wk_part and row_part in the same orders.
+void launch_loo_weight(hipStream_t s, const double* XT, long ld, int Dp, const double* nx, int Np, int N, KernelSpec ks,
+                       const double* alpha, const double* u, const double* M, double* G, double* wk_part, double* row_part);
+void launch_loo_weight_direct(hipStream_t s, const double* X, int D, const double* inv_ell, int Np, int N, KernelSpec ks,
+                              const double* alpha, const double* u, const double* M, double* G, double* wk_part);
+// out[0] = sum_t part[t], out[1] = dL/db = sum_{i < N} (u_i alpha_i - M_ii), both in launch_nll_scalars' orders
+void launch_loo_scalars(hipStream_t s, const double* part, int nparts, const double* alpha, const double* u, const double* M, int Np,
+                        int N, double* out);
+
 }  // namespace slsk

@@ -47,6 +47,40 @@ extern "C" int slsh_gp_map_fit(const double* X, int D, int N, const double* y, i
     }
 }
 
+/// The same with HyperparamCriterion::LeaveOneOut; loo (3 N, may be NULL): the fitted object's leave-one-out means, variances and
+/// log densities (CalcLeaveOneOutPredictions).
+extern "C" int slsh_gp_loo_fit(const double* X, int D, int N, const double* y, int kernel, double* out_x, double* stats, double* loo)
+{
+    try
+    {
+        Eigen::MatrixXd Xm(D, N);
+        std::memcpy(Xm.data(), X, sizeof(double) * D * N);
+        Eigen::VectorXd ym(N);
+        std::memcpy(ym.data(), y, sizeof(double) * N);
+        const bool prev = GaussianProcessRegressor::s_materialize_matrices.exchange(false);
+        GaussianProcessRegressor gp(Xm, ym, KernelOf(kernel), HyperparamCriterion::LeaveOneOut);
+        GaussianProcessRegressor::s_materialize_matrices.store(prev);
+        out_x[0] = gp.GetKernelHyperparams()(0);
+        out_x[1] = gp.GetNoiseHyperparam();
+        for (int d = 0; d < D; ++d) out_x[2 + d] = gp.GetKernelHyperparams()(1 + d);
+        const auto& s = gp.GetMapFitStats();
+        stats[0] = s.final_value; stats[1] = s.direct_value; stats[2] = s.prior_value;
+        stats[3] = s.evals_direct; stats[4] = s.evals_local; stats[5] = s.seconds; stats[6] = stats[7] = 0.0;
+        if (loo)
+        {
+            Eigen::VectorXd mu, var, logp;
+            gp.CalcLeaveOneOutPredictions(mu, var, logp);
+            for (int i = 0; i < N; ++i) { loo[i] = mu(i); loo[N + i] = var(i); loo[2 * N + i] = logp(i); }
+        }
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        g_err = e.what();
+        return -1;
+    }
+}
+
 /// PreferenceRegressor(X, D, use_map, a, r, b, prior_var, btl, iters, kernel): out_y[M] goodness values, out_hyp =
 /// (a, b, r_1..r_D) as used / estimated, *objective = MAP objective at the returned point.
 extern "C" int slsh_pref_map_fit(const double* X, int D, int M, const unsigned* prefs_flat, const int* offsets, int n_prefs,

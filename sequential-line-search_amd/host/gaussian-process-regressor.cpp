@@ -19,8 +19,10 @@ namespace sequential_line_search
     }
 
     // reference: src/gaussian-process-regressor.cpp:198-212
-    GaussianProcessRegressor::GaussianProcessRegressor(const MatrixXd& X, const VectorXd& y, const KernelType kernel_type)
-        : Regressor(kernel_type), m_X(X), m_y(y), m_noise_hyperparam(0.0), m_materialize(s_materialize_matrices.load())
+    GaussianProcessRegressor::GaussianProcessRegressor(const MatrixXd& X, const VectorXd& y, const KernelType kernel_type,
+                                                       HyperparamCriterion criterion)
+        : Regressor(kernel_type), m_X(X), m_y(y), m_noise_hyperparam(0.0), m_materialize(s_materialize_matrices.load()),
+          m_criterion(criterion)
     {
         if (X.rows() == 0) return;   // inert object, like the reference
         PerformMapEstimation();
@@ -69,6 +71,13 @@ namespace sequential_line_search
         }
     }
 
+    void GaussianProcessRegressor::CalcLeaveOneOutPredictions(VectorXd& mu, VectorXd& variance, VectorXd& log_density) const
+    {
+        const long N = m_X.cols();
+        mu = VectorXd(N); variance = VectorXd(N); log_density = VectorXd(N);
+        device::Check(sls_gp_loo(m_handle->h, mu.data(), variance.data(), log_density.data()), "sls_gp_loo");
+    }
+
     sls_gp* GaussianProcessRegressor::GetDeviceHandle() const { return m_handle ? m_handle->h : nullptr; }
 
     // reference: src/gaussian-process-regressor.cpp:234-272 -- single-point forms of the batched device evaluation
@@ -97,7 +106,8 @@ namespace sequential_line_search
         return g;
     }
 
-    // reference: src/gaussian-process-regressor.cpp:274-299.  Objective + gradient on the device (sls_gp_nll_grad);
+    // reference: src/gaussian-process-regressor.cpp:274-299.  Objective + gradient on the device (sls_gp_nll_grad, or
+    // sls_gp_loo_grad for HyperparamCriterion::LeaveOneOut: the same structure, DIRECT's batch one value-only call per point);
     // drivers: DIRECT(300) as the reference (host/direct.cpp), then a bounded L-BFGS in log-parameters in place of
     // TNEWTON(1000) (same bounds [1e-8, 50]; NLopt is unavailable, iterates are not comparable, the optimum is).
     void GaussianProcessRegressor::PerformMapEstimation()
@@ -114,9 +124,11 @@ namespace sequential_line_search
             std::vector<double> x(z.size()), g(z.size());
             for (size_t i = 0; i < z.size(); ++i) x[i] = std::exp(z[i]);
             double    v  = 0.0;
-            const int rc = sls_gp_nll_grad(nll.h, m_y.data(), x.data(), &v, grad ? g.data() : nullptr);
+            const bool loo = m_criterion == HyperparamCriterion::LeaveOneOut;
+            const int  rc  = loo ? sls_gp_loo_grad(nll.h, m_y.data(), x.data(), &v, grad ? g.data() : nullptr)
+                                 : sls_gp_nll_grad(nll.h, m_y.data(), x.data(), &v, grad ? g.data() : nullptr);
             if (rc == SLS_ERR_NOT_SPD) return -HUGE_VAL;   // numerically singular K_y: reject the trial point
-            device::Check(rc, "sls_gp_nll_grad");
+            device::Check(rc, loo ? "sls_gp_loo_grad" : "sls_gp_nll_grad");
             if (grad)
             {
                 grad->resize(z.size());
@@ -131,10 +143,21 @@ namespace sequential_line_search
         // devices configured (device::SetDevices / SLS_DEVICES) and a problem large enough for the tiled pipeline, the points of
         // a batch are dealt over the devices -- the part of a MAP fit that shards (the N^3 factorisation of one evaluation does not)
         std::unique_ptr<device::MultiNllHandle> multi;
-        if (device::Multi() && m_X.cols() > 128) multi.reset(new device::MultiNllHandle(m_X, KernelId(m_kernel_type)));
+        const bool loo = m_criterion == HyperparamCriterion::LeaveOneOut;
+        if (!loo && device::Multi() && m_X.cols() > 128) multi.reset(new device::MultiNllHandle(m_X, KernelId(m_kernel_type)));
         const optim::BatchObjective batch = [&](const std::vector<std::vector<double>>& xs, std::vector<double>& values) {
             values.resize(xs.size());
             if (xs.empty()) return;
+            if (loo)
+            {
+                for (size_t k = 0; k < xs.size(); ++k)
+                {
+                    const int rc = sls_gp_loo_grad(nll.h, m_y.data(), xs[k].data(), &values[k], nullptr);
+                    if (rc == SLS_ERR_NOT_SPD) values[k] = -HUGE_VAL;
+                    else device::Check(rc, "sls_gp_loo_grad");
+                }
+                return;
+            }
             std::vector<double> flat(xs.size() * (D + 2));
             for (size_t k = 0; k < xs.size(); ++k)
                 for (int i = 0; i < D + 2; ++i) flat[k * (D + 2) + i] = xs[k][i];
@@ -159,8 +182,10 @@ namespace sequential_line_search
         const std::vector<double> lower(D + 2, lo), upper(D + 2, hi);
         // N <= 128, D <= 128: the whole local phase is one launch (sls_gp_map_fit); otherwise one device objective call per evaluation
         std::vector<double> z(D + 2);
-        const int rc_fit = sls_gp_map_fit(nll.h, m_y.data(), best.data(), lower.data(), upper.data(), 1000, 0, z.data(),
-                                          &m_map_stats.final_value, &m_map_stats.evals_local);
+        // (the device-resident fit maximises the marginal likelihood: the LOO criterion always takes the host-driven optimiser)
+        const int rc_fit = loo ? SLS_ERR_UNSUPPORTED
+                               : sls_gp_map_fit(nll.h, m_y.data(), best.data(), lower.data(), upper.data(), 1000, 0, z.data(),
+                                                &m_map_stats.final_value, &m_map_stats.evals_local);
         if (rc_fit == SLS_ERR_UNSUPPORTED)
             z = optim::MaximizeBounded(objective, best, lower, upper, 1000, &m_map_stats.final_value, &m_map_stats.evals_local, ftol_rel, xtol_rel);
         else
