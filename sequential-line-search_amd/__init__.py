@@ -805,17 +805,22 @@ class Nll:
         _ck(lib().sls_gp_nll_grad(self.h, _p(y), _p(x), C.byref(val), _p(g) if want_grad else None))
         return (val.value, g) if want_grad else val.value
 
-    def loo(self, y, theta, b, want_grad=True):
+    def loo(self, y, theta, b, want_grad=True, want_mu=True, want_var=True, want_logp=True, want_value=True, want_grad_theta=None,
+            want_grad_b=None):
         """Leave-one-out cross-validation at (theta, b) (sls_nll_loo): per-point mean, variance and log density, their sum
-        `value`, and (want_grad) its gradient in theta = (a, r_1..r_D) and b."""
+        `value`, and (want_grad) its gradient in theta = (a, r_1..r_D) and b.  Every output can be switched off on its own (the
+        C entry gets NULL for it, the dict None); want_grad_theta and want_grad_b default to want_grad."""
         y, theta = _f(y), _f(theta)
+        want_grad_theta = want_grad if want_grad_theta is None else want_grad_theta
+        want_grad_b = want_grad if want_grad_b is None else want_grad_b
         val, gb = C.c_double(), C.c_double()
-        mu, var, logp = np.empty(self.N), np.empty(self.N), np.empty(self.N)
-        gth = np.empty(self.D + 1)
-        _ck(lib().sls_nll_loo(self.h, _p(y), _p(theta), C.c_double(b), _p(mu), _p(var), _p(logp), C.byref(val),
-                              _p(gth) if want_grad else None, C.byref(gb) if want_grad else None))
-        return dict(mu=mu, var=var, logp=logp, value=val.value, grad_theta=gth if want_grad else None,
-                    grad_b=gb.value if want_grad else None)
+        mu, var, logp = (np.empty(self.N) if w else None for w in (want_mu, want_var, want_logp))
+        gth = np.empty(self.D + 1) if want_grad_theta else None
+        _ck(lib().sls_nll_loo(self.h, _p(y), _p(theta), C.c_double(b), _p(mu) if want_mu else None, _p(var) if want_var else None,
+                              _p(logp) if want_logp else None, C.byref(val) if want_value else None, _p(gth) if want_grad_theta else None,
+                              C.byref(gb) if want_grad_b else None))
+        return dict(mu=mu, var=var, logp=logp, value=val.value if want_value else None, grad_theta=gth,
+                    grad_b=gb.value if want_grad_b else None)
 
     def gp_loo_objective(self, y, x, want_grad=True):
         """The LOO log pseudo-likelihood plus the log-normal priors at x = (a, b, r_1..r_D) (sls_gp_loo_grad)."""

@@ -171,6 +171,57 @@ def problem(D, N, seed=None):
     return np.asfortranarray(X), y, theta
 
 
+def scaled_problem(D, N, s):
+    """problem(D, N) with every length scale multiplied by s: the same points and targets, K_f ever closer to rank deficient."""
+    X, y, theta = problem(D, N)
+    theta = theta.copy()
+    theta[1:] *= s
+    return X, y, theta
+
+
+# ---- the conditioning ladder (tests/test_gpu_loo_conditioning.py, tests/golden/loo_illcond.npz) ---------------------------------
+# Rungs (kernel, D, N, s, b): scaled_problem(D, N, s) at b = 1e-8, s chosen per kernel and shape so that cond(K_y) lands in three
+# bands.  The cap: a rung's gradient tolerance 100 cond 2.3e-16 max|g| may not exceed 1e-4 max|g|, so cond <= 4e9 (the Matern rungs
+# of (3, 37) could not go much higher anyway: cond <= N a / b = 2.6e9).  tests/test_loo_cpu.py asserts band and cap for every rung
+# and that numpy itself meets the ladder's bound there.
+CONDITIONING_CAP = 4e9
+CONDITIONING_BANDS = [(3e5, 3e6), (3e7, 3e8), (1e9, CONDITIONING_CAP)]        # about 1e6, about 1e8, the highest below the cap
+RUNG_NOISE = 1e-8
+_RUNG_SCALES = {(0, 3, 37): (2.0, 3.0, 4.5), (0, 5, 130): (1.75, 2.75, 4.0), (1, 3, 37): (5.0, 12.0, 28.0), (1, 5, 130): (4.0, 10.0, 20.0)}
+RUNGS = [(k, D, N, s, RUNG_NOISE) for (k, D, N), scales in _RUNG_SCALES.items() for s in scales]
+
+
+def rung_name(kernel, D, N, s, b):
+    return f"k{kernel}_D{D}_N{N}_s{s:g}_b{b:g}"
+
+
+def rung_band(kernel, D, N, s, b):
+    return CONDITIONING_BANDS[_RUNG_SCALES[(kernel, D, N)].index(s)]
+
+
+def ladder_tolerances(cond):
+    """(vector, gradient): the bound tests/test_loo_cpu.py::test_against_mpmath holds numpy to -- 10 cond eps for mu (absolute scale
+    max|y|), var, logp and L (scale sum|logp|), 100 cond eps max|g| for the D + 2 derivatives."""
+    return 10 * cond * 2.3e-16, 100 * cond * 2.3e-16
+
+
+def direct_form_problem_tiled(N):
+    """(17, 257) or (17, 130): one length scale of 0.01 and near-duplicate pairs (offset 1e-7 in one coordinate) whose members sit
+    in different 128-tiles -- (3, 200), (130, 7), (256, 129) at N = 257, and a third copy of point 256 at index 9 (offset -1e-7):
+    the first two pairs both join tiles 0 and 1, the third tiles 1 and 2, the copy tiles 0 and 2, so that every off-diagonal tile of
+    the 3 x 3 grid, on both sides of the diagonal, holds a strongly weighted entry (tests/test_loo_cpu.py asserts it); at N = 130
+    the pairs that fit: (3, 129), (128, 7)."""
+    X, y, theta = problem(17, N)
+    X = X.copy(order="F")
+    pairs = [(3, 200, 1e-7), (130, 7, 1e-7), (256, 129, 1e-7), (256, 9, -1e-7)] if N == 257 else [(3, 129, 1e-7), (128, 7, 1e-7)]
+    for (i, j, off) in pairs:
+        X[:, j] = X[:, i]
+        X[2, j] += off
+    theta = theta.copy()
+    theta[1 + 2] = 0.01
+    return X, y, theta, 0.005
+
+
 def direct_form_problem():
     """(17, 40): one length scale of 0.01 (beyond the guard of the norm expansion) and a near-duplicate pair (offset 1e-7)."""
     X, y, theta = problem(17, 40)
