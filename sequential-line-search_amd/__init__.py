@@ -540,18 +540,11 @@ class PathSamples:
     def eval_sub(self, maps, Z, draw_of_point, want_grad=True, want_x=False):
         """eval at x = c + A z (sls_path_eval_sub): values (M,), then with want_grad the gradient in z (d, M), then with want_x the
         expanded points (D, M)."""
-        s = _sub_struct(maps)
         Z = _f(Z)
-        rows, M = max(1, s.d), Z.shape[1]
         dr = None if draw_of_point is None else np.ascontiguousarray(np.asarray(draw_of_point, dtype=np.int32))
-        assert dr is None or dr.shape == (M,)
-        val = np.empty(M)
-        grad = np.empty((rows, M), order="F") if want_grad else None
-        X = np.empty((self.D, M), order="F") if want_x else None
-        _ck(lib().sls_path_eval_sub(self.h, C.byref(s), _p(Z), M, dr.ctypes.data_as(C.POINTER(C.c_int)) if dr is not None else None,
-                                    _p(val), _p(grad) if want_grad else None, _p(X) if want_x else None))
-        out = (val,) + ((grad,) if want_grad else ()) + ((X,) if want_x else ())
-        return out if len(out) > 1 else val
+        assert dr is None or dr.shape == (Z.shape[1],)
+        drp = dr.ctypes.data_as(C.POINTER(C.c_int)) if dr is not None else None
+        return self.gp._eval_sub(lambda s, z, M, *out: lib().sls_path_eval_sub(self.h, s, z, M, drp, *out), maps, Z, want_grad, want_x)
 
     def maximize_sub(self, maps, starts_z, n_local, opts=None):
         """maximize over z in [0,1]^d with x = c + A z (sls_path_maximize_sub): starts_z (d, n_draws * S), columns [s S, (s + 1) S) for
@@ -570,42 +563,52 @@ class PathSamples:
                                         idx.ctypes.data_as(C.POINTER(C.c_long))))
         return dict(z=z, x=x, value=val, index=idx)
 
+    # ---- the set-shaped objectives (sls_qeubo_*, sls_qnei_*, sls_qlognei_*, sls_line_*): one body per kind of call
+    def _set_block(self, who, q, block, what, qmin=1):
+        """q within its range and, for a block of sets (block None: the range alone), its qD rows."""
+        q = int(q)
+        if not qmin <= q <= QEUBO_MAX_OPTIONS:
+            raise SlsError(f"{who}: q = {q} ({qmin} .. {QEUBO_MAX_OPTIONS})")
+        if block is not None and (block.ndim != 2 or block.shape[0] != q * self.D):
+            n = "M" if what == "sets" else "S"
+            raise SlsError(f"{who}: {what} must be qD x {n} = {q * self.D} x {n}, got {block.shape}")
+        return q
+
+    def _set_eval(self, call, rows, q, block, want_grad, want_wins, *lead_args):
+        """call(h, q, *lead_args, block, M, val, grad, wins) at the M columns of block: values (M,), then with want_grad the gradient
+        (rows, M), then with want_wins the win counts (q, M) int32."""
+        M = block.shape[1]
+        val = np.empty(M)
+        grad = np.empty((rows, M), order="F") if want_grad else None
+        wins = np.zeros((q, M), dtype=np.int32, order="F") if want_wins else None
+        _ck(call(self.h, q, *lead_args, _p(block), M, _p(val), _p(grad) if want_grad else None,
+                 wins.ctypes.data_as(C.POINTER(C.c_int)) if want_wins else None))
+        out = (val,) + ((grad,) if want_grad else ()) + ((wins,) if want_wins else ())
+        return out if len(out) > 1 else val
+
+    def _set_maximize(self, call, rows, block, n_local, offset, want_all, opts, *lead_args):
+        """call(h, *lead_args, starts, S, n_local, opts, offset, x, value, index, x_stars, y_stars) from the S columns of block."""
+        S = block.shape[1]
+        x, val, idx = np.empty(rows), C.c_double(), C.c_long()
+        xs = np.empty((rows, S), order="F") if want_all else None
+        ys = np.empty(S) if want_all else None
+        _ck(call(self.h, *lead_args, _p(block), S, int(n_local), C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x),
+                 C.byref(val), C.byref(idx), _p(xs) if want_all else None, _p(ys) if want_all else None))
+        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+
     def qeubo_eval(self, sets, q, want_grad=True, want_wins=False):
         """Expected utility of the best of q options on the draws (sls_qeubo_eval) at the columns of sets (qD x M: rows iD..iD+D-1 =
         option i): values (M,), then with want_grad the gradient (qD, M), then with want_wins the win counts (q, M) int32."""
         sets = _f(sets)
-        q = int(q)
-        if not 1 <= q <= QEUBO_MAX_OPTIONS:
-            raise SlsError(f"qeubo_eval: q = {q} (1 .. {QEUBO_MAX_OPTIONS})")
-        if sets.ndim != 2 or sets.shape[0] != q * self.D:
-            raise SlsError(f"qeubo_eval: sets must be qD x M = {q * self.D} x M, got {sets.shape}")
-        M = sets.shape[1]
-        val = np.empty(M)
-        grad = np.empty((q * self.D, M), order="F") if want_grad else None
-        wins = np.zeros((q, M), dtype=np.int32, order="F") if want_wins else None
-        _ck(lib().sls_qeubo_eval(self.h, q, _p(sets), M, _p(val), _p(grad) if want_grad else None,
-                                 wins.ctypes.data_as(C.POINTER(C.c_int)) if want_wins else None))
-        out = (val,) + ((grad,) if want_grad else ()) + ((wins,) if want_wins else ())
-        return out if len(out) > 1 else val
+        q = self._set_block("qeubo_eval", q, sets, "sets")
+        return self._set_eval(lib().sls_qeubo_eval, q * self.D, q, sets, want_grad, want_wins)
 
     def qeubo_maximize(self, starts, q, n_local, offset=0, want_all=True, opts=None):
         """acq_maximize over [0,1]^(qD) with the set objective of qeubo_eval (sls_qeubo_maximize): starts qD x S, x and x_stars have
         qD rows.  GP.last_stats() of the path's handle reports the run."""
         starts = _f(starts)
-        q = int(q)
-        if not 1 <= q <= QEUBO_MAX_OPTIONS:
-            raise SlsError(f"qeubo_maximize: q = {q} (1 .. {QEUBO_MAX_OPTIONS})")
-        if starts.ndim != 2 or starts.shape[0] != q * self.D:
-            raise SlsError(f"qeubo_maximize: starts must be qD x S = {q * self.D} x S, got {starts.shape}")
-        S = starts.shape[1]
-        rows = starts.shape[0]
-        x, val, idx = np.empty(rows), C.c_double(), C.c_long()
-        xs = np.empty((rows, S), order="F") if want_all else None
-        ys = np.empty(S) if want_all else None
-        _ck(lib().sls_qeubo_maximize(self.h, q, _p(starts), S, int(n_local), C.byref(opts) if opts is not None else None,
-                                     C.c_long(offset), _p(x), C.byref(val), C.byref(idx), _p(xs) if want_all else None,
-                                     _p(ys) if want_all else None))
-        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+        q = self._set_block("qeubo_maximize", q, starts, "starts")
+        return self._set_maximize(lib().sls_qeubo_maximize, q * self.D, starts, n_local, offset, want_all, opts, q)
 
     def max_over_points(self, Xb):
         """Per draw, the maximum over the columns of Xb (D x Mb, Mb >= 1) and the lowest column that attains it
@@ -629,40 +632,17 @@ class PathSamples:
         M: rows iD..iD+D-1 = point i): values (M,), then with want_grad the gradient (qD, M), then with want_wins the win counts
         (q, M) int32."""
         sets = _f(sets)
-        q = int(q)
-        if not 1 <= q <= QEUBO_MAX_OPTIONS:
-            raise SlsError(f"qnei_eval: q = {q} (1 .. {QEUBO_MAX_OPTIONS})")
-        if sets.ndim != 2 or sets.shape[0] != q * self.D:
-            raise SlsError(f"qnei_eval: sets must be qD x M = {q * self.D} x M, got {sets.shape}")
+        q = self._set_block("qnei_eval", q, sets, "sets")
         t = self._baseline("qnei_eval", baseline)
-        M = sets.shape[1]
-        val = np.empty(M)
-        grad = np.empty((q * self.D, M), order="F") if want_grad else None
-        wins = np.zeros((q, M), dtype=np.int32, order="F") if want_wins else None
-        _ck(lib().sls_qnei_eval(self.h, q, _p(t), _p(sets), M, _p(val), _p(grad) if want_grad else None,
-                                wins.ctypes.data_as(C.POINTER(C.c_int)) if want_wins else None))
-        out = (val,) + ((grad,) if want_grad else ()) + ((wins,) if want_wins else ())
-        return out if len(out) > 1 else val
+        return self._set_eval(lib().sls_qnei_eval, q * self.D, q, sets, want_grad, want_wins, _p(t))
 
     def qnei_maximize(self, starts, q, n_local, baseline, offset=0, want_all=True, opts=None):
         """acq_maximize over [0,1]^(qD) with the set objective of qnei_eval (sls_qnei_maximize): starts qD x S, x and x_stars have qD
         rows.  GP.last_stats() of the path's handle reports the run."""
         starts = _f(starts)
-        q = int(q)
-        if not 1 <= q <= QEUBO_MAX_OPTIONS:
-            raise SlsError(f"qnei_maximize: q = {q} (1 .. {QEUBO_MAX_OPTIONS})")
-        if starts.ndim != 2 or starts.shape[0] != q * self.D:
-            raise SlsError(f"qnei_maximize: starts must be qD x S = {q * self.D} x S, got {starts.shape}")
+        q = self._set_block("qnei_maximize", q, starts, "starts")
         t = self._baseline("qnei_maximize", baseline)
-        S = starts.shape[1]
-        rows = starts.shape[0]
-        x, val, idx = np.empty(rows), C.c_double(), C.c_long()
-        xs = np.empty((rows, S), order="F") if want_all else None
-        ys = np.empty(S) if want_all else None
-        _ck(lib().sls_qnei_maximize(self.h, q, _p(t), _p(starts), S, int(n_local), C.byref(opts) if opts is not None else None,
-                                    C.c_long(offset), _p(x), C.byref(val), C.byref(idx), _p(xs) if want_all else None,
-                                    _p(ys) if want_all else None))
-        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+        return self._set_maximize(lib().sls_qnei_maximize, q * self.D, starts, n_local, offset, want_all, opts, q, _p(t))
 
     @staticmethod
     def _temperatures(who, tau_relu, tau_max):
@@ -678,48 +658,23 @@ class PathSamples:
         of sets (qD x M: rows iD..iD+D-1 = point i): values (M,), then with want_grad the gradient (qD, M), then with want_wins the
         hard win counts of qnei_eval (q, M) int32."""
         sets = _f(sets)
-        q = int(q)
-        if not 1 <= q <= QEUBO_MAX_OPTIONS:
-            raise SlsError(f"qlognei_eval: q = {q} (1 .. {QEUBO_MAX_OPTIONS})")
-        if sets.ndim != 2 or sets.shape[0] != q * self.D:
-            raise SlsError(f"qlognei_eval: sets must be qD x M = {q * self.D} x M, got {sets.shape}")
+        q = self._set_block("qlognei_eval", q, sets, "sets")
         t = self._baseline("qlognei_eval", baseline)
         t0, tm = self._temperatures("qlognei_eval", tau_relu, tau_max)
-        M = sets.shape[1]
-        val = np.empty(M)
-        grad = np.empty((q * self.D, M), order="F") if want_grad else None
-        wins = np.zeros((q, M), dtype=np.int32, order="F") if want_wins else None
-        _ck(lib().sls_qlognei_eval(self.h, q, _p(t), t0, tm, _p(sets), M, _p(val), _p(grad) if want_grad else None,
-                                   wins.ctypes.data_as(C.POINTER(C.c_int)) if want_wins else None))
-        out = (val,) + ((grad,) if want_grad else ()) + ((wins,) if want_wins else ())
-        return out if len(out) > 1 else val
+        return self._set_eval(lib().sls_qlognei_eval, q * self.D, q, sets, want_grad, want_wins, _p(t), t0, tm)
 
     def qlognei_maximize(self, starts, q, n_local, baseline, tau_relu=QLOGNEI_TAU_RELU, tau_max=QLOGNEI_TAU_MAX, offset=0,
                          want_all=True, opts=None):
         """acq_maximize over [0,1]^(qD) with the set objective of qlognei_eval (sls_qlognei_maximize): starts qD x S, x and x_stars
         have qD rows.  GP.last_stats() of the path's handle reports the run."""
         starts = _f(starts)
-        q = int(q)
-        if not 1 <= q <= QEUBO_MAX_OPTIONS:
-            raise SlsError(f"qlognei_maximize: q = {q} (1 .. {QEUBO_MAX_OPTIONS})")
-        if starts.ndim != 2 or starts.shape[0] != q * self.D:
-            raise SlsError(f"qlognei_maximize: starts must be qD x S = {q * self.D} x S, got {starts.shape}")
+        q = self._set_block("qlognei_maximize", q, starts, "starts")
         t = self._baseline("qlognei_maximize", baseline)
         t0, tm = self._temperatures("qlognei_maximize", tau_relu, tau_max)
-        S = starts.shape[1]
-        rows = starts.shape[0]
-        x, val, idx = np.empty(rows), C.c_double(), C.c_long()
-        xs = np.empty((rows, S), order="F") if want_all else None
-        ys = np.empty(S) if want_all else None
-        _ck(lib().sls_qlognei_maximize(self.h, q, _p(t), t0, tm, _p(starts), S, int(n_local),
-                                       C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val),
-                                       C.byref(idx), _p(xs) if want_all else None, _p(ys) if want_all else None))
-        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+        return self._set_maximize(lib().sls_qlognei_maximize, q * self.D, starts, n_local, offset, want_all, opts, q, _p(t), t0, tm)
 
     def _line_args(self, who, q, anchor, baseline, block, what):
-        q = int(q)
-        if not LINE_MIN_POSITIONS <= q <= QEUBO_MAX_OPTIONS:
-            raise SlsError(f"{who}: q = {q} ({LINE_MIN_POSITIONS} .. {QEUBO_MAX_OPTIONS})")
+        q = self._set_block(who, q, None, what, LINE_MIN_POSITIONS)
         a = None
         if anchor is not None:
             a = np.ascontiguousarray(np.asarray(anchor, dtype=np.float64))
@@ -731,34 +686,24 @@ class PathSamples:
         t = self._baseline(who, baseline) if baseline is not None else None
         return q, a, t, rows
 
+    @staticmethod
+    def _opt(a):
+        return _p(a) if a is not None else None
+
     def line_eval(self, lines, q, anchor=None, baseline=None, want_grad=True, want_wins=False):
         """Expected utility of the best of q grid positions on the slider from a to b (sls_line_eval) at the columns of lines (2D x M:
         rows 0..D-1 = a, D..2D-1 = b; with anchor (D,) every line starts there and lines is D x M = b).  With baseline (n_draws,) the
         qNEI form.  Values (M,), then with want_grad the gradient (2D or D, M), then with want_wins the win counts (q, M) int32."""
         lines = _f(lines)
         q, a, t, rows = self._line_args("line_eval", q, anchor, baseline, lines, "lines")
-        M = lines.shape[1]
-        val = np.empty(M)
-        grad = np.empty((rows, M), order="F") if want_grad else None
-        wins = np.zeros((q, M), dtype=np.int32, order="F") if want_wins else None
-        _ck(lib().sls_line_eval(self.h, q, _p(t) if t is not None else None, _p(a) if a is not None else None, _p(lines), M, _p(val),
-                                _p(grad) if want_grad else None, wins.ctypes.data_as(C.POINTER(C.c_int)) if want_wins else None))
-        out = (val,) + ((grad,) if want_grad else ()) + ((wins,) if want_wins else ())
-        return out if len(out) > 1 else val
+        return self._set_eval(lib().sls_line_eval, rows, q, lines, want_grad, want_wins, self._opt(t), self._opt(a))
 
     def line_maximize(self, starts, q, n_local, anchor=None, baseline=None, offset=0, want_all=True, opts=None):
         """acq_maximize over the ends of a slider with the objective of line_eval (sls_line_maximize): starts 2D x S (D x S with
         anchor), x and x_stars have as many rows.  GP.last_stats() of the path's handle reports the run."""
         starts = _f(starts)
         q, a, t, rows = self._line_args("line_maximize", q, anchor, baseline, starts, "starts")
-        S = starts.shape[1]
-        x, val, idx = np.empty(rows), C.c_double(), C.c_long()
-        xs = np.empty((rows, S), order="F") if want_all else None
-        ys = np.empty(S) if want_all else None
-        _ck(lib().sls_line_maximize(self.h, q, _p(t) if t is not None else None, _p(a) if a is not None else None, _p(starts), S,
-                                    int(n_local), C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val),
-                                    C.byref(idx), _p(xs) if want_all else None, _p(ys) if want_all else None))
-        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+        return self._set_maximize(lib().sls_line_maximize, rows, starts, n_local, offset, want_all, opts, q, self._opt(t), self._opt(a))
 
 
 class PrefCfg(C.Structure):

@@ -831,13 +831,8 @@ static void eval_candidates(sls_gp* g, const double* xr, long ldr, int S, const 
             SLS_HIP(hipMemsetAsync(cw_part, 0, (size_t)2 * nbt * ldk * 8, c->stream));
         } else if (want_grad) {
             ProfScope ps(c, "grad_gemm");
-            double* part = nullptr;
-            if (D <= 64 && grad_gemm_wants_split(Sp)) {
-                g->Gpart.ensure((size_t)8 * Sp * 64);
-                part = g->Gpart.p;
-            }
             launch_grad_gemm(c->stream, g->P.p, Cs, ldk, Sp, g->XT.p, g->XaT.p, Np, Np, D <= 64 ? -g->Dcols : g->Dcols, g->Gs.p, g->Gm.p,
-                             part);
+                             grad_split_scratch(g->Gpart, D, Sp));
         }
         {
             ProfScope ps(c, "finalize");
@@ -1625,12 +1620,8 @@ static void eval_pairs(sls_gp* g, const double* xr, long ldr, int S, double* val
                 SLS_HIP(hipMemsetAsync(cw_part[o], 0, (size_t)2 * nbt * ldk * 8, c->stream));
                 continue;
             }
-            double* part = nullptr;
-            if (D <= 64 && grad_gemm_wants_split(Sp)) {
-                g->Gpart.ensure((size_t)8 * Sp * 64);
-                part = g->Gpart.p;
-            }
-            launch_grad_gemm(c->stream, g->P.p, Cs[o], ldk, Sp, g->XT.p, g->XaT.p, Np, Np, D <= 64 ? -g->Dcols : g->Dcols, Gs[o], Gm[o], part);
+            launch_grad_gemm(c->stream, g->P.p, Cs[o], ldk, Sp, g->XT.p, g->XaT.p, Np, Np, D <= 64 ? -g->Dcols : g->Dcols, Gs[o], Gm[o],
+                             grad_split_scratch(g->Gpart, D, Sp));
         }
         {
             ProfScope ps(c, "eubo");

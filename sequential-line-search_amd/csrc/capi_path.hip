@@ -1,6 +1,16 @@
-// C-ABI of the pathwise posterior function draws (include/sls_hip.h: sls_path_*, and sls_qeubo_* / sls_qnei_* on them): host orchestration of
-// kernels_path.hip and kernels_qeubo.hip, the cross Gram / gradient products of kernels_gram.hip / kernels_acq.hip, the tile GEMM
-// and block solve of kernels_tri.hip and the lock-step L-BFGS rounds of lbfgs_driver.hpp.  No CPU fallback.
+// C-ABI of the pathwise posterior function draws (include/sls_hip.h: sls_path_*, and sls_qeubo_* / sls_qnei_* / sls_qlognei_* /
+// sls_line_* on them): host orchestration of kernels_path.hip and kernels_qeubo.hip, the cross Gram / gradient products of
+// kernels_gram.hip / kernels_acq.hip, the tile GEMM and block solve of kernels_tri.hip and the lock-step L-BFGS rounds of
+// lbfgs_driver.hpp.  No CPU fallback.
+// Every route is put together from the same pieces:
+//   PassWs / SetWs          the device blocks of a pass of points, and what a pass of sets adds to them
+//   PassPoints              where the raw coordinates of a pass live (point-major, candidate-major, q option segments)
+//   pass_cross_gram         scaled coordinates and K*, C* of a pass, tiled or from the raw differences (gram_direct)
+//   every_draw_prefix       pass_cross_gram, the features and Phi^T W: every draw at every point, before the caller's data term
+//   gathered_route          one weight column per point: value, data term and gradient (tiled, or direct beyond the guard)
+//   path_eval_gathered      host body of sls_path_eval (gathered form) and sls_path_eval_sub
+//   path_maximize           host body of sls_path_maximize and sls_path_maximize_sub
+//   set_eval / set_maximize host bodies of sls_qeubo_*, sls_qnei_*, sls_qlognei_* and sls_line_* (SetCall tells them apart)
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -42,119 +52,154 @@ namespace {
 // candidates per device pass: the chunk x Np blocks (K*, C*, Pm) and the chunk x 2Fp block (G / Phi) stay below 2^26 doubles each
 int chunk_of(int Np, int Fp) { return std::max(128, std::min(16384, ((1 << 26) / std::max(Np, 2 * Fp)) / 128 * 128)); }
 
-// Device blocks of one evaluation pass (one call)
-struct EvalWs {
-    // Pm and G share one block: G = Pm + Cp Np (same leading dimension), so that [Pm | G] is ONE operand of the gradient contraction
-    // against B2 = [X~ ; Om] (k-stacked, built once per call)
-    // Gd: the data term's gradient contraction over raw coordinate differences, for handles beyond the guard of the norm expansion
+// Device blocks of a pass of points (one call).  Pm and G share one block: G = Pm + Pp Np (same leading dimension), so that [Pm | G]
+// is ONE operand of the gradient contraction against B2 = [X~ ; Om] (k-stacked, built once per call).  Gd: the data term's gradient
+// contraction over raw coordinate differences, for handles beyond the guard of the norm expansion.
+struct PassWs {
     DBuf XsT, ns, Ks, Cs, PG, csum, vpart, Gt, B2, Gpart, Gd;
     bool b2_ready = false;
-    void ensure(const sls_path* p, const GpView& g, int chunk) {
-        const size_t C = chunk, Np = g.Np;
-        if (g.gram_direct) Gd.ensure(C * g.Dcols);
-        XsT.ensure(C * g.Dcols);
-        ns.ensure(C);
-        Ks.ensure(C * Np);
-        if (g.kernel == SLS_KERNEL_ARD_MATERN52) Cs.ensure(C * Np);
-        PG.ensure(C * (Np + 2 * (size_t)p->Fp));
-        csum.ensure(C);
-        vpart.ensure(C * (size_t)(p->Fp / 128));
-        Gt.ensure(C * g.Dcols);
+    // Pp points; values_only: the blocks of the every-draw values alone (sls_path_max_over_points)
+    void ensure(const sls_path* p, const GpView& g, int Pp, bool values_only = false) {
+        const size_t P = Pp, Np = g.Np, Fp = p->Fp;
+        XsT.ensure(P * g.Dcols);
+        ns.ensure(P);
+        Ks.ensure(P * Np);
+        if (g.kernel == SLS_KERNEL_ARD_MATERN52) Cs.ensure(P * Np);
+        PG.ensure(P * (Np + 2 * Fp));
+        if (values_only) return;
+        csum.ensure(P);
+        vpart.ensure(P * (Fp / 128));
+        Gt.ensure(P * g.Dcols);
+        if (g.gram_direct) Gd.ensure(P * g.Dcols);
     }
+    // B2 = [X~ ; Om], Np + Fp deep: for the gradient of a handle inside the guard
+    void ensure_b2(const sls_path* p, const GpView& g) {
+        if (b2_ready) return;
+        const long Np = g.Np, Fp = p->Fp, Kc = Np + Fp;
+        hipStream_t s = g.ctx->stream;
+        B2.ensure((size_t)Kc * g.Dcols);
+        SLS_HIP(hipMemcpy2DAsync(B2.p, Kc * 8, g.XT, (size_t)Np * 8, (size_t)Np * 8, g.Dcols, hipMemcpyDeviceToDevice, s));
+        SLS_HIP(hipMemcpy2DAsync(B2.p + Np, Kc * 8, p->Om.p, (size_t)Fp * 8, (size_t)Fp * 8, g.Dcols, hipMemcpyDeviceToDevice, s));
+        b2_ready = true;
+    }
+    double* cstar(const GpView& g) { return g.kernel == SLS_KERNEL_ARD_MATERN52 ? Cs.p : Ks.p; }   // C* (the SE kernel's is K*)
 };
 
-// S candidates at raw coordinates xr: candidate-major xr[n + d*ldr], or point-major xr[d + n*D].
-//   draw != nullptr (device, S ints): val[n] = f_{draw[n]}(x_n), grad[n + d*ldgrad] (may be nullptr);
-//   draw == nullptr: val[n + s*ldall] = f_s(x_n) for every draw s (val has Rp columns), no gradient.
-// Per chunk: cross_gram (K*, C*) -> the random-feature contraction on the matrix cores (path_feat) -> gathered form: chunk sums of the
-// value, data term (path_data), gradient = G Om^T + Pm X~^T on the tile GEMM (path_grad); every-draw form: Phi^T W on the tile GEMM,
-// then the data term.
-void path_eval_device(sls_path* p, const GpView& g, EvalWs& w, const double* xr, long ldr, bool point_major, int S, const int* draw,
+// Where the raw coordinates of a pass's points live: nseg segments of `rows` padded rows each (the pass's points are segment-major,
+// nseg * rows in all), the first `live` of every segment real, coordinate d of point n of segment i at x[(i D + d) sd + n sn].  This is
+// the point-major block (sn = D, sd = 1, one segment), the candidate-major block (sn = 1, sd = its leading dimension, one segment)
+// and the candidate-major set block (segment i = option i of every set).  Candidate-major blocks are padded to 128 columns, so
+// sd == 1 says point-major.
+struct PassPoints {
+    const double* x;
+    long sn, sd;
+    int nseg, rows, live;
+    int padded() const { return nseg * rows; }
+    const double* seg(int i, int D) const { return x + (size_t)i * D * sd; }
+};
+
+// Scaled coordinates, norms and K* / C* of a pass: cross_gram on the tiles, or, for handles beyond the guard of the norm expansion
+// (kernels.hpp), the data term from the raw coordinate differences.
+void pass_cross_gram(const GpView& g, PassWs& w, const PassPoints& pt) {
+    sls_ctx* c = g.ctx;
+    const int D = g.D, Pp = pt.padded();
+    KernelSpec ks{g.kernel, g.a};
+    ProfScope ps(c, "cross_gram");
+    for (int i = 0; i < pt.nseg; ++i) {
+        const size_t o = (size_t)i * pt.rows;
+        if (pt.sd == 1) launch_prep_points(c->stream, pt.seg(i, D), D, pt.live, g.inv_ell, w.XsT.p + o, Pp, pt.rows, g.Dcols, w.ns.p + o);
+        else launch_prep_cands(c->stream, pt.seg(i, D), pt.sd, D, pt.live, g.inv_ell, w.XsT.p + o, Pp, pt.rows, g.Dcols, w.ns.p + o);
+    }
+    if (!g.gram_direct)
+        launch_cross_gram(c->stream, w.XsT.p, Pp, w.ns.p, Pp, g.XT, g.Np, g.nx, g.Np, g.N, g.Dp, ks, nullptr, w.Ks.p, w.cstar(g), Pp, nullptr,
+                          nullptr);
+    else
+        for (int i = 0; i < pt.nseg; ++i)
+            launch_cross_gram_direct(c->stream, pt.seg(i, D), pt.sn, pt.sd, pt.live, pt.rows, g.X, D, g.inv_ell, g.Np, g.N, ks, nullptr,
+                                     w.Ks.p + (size_t)i * pt.rows, w.cstar(g) + (size_t)i * pt.rows, Pp, nullptr, nullptr);
+}
+
+// The prior part of every draw at every point of a pass: pass_cross_gram, the features Phi (nfeat rows of them) into G's 2Fp
+// columns, dst[n + s*ldd] = (Phi^T W)[n, s] on the tile GEMM.  The data term is the caller's: the two every-draw routes add it in
+// different ways (path_data / an accumulating tile GEMM) and so differ in their bits.
+void every_draw_prefix(sls_path* p, const GpView& g, PassWs& w, const PassPoints& pt, int nfeat, double* dst, long ldd) {
+    sls_ctx* c = g.ctx;
+    const int Fp = p->Fp, Pp = pt.padded();
+    double* G = w.PG.p + (size_t)Pp * g.Np;
+    pass_cross_gram(g, w, pt);
+    ProfScope ps(c, "path_prior");
+    launch_path_feat(c->stream, w.XsT.p, Pp, g.Dp, Pp, p->Om.p, Fp, p->W.p, 2L * Fp, nullptr, nfeat, G, Pp, nullptr, 0);
+    launch_gemm_plain(c->stream, G, Pp, false, p->W.p, 2L * Fp, true, dst, ldd, Pp / 128, p->Rp / 128, 2 * Fp, 1.0, 0.0);
+}
+
+// The gathered route on a pass whose K* / C* stand (pass_cross_gram): point n < count under column draw[n] of the weight blocks W
+// (2Fp rows) and V (Np rows).  val[n] = the chunk sums of the random-feature contraction on the matrix cores (path_feat) plus the data
+// term (path_data); with want_grad, grad[n + d*ldgrad] = G Om^T + Pm X~^T on the tile GEMM (path_grad), or beyond the guard G Om^T
+// and the data term over the raw coordinate differences of pt (path_grad_direct).
+void gathered_route(sls_path* p, const GpView& g, PassWs& w, const PassPoints& pt, const double* W, long ldw, const double* V, long ldv,
+                    const int* draw, int count, bool want_grad, double* val, double* grad, long ldgrad) {
+    sls_ctx* c = g.ctx;
+    const int D = g.D, Np = g.Np, Fp = p->Fp, Pp = pt.padded();
+    double* Pm = w.PG.p;
+    double* G = w.PG.p + (size_t)Pp * Np;
+    {
+        ProfScope ps(c, "path_prior");
+        launch_path_feat(c->stream, w.XsT.p, Pp, g.Dp, Pp, p->Om.p, Fp, W, ldw, draw, count, G, Pp, w.vpart.p, Pp);
+        launch_path_vsum(c->stream, w.vpart.p, Pp, Fp / 128, count, val);
+    }
+    {
+        ProfScope ps(c, "path_data");
+        launch_path_data(c->stream, w.Ks.p, w.cstar(g), Pp, g.N, Np, V, ldv, draw, 0, 0, count, val, want_grad ? Pm : nullptr, w.csum.p);
+    }
+    if (!want_grad) return;
+    {
+        ProfScope ps(c, "path_grad_gemm");
+        double* part = grad_split_scratch(w.Gpart, D, Pp);
+        const int dcols = D <= 64 ? -g.Dcols : g.Dcols;
+        if (g.gram_direct) {
+            // Beyond the guard: Gt = G Om alone (Fp deep) and the data term over raw coordinate differences (grad_direct).  In the one
+            // contraction below the accumulator carries x~* sum_i c_i (|x~| ~ 1 / (2 l)) through the Fp additions of the prior and
+            // loses it again only in path_grad: eps |x~| |csum| sqrt(Fp) / l, 20 times the rounding of the terms themselves at
+            // F = 16384, l = 3e-3 (DESIGN.md 9a).
+            launch_grad_gemm(c->stream, G, nullptr, Pp, Pp, p->Om.p, nullptr, Fp, Fp, dcols, w.Gt.p, nullptr, part, 1);
+            for (int i = 0; i < pt.nseg; ++i)
+                launch_grad_direct(c->stream, Pm + (size_t)i * pt.rows, nullptr, Pp, pt.rows, pt.seg(i, D), pt.sn, pt.sd, pt.live, g.X, D,
+                                   g.inv_ell, g.N, nullptr, w.Gd.p + (size_t)i * pt.rows, nullptr);
+        } else {
+            // Gt = [Pm | G] [X~ ; Om]: X~^T c of the data term plus the prior's gradient in scaled coordinates, ONE MFMA contraction
+            // (Np + Fp deep) on grad_gemm's P-pass alone (fixed quarter order: a candidate's bits do not depend on the launch)
+            const long Kc = (long)Np + Fp;
+            launch_grad_gemm(c->stream, Pm, nullptr, Pp, Pp, w.B2.p, nullptr, Kc, (int)Kc, dcols, w.Gt.p, nullptr, part, 1);
+        }
+    }
+    ProfScope ps(c, "path_data");
+    if (g.gram_direct) launch_path_grad_direct(c->stream, count, D, Pp, w.Gt.p, w.Gd.p, g.inv_ell, grad, ldgrad);
+    else launch_path_grad(c->stream, count, D, Pp, w.Gt.p, w.XsT.p, w.csum.p, g.inv_ell, grad, ldgrad);
+}
+
+// S candidates at raw coordinates xr: candidate-major xr[n + d*ldr], or point-major xr[d + n*D], in chunks of chunk_of.
+//   draw != nullptr (device, S ints): val[n] = f_{draw[n]}(x_n), grad[n + d*ldgrad] (may be nullptr): the gathered route;
+//   draw == nullptr: val[n + s*ldall] = f_s(x_n) for every draw s (val has Rp columns), no gradient: the every-draw prefix, then the
+//   data term (path_data).
+void path_eval_device(sls_path* p, const GpView& g, PassWs& w, const double* xr, long ldr, bool point_major, int S, const int* draw,
                       double* val, long ldall, double* grad, long ldgrad) {
     sls_ctx* c = g.ctx;
     const int D = g.D, Np = g.Np, Fp = p->Fp;
     const int chunk_max = std::min(round_up(S, 128), chunk_of(Np, Fp));
     w.ensure(p, g, chunk_max);
-    KernelSpec ks{g.kernel, g.a};
-    double* Cs = g.kernel == SLS_KERNEL_ARD_MATERN52 ? w.Cs.p : w.Ks.p;
-    const long Kc = (long)Np + Fp;   // depth of the gradient contraction [Pm | G] [X~ ; Om]
-    if (grad && !g.gram_direct && !w.b2_ready) {
-        w.B2.ensure((size_t)Kc * g.Dcols);
-        SLS_HIP(hipMemcpy2DAsync(w.B2.p, Kc * 8, g.XT, (size_t)Np * 8, (size_t)Np * 8, g.Dcols, hipMemcpyDeviceToDevice, c->stream));
-        SLS_HIP(hipMemcpy2DAsync(w.B2.p + Np, Kc * 8, p->Om.p, (size_t)Fp * 8, (size_t)Fp * 8, g.Dcols, hipMemcpyDeviceToDevice, c->stream));
-        w.b2_ready = true;
-    }
+    if (grad && !g.gram_direct) w.ensure_b2(p, g);
     for (int s0 = 0; s0 < S; s0 += chunk_max) {
         const int sc = std::min(chunk_max, S - s0), Cp = round_up(sc, 128);
-        double* Pm = w.PG.p;
-        double* G = w.PG.p + (size_t)Cp * Np;
-        {
-            ProfScope ps(c, "cross_gram");
-            if (point_major) launch_prep_points(c->stream, xr + (size_t)s0 * D, D, sc, g.inv_ell, w.XsT.p, Cp, Cp, g.Dcols, w.ns.p);
-            else launch_prep_cands(c->stream, xr + s0, ldr, D, sc, g.inv_ell, w.XsT.p, Cp, Cp, g.Dcols, w.ns.p);
-            if (g.gram_direct)   // beyond the guard of the norm expansion (kernels.hpp): the data term from the raw coordinate differences
-                launch_cross_gram_direct(c->stream, point_major ? xr + (size_t)s0 * D : xr + s0, point_major ? D : 1, point_major ? 1 : ldr, sc,
-                                         Cp, g.X, D, g.inv_ell, Np, g.N, ks, nullptr, w.Ks.p, Cs, Cp, nullptr, nullptr);
-            else
-                launch_cross_gram(c->stream, w.XsT.p, Cp, w.ns.p, Cp, g.XT, g.Np, g.nx, Np, g.N, g.Dp, ks, nullptr, w.Ks.p, Cs, Cp,
-                                  nullptr, nullptr);
-        }
+        const PassPoints pt = point_major ? PassPoints{xr + (size_t)s0 * D, D, 1, 1, Cp, sc} : PassPoints{xr + s0, 1, ldr, 1, Cp, sc};
         if (!draw) {
-            {
-                ProfScope ps(c, "path_prior");
-                launch_path_feat(c->stream, w.XsT.p, Cp, g.Dp, Cp, p->Om.p, Fp, p->W.p, 2L * Fp, nullptr, sc, G, Cp, nullptr, 0);
-                launch_gemm_plain(c->stream, G, Cp, false, p->W.p, 2L * Fp, true, val + s0, ldall, Cp / 128, p->Rp / 128, 2 * Fp, 1.0,
-                                  0.0);
-            }
+            every_draw_prefix(p, g, w, pt, sc, val + s0, ldall);
             ProfScope ps(c, "path_data");
-            launch_path_data(c->stream, w.Ks.p, Cs, Cp, g.N, Np, p->V.p, Np, nullptr, sc, ldall, sc * p->n_draws, val + s0, nullptr,
+            launch_path_data(c->stream, w.Ks.p, w.cstar(g), Cp, g.N, Np, p->V.p, Np, nullptr, sc, ldall, sc * p->n_draws, val + s0, nullptr,
                              nullptr);
             continue;
         }
-        {
-            ProfScope ps(c, "path_prior");
-            launch_path_feat(c->stream, w.XsT.p, Cp, g.Dp, Cp, p->Om.p, Fp, p->W.p, 2L * Fp, draw + s0, sc, G, Cp, w.vpart.p, Cp);
-            launch_path_vsum(c->stream, w.vpart.p, Cp, Fp / 128, sc, val + s0);
-        }
-        {
-            ProfScope ps(c, "path_data");
-            launch_path_data(c->stream, w.Ks.p, Cs, Cp, g.N, Np, p->V.p, Np, draw + s0, 0, 0, sc, val + s0, grad ? Pm : nullptr,
-                             w.csum.p);
-        }
-        if (grad && g.gram_direct) {
-            // Beyond the guard: Gt = G Om alone (Fp deep) and the data term over raw coordinate differences (grad_direct).  In the one
-            // contraction below the accumulator carries x~* sum_i c_i (|x~| ~ 1 / (2 l)) through the Fp additions of the prior and
-            // loses it again only in path_grad: eps |x~| |csum| sqrt(Fp) / l, 20 times the rounding of the terms themselves at
-            // F = 16384, l = 3e-3 (DESIGN.md 9a).
-            {
-                ProfScope ps(c, "path_grad_gemm");
-                double* part = nullptr;
-                if (D <= 64 && grad_gemm_wants_split(Cp)) {
-                    w.Gpart.ensure((size_t)8 * Cp * 64);
-                    part = w.Gpart.p;
-                }
-                launch_grad_gemm(c->stream, G, nullptr, Cp, Cp, p->Om.p, nullptr, Fp, Fp, D <= 64 ? -g.Dcols : g.Dcols, w.Gt.p, nullptr, part, 1);
-                launch_grad_direct(c->stream, Pm, nullptr, Cp, Cp, point_major ? xr + (size_t)s0 * D : xr + s0, point_major ? D : 1,
-                                   point_major ? 1 : ldr, sc, g.X, D, g.inv_ell, g.N, nullptr, w.Gd.p, nullptr);
-            }
-            ProfScope ps(c, "path_data");
-            launch_path_grad_direct(c->stream, sc, D, Cp, w.Gt.p, w.Gd.p, g.inv_ell, grad + s0, ldgrad);
-        } else if (grad) {
-            {
-                // Gt = [Pm | G] [X~ ; Om]: X~^T c of the data term plus the prior's gradient in scaled coordinates, ONE MFMA contraction
-                // (Np + Fp deep) on grad_gemm's P-pass alone (fixed quarter order: a candidate's bits do not depend on the launch)
-                ProfScope ps(c, "path_grad_gemm");
-                double* part = nullptr;
-                if (D <= 64 && grad_gemm_wants_split(Cp)) {
-                    w.Gpart.ensure((size_t)8 * Cp * 64);
-                    part = w.Gpart.p;
-                }
-                launch_grad_gemm(c->stream, Pm, nullptr, Cp, Cp, w.B2.p, nullptr, Kc, (int)Kc, D <= 64 ? -g.Dcols : g.Dcols, w.Gt.p, nullptr,
-                                 part, 1);
-            }
-            ProfScope ps(c, "path_data");
-            launch_path_grad(c->stream, sc, D, Cp, w.Gt.p, w.XsT.p, w.csum.p, g.inv_ell, grad + s0, ldgrad);
-        }
+        pass_cross_gram(g, w, pt);
+        gathered_route(p, g, w, pt, p->W.p, 2L * Fp, p->V.p, Np, draw + s0, sc, grad != nullptr, val + s0, grad ? grad + s0 : nullptr, ldgrad);
     }
 }
 
@@ -217,87 +262,6 @@ extern "C" int sls_path_destroy(sls_path* p) {
     return SLS_OK;
 }
 
-extern "C" int sls_path_eval(sls_path* p, const double* Xs, int M, const int* draw_of_point, double* val, double* grad) {
-    SLS_TRY
-    SLS_REQUIRE(p != nullptr, "sls_path_eval: p is NULL");
-    SLS_REQUIRE(M >= 0, "sls_path_eval: M = %d", M);
-    SLS_REQUIRE(draw_of_point || !grad, "sls_path_eval: grad must be NULL when draw_of_point is NULL (every-draw form)");
-    if (M == 0) return SLS_OK;
-    SLS_REQUIRE(Xs && val, "sls_path_eval: Xs / val is NULL");
-    if (draw_of_point)
-        for (int m = 0; m < M; ++m)
-            SLS_REQUIRE(draw_of_point[m] >= 0 && draw_of_point[m] < p->n_draws, "sls_path_eval: draw_of_point[%d] = %d (n_draws = %d)", m,
-                        draw_of_point[m], p->n_draws);
-    GpReadCall call(p->gp, p->generation, "sls_path_eval");
-    const GpView& g = call.g;
-    sls_ctx* c = g.ctx;
-    const int D = g.D, Mp = round_up(M, 128), nd = p->n_draws;
-    DBuf raw, vout, gout, dbuf;
-    raw.ensure((size_t)D * M);
-    h2d(c, raw.p, Xs, (size_t)D * M);
-    if (draw_of_point) {
-        int* d_draw = ints(dbuf, (size_t)M);
-        SLS_HIP(hipMemcpyAsync(d_draw, draw_of_point, (size_t)M * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        vout.ensure(Mp);
-        if (grad) gout.ensure((size_t)Mp * D);
-        EvalWs ws;
-        path_eval_device(p, g, ws, raw.p, 0, true, M, d_draw, vout.p, 0, grad ? gout.p : nullptr, Mp);
-        d2h(c, val, vout.p, (size_t)M);
-        std::vector<double> gh(grad ? (size_t)Mp * D : 0);
-        if (grad) d2h(c, gh.data(), gout.p, gh.size());
-        SLS_HIP(hipStreamSynchronize(c->stream));
-        cm_to_host(gh.data(), Mp, D, M, grad);
-    } else {
-        vout.ensure((size_t)Mp * p->Rp);
-        EvalWs ws;
-        path_eval_device(p, g, ws, raw.p, 0, true, M, nullptr, vout.p, Mp, nullptr, 0);
-        SLS_HIP(hipMemcpy2DAsync(val, (size_t)M * 8, vout.p, (size_t)Mp * 8, (size_t)M * 8, nd, hipMemcpyDeviceToHost, c->stream));
-        SLS_HIP(hipStreamSynchronize(c->stream));
-    }
-    SLS_CATCH
-}
-
-extern "C" int sls_path_maximize(sls_path* p, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts, double* x_out,
-                                 double* val_out, long* idx_out) {
-    SLS_TRY
-    SLS_REQUIRE(p && starts, "sls_path_maximize: NULL argument");
-    SLS_REQUIRE(S >= 1 && (long)S * p->n_draws <= (1L << 26), "sls_path_maximize: S = %d starts per draw (1 .. 2^26 / n_draws)", S);
-    GpReadCall call(p->gp, p->generation, "sls_path_maximize");
-    const GpView& g = call.g;
-    sls_ctx* c = g.ctx;
-    const int D = g.D, nd = p->n_draws, T = S * nd, Sp = round_up(T, 128);
-    // the shared prologue and search over all T = n_draws S starts at once; the winner is per DRAW, so the epilogue below is this
-    // entry point's own (and sls_acq_last_stats, which speaks of one winner's run, is left alone)
-    LbfgsWs lb;
-    EvalWs ws;
-    MultistartRun r = maximize_begin("sls_path_maximize", nullptr, lb, opts, T, n_local, D, Sp);
-    const LbfgsState& st = r.st;
-    int* d_draw = lb.tail();   // the draw of every live column
-    DBuf sd;
-    sd.ensure((size_t)D * T);
-    h2d(c, sd.p, starts, (size_t)D * T);
-    // f_{live[j] / S} is the objective of compacted column j
-    lockstep_rounds(c, r.st, lb, sd.p, T, n_local,
-                    [&](const double* trial, long ld, int nlive, const int* live, double* val, double* grad) {
-                        launch_path_draw_of_live(c->stream, live, nlive, S, d_draw);
-                        path_eval_device(p, g, ws, trial, ld, false, nlive, d_draw, val, 0, grad, ld);
-                    },
-                    nullptr);
-    DBuf best;
-    best.ensure((size_t)nd * (D + 2));
-    launch_path_argmax(c->stream, st.f, S, nd, st.x, Sp, D, best.p);
-    std::vector<double> bh((size_t)nd * (D + 2));
-    d2h(c, bh.data(), best.p, bh.size());
-    SLS_HIP(hipStreamSynchronize(c->stream));
-    for (int s = 0; s < nd; ++s) {
-        const double* b = bh.data() + (size_t)s * (D + 2);
-        if (val_out) val_out[s] = b[0];
-        if (idx_out) idx_out[s] = (long)b[1];
-        if (x_out) std::copy(b + 2, b + 2 + D, x_out + (size_t)s * D);
-    }
-    SLS_CATCH
-}
-
 // ---- the draws over affine subspaces (include/sls_hip.h "maximisation over affine subspaces") ------------------------------------
 namespace {
 
@@ -308,7 +272,7 @@ struct SubWs {
 
 // path_eval_device (gathered form) at x = c + A z: z[n + j*ld] candidate-major, n < count, column n is start live[n] (nullptr:
 // identity) under draw[n]; the fold of the gradient onto z goes to grad_z[n + j*ld] (may be nullptr).
-void path_sub_eval_device(sls_path* p, const GpView& g, EvalWs& ws, SubWs& sw, const SubMaps& m, const double* z, long ld, int count,
+void path_sub_eval_device(sls_path* p, const GpView& g, PassWs& ws, SubWs& sw, const SubMaps& m, const double* z, long ld, int count,
                           const int* live, const int* draw, double* val, double* grad_z) {
     sls_ctx* c = g.ctx;
     sw.x.ensure((size_t)g.D * ld);
@@ -320,6 +284,68 @@ void path_sub_eval_device(sls_path* p, const GpView& g, EvalWs& ws, SubWs& sw, c
 
 }  // namespace
 
+// The gathered evaluation behind sls_path_eval (pts = Xs, point-major as the caller holds them) and, with sub, sls_path_eval_sub (pts =
+// Z, evaluated at x = c + A z): the draw indices checked and uploaded, one device call, values / gradient (in the variables: D rows, or
+// d with sub) / expanded points (sub only) back through pageable memory.
+static void path_eval_gathered(const char* who, sls_path* p, bool sub, const sls_submaps* maps, const double* pts, int M,
+                               const int* draw_of_point, double* val, double* grad, double* X_out) {
+    for (int m = 0; m < M; ++m)
+        SLS_REQUIRE(draw_of_point[m] >= 0 && draw_of_point[m] < p->n_draws, "%s: draw_of_point[%d] = %d (n_draws = %d)", who, m,
+                    draw_of_point[m], p->n_draws);
+    GpReadCall call(p->gp, p->generation, who);
+    const GpView& g = call.g;
+    sls_ctx* c = g.ctx;
+    SubMapsDev up;
+    if (sub) upload_sub_maps(who, c, maps, g.D, M, up);
+    const int D = g.D, rows = sub ? up.m.d : D, Mp = round_up(M, 128);
+    const std::vector<double> zh = sub ? host_to_cm(pts, rows, M, Mp) : std::vector<double>();   // alive until the synchronisation
+    const size_t n_in = sub ? zh.size() : (size_t)D * M;
+    DBuf in, vout, gout, dbuf;
+    in.ensure(n_in);
+    h2d(c, in.p, sub ? zh.data() : pts, n_in);
+    int* d_draw = ints(dbuf, (size_t)M);
+    SLS_HIP(hipMemcpyAsync(d_draw, draw_of_point, (size_t)M * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    vout.ensure(Mp);
+    if (grad) gout.ensure((size_t)Mp * rows);
+    PassWs ws;
+    SubWs sw;
+    if (sub) path_sub_eval_device(p, g, ws, sw, up.m, in.p, Mp, M, nullptr, d_draw, vout.p, grad ? gout.p : nullptr);
+    else path_eval_device(p, g, ws, in.p, 0, true, M, d_draw, vout.p, 0, grad ? gout.p : nullptr, Mp);
+    d2h(c, val, vout.p, (size_t)M);
+    std::vector<double> gh(grad ? (size_t)Mp * rows : 0), xh(X_out ? (size_t)Mp * D : 0);
+    if (grad) d2h(c, gh.data(), gout.p, gh.size());
+    if (X_out) d2h(c, xh.data(), sw.x.p, xh.size());
+    SLS_HIP(hipStreamSynchronize(c->stream));
+    cm_to_host(gh.data(), Mp, rows, M, grad);
+    cm_to_host(xh.data(), Mp, D, M, X_out);
+}
+
+extern "C" int sls_path_eval(sls_path* p, const double* Xs, int M, const int* draw_of_point, double* val, double* grad) {
+    SLS_TRY
+    SLS_REQUIRE(p != nullptr, "sls_path_eval: p is NULL");
+    SLS_REQUIRE(M >= 0, "sls_path_eval: M = %d", M);
+    SLS_REQUIRE(draw_of_point || !grad, "sls_path_eval: grad must be NULL when draw_of_point is NULL (every-draw form)");
+    if (M == 0) return SLS_OK;
+    SLS_REQUIRE(Xs && val, "sls_path_eval: Xs / val is NULL");
+    if (draw_of_point) {
+        path_eval_gathered("sls_path_eval", p, false, nullptr, Xs, M, draw_of_point, val, grad, nullptr);
+        return SLS_OK;
+    }
+    GpReadCall call(p->gp, p->generation, "sls_path_eval");
+    const GpView& g = call.g;
+    sls_ctx* c = g.ctx;
+    const int D = g.D, Mp = round_up(M, 128);
+    DBuf raw, vout;
+    raw.ensure((size_t)D * M);
+    h2d(c, raw.p, Xs, (size_t)D * M);
+    vout.ensure((size_t)Mp * p->Rp);
+    PassWs ws;
+    path_eval_device(p, g, ws, raw.p, 0, true, M, nullptr, vout.p, Mp, nullptr, 0);
+    SLS_HIP(hipMemcpy2DAsync(val, (size_t)M * 8, vout.p, (size_t)Mp * 8, (size_t)M * 8, p->n_draws, hipMemcpyDeviceToHost, c->stream));
+    SLS_HIP(hipStreamSynchronize(c->stream));
+    SLS_CATCH
+}
+
 extern "C" int sls_path_eval_sub(sls_path* p, const sls_submaps* maps, const double* Z, int M, const int* draw_of_point, double* val,
                                  double* grad_z, double* X_out) {
     SLS_TRY
@@ -328,83 +354,78 @@ extern "C" int sls_path_eval_sub(sls_path* p, const sls_submaps* maps, const dou
     if (M == 0) return SLS_OK;
     SLS_REQUIRE(draw_of_point != nullptr, "sls_path_eval_sub: draw_of_point is NULL (the every-draw form has no _sub call)");
     SLS_REQUIRE(Z && val, "sls_path_eval_sub: Z / val is NULL");
-    for (int m = 0; m < M; ++m)
-        SLS_REQUIRE(draw_of_point[m] >= 0 && draw_of_point[m] < p->n_draws, "sls_path_eval_sub: draw_of_point[%d] = %d (n_draws = %d)", m,
-                    draw_of_point[m], p->n_draws);
-    GpReadCall call(p->gp, p->generation, "sls_path_eval_sub");
+    path_eval_gathered("sls_path_eval_sub", p, true, maps, Z, M, draw_of_point, val, grad_z, X_out);
+    SLS_CATCH
+}
+
+// sls_path_maximize and, with sub, sls_path_maximize_sub (the same search in the d variables z, x = c + A z: expand and fold around
+// the objective).  All T = n_draws S starts in one search through the shared prologue; the winner is per DRAW, so the epilogue is this
+// body's own (and sls_acq_last_stats, which speaks of one winner's run, is left alone): the per-draw first maximum with the end
+// variables, and with sub once more with their points (one more expand launch).  z_out: sub only.
+static void path_maximize(const char* who, sls_path* p, bool sub, const sls_submaps* maps, const double* starts, int S, int n_local,
+                          const sls_lbfgs_opts* opts, double* z_out, double* x_out, double* val_out, long* idx_out) {
+    SLS_REQUIRE(p && starts, "%s: NULL argument", who);
+    SLS_REQUIRE(S >= 1 && (long)S * p->n_draws <= (1L << 26), "%s: S = %d starts per draw (1 .. 2^26 / n_draws)", who, S);
+    GpReadCall call(p->gp, p->generation, who);
     const GpView& g = call.g;
     sls_ctx* c = g.ctx;
+    const int D = g.D, nd = p->n_draws, T = S * nd, Sp = round_up(T, 128);
     SubMapsDev up;
-    upload_sub_maps("sls_path_eval_sub", c, maps, g.D, M, up);
-    const int D = g.D, d = up.m.d, Mp = round_up(M, 128);
-    const std::vector<double> zh = host_to_cm(Z, d, M, Mp);
-    DBuf zd, vout, gout, dbuf;
-    zd.ensure(zh.size());
-    h2d(c, zd.p, zh.data(), zh.size());
-    int* d_draw = ints(dbuf, (size_t)M);
-    SLS_HIP(hipMemcpyAsync(d_draw, draw_of_point, (size_t)M * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    vout.ensure(Mp);
-    if (grad_z) gout.ensure((size_t)Mp * d);
-    EvalWs ws;
+    if (sub) upload_sub_maps(who, c, maps, D, T, up);
+    const int d = sub ? up.m.d : D;
+    LbfgsWs lb;
+    PassWs ws;
     SubWs sw;
-    path_sub_eval_device(p, g, ws, sw, up.m, zd.p, Mp, M, nullptr, d_draw, vout.p, grad_z ? gout.p : nullptr);
-    d2h(c, val, vout.p, (size_t)M);
-    std::vector<double> gh(grad_z ? (size_t)Mp * d : 0), xh(X_out ? (size_t)Mp * D : 0);
-    if (grad_z) d2h(c, gh.data(), gout.p, gh.size());
-    if (X_out) d2h(c, xh.data(), sw.x.p, xh.size());
+    MultistartRun r = maximize_begin(who, nullptr, lb, opts, T, n_local, d, Sp);
+    const LbfgsState& st = r.st;
+    int* d_draw = lb.tail();   // the draw of every live column
+    DBuf sd;
+    sd.ensure((size_t)d * T);
+    h2d(c, sd.p, starts, (size_t)d * T);
+    // f_{live[j] / S} is the objective of compacted column j
+    lockstep_rounds(c, r.st, lb, sd.p, T, n_local,
+                    [&](const double* trial, long ld, int nlive, const int* live, double* val, double* grad) {
+                        launch_path_draw_of_live(c->stream, live, nlive, S, d_draw);
+                        if (sub) path_sub_eval_device(p, g, ws, sw, up.m, trial, ld, nlive, live, d_draw, val, grad);
+                        else path_eval_device(p, g, ws, trial, ld, false, nlive, d_draw, val, 0, grad, ld);
+                    },
+                    nullptr);
+    if (sub) {
+        sw.x.ensure((size_t)D * Sp);
+        sub_expand(c, up.m, T, nullptr, st.x, Sp, sw.x.p, Sp);
+    }
+    DBuf best;
+    const size_t nz = (size_t)nd * (d + 2), nx = sub ? (size_t)nd * (D + 2) : 0;
+    best.ensure(nz + nx);
+    launch_path_argmax(c->stream, st.f, S, nd, st.x, Sp, d, best.p);
+    if (sub) launch_path_argmax(c->stream, st.f, S, nd, sw.x.p, Sp, D, best.p + nz);
+    std::vector<double> bh(nz + nx);
+    d2h(c, bh.data(), best.p, bh.size());
     SLS_HIP(hipStreamSynchronize(c->stream));
-    cm_to_host(gh.data(), Mp, d, M, grad_z);
-    cm_to_host(xh.data(), Mp, D, M, X_out);
+    double* var_out = sub ? z_out : x_out;   // without maps the variables are the points
+    for (int s = 0; s < nd; ++s) {
+        const double* bz = bh.data() + (size_t)s * (d + 2);
+        if (val_out) val_out[s] = bz[0];
+        if (idx_out) idx_out[s] = (long)bz[1];
+        if (var_out) std::copy(bz + 2, bz + 2 + d, var_out + (size_t)s * d);
+        if (sub && x_out) {
+            const double* bx = bh.data() + nz + (size_t)s * (D + 2);
+            std::copy(bx + 2, bx + 2 + D, x_out + (size_t)s * D);
+        }
+    }
+}
+
+extern "C" int sls_path_maximize(sls_path* p, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts, double* x_out,
+                                 double* val_out, long* idx_out) {
+    SLS_TRY
+    path_maximize("sls_path_maximize", p, false, nullptr, starts, S, n_local, opts, nullptr, x_out, val_out, idx_out);
     SLS_CATCH
 }
 
 extern "C" int sls_path_maximize_sub(sls_path* p, const sls_submaps* maps, const double* starts_z, int S, int n_local,
                                      const sls_lbfgs_opts* opts, double* z_out, double* x_out, double* val_out, long* idx_out) {
     SLS_TRY
-    SLS_REQUIRE(p && starts_z, "sls_path_maximize_sub: NULL argument");
-    SLS_REQUIRE(S >= 1 && (long)S * p->n_draws <= (1L << 26), "sls_path_maximize_sub: S = %d starts per draw (1 .. 2^26 / n_draws)", S);
-    GpReadCall call(p->gp, p->generation, "sls_path_maximize_sub");
-    const GpView& g = call.g;
-    sls_ctx* c = g.ctx;
-    const int D = g.D, nd = p->n_draws, T = S * nd, Sp = round_up(T, 128);
-    SubMapsDev up;
-    upload_sub_maps("sls_path_maximize_sub", c, maps, D, T, up);
-    const int d = up.m.d;
-    // sls_path_maximize in the d variables: all T = n_draws S starts in one search, the winner per draw
-    LbfgsWs lb;
-    EvalWs ws;
-    SubWs sw;
-    MultistartRun r = maximize_begin("sls_path_maximize_sub", nullptr, lb, opts, T, n_local, d, Sp);
-    const LbfgsState& st = r.st;
-    int* d_draw = lb.tail();   // the draw of every live column
-    DBuf sd;
-    sd.ensure((size_t)d * T);
-    h2d(c, sd.p, starts_z, (size_t)d * T);
-    lockstep_rounds(c, r.st, lb, sd.p, T, n_local,
-                    [&](const double* trial, long ld, int nlive, const int* live, double* val, double* grad) {
-                        launch_path_draw_of_live(c->stream, live, nlive, S, d_draw);
-                        path_sub_eval_device(p, g, ws, sw, up.m, trial, ld, nlive, live, d_draw, val, grad);
-                    },
-                    nullptr);
-    // the points of the end variables (one more expand launch), then the per-draw first maximum once with z and once with x
-    sw.x.ensure((size_t)D * Sp);
-    sub_expand(c, up.m, T, nullptr, st.x, Sp, sw.x.p, Sp);
-    DBuf best;
-    const size_t nz = (size_t)nd * (d + 2), nx = (size_t)nd * (D + 2);
-    best.ensure(nz + nx);
-    launch_path_argmax(c->stream, st.f, S, nd, st.x, Sp, d, best.p);
-    launch_path_argmax(c->stream, st.f, S, nd, sw.x.p, Sp, D, best.p + nz);
-    std::vector<double> bh(nz + nx);
-    d2h(c, bh.data(), best.p, bh.size());
-    SLS_HIP(hipStreamSynchronize(c->stream));
-    for (int s = 0; s < nd; ++s) {
-        const double* bz = bh.data() + (size_t)s * (d + 2);
-        const double* bx = bh.data() + nz + (size_t)s * (D + 2);
-        if (val_out) val_out[s] = bz[0];
-        if (idx_out) idx_out[s] = (long)bz[1];
-        if (z_out) std::copy(bz + 2, bz + 2 + d, z_out + (size_t)s * d);
-        if (x_out) std::copy(bx + 2, bx + 2 + D, x_out + (size_t)s * D);
-    }
+    path_maximize("sls_path_maximize_sub", p, true, maps, starts_z, S, n_local, opts, z_out, x_out, val_out, idx_out);
     SLS_CATCH
 }
 
@@ -431,8 +452,9 @@ struct SetMode {
     double tau_relu = 0.0, tau_max = 0.0;
 };
 
-struct QeuboWs {
-    DBuf XsT, ns, Ks, Cs, PG, csum, vpart, Gt, B2, Gpart, Gd, VM, Wbar, Vbar, sum, fbar, gpt, badb, identb;
+// What a pass of sets adds to the blocks of its q Sp points
+struct SetWs : PassWs {
+    DBuf VM, Wbar, Vbar, sum, fbar, gpt, badb, identb;
     DBuf lmq, lzq, lpmx, lpsm, lpbadb, lpwinb;   // the scratch of the log-form selection (launch_qlognei_select)
     int *lpbad = nullptr, *lpwin = nullptr;
     void ensure_log(const sls_path* p, int q, int Sp) {
@@ -444,24 +466,15 @@ struct QeuboWs {
         lpbad = ints(lpbadb, (size_t)Sp * nsl);
         lpwin = ints(lpwinb, (size_t)Sp * nsl * q);
     }
-    bool b2_ready = false;
     int* bad = nullptr;     // one flag per set of the pass
     int* ident = nullptr;   // ident[j] = j: point j is evaluated under aggregated column j
     int ident_n = 0;
-    // values_only: the blocks of the every-draw values alone (sls_path_max_over_points)
-    void ensure(sls_ctx* c, const sls_path* p, const GpView& g, int Pp, int Sp, bool values_only = false) {
+    // Pp points in Sp sets; values_only: the blocks of the every-draw values alone (sls_path_max_over_points)
+    void ensure_sets(sls_ctx* c, const sls_path* p, const GpView& g, int Pp, int Sp, bool values_only = false) {
         const size_t P = Pp, Np = g.Np, Fp = p->Fp;
-        XsT.ensure(P * g.Dcols);
-        ns.ensure(P);
-        Ks.ensure(P * Np);
-        if (g.kernel == SLS_KERNEL_ARD_MATERN52) Cs.ensure(P * Np);
-        PG.ensure(P * (Np + 2 * Fp));
+        ensure(p, g, Pp, values_only);
         VM.ensure(P * p->Rp);
         if (values_only) return;
-        csum.ensure(P);
-        vpart.ensure(P * (Fp / 128));
-        Gt.ensure(P * g.Dcols);
-        if (g.gram_direct) Gd.ensure(P * g.Dcols);
         Wbar.ensure(2 * Fp * P);
         Vbar.ensure(Np * P);
         sum.ensure(Sp);
@@ -476,31 +489,13 @@ struct QeuboWs {
     }
 };
 
-// Every draw at the Pp points of a pass into w.VM (Pp x Rp): `prep` fills XsT / ns, then cross_gram, Phi^T W and K* V accumulated onto
-// it, both on the tile GEMM.  `direct(ks, Cs)`: the cross Gram of the same points from their raw coordinates, for handles beyond the
-// guard of the norm expansion (kernels.hpp).
-template <class Prep, class Direct>
-void draw_values_device(sls_path* p, const GpView& g, QeuboWs& w, int Pp, Prep&& prep, Direct&& direct) {
+// Every draw at the points of a pass into w.VM (Pp x Rp): the every-draw prefix, then K* V accumulated onto it on the tile GEMM
+void draw_values_device(sls_path* p, const GpView& g, SetWs& w, const PassPoints& pt) {
     sls_ctx* c = g.ctx;
-    const int Np = g.Np, Fp = p->Fp, Rp = p->Rp;
-    KernelSpec ks{g.kernel, g.a};
-    double* Cs = g.kernel == SLS_KERNEL_ARD_MATERN52 ? w.Cs.p : w.Ks.p;
-    double* G = w.PG.p + (size_t)Pp * Np;
-    {
-        ProfScope ps(c, "cross_gram");
-        prep();
-        if (g.gram_direct) direct(ks, Cs);
-        else launch_cross_gram(c->stream, w.XsT.p, Pp, w.ns.p, Pp, g.XT, g.Np, g.nx, Np, g.N, g.Dp, ks, nullptr, w.Ks.p, Cs, Pp, nullptr, nullptr);
-    }
-    {
-        ProfScope ps(c, "path_prior");
-        launch_path_feat(c->stream, w.XsT.p, Pp, g.Dp, Pp, p->Om.p, Fp, p->W.p, 2L * Fp, nullptr, Pp, G, Pp, nullptr, 0);
-        launch_gemm_plain(c->stream, G, Pp, false, p->W.p, 2L * Fp, true, w.VM.p, Pp, Pp / 128, Rp / 128, 2 * Fp, 1.0, 0.0);
-    }
-    {
-        ProfScope ps(c, "qeubo_data_gemm");
-        launch_gemm_plain(c->stream, w.Ks.p, Pp, false, p->V.p, Np, true, w.VM.p, Pp, Pp / 128, Rp / 128, Np, 1.0, 1.0);
-    }
+    const int Pp = pt.padded();
+    every_draw_prefix(p, g, w, pt, Pp, w.VM.p, Pp);
+    ProfScope ps(c, "qeubo_data_gemm");
+    launch_gemm_plain(c->stream, w.Ks.p, Pp, false, p->V.p, g.Np, true, w.VM.p, Pp, Pp / 128, p->Rp / 128, g.Np, 1.0, 1.0);
 }
 
 // qEUBO (+ its qD gradient and the win counts; val, grad, wins may each be nullptr) at M sets, candidate-major raw coordinates
@@ -509,7 +504,7 @@ void draw_values_device(sls_path* p, const GpView& g, QeuboWs& w, int Pp, Prep&&
 // base != nullptr (device, n_draws doubles): qNEI -- the selection competes against the per-draw baseline, the guard value is 0 and
 // the two kernels count under "qnei".  mode.log_form: qLogNEI -- the selection is launch_qlognei_select (real weights in place of the
 // mask), the finish divides nothing, the guard value is SLS_QEUBO_FLOOR and the launches count under "qlognei".
-void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const SetMode& mode, const double* xr, long ldr, int M,
+void qeubo_eval_device(sls_path* p, const GpView& g, SetWs& w, int q, const SetMode& mode, const double* xr, long ldr, int M,
                        double* val, double* grad, long ldo, int* wins, long ldw) {
     sls_ctx* c = g.ctx;
     const double* base = mode.base;
@@ -517,29 +512,13 @@ void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const Se
     const double floor = base && !mode.log_form ? 0.0 : SLS_QEUBO_FLOOR;
     const int D = g.D, Np = g.Np, Fp = p->Fp, Rp = p->Rp, S = p->n_draws;
     const int pass_max = std::min(round_up(M, 128), qeubo_sets_per_pass(c, q, Np, Fp, Rp));
-    w.ensure(c, p, g, q * pass_max, pass_max);
+    w.ensure_sets(c, p, g, q * pass_max, pass_max);
     if (mode.log_form) w.ensure_log(p, q, pass_max);
-    double* Cs = g.kernel == SLS_KERNEL_ARD_MATERN52 ? w.Cs.p : w.Ks.p;
-    const long Kc = (long)Np + Fp;
-    if (!g.gram_direct && !w.b2_ready) {
-        w.B2.ensure((size_t)Kc * g.Dcols);
-        SLS_HIP(hipMemcpy2DAsync(w.B2.p, Kc * 8, g.XT, (size_t)Np * 8, (size_t)Np * 8, g.Dcols, hipMemcpyDeviceToDevice, c->stream));
-        SLS_HIP(hipMemcpy2DAsync(w.B2.p + Np, Kc * 8, p->Om.p, (size_t)Fp * 8, (size_t)Fp * 8, g.Dcols, hipMemcpyDeviceToDevice, c->stream));
-        w.b2_ready = true;
-    }
+    if (!g.gram_direct) w.ensure_b2(p, g);
     for (int s0 = 0; s0 < M; s0 += pass_max) {
         const int sc = std::min(pass_max, M - s0), Sp = round_up(sc, 128), Pp = q * Sp;
-        double* Pm = w.PG.p;
-        double* G = w.PG.p + (size_t)Pp * Np;
-        draw_values_device(p, g, w, Pp, [&] {
-            for (int i = 0; i < q; ++i)
-                launch_prep_cands(c->stream, xr + (size_t)i * D * ldr + s0, ldr, D, sc, g.inv_ell, w.XsT.p + (size_t)i * Sp, Pp, Sp, g.Dcols,
-                                  w.ns.p + (size_t)i * Sp);
-        }, [&](KernelSpec ks, double* Cs) {
-            for (int i = 0; i < q; ++i)
-                launch_cross_gram_direct(c->stream, xr + (size_t)i * D * ldr + s0, 1, ldr, sc, Sp, g.X, D, g.inv_ell, g.Np, g.N, ks, nullptr,
-                                         w.Ks.p + (size_t)i * Sp, Cs + (size_t)i * Sp, Pp, nullptr, nullptr);
-        });
+        const PassPoints pt{xr + s0, 1, ldr, q, Sp, sc};   // segment i: option i of the pass's sets
+        draw_values_device(p, g, w, pt);
         {
             ProfScope ps(c, scope);
             if (mode.log_form)
@@ -554,40 +533,9 @@ void qeubo_eval_device(sls_path* p, const GpView& g, QeuboWs& w, int q, const Se
             launch_gemm_plain(c->stream, p->W.p, 2L * Fp, false, w.VM.p, Pp, false, w.Wbar.p, 2L * Fp, 2 * Fp / 128, Pp / 128, Rp, 1.0, 0.0);
             launch_gemm_plain(c->stream, p->V.p, Np, false, w.VM.p, Pp, false, w.Vbar.p, Np, Np / 128, Pp / 128, Rp, 1.0, 0.0);
         }
-        {
-            // the gathered route of a path evaluation with point j under "draw" j of (Wbar, Vbar)
-            ProfScope ps(c, "path_prior");
-            launch_path_feat(c->stream, w.XsT.p, Pp, g.Dp, Pp, p->Om.p, Fp, w.Wbar.p, 2L * Fp, w.ident, Pp, G, Pp, w.vpart.p, Pp);
-            // fbar = fbar_i(x_i) is scratch with no consumer: the reused kernels accumulate a value beside the gradient weights, and
-            // path_data adds onto it, so it starts from path_feat's chunk sums rather than from whatever the block held
-            launch_path_vsum(c->stream, w.vpart.p, Pp, Fp / 128, Pp, w.fbar.p);
-        }
-        {
-            ProfScope ps(c, "path_data");
-            launch_path_data(c->stream, w.Ks.p, Cs, Pp, g.N, Np, w.Vbar.p, Np, w.ident, 0, 0, Pp, w.fbar.p, Pm, w.csum.p);
-        }
-        {
-            ProfScope ps(c, "path_grad_gemm");
-            double* part = nullptr;
-            if (D <= 64 && grad_gemm_wants_split(Pp)) {
-                w.Gpart.ensure((size_t)8 * Pp * 64);
-                part = w.Gpart.p;
-            }
-            if (g.gram_direct) {   // as in path_eval_device: G Om alone, the data term over raw coordinate differences per option
-                launch_grad_gemm(c->stream, G, nullptr, Pp, Pp, p->Om.p, nullptr, Fp, Fp, D <= 64 ? -g.Dcols : g.Dcols, w.Gt.p, nullptr, part, 1);
-                for (int i = 0; i < q; ++i)
-                    launch_grad_direct(c->stream, Pm + (size_t)i * Sp, nullptr, Pp, Sp, xr + (size_t)i * D * ldr + s0, 1, ldr, sc, g.X, D,
-                                       g.inv_ell, g.N, nullptr, w.Gd.p + (size_t)i * Sp, nullptr);
-            } else {
-                launch_grad_gemm(c->stream, Pm, nullptr, Pp, Pp, w.B2.p, nullptr, Kc, (int)Kc, D <= 64 ? -g.Dcols : g.Dcols, w.Gt.p, nullptr,
-                                 part, 1);
-            }
-        }
-        {
-            ProfScope ps(c, "path_data");
-            if (g.gram_direct) launch_path_grad_direct(c->stream, Pp, D, Pp, w.Gt.p, w.Gd.p, g.inv_ell, w.gpt.p, Pp);
-            else launch_path_grad(c->stream, Pp, D, Pp, w.Gt.p, w.XsT.p, w.csum.p, g.inv_ell, w.gpt.p, Pp);
-        }
+        // The gathered route with point j under "draw" j of (Wbar, Vbar).  fbar = fbar_i(x_i) is scratch with no consumer: the route
+        // accumulates a value beside the gradient weights, path_data adding onto path_feat's chunk sums.
+        gathered_route(p, g, w, pt, w.Wbar.p, 2L * Fp, w.Vbar.p, Np, w.ident, Pp, true, w.fbar.p, w.gpt.p, Pp);
         {
             ProfScope ps(c, scope);
             launch_qeubo_finish(c->stream, sc, Sp, q, D, S, w.sum.p, w.bad, w.gpt.p, Pp, floor, val ? val + s0 : nullptr,
@@ -603,113 +551,10 @@ static void require_temperatures(const char* who, const double* taus) {
     SLS_REQUIRE(std::isfinite(taus[0]) && taus[0] > 0.0, "%s: tau_relu = %g (finite, > 0)", who, taus[0]);
     SLS_REQUIRE(std::isfinite(taus[1]) && taus[1] > 0.0, "%s: tau_max = %g (finite, > 0)", who, taus[1]);
 }
-static SetMode set_mode(const double* device_base, const double* taus) {
-    SetMode m;
-    m.base = device_base;
-    if (taus) {
-        m.log_form = true;
-        m.tau_relu = taus[0];
-        m.tau_max = taus[1];
-    }
-    return m;
-}
 
 static void require_finite_baseline(const char* who, const sls_path* p, const double* baseline) {
     SLS_REQUIRE(baseline != nullptr, "%s: baseline is NULL", who);
     for (int s = 0; s < p->n_draws; ++s) SLS_REQUIRE(std::isfinite(baseline[s]), "%s: baseline[%d] is not finite", who, s);
-}
-
-// sls_qeubo_eval / sls_qnei_eval (want_base: competes against the per-draw baseline)
-static int set_eval(const char* who, sls_path* p, int q, const double* baseline, bool want_base, const double* sets, int M, double* val,
-                    double* grad, int* wins, const double* taus = nullptr) {
-    SLS_TRY
-    SLS_REQUIRE(p != nullptr, "%s: p is NULL", who);
-    SLS_REQUIRE(q >= 1 && q <= SLS_QEUBO_MAX_OPTIONS, "%s: q = %d (1 .. %d)", who, q, SLS_QEUBO_MAX_OPTIONS);
-    SLS_REQUIRE(M >= 0, "%s: M = %d", who, M);
-    SLS_REQUIRE(sets != nullptr, "%s: sets is NULL", who);
-    if (taus) require_temperatures(who, taus);
-    if (want_base) require_finite_baseline(who, p, baseline);
-    GpReadCall call(p->gp, p->generation, who);
-    if (M == 0) return SLS_OK;
-    const GpView& g = call.g;
-    sls_ctx* c = g.ctx;
-    const int qD = q * g.D, Mp = round_up(M, 128);
-    const std::vector<double> t = host_to_cm(sets, qD, M, Mp);   // alive until the synchronisation below
-    DBuf raw, out, wb, tb;
-    raw.ensure(t.size());
-    h2d(c, raw.p, t.data(), t.size());
-    if (want_base) {
-        tb.ensure((size_t)p->n_draws);
-        h2d(c, tb.p, baseline, (size_t)p->n_draws);
-    }
-    out.ensure((size_t)Mp * (1 + qD));
-    int* d_wins = wins ? ints(wb, (size_t)Mp * q) : nullptr;
-    QeuboWs ws;
-    qeubo_eval_device(p, g, ws, q, set_mode(tb.p, taus), raw.p, Mp, M, out.p, grad ? out.p + Mp : nullptr, Mp, d_wins, Mp);
-    std::vector<double> oh((size_t)Mp * (grad ? 1 + qD : 1));
-    std::vector<int> wh(wins ? (size_t)Mp * q : 0);
-    d2h(c, oh.data(), out.p, oh.size());
-    if (wins) SLS_HIP(hipMemcpyAsync(wh.data(), d_wins, wh.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    SLS_HIP(hipStreamSynchronize(c->stream));
-    cm_to_host(oh.data(), Mp, 1, M, val);
-    cm_to_host(oh.data() + Mp, Mp, qD, M, grad);
-    cm_to_host(wh.data(), Mp, q, M, wins);
-    SLS_CATCH
-}
-
-extern "C" int sls_qeubo_eval(sls_path* p, int q, const double* sets, int M, double* val, double* grad, int* wins) {
-    return set_eval("sls_qeubo_eval", p, q, nullptr, false, sets, M, val, grad, wins);
-}
-
-// sls_qeubo_maximize / sls_qnei_maximize
-static int set_maximize(const char* who, sls_path* p, int q, const double* baseline, bool want_base, const double* starts, int S_starts,
-                        int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
-                        double* x_stars, double* y_stars, const double* taus = nullptr) {
-    SLS_TRY
-    SLS_REQUIRE(p && starts, "%s: NULL argument", who);
-    SLS_REQUIRE(q >= 1 && q <= SLS_QEUBO_MAX_OPTIONS, "%s: q = %d (1 .. %d)", who, q, SLS_QEUBO_MAX_OPTIONS);
-    if (taus) require_temperatures(who, taus);
-    if (want_base) require_finite_baseline(who, p, baseline);
-    GpReadCall call(p->gp, p->generation, who);
-    const GpView& g = call.g;
-    sls_ctx* c = g.ctx;
-    // the maximiser of sls_acq_maximize over [0,1]^(qD): one start = one set of q options.  Workspaces are per call; the best start
-    // and every fetch come back through pageable memory.
-    const int S = S_starts, qD = q * g.D;
-    LbfgsWs lb;
-    QeuboWs ws;
-    MultistartRun r = maximize_begin(who, p->gp, lb, opts, S, n_local, qD);
-    DBuf sd, best, tb;
-    sd.ensure((size_t)qD * S);
-    best.ensure((size_t)8 + qD);
-    h2d(c, sd.p, starts, (size_t)qD * S);
-    if (want_base) {   // once, before the first round
-        tb.ensure((size_t)p->n_draws);
-        h2d(c, tb.p, baseline, (size_t)p->n_draws);
-    }
-    const SetMode mode = set_mode(tb.p, taus);
-    LockstepStats ls;
-    lockstep_rounds(c, r.st, lb, sd.p, S, n_local,
-                    [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
-                        qeubo_eval_device(p, g, ws, q, mode, trial, ld, nlive, val, grad, ld, nullptr, 0);
-                    },
-                    &ls);
-    std::vector<double> bh((size_t)8 + qD), pageable;
-    auto fetch = [&](const double* dev, size_t n) {
-        pageable.resize(n);
-        d2h(c, pageable.data(), dev, n);
-        SLS_HIP(hipStreamSynchronize(c->stream));
-        return pageable.data();
-    };
-    maximize_finish(c, r, ls, BestBlock{best.p, bh.data(), true}, fetch, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars);
-    SLS_CATCH
-}
-
-extern "C" int sls_qeubo_maximize(sls_path* p, int q, const double* starts, int S_starts, int n_local, const sls_lbfgs_opts* opts,
-                                  long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars,
-                                  double* y_stars) {
-    return set_maximize("sls_qeubo_maximize", p, q, nullptr, false, starts, S_starts, n_local, opts, start_index_offset, x_out, val_out,
-                        idx_out, x_stars, y_stars);
 }
 
 // ---- noisy expected improvement on the draws (include/sls_hip.h) ---------------------------------------------------------------
@@ -723,8 +568,8 @@ extern "C" int sls_path_max_over_points(sls_path* p, const double* Xb, int Mb, d
     const int D = g.D, nd = p->n_draws;
     // passes of points bounded as a qEUBO pass of one-option sets bounds them; the running (max, argmax) per draw merges across passes
     const int pass_max = std::min(round_up(Mb, 128), qeubo_sets_per_pass(c, 1, g.Np, p->Fp, p->Rp));
-    QeuboWs ws;
-    ws.ensure(c, p, g, pass_max, pass_max, true);
+    SetWs ws;
+    ws.ensure_sets(c, p, g, pass_max, pass_max, true);
     DBuf raw, tb, ab;
     raw.ensure((size_t)D * Mb);
     h2d(c, raw.p, Xb, (size_t)D * Mb);
@@ -732,12 +577,7 @@ extern "C" int sls_path_max_over_points(sls_path* p, const double* Xb, int Mb, d
     int* d_arg = ints(ab, (size_t)nd);
     for (int p0 = 0; p0 < Mb; p0 += pass_max) {
         const int pc = std::min(pass_max, Mb - p0), Pp = round_up(pc, 128);
-        draw_values_device(p, g, ws, Pp, [&] {
-            launch_prep_points(c->stream, raw.p + (size_t)p0 * D, D, pc, g.inv_ell, ws.XsT.p, Pp, Pp, g.Dcols, ws.ns.p);
-        }, [&](KernelSpec ks, double* Cs) {
-            launch_cross_gram_direct(c->stream, raw.p + (size_t)p0 * D, D, 1, pc, Pp, g.X, D, g.inv_ell, g.Np, g.N, ks, nullptr, ws.Ks.p, Cs,
-                                     Pp, nullptr, nullptr);
-        });
+        draw_values_device(p, g, ws, PassPoints{raw.p + (size_t)p0 * D, D, 1, 1, Pp, pc});
         ProfScope ps(c, "path_max");
         launch_path_colmax(c->stream, ws.VM.p, Pp, pc, nd, p0, tb.p, d_arg);   // the pc live rows only
     }
@@ -747,37 +587,11 @@ extern "C" int sls_path_max_over_points(sls_path* p, const double* Xb, int Mb, d
     SLS_CATCH
 }
 
-extern "C" int sls_qnei_eval(sls_path* p, int q, const double* baseline, const double* sets, int M, double* val, double* grad, int* wins) {
-    return set_eval("sls_qnei_eval", p, q, baseline, true, sets, M, val, grad, wins);
-}
-
-extern "C" int sls_qnei_maximize(sls_path* p, int q, const double* baseline, const double* starts, int S_starts, int n_local,
-                                 const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
-                                 double* x_stars, double* y_stars) {
-    return set_maximize("sls_qnei_maximize", p, q, baseline, true, starts, S_starts, n_local, opts, start_index_offset, x_out, val_out,
-                        idx_out, x_stars, y_stars);
-}
-
-// ---- log-space noisy expected improvement on the draws (include/sls_hip.h) --------------------------------------------------
-extern "C" int sls_qlognei_eval(sls_path* p, int q, const double* baseline, double tau_relu, double tau_max, const double* sets, int M,
-                                double* val, double* grad, int* wins) {
-    const double taus[2] = {tau_relu, tau_max};
-    return set_eval("sls_qlognei_eval", p, q, baseline, true, sets, M, val, grad, wins, taus);
-}
-
-extern "C" int sls_qlognei_maximize(sls_path* p, int q, const double* baseline, double tau_relu, double tau_max, const double* starts,
-                                    int S_starts, int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out,
-                                    double* val_out, long* idx_out, double* x_stars, double* y_stars) {
-    const double taus[2] = {tau_relu, tau_max};
-    return set_maximize("sls_qlognei_maximize", p, q, baseline, true, starts, S_starts, n_local, opts, start_index_offset, x_out, val_out,
-                        idx_out, x_stars, y_stars, taus);
-}
-
 // ---- expected utility of the best slider position on the draws (include/sls_hip.h) ------------------------------------------
 namespace {
 
 struct LineWs {
-    QeuboWs q;
+    SetWs q;
     DBuf sets, sgrad;   // the expanded sets and their gradient of ONE pass (qD x pass), never of the whole call
 };
 
@@ -797,8 +611,8 @@ void line_eval_device(sls_path* p, const GpView& g, LineWs& w, int q, const doub
             ProfScope ps(c, "line");
             launch_line_expand(c->stream, sc, D, q, lines + s0, ld, anchor, w.sets.p, pass_max);
         }
-        qeubo_eval_device(p, g, w.q, q, set_mode(base, nullptr), w.sets.p, pass_max, sc, val ? val + s0 : nullptr,
-                          grad ? w.sgrad.p : nullptr, pass_max, wins ? wins + s0 : nullptr, ldw);
+        qeubo_eval_device(p, g, w.q, q, SetMode{base}, w.sets.p, pass_max, sc, val ? val + s0 : nullptr, grad ? w.sgrad.p : nullptr,
+                          pass_max, wins ? wins + s0 : nullptr, ldw);
         if (grad) {
             ProfScope ps(c, "line");
             launch_line_fold(c->stream, sc, D, q, anchor != nullptr, w.sgrad.p, pass_max, grad + s0, ldo);
@@ -815,36 +629,85 @@ void require_line_args(const char* who, const sls_path* p, int q, const double* 
         for (int d = 0; d < p->D; ++d) SLS_REQUIRE(std::isfinite(anchor[d]), "%s: anchor[%d] is not finite", who, d);
 }
 
-}  // namespace
+// ---- the host front end of the set-shaped objectives --------------------------------------------------------------------------
+// What tells their entry points apart.  sls_qeubo_*: q alone; sls_qnei_*: need_base, the per-draw baseline the options compete
+// against; sls_qlognei_*: need_base and taus = (tau_relu, tau_max); sls_line_*: line, with the optional baseline and the optional
+// anchor -- one start is then one line, 2D variables (D with the anchor) whatever q is.
+struct SetCall {
+    const char* who;
+    int q;
+    const double* baseline = nullptr;
+    bool need_base = false;
+    const double* taus = nullptr;
+    bool line = false;
+    const double* anchor = nullptr;
+    int nvar(int D) const { return !line ? q * D : anchor ? D : 2 * D; }
+};
 
-extern "C" int sls_line_eval(sls_path* p, int q, const double* baseline, const double* anchor, const double* lines, int M, double* val,
-                             double* grad, int* wins) {
+// Every refusal ahead of the generation check, in each entry point's order.  M: of an evaluation (nullptr: a maximisation); block:
+// the sets / lines / starts.
+void require_set_args(const SetCall& s, const sls_path* p, const int* M, const double* block) {
+    const char* who = s.who;
+    if (!M) SLS_REQUIRE(p && block, "%s: NULL argument", who);
+    if (s.line) {
+        require_line_args(who, p, s.q, s.baseline, s.anchor);
+    } else {
+        SLS_REQUIRE(p != nullptr, "%s: p is NULL", who);
+        SLS_REQUIRE(s.q >= 1 && s.q <= SLS_QEUBO_MAX_OPTIONS, "%s: q = %d (1 .. %d)", who, s.q, SLS_QEUBO_MAX_OPTIONS);
+    }
+    if (M) {
+        SLS_REQUIRE(*M >= 0, "%s: M = %d", who, *M);
+        SLS_REQUIRE(block != nullptr, "%s: %s is NULL", who, s.line ? "lines" : "sets");
+    }
+    if (s.taus) require_temperatures(who, s.taus);
+    if (s.need_base) require_finite_baseline(who, p, s.baseline);
+}
+
+// The optional per-draw baseline and the optional anchor of a call, once to the device (nullptr where absent)
+struct SetInputs {
+    DBuf base, anchor;
+    void upload(sls_ctx* c, const sls_path* p, const SetCall& s) {
+        if (s.baseline) {
+            base.ensure((size_t)p->n_draws);
+            h2d(c, base.p, s.baseline, (size_t)p->n_draws);
+        }
+        if (s.anchor) {
+            anchor.ensure((size_t)p->D);
+            h2d(c, anchor.p, s.anchor, (size_t)p->D);
+        }
+    }
+};
+
+// The objective of a call at n columns of candidate-major variables trial[j + r*ld]: val[j], grad[j + r*ldo], wins[j + i*ldw]
+void set_objective(sls_path* p, const GpView& g, LineWs& w, const SetCall& s, const SetInputs& in, const double* trial, long ld, int n,
+                   double* val, double* grad, long ldo, int* wins, long ldw) {
+    if (s.line) {
+        line_eval_device(p, g, w, s.q, in.base.p, in.anchor.p, trial, ld, n, val, grad, ldo, wins, ldw);
+        return;
+    }
+    const SetMode mode{in.base.p, s.taus != nullptr, s.taus ? s.taus[0] : 0.0, s.taus ? s.taus[1] : 0.0};
+    qeubo_eval_device(p, g, w.q, s.q, mode, trial, ld, n, val, grad, ldo, wins, ldw);
+}
+
+// sls_qeubo_eval / sls_qnei_eval / sls_qlognei_eval / sls_line_eval
+int set_eval(const SetCall& s, sls_path* p, const double* block, int M, double* val, double* grad, int* wins) {
     SLS_TRY
-    const char* who = "sls_line_eval";
-    require_line_args(who, p, q, baseline, anchor);
-    SLS_REQUIRE(M >= 0, "%s: M = %d", who, M);
-    SLS_REQUIRE(lines != nullptr, "%s: lines is NULL", who);
-    GpReadCall call(p->gp, p->generation, who);
+    require_set_args(s, p, &M, block);
+    GpReadCall call(p->gp, p->generation, s.who);
     if (M == 0) return SLS_OK;
     const GpView& g = call.g;
     sls_ctx* c = g.ctx;
-    const int D = g.D, nvar = anchor ? D : 2 * D, Mp = round_up(M, 128);
-    const std::vector<double> t = host_to_cm(lines, nvar, M, Mp);   // alive until the synchronisation below
-    DBuf raw, out, wb, tb, ab;
+    const int q = s.q, nvar = s.nvar(g.D), Mp = round_up(M, 128);
+    const std::vector<double> t = host_to_cm(block, nvar, M, Mp);   // alive until the synchronisation below
+    DBuf raw, out, wb;
+    SetInputs in;
     raw.ensure(t.size());
     h2d(c, raw.p, t.data(), t.size());
-    if (baseline) {
-        tb.ensure((size_t)p->n_draws);
-        h2d(c, tb.p, baseline, (size_t)p->n_draws);
-    }
-    if (anchor) {
-        ab.ensure((size_t)D);
-        h2d(c, ab.p, anchor, (size_t)D);
-    }
+    in.upload(c, p, s);
     out.ensure((size_t)Mp * (1 + nvar));
     int* d_wins = wins ? ints(wb, (size_t)Mp * q) : nullptr;
     LineWs ws;
-    line_eval_device(p, g, ws, q, tb.p, ab.p, raw.p, Mp, M, out.p, grad ? out.p + Mp : nullptr, Mp, d_wins, Mp);
+    set_objective(p, g, ws, s, in, raw.p, Mp, M, out.p, grad ? out.p + Mp : nullptr, Mp, d_wins, Mp);
     std::vector<double> oh((size_t)Mp * (grad ? 1 + nvar : 1));
     std::vector<int> wh(wins ? (size_t)Mp * q : 0);
     d2h(c, oh.data(), out.p, oh.size());
@@ -856,37 +719,30 @@ extern "C" int sls_line_eval(sls_path* p, int q, const double* baseline, const d
     SLS_CATCH
 }
 
-extern "C" int sls_line_maximize(sls_path* p, int q, const double* baseline, const double* anchor, const double* starts, int S_starts,
-                                 int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out,
-                                 long* idx_out, double* x_stars, double* y_stars) {
+// sls_qeubo_maximize / sls_qnei_maximize / sls_qlognei_maximize / sls_line_maximize: the maximiser of sls_acq_maximize over the
+// box of the call's variables, one start = one set of q options (one line).  Workspaces are per call; the best start and every fetch
+// come back through pageable memory.
+int set_maximize(const SetCall& s, sls_path* p, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts,
+                 long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars, double* y_stars) {
     SLS_TRY
-    const char* who = "sls_line_maximize";
-    SLS_REQUIRE(p && starts, "%s: NULL argument", who);
-    require_line_args(who, p, q, baseline, anchor);
-    GpReadCall call(p->gp, p->generation, who);
+    require_set_args(s, p, nullptr, starts);
+    GpReadCall call(p->gp, p->generation, s.who);
     const GpView& g = call.g;
     sls_ctx* c = g.ctx;
-    // the maximiser of sls_qeubo_maximize over the ENDS: one start = one line, 2D variables (D with the anchor) whatever q is
-    const int S = S_starts, D = g.D, nvar = anchor ? D : 2 * D;
+    const int nvar = s.nvar(g.D);
     LbfgsWs lb;
     LineWs ws;
-    MultistartRun r = maximize_begin(who, p->gp, lb, opts, S, n_local, nvar);
-    DBuf sd, best, tb, ab;
+    MultistartRun r = maximize_begin(s.who, p->gp, lb, opts, S, n_local, nvar);
+    DBuf sd, best;
+    SetInputs in;
     sd.ensure((size_t)nvar * S);
     best.ensure((size_t)8 + nvar);
     h2d(c, sd.p, starts, (size_t)nvar * S);
-    if (baseline) {   // both once, before the first round
-        tb.ensure((size_t)p->n_draws);
-        h2d(c, tb.p, baseline, (size_t)p->n_draws);
-    }
-    if (anchor) {
-        ab.ensure((size_t)D);
-        h2d(c, ab.p, anchor, (size_t)D);
-    }
+    in.upload(c, p, s);   // once, before the first round
     LockstepStats ls;
     lockstep_rounds(c, r.st, lb, sd.p, S, n_local,
                     [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
-                        line_eval_device(p, g, ws, q, tb.p, ab.p, trial, ld, nlive, val, grad, ld, nullptr, 0);
+                        set_objective(p, g, ws, s, in, trial, ld, nlive, val, grad, ld, nullptr, 0);
                     },
                     &ls);
     std::vector<double> bh((size_t)8 + nvar), pageable;
@@ -898,4 +754,55 @@ extern "C" int sls_line_maximize(sls_path* p, int q, const double* baseline, con
     };
     maximize_finish(c, r, ls, BestBlock{best.p, bh.data(), true}, fetch, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars);
     SLS_CATCH
+}
+
+}  // namespace
+
+// ---- the entry points of the set-shaped objectives: what each asks of set_eval / set_maximize ---------------------------------
+extern "C" int sls_qeubo_eval(sls_path* p, int q, const double* sets, int M, double* val, double* grad, int* wins) {
+    return set_eval({"sls_qeubo_eval", q}, p, sets, M, val, grad, wins);
+}
+
+extern "C" int sls_qeubo_maximize(sls_path* p, int q, const double* starts, int S_starts, int n_local, const sls_lbfgs_opts* opts,
+                                  long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars,
+                                  double* y_stars) {
+    return set_maximize({"sls_qeubo_maximize", q}, p, starts, S_starts, n_local, opts, start_index_offset, x_out, val_out, idx_out,
+                        x_stars, y_stars);
+}
+
+extern "C" int sls_qnei_eval(sls_path* p, int q, const double* baseline, const double* sets, int M, double* val, double* grad, int* wins) {
+    return set_eval({"sls_qnei_eval", q, baseline, true}, p, sets, M, val, grad, wins);
+}
+
+extern "C" int sls_qnei_maximize(sls_path* p, int q, const double* baseline, const double* starts, int S_starts, int n_local,
+                                 const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
+                                 double* x_stars, double* y_stars) {
+    return set_maximize({"sls_qnei_maximize", q, baseline, true}, p, starts, S_starts, n_local, opts, start_index_offset, x_out, val_out,
+                        idx_out, x_stars, y_stars);
+}
+
+extern "C" int sls_qlognei_eval(sls_path* p, int q, const double* baseline, double tau_relu, double tau_max, const double* sets, int M,
+                                double* val, double* grad, int* wins) {
+    const double taus[2] = {tau_relu, tau_max};
+    return set_eval({"sls_qlognei_eval", q, baseline, true, taus}, p, sets, M, val, grad, wins);
+}
+
+extern "C" int sls_qlognei_maximize(sls_path* p, int q, const double* baseline, double tau_relu, double tau_max, const double* starts,
+                                    int S_starts, int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out,
+                                    double* val_out, long* idx_out, double* x_stars, double* y_stars) {
+    const double taus[2] = {tau_relu, tau_max};
+    return set_maximize({"sls_qlognei_maximize", q, baseline, true, taus}, p, starts, S_starts, n_local, opts, start_index_offset, x_out,
+                        val_out, idx_out, x_stars, y_stars);
+}
+
+extern "C" int sls_line_eval(sls_path* p, int q, const double* baseline, const double* anchor, const double* lines, int M, double* val,
+                             double* grad, int* wins) {
+    return set_eval({"sls_line_eval", q, baseline, false, nullptr, true, anchor}, p, lines, M, val, grad, wins);
+}
+
+extern "C" int sls_line_maximize(sls_path* p, int q, const double* baseline, const double* anchor, const double* starts, int S_starts,
+                                 int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out,
+                                 long* idx_out, double* x_stars, double* y_stars) {
+    return set_maximize({"sls_line_maximize", q, baseline, false, nullptr, true, anchor}, p, starts, S_starts, n_local, opts,
+                        start_index_offset, x_out, val_out, idx_out, x_stars, y_stars);
 }

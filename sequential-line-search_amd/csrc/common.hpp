@@ -109,6 +109,13 @@ struct DBuf {
         n = doubles;
     }
 };
+// launch_grad_gemm's `part` for a launch of Sp candidates (kernels.hpp): b grown to the split form's scratch, or nullptr where the
+// launch does not split (D > 64, or SLS_GRAD_SPLIT_TILES says so)
+inline double* grad_split_scratch(DBuf& b, int D, int Sp) {
+    if (D > 64 || !grad_gemm_wants_split(Sp)) return nullptr;
+    b.ensure((size_t)8 * Sp * 64);
+    return b.p;
+}
 
 // Owning page-locked host block from a context's pool (sls_ctx::host_take / host_give), device-mapped on request.  The block
 // remembers the context it was taken from, so release() and the destructor need no argument.  The pool is not thread safe and this
