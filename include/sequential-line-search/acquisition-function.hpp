@@ -266,6 +266,28 @@ namespace sequential_line_search
             const unsigned num_draws = 256, const unsigned num_local_search_iters = 50, const unsigned long long seed = 0,
             const int num_frequencies = 2048, double* value = nullptr);
 
+        /// The next gallery by the expected utility of the best cell of it (not in the reference; gallery EUBO, include/sls_hip.h
+        /// sls_patch_*): the query of SequentialGallerySearchOptimizer is a two-dimensional patch of designs shown as a grid_s x
+        /// grid_t grid (at least 2 per axis, at most 16 cells) and the user picks the best cell, so the criterion is
+        /// E[max_{s,t} f(x(s,t))] on the grid of the bilinear patch spanned by four corners, over num_draws pathwise posterior draws
+        /// (stream `seed`, num_frequencies random features), maximised over the corners: with `anchor` (D values, e.g. the current
+        /// best point) the corner c00 is fixed there and the other three are searched over [0,1]^(3D); with an empty anchor all four
+        /// are free ([0,1]^(4D)).  Starts, local search and tolerances as FindNextSliderByExpectedUtility; the same seed gives the
+        /// same gallery.  Returns the corners c00, c10, c01, c11; value (may be nullptr) receives the utility there.  Device-resident
+        /// regressors only (std::invalid_argument otherwise).
+        std::vector<Eigen::VectorXd> FindNextGalleryByExpectedUtility(const Regressor& regressor, const Eigen::VectorXd& anchor,
+                                                                      const int grid_s = 4, const int grid_t = 4,
+                                                                      const unsigned num_draws = 256,
+                                                                      const unsigned num_global_search_iters = 100,
+                                                                      const unsigned num_local_search_iters = 50,
+                                                                      const unsigned long long seed = 0,
+                                                                      const int num_frequencies = 2048, double* value = nullptr);
+        /// The same from an explicit start set (4D x S: rows in blocks of D start c00, c10, c01, c11; 3D x S with an anchor).
+        std::vector<Eigen::VectorXd> FindNextGalleryByExpectedUtilityFromStarts(
+            const Regressor& regressor, const Eigen::VectorXd& anchor, const Eigen::MatrixXd& starts, const int grid_s = 4,
+            const int grid_t = 4, const unsigned num_draws = 256, const unsigned num_local_search_iters = 50,
+            const unsigned long long seed = 0, const int num_frequencies = 2048, double* value = nullptr);
+
         /// The starts of every seeded search above and below (FindNextPointsByThompsonSampling, FindNextPointByMaxValueEntropySearch,
         /// FindNextPointInSubspace, ...): num_dims x count numbers uniform in [0,1), column after column from one std::mt19937_64
         /// seeded with `seed`.  With them and the tolerances of GetLocalSearchTolerances the ...FromStarts forms -- and the C ABI --

@@ -163,6 +163,28 @@ namespace sequential_line_search
         std::pair<Eigen::VectorXd, Eigen::VectorXd> MaximizeExpectedUtilityOfBestSliderPosition(
             int num_positions, const Eigen::MatrixXd& starts, unsigned num_local_search_iters, const Eigen::VectorXd* anchor = nullptr,
             const Eigen::VectorXd* baseline = nullptr, double* value = nullptr) const;
+        /// Expected utility of the best cell of a grid_s x grid_t grid on the bilinear patch spanned by the corners corners00.col(m),
+        /// corners10.col(m), corners01.col(m), corners11.col(m) (gallery EUBO; include/sls_hip.h sls_patch_*):
+        /// CalcExpectedUtilitiesOfBestOption at the cells (1 - t_j) ((1 - s_i) c00 + s_i c10) + t_j ((1 - s_i) c01 + s_i c11), s_i =
+        /// i / (grid_s - 1), t_j = j / (grid_t - 1), grid_s, grid_t >= 2 and grid_s grid_t <= 16.  Every corner block D x M.  Returns
+        /// the M values; grads (may be nullptr) receives four matrices D x M, the gradients with respect to c00, c10, c01, c11;
+        /// win_counts (may be nullptr) (grid_s grid_t) x M, the number of draws cell i + grid_s j wins.  With baseline (num_draws
+        /// finite values) the criterion is CalcNoisyExpectedImprovements at the same cells.
+        Eigen::VectorXd CalcExpectedUtilitiesOfBestGalleryCell(const Eigen::MatrixXd& corners00, const Eigen::MatrixXd& corners10,
+                                                               const Eigen::MatrixXd& corners01, const Eigen::MatrixXd& corners11,
+                                                               int grid_s, int grid_t, std::vector<Eigen::MatrixXd>* grads = nullptr,
+                                                               Eigen::MatrixXi* win_counts = nullptr,
+                                                               const Eigen::VectorXd* baseline = nullptr) const;
+        /// Maximiser of that utility over the corners: starts is 4D x S (rows in blocks of D start c00, c10, c01, c11), or with
+        /// `anchor` (D values; the corner c00 of every patch, e.g. the current best point) 3D x S, the other three corners -- 4D or 3D
+        /// variables whatever the grid.  One lock-step bounded L-BFGS of num_local_search_iters evaluations per start (the
+        /// acquisition maximiser's local search tolerances); returns the best patch's four corners c00, c10, c01, c11 (the first is
+        /// the anchor when there is one).  value (may be nullptr) receives the utility there.
+        std::vector<Eigen::VectorXd> MaximizeExpectedUtilityOfBestGalleryCell(int grid_s, int grid_t, const Eigen::MatrixXd& starts,
+                                                                              unsigned               num_local_search_iters,
+                                                                              const Eigen::VectorXd* anchor   = nullptr,
+                                                                              const Eigen::VectorXd* baseline = nullptr,
+                                                                              double*                value    = nullptr) const;
 
     private:
         // the set criteria of every kind: baseline == nullptr is the expected utility of the best option, taus != nullptr

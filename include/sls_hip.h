@@ -541,6 +541,68 @@ int sls_line_maximize(sls_path* p, int q, const double* baseline, const double* 
                       int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out,
                       long* idx_out, double* x_stars, double* y_stars);
 
+/* ---- expected utility of the best gallery cell on posterior draws (not in the reference) -------------------------------------
+ * Gallery EUBO: the query of the sequential gallery (Koyama et al. 2020) is a two-dimensional patch of designs shown as a grid, and
+ * the user picks the best cell.  The one-step criterion of that query is E[ max_{s,t} f(x(s,t)) ], estimated on a qs x qt grid of the
+ * bilinear patch spanned by four corners over the FIXED draws of a path object p -- line EUBO (above) one dimension up.
+ * Patch and grid: a patch is its corners c00, c10, c01, c11, each in [0,1]^D; qs >= SLS_PATCH_MIN_POSITIONS, qt >=
+ * SLS_PATCH_MIN_POSITIONS and qs qt <= SLS_QEUBO_MAX_OPTIONS cells.  The weights are the line's along each axis, each ONE double
+ * division of two exact integers, on the device:
+ *   u_i = (qs-1-i)/(qs-1),  s_i = i/(qs-1),  v_j = (qt-1-j)/(qt-1),  t_j = j/(qt-1)
+ * Expansion: option k = i + qs j is
+ *   lo = u_i c00 + s_i c10,  hi = u_i c01 + s_i c11,  x_k = v_j lo + t_j hi
+ * each of the three two products and one sum per coordinate, rounded separately, NO fused multiply-add, no clamp.  The patch is
+ * bilinear: every cell is a convex combination of the corners, so it lies in the cube whenever the corners do; cells (0,0), (qs-1,0),
+ * (0,qt-1), (qs-1,qt-1) are c00, c10, c01, c11 exactly.  The patch is planar exactly when c11 = c10 + c01 - c00.
+ *   value  = sls_qeubo_eval at the expanded set of q = qs qt options; with a per-draw baseline (n_draws finite doubles)
+ *            sls_qnei_eval at it
+ *   wins   = as there, (qs qt) x M, indexed by k: wins_k / n_draws estimates the probability that the user picks cell k
+ * Fold: with g_k the set gradient's block of option k, per grid row j
+ *   A_j = sum_i u_i g_{i + qs j}  from zero in INCREASING i,   B_j = sum_i s_i g_{i + qs j}  from zero in DECREASING i
+ *   grad_c00 = sum_j v_j A_j,  grad_c10 = sum_j v_j B_j        from zero in INCREASING j
+ *   grad_c01 = sum_j t_j A_j,  grad_c11 = sum_j t_j B_j        from zero in DECREASING j
+ * every step a product and a sum rounded separately.  The orders are the line's along each axis: the sums with the weights that fall
+ * along an axis run up it, those with the weights that rise run down it, so that a mirror of the axis maps each sum onto its partner
+ * term by term.
+ * Guard: the set's guard passes through -- a guarded set gives SLS_QEUBO_FLOOR (0 with a baseline) and an exactly zero patch gradient.
+ * Anchored form: with `anchor` (D host doubles, all finite, else SLS_ERR_INVALID; uploaded once per call) c00 = anchor for every patch
+ * of the call, a patch is (c10, c01, c11) (3D variables) and only those three gradients are returned.  This is the gallery with the
+ * current best point x+ in its corner.
+ * Contract:
+ *   - A patch's value and wins are bit for bit those of sls_qeubo_eval / sls_qnei_eval at the expanded set, and its gradient is bit
+ *     for bit the fold above of that call's gradient.
+ *   - A patch's bits depend on neither its column, the other patches of the call, the patches per pass nor SLS_COMPACT.
+ *   - s-mirror (c00 <-> c10, c01 <-> c11) and t-mirror (c00 <-> c01, c10 <-> c11): the value's bits are unchanged, wins are reversed
+ *     along i (along j), and the gradient blocks swap the same way, bit for bit, with or without a baseline (ties aside: a tie goes to
+ *     the lowest k on either side).
+ *   - Transposition (c10 <-> c01 together with qs <-> qt) describes the same cells but is NOT bit-exact: the two nestings of the
+ *     expansion round differently, so value and gradient agree to rounding only.
+ *   - Degenerate rows: with qt = 2, c01 = c00, c11 = c10 the two grid rows are the same points bit for bit (the weights along t are
+ *     exactly 0 and 1), every draw's winner lies in row 0, and the value is bit for bit sls_line_eval of the line (c00, c10) with q =
+ *     qs, wins of row 0 are the line's and wins of row 1 are zero, (grad_c00, grad_c10) are the line's (grad_a, grad_b) bit for bit and
+ *     grad_c01, grad_c11 are exactly zero.
+ * Route per pass: patch_expand (patches -> the candidate-major set block), ONE pass of the qEUBO evaluation unchanged, patch_fold (set
+ * gradient -> patch gradient).  Patches per pass are the sets per pass of sls_qeubo_eval for q = qs qt, and the expanded sets and
+ * their gradient are held for one pass only.  The maximiser runs L-BFGS over 4D variables (3D anchored) whatever the grid.  Locks
+ * and the staleness rule are those of sls_qeubo_eval.
+ * Out of scope: grids above SLS_QEUBO_MAX_OPTIONS = 16 cells (the selection kernels are written for that limit and the pass-size
+ * rules are stated for it; a finer gallery is shown by the caller zooming -- a sub-patch is again four corners); a log form; _sub
+ * forms; sls_multi_*; and the centre-anchored parallelogram of the 2020 paper as a SEARCH parametrisation (its reflected corners can
+ * leave the cube; sls_patch_eval scores any four corners, so such a gallery can be evaluated). */
+#define SLS_PATCH_MIN_POSITIONS 2
+/* patches: (anchor ? 3D : 4D) x M column-major, rows in blocks of D: c00 (free form only), c10, c01, c11.  baseline NULL: EUBO form;
+ * else n_draws finite doubles.  val (M), grad ((anchor ? 3D : 4D) x M, the blocks of patches), wins ((qs qt) x M ints): each may be
+ * NULL.  M = 0 is a no-op; qs or qt below SLS_PATCH_MIN_POSITIONS, qs qt > SLS_QEUBO_MAX_OPTIONS, M < 0, NULL p, NULL patches, a
+ * non-finite anchor or baseline is SLS_ERR_INVALID, checked before any launch. */
+int sls_patch_eval(sls_path* p, int qs, int qt, const double* baseline, const double* anchor, const double* patches, int M,
+                   double* val, double* grad, int* wins);
+/* sls_qeubo_maximize over [0,1]^(4D) (or [0,1]^(3D) anchored) with this objective: starts, x_out, x_stars have 4D (3D) rows; the
+ * other outputs and sls_acq_last_stats as there.  Anchor and baseline are validated and uploaded once, before the first round.
+ * S_starts < 1 or n_local < 1 is SLS_ERR_INVALID. */
+int sls_patch_maximize(sls_path* p, int qs, int qt, const double* baseline, const double* anchor, const double* starts, int S_starts,
+                       int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out,
+                       long* idx_out, double* x_stars, double* y_stars);
+
 /* ---- maximisation over affine subspaces: boxes, lines, embeddings (not in the reference) ---------------------------------
  * Every maximiser above searches [0,1]^D.  Trust regions (x = lo + diag(hi - lo) z), line and plane searches (x = a + (b - a) z)
  * and random embeddings (x = c + A z, d << D) all search the affine image of a small box instead.  The *_sub entry points take the
@@ -566,8 +628,8 @@ int sls_line_maximize(sls_path* p, int q, const double* baseline, const double* 
  * or taken from the device pool for the call (sls_path_*_sub).
  * Profiler scopes: "sub_expand" and "sub_fold", one launch each per evaluation / per round of a maximiser (plus one "sub_expand" for
  * x_out / x_stars); everything between them counts as in the plain call.
- * Out of scope: the pair and set criteria (sls_eubo_*, sls_qeubo_*, sls_qnei_*, sls_qlognei_*, sls_line_*), sls_acq_maximize_pair,
- * sls_acq_maximize_dev and sls_multi_* have no _sub form. */
+ * Out of scope: the pair and set criteria (sls_eubo_*, sls_qeubo_*, sls_qnei_*, sls_qlognei_*, sls_line_*, sls_patch_*),
+ * sls_acq_maximize_pair, sls_acq_maximize_dev and sls_multi_* have no _sub form. */
 typedef struct sls_submaps {
     int struct_size;            /* sizeof(sls_submaps) as the caller's header declares it, as sls_lbfgs_opts */
     int d;                      /* variables per column, 1 <= d <= D */
@@ -761,6 +823,8 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
  * sls_qlognei_eval / per pass and round of sls_qlognei_maximize; every other stage counts as under qEUBO);
  * "line" (line_expand and line_fold: two launches per pass of sls_line_eval -- one without a gradient -- / per pass and round of
  * sls_line_maximize; the pass between them counts as under qEUBO / qNEI);
+ * "patch" (patch_expand and patch_fold: two launches per pass of sls_patch_eval -- one without a gradient -- / per pass and round of
+ * sls_patch_maximize; the pass between them counts as under qEUBO / qNEI);
  * "sub_expand" and "sub_fold" (the two kernels of the *_sub calls: one launch each per evaluation / per round of a maximiser, one more
  * "sub_expand" for x_out / x_stars; the evaluation between them counts as in the plain call);
  * "loo_terms" (the per-point terms and L: one launch per sls_nll_loo / sls_gp_loo_grad / sls_gp_loo call, two in the Cholesky-solve

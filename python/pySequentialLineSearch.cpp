@@ -15,6 +15,7 @@
 #include <sequential-line-search/gaussian-process-regressor.hpp>
 #include <sequential-line-search/preference-regressor.hpp>
 #include <sequential-line-search/preferential-bayesian-optimizer.hpp>
+#include <sequential-line-search/sequential-gallery-search.hpp>
 #include <sequential-line-search/sequential-line-search.hpp>
 #include <sequential-line-search/utils.hpp>
 
@@ -297,7 +298,27 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
                                                                                  anchor.size() != 0 ? &anchor : nullptr, nullptr, &value);
                  return std::make_pair(ends, value);
              },
-             "num_positions"_a, "starts"_a, "num_local_search_iters"_a = 50, "anchor"_a = VectorXd());
+             "num_positions"_a, "starts"_a, "num_local_search_iters"_a = 50, "anchor"_a = VectorXd())
+        // the expected utility of the best gallery cell on the draws: (values, gradients for c00, c10, c01, c11, win counts (grid_s
+        // grid_t) x M); maximize_... ((c00, c10, c01, c11), value)
+        .def("calc_expected_utilities_of_best_gallery_cell",
+             [](const PosteriorFunctionSamples& s, const MatrixXd& c00, const MatrixXd& c10, const MatrixXd& c01, const MatrixXd& c11,
+                int grid_s, int grid_t) {
+                 std::vector<MatrixXd> grads;
+                 Eigen::MatrixXi       wins;
+                 const VectorXd        v = s.CalcExpectedUtilitiesOfBestGalleryCell(c00, c10, c01, c11, grid_s, grid_t, &grads, &wins);
+                 return std::make_tuple(v, grads, wins);
+             },
+             "corners00"_a, "corners10"_a, "corners01"_a, "corners11"_a, "grid_s"_a = 4, "grid_t"_a = 4)
+        .def("maximize_expected_utility_of_best_gallery_cell",
+             [](const PosteriorFunctionSamples& s, int grid_s, int grid_t, const MatrixXd& starts, unsigned num_local_search_iters,
+                const VectorXd& anchor) {
+                 double     value   = 0.0;
+                 const auto corners = s.MaximizeExpectedUtilityOfBestGalleryCell(grid_s, grid_t, starts, num_local_search_iters,
+                                                                                 anchor.size() != 0 ? &anchor : nullptr, nullptr, &value);
+                 return std::make_pair(corners, value);
+             },
+             "grid_s"_a, "grid_t"_a, "starts"_a, "num_local_search_iters"_a = 50, "anchor"_a = VectorXd());
     m.def("sample_posterior_functions",
           [](const Regressor& r, int num_draws, unsigned long long seed, int num_frequencies) {
               return r.SamplePosteriorFunctions(num_draws, seed, num_frequencies);
@@ -421,6 +442,40 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
           "regressor"_a, "anchor"_a, "starts"_a, "num_positions"_a = 9, "num_draws"_a = 256, "num_local_search_iters"_a = 50,
           "seed"_a = 0ULL, "num_frequencies"_a = 2048);
 
+    // the gallery counterparts (acquisition-function.hpp).  calc_...: (values, gradients for c00, c10, c01, c11, win counts) on
+    // num_draws draws of the regressor (stream `seed`); find_...: ((c00, c10, c01, c11), value), an empty anchor leaves all four free
+    m.def("calc_expected_utilities_of_best_gallery_cell",
+          [](const Regressor& r, const MatrixXd& c00, const MatrixXd& c10, const MatrixXd& c01, const MatrixXd& c11, int grid_s,
+             int grid_t, int num_draws, unsigned long long seed, int num_frequencies) {
+              const PosteriorFunctionSamples draws = r.SamplePosteriorFunctions(num_draws, seed, num_frequencies);
+              std::vector<MatrixXd>          grads;
+              Eigen::MatrixXi                wins;
+              const VectorXd v = draws.CalcExpectedUtilitiesOfBestGalleryCell(c00, c10, c01, c11, grid_s, grid_t, &grads, &wins);
+              return std::make_tuple(v, grads, wins);
+          },
+          "regressor"_a, "corners00"_a, "corners10"_a, "corners01"_a, "corners11"_a, "grid_s"_a = 4, "grid_t"_a = 4, "num_draws"_a = 256,
+          "seed"_a = 0ULL, "num_frequencies"_a = 2048);
+    m.def("find_next_gallery_by_expected_utility",
+          [](const Regressor& r, const VectorXd& anchor, int grid_s, int grid_t, unsigned num_draws, unsigned num_global_search_iters,
+             unsigned num_local_search_iters, unsigned long long seed, int num_frequencies) {
+              double     value   = 0.0;
+              const auto corners = acquisition_func::FindNextGalleryByExpectedUtility(
+                  r, anchor, grid_s, grid_t, num_draws, num_global_search_iters, num_local_search_iters, seed, num_frequencies, &value);
+              return std::make_pair(corners, value);
+          },
+          "regressor"_a, "anchor"_a = VectorXd(), "grid_s"_a = 4, "grid_t"_a = 4, "num_draws"_a = 256,
+          "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50, "seed"_a = 0ULL, "num_frequencies"_a = 2048);
+    m.def("find_next_gallery_by_expected_utility_from_starts",
+          [](const Regressor& r, const VectorXd& anchor, const MatrixXd& starts, int grid_s, int grid_t, unsigned num_draws,
+             unsigned num_local_search_iters, unsigned long long seed, int num_frequencies) {
+              double     value   = 0.0;
+              const auto corners = acquisition_func::FindNextGalleryByExpectedUtilityFromStarts(
+                  r, anchor, starts, grid_s, grid_t, num_draws, num_local_search_iters, seed, num_frequencies, &value);
+              return std::make_pair(corners, value);
+          },
+          "regressor"_a, "anchor"_a, "starts"_a, "grid_s"_a = 4, "grid_t"_a = 4, "num_draws"_a = 256, "num_local_search_iters"_a = 50,
+          "seed"_a = 0ULL, "num_frequencies"_a = 2048);
+
     // DIRECT, then one L-BFGS from its result (acquisition_func::FindNextPointDirect) on such a regressor: (point, value)
     m.def("find_next_point_direct",
           [](const Regressor& r, unsigned num_global_search_iters, unsigned num_local_search_iters, AcquisitionFuncType func_type,
@@ -471,6 +526,37 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
         .def("damp_data", &SequentialLineSearchOptimizer::DampData, "directory_path"_a)
         .def("set_gaussian_process_upper_confidence_bound_hyperparam",
              &SequentialLineSearchOptimizer::SetGaussianProcessUpperConfidenceBoundHyperparam, "hyperparam"_a);
+
+    using GalleryCornersGenerator = std::function<GalleryCorners(const int)>;
+    m.def("generate_random_gallery_corners", &GenerateRandomGalleryCorners, "num_dims"_a);
+
+    py::class_<SequentialGallerySearchOptimizer>(m, "SequentialGallerySearchOptimizer")
+        .def(py::init<const int, const bool, const KernelType, const AcquisitionFuncType, const GalleryCornersGenerator&,
+                      const CurrentBestSelectionStrategy>(),
+             "num_dims"_a, "use_map_hyperparams"_a = true, "kernel_type"_a = KernelType::ArdMatern52Kernel,
+             "acquisition_func_type"_a           = AcquisitionFuncType::ExpectedImprovement,
+             "initial_query_generator"_a         = GalleryCornersGenerator(GenerateRandomGalleryCorners),
+             "current_best_selection_strategy"_a = CurrentBestSelectionStrategy::LargestExpectValue)
+        .def("set_hyperparams", &SequentialGallerySearchOptimizer::SetHyperparams, "kernel_signal_var"_a = 0.500,
+             "kernel_length_scale"_a = 0.500, "noise_level"_a = 0.005, "kernel_hyperparams_prior_var"_a = 0.250, "btl_scale"_a = 0.010)
+        .def("submit_feedback_data", &SequentialGallerySearchOptimizer::SubmitFeedbackData, "position_s"_a, "position_t"_a,
+             "grid_s"_a = 4, "grid_t"_a = 4, "num_draws"_a = 256, "num_map_estimation_iters"_a = 100, "num_global_search_iters"_a = 100,
+             "num_local_search_iters"_a = 50, "seed"_a = 0ULL, "num_frequencies"_a = 2048)
+        .def("get_gallery_corners", &SequentialGallerySearchOptimizer::GetGalleryCorners)
+        .def("calc_point_from_gallery_position", &SequentialGallerySearchOptimizer::CalcPointFromGalleryPosition, "position_s"_a,
+             "position_t"_a)
+        .def("get_gallery_points", &SequentialGallerySearchOptimizer::GetGalleryPoints, "grid_s"_a = 4, "grid_t"_a = 4)
+        .def("get_maximizer", &SequentialGallerySearchOptimizer::GetMaximizer)
+        .def("get_preference_value_mean", &SequentialGallerySearchOptimizer::GetPreferenceValueMean, "point"_a)
+        .def("get_preference_value_stdev", &SequentialGallerySearchOptimizer::GetPreferenceValueStdev, "point"_a)
+        .def("get_acquisition_func_value", &SequentialGallerySearchOptimizer::GetAcquisitionFuncValue, "point"_a)
+        .def("get_preference_value_means", &SequentialGallerySearchOptimizer::GetPreferenceValueMeans, "points"_a)
+        .def("get_preference_value_stdevs", &SequentialGallerySearchOptimizer::GetPreferenceValueStdevs, "points"_a)
+        .def("get_acquisition_func_values", &SequentialGallerySearchOptimizer::GetAcquisitionFuncValues, "points"_a)
+        .def("get_raw_data_points", &SequentialGallerySearchOptimizer::GetRawDataPoints)
+        .def("damp_data", &SequentialGallerySearchOptimizer::DampData, "directory_path"_a)
+        .def("set_gaussian_process_upper_confidence_bound_hyperparam",
+             &SequentialGallerySearchOptimizer::SetGaussianProcessUpperConfidenceBoundHyperparam, "hyperparam"_a);
 
     py::class_<PreferentialBayesianOptimizer>(m, "PreferentialBayesianOptimizer")
         .def(py::init<const int, const bool, const KernelType, const AcquisitionFuncType, const InitialQueryGenerator&,

@@ -106,7 +106,7 @@ EXPORTS = [
     "sls_mes_terms", "sls_mes_eval", "sls_mes_maximize", "sls_logei_terms",
     "sls_eubo_eval", "sls_eubo_maximize", "sls_qeubo_eval", "sls_qeubo_maximize",
     "sls_path_max_over_points", "sls_qnei_eval", "sls_qnei_maximize",
-    "sls_line_eval", "sls_line_maximize",
+    "sls_line_eval", "sls_line_maximize", "sls_patch_eval", "sls_patch_maximize",
     "sls_qlognei_terms", "sls_qlognei_eval", "sls_qlognei_maximize",
     "sls_acq_eval_sub", "sls_acq_maximize_sub", "sls_mes_eval_sub", "sls_mes_maximize_sub", "sls_path_eval_sub", "sls_path_maximize_sub",
     "sls_nll_loo", "sls_gp_loo_grad", "sls_gp_loo",
@@ -480,6 +480,7 @@ class GP:
 
 QEUBO_MAX_OPTIONS = 16   # SLS_QEUBO_MAX_OPTIONS
 LINE_MIN_POSITIONS = 2   # SLS_LINE_MIN_POSITIONS
+PATCH_MIN_POSITIONS = 2  # SLS_PATCH_MIN_POSITIONS
 QEUBO_FLOOR = -1.0e300   # SLS_QEUBO_FLOOR
 QLOGNEI_TAU_RELU, QLOGNEI_TAU_MAX = 1e-6, 1e-2   # SLS_QLOGNEI_TAU_RELU, SLS_QLOGNEI_TAU_MAX
 
@@ -563,7 +564,7 @@ class PathSamples:
                                         idx.ctypes.data_as(C.POINTER(C.c_long))))
         return dict(z=z, x=x, value=val, index=idx)
 
-    # ---- the set-shaped objectives (sls_qeubo_*, sls_qnei_*, sls_qlognei_*, sls_line_*): one body per kind of call
+    # ---- the set-shaped objectives (sls_qeubo_*, sls_qnei_*, sls_qlognei_*, sls_line_*, sls_patch_*): one body per kind of call
     def _set_block(self, who, q, block, what, qmin=1):
         """q within its range and, for a block of sets (block None: the range alone), its qD rows."""
         q = int(q)
@@ -574,14 +575,14 @@ class PathSamples:
             raise SlsError(f"{who}: {what} must be qD x {n} = {q * self.D} x {n}, got {block.shape}")
         return q
 
-    def _set_eval(self, call, rows, q, block, want_grad, want_wins, *lead_args):
-        """call(h, q, *lead_args, block, M, val, grad, wins) at the M columns of block: values (M,), then with want_grad the gradient
-        (rows, M), then with want_wins the win counts (q, M) int32."""
+    def _set_eval(self, call, rows, q, block, want_grad, want_wins, *lead_args, grid=None):
+        """call(h, q, *lead_args, block, M, val, grad, wins) at the M columns of block (with grid = (qs, qt) in the place of q = qs qt):
+        values (M,), then with want_grad the gradient (rows, M), then with want_wins the win counts (q, M) int32."""
         M = block.shape[1]
         val = np.empty(M)
         grad = np.empty((rows, M), order="F") if want_grad else None
         wins = np.zeros((q, M), dtype=np.int32, order="F") if want_wins else None
-        _ck(call(self.h, q, *lead_args, _p(block), M, _p(val), _p(grad) if want_grad else None,
+        _ck(call(self.h, *(grid or (q,)), *lead_args, _p(block), M, _p(val), _p(grad) if want_grad else None,
                  wins.ctypes.data_as(C.POINTER(C.c_int)) if want_wins else None))
         out = (val,) + ((grad,) if want_grad else ()) + ((wins,) if want_wins else ())
         return out if len(out) > 1 else val
@@ -704,6 +705,39 @@ class PathSamples:
         starts = _f(starts)
         q, a, t, rows = self._line_args("line_maximize", q, anchor, baseline, starts, "starts")
         return self._set_maximize(lib().sls_line_maximize, rows, starts, n_local, offset, want_all, opts, q, self._opt(t), self._opt(a))
+
+    def _patch_args(self, who, qs, qt, anchor, baseline, block, what):
+        qs, qt = int(qs), int(qt)
+        if qs < PATCH_MIN_POSITIONS or qt < PATCH_MIN_POSITIONS or qs * qt > QEUBO_MAX_OPTIONS:
+            raise SlsError(f"{who}: grid {qs} x {qt} (at least {PATCH_MIN_POSITIONS} per axis, at most {QEUBO_MAX_OPTIONS} cells)")
+        a = None
+        if anchor is not None:
+            a = np.ascontiguousarray(np.asarray(anchor, dtype=np.float64))
+            if a.shape != (self.D,):
+                raise SlsError(f"{who}: anchor must hold D = {self.D} values, got shape {a.shape}")
+        rows = (3 if a is not None else 4) * self.D
+        if block.ndim != 2 or block.shape[0] != rows:
+            raise SlsError(f"{who}: {what} must be {'3D' if a is not None else '4D'} x M = {rows} x M, got {block.shape}")
+        t = self._baseline(who, baseline) if baseline is not None else None
+        return qs, qt, a, t, rows
+
+    def patch_eval(self, patches, qs, qt, anchor=None, baseline=None, want_grad=True, want_wins=False):
+        """Expected utility of the best cell of a qs x qt grid on the bilinear patch spanned by four corners (sls_patch_eval) at the
+        columns of patches (4D x M: rows in blocks of D = c00, c10, c01, c11; with anchor (D,) every patch has c00 there and patches is
+        3D x M = c10, c01, c11).  With baseline (n_draws,) the qNEI form.  Values (M,), then with want_grad the gradient (4D or 3D, M),
+        then with want_wins the win counts (qs qt, M) int32, cell (i, j) in row i + qs j."""
+        patches = _f(patches)
+        qs, qt, a, t, rows = self._patch_args("patch_eval", qs, qt, anchor, baseline, patches, "patches")
+        return self._set_eval(lib().sls_patch_eval, rows, qs * qt, patches, want_grad, want_wins, self._opt(t), self._opt(a),
+                              grid=(qs, qt))
+
+    def patch_maximize(self, starts, qs, qt, n_local, anchor=None, baseline=None, offset=0, want_all=True, opts=None):
+        """acq_maximize over the corners of a patch with the objective of patch_eval (sls_patch_maximize): starts 4D x S (3D x S with
+        anchor), x and x_stars have as many rows.  GP.last_stats() of the path's handle reports the run."""
+        starts = _f(starts)
+        qs, qt, a, t, rows = self._patch_args("patch_maximize", qs, qt, anchor, baseline, starts, "starts")
+        return self._set_maximize(lib().sls_patch_maximize, rows, starts, n_local, offset, want_all, opts, qs, qt, self._opt(t),
+                                  self._opt(a))
 
 
 class PrefCfg(C.Structure):

@@ -1,5 +1,5 @@
 // C-ABI of the pathwise posterior function draws (include/sls_hip.h: sls_path_*, and sls_qeubo_* / sls_qnei_* / sls_qlognei_* /
-// sls_line_* on them): host orchestration of kernels_path.hip and kernels_qeubo.hip, the cross Gram / gradient products of
+// sls_line_* / sls_patch_* on them): host orchestration of kernels_path.hip and kernels_qeubo.hip, the cross Gram / gradient products of
 // kernels_gram.hip / kernels_acq.hip, the tile GEMM and block solve of kernels_tri.hip and the lock-step L-BFGS rounds of
 // lbfgs_driver.hpp.  No CPU fallback.
 // Every route is put together from the same pieces:
@@ -10,7 +10,7 @@
 //   gathered_route          one weight column per point: value, data term and gradient (tiled, or direct beyond the guard)
 //   path_eval_gathered      host body of sls_path_eval (gathered form) and sls_path_eval_sub
 //   path_maximize           host body of sls_path_maximize and sls_path_maximize_sub
-//   set_eval / set_maximize host bodies of sls_qeubo_*, sls_qnei_*, sls_qlognei_* and sls_line_* (SetCall tells them apart)
+//   set_eval / set_maximize host bodies of sls_qeubo_*, sls_qnei_*, sls_qlognei_*, sls_line_* and sls_patch_* (SetCall tells them apart)
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -620,19 +620,67 @@ void line_eval_device(sls_path* p, const GpView& g, LineWs& w, int q, const doub
     }
 }
 
-void require_line_args(const char* who, const sls_path* p, int q, const double* baseline, const double* anchor) {
-    SLS_REQUIRE(p != nullptr, "%s: p is NULL", who);
-    SLS_REQUIRE(q >= SLS_LINE_MIN_POSITIONS && q <= SLS_QEUBO_MAX_OPTIONS, "%s: q = %d (%d .. %d)", who, q, SLS_LINE_MIN_POSITIONS,
-                SLS_QEUBO_MAX_OPTIONS);
+// The optional baseline and the optional anchor of the slider and gallery forms
+void require_baseline_and_anchor(const char* who, const sls_path* p, const double* baseline, const double* anchor) {
     if (baseline) require_finite_baseline(who, p, baseline);
     if (anchor)
         for (int d = 0; d < p->D; ++d) SLS_REQUIRE(std::isfinite(anchor[d]), "%s: anchor[%d] is not finite", who, d);
 }
 
+void require_line_args(const char* who, const sls_path* p, int q, const double* baseline, const double* anchor) {
+    SLS_REQUIRE(p != nullptr, "%s: p is NULL", who);
+    SLS_REQUIRE(q >= SLS_LINE_MIN_POSITIONS && q <= SLS_QEUBO_MAX_OPTIONS, "%s: q = %d (%d .. %d)", who, q, SLS_LINE_MIN_POSITIONS,
+                SLS_QEUBO_MAX_OPTIONS);
+    require_baseline_and_anchor(who, p, baseline, anchor);
+}
+
+// ---- expected utility of the best gallery cell on the draws (include/sls_hip.h) ----------------------------------------------
+// Gallery EUBO (qNEI form with base) at M patches, candidate-major patches[n + r*ld] (4D rows, or 3D rows with the device D-vector
+// anchor as c00).  val[n], grad[n + r*ldo] (4D / 3D rows), wins[n + k*ldw] for cell k = i + qs j; each may be nullptr.  Per pass of the
+// qEUBO sizing for q = qs qt: expand, ONE pass of qeubo_eval_device, fold -- line_eval_device with the patch's two kernels.
+void patch_eval_device(sls_path* p, const GpView& g, LineWs& w, int qs, int qt, const double* base, const double* anchor,
+                       const double* patches, long ld, int M, double* val, double* grad, long ldo, int* wins, long ldw) {
+    sls_ctx* c = g.ctx;
+    const int D = g.D, q = qs * qt;
+    const int pass_max = std::min(round_up(M, 128), qeubo_sets_per_pass(c, q, g.Np, p->Fp, p->Rp));
+    w.sets.ensure((size_t)q * D * pass_max);
+    if (grad) w.sgrad.ensure((size_t)q * D * pass_max);
+    for (int s0 = 0; s0 < M; s0 += pass_max) {
+        const int sc = std::min(pass_max, M - s0);
+        {
+            ProfScope ps(c, "patch");
+            launch_patch_expand(c->stream, sc, D, qs, qt, patches + s0, ld, anchor, w.sets.p, pass_max);
+        }
+        qeubo_eval_device(p, g, w.q, q, SetMode{base}, w.sets.p, pass_max, sc, val ? val + s0 : nullptr, grad ? w.sgrad.p : nullptr,
+                          pass_max, wins ? wins + s0 : nullptr, ldw);
+        if (grad) {
+            ProfScope ps(c, "patch");
+            launch_patch_fold(c->stream, sc, D, qs, qt, anchor != nullptr, w.sgrad.p, pass_max, grad + s0, ldo);
+        }
+    }
+}
+
+// The cells of a qs x qt grid, or 0 where the grid is outside the contract (either axis below SLS_PATCH_MIN_POSITIONS, or more than
+// SLS_QEUBO_MAX_OPTIONS cells); no product is formed of numbers that could overflow it
+int patch_cells(int qs, int qt) {
+    const bool ok = qs >= SLS_PATCH_MIN_POSITIONS && qt >= SLS_PATCH_MIN_POSITIONS && qs <= SLS_QEUBO_MAX_OPTIONS &&
+                    qt <= SLS_QEUBO_MAX_OPTIONS && qs * qt <= SLS_QEUBO_MAX_OPTIONS;
+    return ok ? qs * qt : 0;
+}
+
+void require_patch_args(const char* who, const sls_path* p, int qs, int qt, const double* baseline, const double* anchor) {
+    SLS_REQUIRE(p != nullptr, "%s: p is NULL", who);
+    SLS_REQUIRE(patch_cells(qs, qt) > 0, "%s: grid %d x %d (at least %d per axis, at most %d cells)", who, qs, qt,
+                SLS_PATCH_MIN_POSITIONS, SLS_QEUBO_MAX_OPTIONS);
+    require_baseline_and_anchor(who, p, baseline, anchor);
+}
+
 // ---- the host front end of the set-shaped objectives --------------------------------------------------------------------------
 // What tells their entry points apart.  sls_qeubo_*: q alone; sls_qnei_*: need_base, the per-draw baseline the options compete
 // against; sls_qlognei_*: need_base and taus = (tau_relu, tau_max); sls_line_*: line, with the optional baseline and the optional
-// anchor -- one start is then one line, 2D variables (D with the anchor) whatever q is.
+// anchor -- one start is then one line, 2D variables (D with the anchor) whatever q is; sls_patch_*: the grid (qs, qt) with q = its
+// cells (patch_cells: 0 for a grid outside the contract), the optional baseline and anchor -- one start is one patch, 4D variables
+// (3D with the anchor) whatever the grid.
 struct SetCall {
     const char* who;
     int q;
@@ -641,15 +689,20 @@ struct SetCall {
     const double* taus = nullptr;
     bool line = false;
     const double* anchor = nullptr;
-    int nvar(int D) const { return !line ? q * D : anchor ? D : 2 * D; }
+    bool patch = false;
+    int qs = 0, qt = 0;
+    int nvar(int D) const { return patch ? (anchor ? 3 : 4) * D : !line ? q * D : anchor ? D : 2 * D; }
+    const char* block_name() const { return patch ? "patches" : line ? "lines" : "sets"; }
 };
 
 // Every refusal ahead of the generation check, in each entry point's order.  M: of an evaluation (nullptr: a maximisation); block:
-// the sets / lines / starts.
+// the sets / lines / patches / starts.
 void require_set_args(const SetCall& s, const sls_path* p, const int* M, const double* block) {
     const char* who = s.who;
     if (!M) SLS_REQUIRE(p && block, "%s: NULL argument", who);
-    if (s.line) {
+    if (s.patch) {
+        require_patch_args(who, p, s.qs, s.qt, s.baseline, s.anchor);
+    } else if (s.line) {
         require_line_args(who, p, s.q, s.baseline, s.anchor);
     } else {
         SLS_REQUIRE(p != nullptr, "%s: p is NULL", who);
@@ -657,7 +710,7 @@ void require_set_args(const SetCall& s, const sls_path* p, const int* M, const d
     }
     if (M) {
         SLS_REQUIRE(*M >= 0, "%s: M = %d", who, *M);
-        SLS_REQUIRE(block != nullptr, "%s: %s is NULL", who, s.line ? "lines" : "sets");
+        SLS_REQUIRE(block != nullptr, "%s: %s is NULL", who, s.block_name());
     }
     if (s.taus) require_temperatures(who, s.taus);
     if (s.need_base) require_finite_baseline(who, p, s.baseline);
@@ -681,6 +734,10 @@ struct SetInputs {
 // The objective of a call at n columns of candidate-major variables trial[j + r*ld]: val[j], grad[j + r*ldo], wins[j + i*ldw]
 void set_objective(sls_path* p, const GpView& g, LineWs& w, const SetCall& s, const SetInputs& in, const double* trial, long ld, int n,
                    double* val, double* grad, long ldo, int* wins, long ldw) {
+    if (s.patch) {
+        patch_eval_device(p, g, w, s.qs, s.qt, in.base.p, in.anchor.p, trial, ld, n, val, grad, ldo, wins, ldw);
+        return;
+    }
     if (s.line) {
         line_eval_device(p, g, w, s.q, in.base.p, in.anchor.p, trial, ld, n, val, grad, ldo, wins, ldw);
         return;
@@ -689,7 +746,7 @@ void set_objective(sls_path* p, const GpView& g, LineWs& w, const SetCall& s, co
     qeubo_eval_device(p, g, w.q, s.q, mode, trial, ld, n, val, grad, ldo, wins, ldw);
 }
 
-// sls_qeubo_eval / sls_qnei_eval / sls_qlognei_eval / sls_line_eval
+// sls_qeubo_eval / sls_qnei_eval / sls_qlognei_eval / sls_line_eval / sls_patch_eval
 int set_eval(const SetCall& s, sls_path* p, const double* block, int M, double* val, double* grad, int* wins) {
     SLS_TRY
     require_set_args(s, p, &M, block);
@@ -719,9 +776,9 @@ int set_eval(const SetCall& s, sls_path* p, const double* block, int M, double* 
     SLS_CATCH
 }
 
-// sls_qeubo_maximize / sls_qnei_maximize / sls_qlognei_maximize / sls_line_maximize: the maximiser of sls_acq_maximize over the
-// box of the call's variables, one start = one set of q options (one line).  Workspaces are per call; the best start and every fetch
-// come back through pageable memory.
+// sls_qeubo_maximize / sls_qnei_maximize / sls_qlognei_maximize / sls_line_maximize / sls_patch_maximize: the maximiser of
+// sls_acq_maximize over the box of the call's variables, one start = one set of q options (one line, one patch).  Workspaces are per
+// call; the best start and every fetch come back through pageable memory.
 int set_maximize(const SetCall& s, sls_path* p, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts,
                  long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars, double* y_stars) {
     SLS_TRY
@@ -805,4 +862,17 @@ extern "C" int sls_line_maximize(sls_path* p, int q, const double* baseline, con
                                  long* idx_out, double* x_stars, double* y_stars) {
     return set_maximize({"sls_line_maximize", q, baseline, false, nullptr, true, anchor}, p, starts, S_starts, n_local, opts,
                         start_index_offset, x_out, val_out, idx_out, x_stars, y_stars);
+}
+
+extern "C" int sls_patch_eval(sls_path* p, int qs, int qt, const double* baseline, const double* anchor, const double* patches, int M,
+                              double* val, double* grad, int* wins) {
+    return set_eval({"sls_patch_eval", patch_cells(qs, qt), baseline, false, nullptr, false, anchor, true, qs, qt}, p, patches, M, val,
+                    grad, wins);
+}
+
+extern "C" int sls_patch_maximize(sls_path* p, int qs, int qt, const double* baseline, const double* anchor, const double* starts,
+                                  int S_starts, int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out,
+                                  double* val_out, long* idx_out, double* x_stars, double* y_stars) {
+    return set_maximize({"sls_patch_maximize", patch_cells(qs, qt), baseline, false, nullptr, false, anchor, true, qs, qt}, p, starts,
+                        S_starts, n_local, opts, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars);
 }

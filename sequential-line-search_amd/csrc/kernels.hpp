@@ -563,6 +563,20 @@ void launch_line_expand(hipStream_t s, int nlines, int D, int q, const double* t
 // grad_b; anchored: grad[n + d*ldo] = grad_b alone.
 void launch_line_fold(hipStream_t s, int nlines, int D, int q, bool anchored, const double* sgrad, long lds, double* grad, long ldo);
 
+// ---- kernels_patch.hip: expected utility of the best gallery cell (sls_patch_*) -------------------------------------------
+// A patch is its corners (c00, c10, c01, c11); cell (i, j) of the qs x qt grid is option k = i + qs j of the expanded set:
+// x_k = v_j (u_i c00 + s_i c10) + t_j (u_i c01 + s_i c11), the weights of launch_line_expand along each axis, three sums of two
+// products, never fused.  trial[n + r*ld] is the candidate-major patch block: rows 0, D, 2D, 3D start c00, c10, c01, c11 (anchor ==
+// nullptr), or rows 0, D, 2D start c10, c01, c11 with c00 = anchor[d] (device, D doubles).
+// sets[n + (k*D + d)*lds] = x_k[d] for n < npatches: the block qeubo_eval_device reads.  qs, qt >= 2, qs qt <= 16.
+void launch_patch_expand(hipStream_t s, int npatches, int D, int qs, int qt, const double* trial, long ld, const double* anchor,
+                         double* sets, long lds);
+// The fold of launch_line_fold along i within every grid row (A_j with u in increasing i, B_j with s in decreasing i), then along j
+// over the row sums (v in increasing j for c00 / c10, t in decreasing j for c01 / c11), of the set gradient sgrad[n + (k*D + d)*lds].
+// grad[n + r*ldo] in the rows of the patch block (3D rows, without c00, when anchored).
+void launch_patch_fold(hipStream_t s, int npatches, int D, int qs, int qt, bool anchored, const double* sgrad, long lds, double* grad,
+                       long ldo);
+
 // ---- kernels_sub.hip: search over affine subspaces (the *_sub entry points) ------------------------------------------------
 // The maps of one call as the kernels read them (device pointers into ONE block, uploaded once per call): n_maps blocks A_k of D x d,
 // column-major A_k[r + j*D], n_maps blocks c_k of D, and the map of every column of the call (nullptr: every column uses map 0).

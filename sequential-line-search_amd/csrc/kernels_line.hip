@@ -3,28 +3,9 @@
 // expanded into the set (x_0..x_{q-1}) the pass evaluates, and the set gradient is folded back onto the ends by the chain rule.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "line_mix.hpp"   // line_weights, line_mix, line_acc
 
 namespace slsk {
-
-// u_i = (q-1-i)/(q-1), t_i = i/(q-1): each ONE division of two exact integers, so u_i = t_{q-1-i} to the bit
-__device__ __forceinline__ void line_weights(int i, int q, double& u, double& t) {
-    const double den = (double)(q - 1);
-    u = (double)(q - 1 - i) / den;
-    t = (double)i / den;
-}
-// u a + t b and acc + w g: products and sum are separate roundings.  A fused multiply-add would round u a + t b differently from
-// t b + u a, and the mirror contract needs the two to be the same number.
-__device__ __forceinline__ double line_mix(double u, double a, double t, double b) {
-#pragma clang fp contract(off)
-    const double ua = u * a;
-    const double tb = t * b;
-    return ua + tb;
-}
-__device__ __forceinline__ double line_acc(double acc, double w, double g) {
-#pragma clang fp contract(off)
-    const double wg = w * g;
-    return acc + wg;
-}
 
 // ONE lane per (n, d), lanes along n: a = anchor[d] (anchored form, the line block has D rows) or trial[n + d ld] (free form, 2D rows),
 // b = the block's last D rows; sets[n + (i D + d) lds] = u_i a + t_i b for i = 0..q-1.  No clamp.

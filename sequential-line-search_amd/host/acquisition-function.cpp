@@ -602,6 +602,35 @@ namespace sequential_line_search
                                                          num_positions, num_draws, num_local_search_iters, seed, num_frequencies, value);
     }
 
+    // ---- the next gallery by the expected utility of its best cell (include/sls_hip.h sls_patch_*) ----
+    std::vector<VectorXd> acquisition_func::FindNextGalleryByExpectedUtilityFromStarts(
+        const Regressor& regressor, const VectorXd& anchor, const MatrixXd& starts, const int grid_s, const int grid_t,
+        const unsigned num_draws, const unsigned num_local_search_iters, const unsigned long long seed, const int num_frequencies,
+        double* value)
+    {
+        RequireDeviceHandleForExpectedUtility(regressor);
+        if (anchor.size() != 0 && anchor.size() != static_cast<long>(regressor.GetNumDims()))
+            throw std::invalid_argument("FindNextGalleryByExpectedUtilityFromStarts: the anchor must be empty or hold D values");
+        const PosteriorFunctionSamples draws =
+            regressor.SamplePosteriorFunctions(static_cast<int>(std::max(1u, num_draws)), seed, num_frequencies);
+        return draws.MaximizeExpectedUtilityOfBestGalleryCell(grid_s, grid_t, starts, num_local_search_iters,
+                                                              anchor.size() != 0 ? &anchor : nullptr, nullptr, value);
+    }
+
+    std::vector<VectorXd> acquisition_func::FindNextGalleryByExpectedUtility(
+        const Regressor& regressor, const VectorXd& anchor, const int grid_s, const int grid_t, const unsigned num_draws,
+        const unsigned num_global_search_iters, const unsigned num_local_search_iters, const unsigned long long seed,
+        const int num_frequencies, double* value)
+    {
+        RequireDeviceHandleForExpectedUtility(regressor);
+        if (grid_s < SLS_PATCH_MIN_POSITIONS || grid_t < SLS_PATCH_MIN_POSITIONS || grid_s > SLS_QEUBO_MAX_OPTIONS ||
+            grid_t > SLS_QEUBO_MAX_OPTIONS || grid_s * grid_t > SLS_QEUBO_MAX_OPTIONS)
+            throw std::invalid_argument("FindNextGalleryByExpectedUtility: a grid of at least 2 positions per axis and at most 16 cells");
+        const unsigned nvar = (anchor.size() != 0 ? 3u : 4u) * regressor.GetNumDims();
+        return FindNextGalleryByExpectedUtilityFromStarts(regressor, anchor, SeededStarts(nvar, std::max(1u, num_global_search_iters), seed),
+                                                          grid_s, grid_t, num_draws, num_local_search_iters, seed, num_frequencies, value);
+    }
+
     MatrixXd acquisition_func::SeededUniformStarts(const unsigned num_dims, const long count, const unsigned long long seed)
     {
         return SeededStarts(num_dims, count, seed);

@@ -422,6 +422,79 @@ namespace sequential_line_search
         return std::make_pair(VectorXd(x.segment(0, D)), VectorXd(x.segment(D, D)));
     }
 
+    namespace
+    {
+        void RequireGalleryGrid(const std::string& name, int grid_s, int grid_t)
+        {
+            if (grid_s < SLS_PATCH_MIN_POSITIONS || grid_t < SLS_PATCH_MIN_POSITIONS || grid_s > SLS_QEUBO_MAX_OPTIONS ||
+                grid_t > SLS_QEUBO_MAX_OPTIONS || grid_s * grid_t > SLS_QEUBO_MAX_OPTIONS)
+                throw std::invalid_argument(name + ": a grid of at least 2 positions per axis and at most 16 cells");
+        }
+    } // namespace
+
+    VectorXd PosteriorFunctionSamples::CalcExpectedUtilitiesOfBestGalleryCell(const MatrixXd& corners00, const MatrixXd& corners10,
+                                                                              const MatrixXd& corners01, const MatrixXd& corners11,
+                                                                              int grid_s, int grid_t, std::vector<MatrixXd>* grads,
+                                                                              Eigen::MatrixXi* win_counts, const VectorXd* baseline) const
+    {
+        const std::string name = "PosteriorFunctionSamples::CalcExpectedUtilitiesOfBestGalleryCell";
+        RequireGalleryGrid(name, grid_s, grid_t);
+        if (baseline && baseline->size() != m_num_draws) throw std::invalid_argument(name + ": the baseline must hold one value per draw");
+        const long      D = m_num_dims, M = corners00.cols();
+        const MatrixXd* corners[4] = {&corners00, &corners10, &corners01, &corners11};
+        for (const MatrixXd* c : corners)
+            if (c->rows() != D || c->cols() != M) throw std::invalid_argument(name + ": every corner block must be D x M");
+        MatrixXd patches(4 * D, M);
+        for (long c = 0; c < 4; ++c)
+            for (long m = 0; m < M; ++m)
+                for (long d = 0; d < D; ++d) patches(c * D + d, m) = (*corners[c])(d, m);
+        VectorXd v = VectorXd::Zero(M);
+        MatrixXd g(grads ? 4 * D : 0, grads ? M : 0);
+        if (win_counts) *win_counts = Eigen::MatrixXi::Zero(grid_s * grid_t, M);
+        device::Check(sls_patch_eval(m_path, grid_s, grid_t, baseline ? baseline->data() : nullptr, nullptr, patches.data(),
+                                     static_cast<int>(M), v.data(), grads ? g.data() : nullptr,
+                                     win_counts ? win_counts->data() : nullptr),
+                      "sls_patch_eval");
+        if (grads)
+        {
+            grads->assign(4, MatrixXd(D, M));
+            for (long c = 0; c < 4; ++c)
+                for (long m = 0; m < M; ++m)
+                    for (long d = 0; d < D; ++d) (*grads)[c](d, m) = g(c * D + d, m);
+        }
+        return v;
+    }
+
+    std::vector<VectorXd> PosteriorFunctionSamples::MaximizeExpectedUtilityOfBestGalleryCell(int grid_s, int grid_t, const MatrixXd& starts,
+                                                                                             unsigned        num_local_search_iters,
+                                                                                             const VectorXd* anchor,
+                                                                                             const VectorXd* baseline, double* value) const
+    {
+        const std::string name = "PosteriorFunctionSamples::MaximizeExpectedUtilityOfBestGalleryCell";
+        RequireGalleryGrid(name, grid_s, grid_t);
+        if (baseline && baseline->size() != m_num_draws) throw std::invalid_argument(name + ": the baseline must hold one value per draw");
+        const long D = m_num_dims, nvar = (anchor ? 3 : 4) * D;
+        if (anchor && anchor->size() != D) throw std::invalid_argument(name + ": the anchor must hold D values");
+        if (starts.rows() != nvar || starts.cols() < 1)
+            throw std::invalid_argument(name + ": starts must be 4D x S (3D x S with an anchor) with S >= 1");
+        sls_lbfgs_opts o;
+        sls_lbfgs_default_opts(&o);
+        optim::SearchTolerances(&o.ftol_rel, &o.xtol_rel);   // the acquisition maximiser's local search tolerances
+        VectorXd x(nvar);
+        double   v   = 0.0;
+        long     idx = 0;
+        device::Check(sls_patch_maximize(m_path, grid_s, grid_t, baseline ? baseline->data() : nullptr, anchor ? anchor->data() : nullptr,
+                                         starts.data(), static_cast<int>(starts.cols()),
+                                         std::max(1, static_cast<int>(num_local_search_iters)), &o, 0, x.data(), &v, &idx, nullptr,
+                                         nullptr),
+                      "sls_patch_maximize");
+        if (value) *value = v;
+        std::vector<VectorXd> out;
+        if (anchor) out.push_back(*anchor);
+        for (long c = 0; c < (anchor ? 3 : 4); ++c) out.push_back(VectorXd(x.segment(c * D, D)));
+        return out;
+    }
+
     MatrixXd Regressor::SamplePosterior(const MatrixXd& Xs, int num_samples, unsigned long long seed, double* jitter_used) const
     {
         sls_gp* h = GetDeviceHandle();
