@@ -202,6 +202,27 @@ namespace sequential_line_search
                                                                               const unsigned long long seed = 0,
                                                                               const int num_frequencies = 2048, double* value = nullptr);
 
+        /// A whole query of num_options options by the information it is expected to give (not in the reference; qBALD after
+        /// Houlsby et al. 2011, include/sls_hip.h sls_qbald_*): the mutual information between the user's pick and the latent
+        /// function under the BTL likelihood of scale btl_scale, estimated on num_draws pathwise posterior draws and maximised as
+        /// FindNextQueryByExpectedUtility maximises its criterion (the same starts, tolerances and seed rule).  It asks which query
+        /// teaches the model most, not where the best option is: the criterion for the first rounds of a session, or for learning
+        /// the whole preference landscape.  With btl_scale far below the spread of the draws every query whose winner is uncertain
+        /// is worth the same one answer and the search stalls; see the header.  value receives the information gain in nats.
+        std::vector<Eigen::VectorXd> FindNextQueryByInformationGain(const Regressor& regressor, const int num_options,
+                                                                    const double btl_scale, const unsigned num_draws = 256,
+                                                                    const unsigned num_global_search_iters = 100,
+                                                                    const unsigned num_local_search_iters = 50,
+                                                                    const unsigned long long seed = 0, const int num_frequencies = 2048,
+                                                                    double* value = nullptr);
+        /// The same from an explicit start set ((num_options D) x S: rows iD..iD+D-1 start option i).
+        std::vector<Eigen::VectorXd> FindNextQueryByInformationGainFromStarts(const Regressor& regressor, const int num_options,
+                                                                              const double btl_scale, const Eigen::MatrixXd& starts,
+                                                                              const unsigned num_draws = 256,
+                                                                              const unsigned num_local_search_iters = 50,
+                                                                              const unsigned long long seed = 0,
+                                                                              const int num_frequencies = 2048, double* value = nullptr);
+
         /// A batch of num_points >= 1 points chosen jointly by noisy expected improvement on posterior draws (not in the reference;
         /// qNEI, Letham et al. 2019, include/sls_hip.h sls_qnei_*): num_draws pathwise posterior draws (SamplePosteriorFunctions with
         /// stream `seed` and num_frequencies random features) fix the estimator (1 / num_draws) sum_s max(0, max_i f_s(x_i) - t_s)

@@ -66,6 +66,14 @@ namespace sequential_line_search
         /// any feedback it throws as DetermineNextQuery does; non-positive iteration counts select the same heuristic.
         void DetermineNextQueryByExpectedUtilityOfDraws(const unsigned long long seed, const int num_draws = 256,
                                                         const int num_global_search_iters = 0, const int num_local_search_iters = 0);
+        /// Opt-in alternative that explores: ALL options are the joint maximiser of the information the user's answer is expected to
+        /// give about the latent function (acquisition_func::FindNextQueryByInformationGain with draw and start stream `seed`) under
+        /// the BTL likelihood of scale btl_scale; btl_scale <= 0 means the optimiser's own (the constructor's btl_scale).  The
+        /// option with the largest posterior mean is moved to position 0 (GetMaximizer()); the others keep their order.  Before any
+        /// feedback it throws as DetermineNextQuery does; non-positive iteration counts select the same heuristic.
+        void DetermineNextQueryByInformationGain(const unsigned long long seed, const int num_draws = 256,
+                                                 const int num_global_search_iters = 0, const int num_local_search_iters = 0,
+                                                 const double btl_scale = 0.0);
         /// Opt-in alternative: option 0 as in DetermineNextQuery, the other m_num_options - 1 options the JOINT maximiser of noisy
         /// expected improvement on num_draws posterior draws (acquisition_func::FindNextPointsByNoisyExpectedImprovement with draw
         /// and start stream `seed`): improvement over the per-draw incumbent rather than over a known best value, which a

@@ -144,6 +144,18 @@ namespace sequential_line_search
                                                                          const Eigen::MatrixXd& starts, unsigned num_local_search_iters,
                                                                          double* value = nullptr, double tau_relu = 1e-6,
                                                                          double tau_max = 1e-2) const;
+        /// Information gain of a choice query (qBALD; include/sls_hip.h sls_qbald_*): the mutual information between the user's pick
+        /// among options[i].col(m), i = 0 .. q-1, and the latent function, under the BTL likelihood of the given scale
+        /// (PreferenceRegressor's btl_scale), estimated on the draws.  options as for CalcExpectedUtilitiesOfBestOption.  Returns the M
+        /// values, each in [0, ln q]; *grads (optional) the gradients, *probabilities (optional, q x M) the predicted probability that
+        /// the user picks option i -- what a held-out preference log-loss is computed from --, *win_counts (optional, q x M) the hard
+        /// win counts of CalcExpectedUtilitiesOfBestOption.
+        Eigen::VectorXd CalcChoiceInformationGains(const std::vector<Eigen::MatrixXd>& options, double scale,
+                                                   std::vector<Eigen::MatrixXd>* grads = nullptr, Eigen::MatrixXd* probabilities = nullptr,
+                                                   Eigen::MatrixXi* win_counts = nullptr) const;
+        /// Maximiser of that criterion over [0,1]^(num_options D): as MaximizeExpectedUtilityOfBestOption.
+        std::vector<Eigen::VectorXd> MaximizeChoiceInformationGain(int num_options, double scale, const Eigen::MatrixXd& starts,
+                                                                   unsigned num_local_search_iters, double* value = nullptr) const;
         /// Expected utility of the best of num_positions grid positions on the slider from ends_a.col(m) to ends_b.col(m) (line EUBO;
         /// include/sls_hip.h sls_line_*): CalcExpectedUtilitiesOfBestOption at the positions (1 - t_i) a + t_i b, t_i = i /
         /// (num_positions - 1), 2 <= num_positions <= 16 -- Slider::GetValue on the grid.  ends_a, ends_b D x M.  Returns the M values;
@@ -188,13 +200,16 @@ namespace sequential_line_search
 
     private:
         // the set criteria of every kind: baseline == nullptr is the expected utility of the best option, taus != nullptr
-        // (tau_relu, tau_max) the log form of the noisy expected improvement
+        // (tau_relu, tau_max) the log form of the noisy expected improvement, scale != nullptr (the BTL scale, without a baseline) the
+        // information gain of the choice, with its optional probabilities
         Eigen::VectorXd              CalcSetCriterion(const char* who, const std::vector<Eigen::MatrixXd>& options,
                                                       const Eigen::VectorXd* baseline, std::vector<Eigen::MatrixXd>* grads,
-                                                      Eigen::MatrixXi* win_counts, const double* taus = nullptr) const;
+                                                      Eigen::MatrixXi* win_counts, const double* taus = nullptr,
+                                                      const double* scale = nullptr, Eigen::MatrixXd* probabilities = nullptr) const;
         std::vector<Eigen::VectorXd> MaximizeSetCriterion(const char* who, int num_options, const Eigen::VectorXd* baseline,
                                                           const Eigen::MatrixXd& starts, unsigned num_local_search_iters,
-                                                          double* value, const double* taus = nullptr) const;
+                                                          double* value, const double* taus = nullptr,
+                                                          const double* scale = nullptr) const;
 
         sls_path* m_path      = nullptr;
         int       m_num_draws = 0;

@@ -495,6 +495,48 @@ int sls_qlognei_maximize(sls_path* p, int q, const double* baseline, double tau_
                          int S_starts, int n_local, const sls_lbfgs_opts* opts, long start_index_offset, double* x_out,
                          double* val_out, long* idx_out, double* x_stars, double* y_stars);
 
+/* ---- information gain of a choice query on posterior draws (not in the reference) -------------------------------------------
+ * qBALD: the mutual information between the user's answer to a q-option choice query and the latent function (Houlsby et al. 2011,
+ * "Bayesian active learning by disagreement", there for pairs), under the Bradley-Terry-Luce likelihood the preference model is fitted
+ * with (PreferenceRegressor's btl_scale; CalcBtl of the reference).  Where qEUBO asks where the best option probably is, this asks
+ * which query teaches the model most; its by-product is the predicted choice probability of every option, the quantity a held-out
+ * preference log-loss is computed from.  For a path object p (S = n_draws draws f_s), a BTL scale tau > 0 and a set of q options:
+ *   v_{i,s}  = f_s(x_i)                                  formed exactly as sls_qeubo_eval forms it
+ *   z_{i,s}  = (v_{i,s} - max_j v_{j,s}) / tau           subtract first, then divide: <= 0, exactly 0 at the largest value
+ *   Z_s      = sum_i exp(z_{i,s})                        the order-free sum of sls_qlognei_eval: terms in [0,1] rounded to multiples of
+ *                                                        2^-58, added as 64-bit integers; Z_s >= 1
+ *   p_{i,s}  = exp(z_{i,s}) / Z_s                        the BTL probability that option i is chosen under draw s
+ *   pbar_i   = ( sum_s p_{i,s} ) / S                     from zero, s increasing inside slices of 16 draws, slices increasing, ONE
+ *                                                        division: the predicted choice probability of option i (prob)
+ *   l_{i,s}  = log p_{i,s} - log pbar_i                  both logarithms of the numbers as formed; taken as 0 where p_{i,s} = 0
+ *   KL_s     = sum_i p_{i,s} l_{i,s}                     a signed sum in increasing i
+ *   value    = ( sum_s KL_s ) / S                        = H(pbar) - mean_s H(p_s) = I(choice; f); the same fixed order over s
+ *   c_{i,s}  = p_{i,s} (l_{i,s} - KL_s) / (S tau)        = d value / d v_{i,s};  sum_i c_{i,s} = 0 for every draw
+ *   grad_{x_i} value = grad fbar_i(x_i),  fbar_i = the path function with weights (W c_i, V c_i)      -- no further division
+ *   wins_i   = sls_qeubo_eval's wins (hard, strictly greater, lowest index on ties), bit for bit
+ * The criterion is smooth everywhere.  0 <= value <= ln q to rounding (the value may be -O(eps)).  q = 1 gives value and gradient
+ * exactly 0 and prob exactly 1; S = 1 gives value and gradient exactly 0, because l is then exactly 0; an option with pbar_i = 0
+ * gets an exactly zero gradient block; sum_i prob_i = 1 to q eps.
+ * The saturated regime: when tau is far below the spread of the draws at the options, every p_s is one-hot, the value tends to the
+ * entropy of the win frequencies wins / S, and the weights tend to 0 because l - KL_s vanishes at the winner.  Such a start is
+ * stationary and leaves the maximiser's batch, as a start with expected improvement exactly 0 does.  That is a property of the
+ * criterion -- with a near-deterministic user every query whose winner is uncertain is worth the same one answer -- not of the
+ * estimator.
+ * Guard: a NaN among the set's q S values or its qD gradient components gives the value SLS_QEUBO_FLOOR, the zero gradient, a zero prob
+ * column, and wins as sls_qeubo_eval reports them for that set; the scan runs before any write and whether or not the gradient is
+ * asked for.
+ * Bits: a set's value, gradient, prob and wins depend on neither its column, the other sets of the call, the number of sets per pass
+ * nor SLS_COMPACT.  Permuting the options of a set permutes wins and prob exactly (Z_s has no order and each pbar_i has its own fixed
+ * order over s); KL_s is a signed sum over the options in index order, so the value and the gradient are unchanged to rounding only.
+ * scale not finite, <= 0 or subnormal is SLS_ERR_INVALID (checked once per call, before any upload); q, M, NULL arguments, M = 0, the
+ * locks and the staleness rule are as sls_qeubo_eval.  The slider and gallery forms have no such variant. */
+#define SLS_QBALD_SCALE 0.010 /* the reference's default btl_scale */
+/* prob: q x M column-major, prob[i + n q] = pbar_i of set n.  val, grad, prob and wins may each be NULL. */
+int sls_qbald_eval(sls_path* p, int q, double scale, const double* sets, int M, double* val, double* grad, double* prob, int* wins);
+/* sls_qeubo_maximize with this objective; the scale is validated once, before the first round. */
+int sls_qbald_maximize(sls_path* p, int q, double scale, const double* starts, int S_starts, int n_local, const sls_lbfgs_opts* opts,
+                       long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars, double* y_stars);
+
 /* ---- expected utility of the best slider position on posterior draws (not in the reference) --------------------------------
  * Line EUBO: the query of SequentialLineSearchOptimizer is a slider from a to b, and the user picks the best point anywhere on it.
  * The one-step criterion of that query is E[ max_t f((1-t) a + t b) ], estimated on a grid of q positions over the FIXED draws of a
@@ -821,6 +863,8 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
  * launch per pass; its values count under "cross_gram", "path_prior", "qeubo_data_gemm");
  * "qlognei" (the selection of the log form, two kernels under one entry, and the finish under another: two entries per pass of
  * sls_qlognei_eval / per pass and round of sls_qlognei_maximize; every other stage counts as under qEUBO);
+ * "qbald" (the selection under the BTL likelihood, two kernels under one entry, and its finish under another: two entries per pass of
+ * sls_qbald_eval / per pass and round of sls_qbald_maximize; every other stage counts as under qEUBO);
  * "line" (line_expand and line_fold: two launches per pass of sls_line_eval -- one without a gradient -- / per pass and round of
  * sls_line_maximize; the pass between them counts as under qEUBO / qNEI);
  * "patch" (patch_expand and patch_fold: two launches per pass of sls_patch_eval -- one without a gradient -- / per pass and round of

@@ -280,6 +280,24 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
                  return std::make_pair(q, value);
              },
              "num_points"_a, "baseline"_a, "starts"_a, "num_local_search_iters"_a = 50, "tau_relu"_a = 1e-6, "tau_max"_a = 1e-2)
+        // the information gain of a choice query under the BTL likelihood: calc_... (values, [gradient per option], predicted choice
+        // probabilities q x M, win counts q x M), maximize_... (options, value)
+        .def("calc_choice_information_gains",
+             [](const PosteriorFunctionSamples& s, const std::vector<MatrixXd>& options, double scale) {
+                 std::vector<MatrixXd> grads;
+                 MatrixXd              prob;
+                 Eigen::MatrixXi       wins;
+                 const VectorXd        v = s.CalcChoiceInformationGains(options, scale, &grads, &prob, &wins);
+                 return std::make_tuple(v, grads, prob, wins);
+             },
+             "options"_a, "scale"_a = 0.010)
+        .def("maximize_choice_information_gain",
+             [](const PosteriorFunctionSamples& s, int num_options, const MatrixXd& starts, unsigned num_local_search_iters, double scale) {
+                 double     value = 0.0;
+                 const auto q     = s.MaximizeChoiceInformationGain(num_options, scale, starts, num_local_search_iters, &value);
+                 return std::make_pair(q, value);
+             },
+             "num_options"_a, "starts"_a, "num_local_search_iters"_a = 50, "scale"_a = 0.010)
         // the expected utility of the best slider position on the draws: (values, gradient for the first end, for the second, win
         // counts num_positions x M); maximize_... ((end_0, end_1), value)
         .def("calc_expected_utilities_of_best_slider_position",
@@ -344,6 +362,28 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
           },
           "regressor"_a, "num_options"_a, "starts"_a, "num_draws"_a = 256, "num_local_search_iters"_a = 50, "seed"_a = 0ULL,
           "num_frequencies"_a = 2048);
+
+    // a whole query by the information the answer is expected to give (acquisition-function.hpp): (options, value)
+    m.def("find_next_query_by_information_gain",
+          [](const Regressor& r, int num_options, double btl_scale, unsigned num_draws, unsigned num_global_search_iters,
+             unsigned num_local_search_iters, unsigned long long seed, int num_frequencies) {
+              double     value = 0.0;
+              const auto q     = acquisition_func::FindNextQueryByInformationGain(
+                  r, num_options, btl_scale, num_draws, num_global_search_iters, num_local_search_iters, seed, num_frequencies, &value);
+              return std::make_pair(q, value);
+          },
+          "regressor"_a, "num_options"_a, "btl_scale"_a = 0.010, "num_draws"_a = 256, "num_global_search_iters"_a = 100,
+          "num_local_search_iters"_a = 50, "seed"_a = 0ULL, "num_frequencies"_a = 2048);
+    m.def("find_next_query_by_information_gain_from_starts",
+          [](const Regressor& r, int num_options, const MatrixXd& starts, double btl_scale, unsigned num_draws,
+             unsigned num_local_search_iters, unsigned long long seed, int num_frequencies) {
+              double     value = 0.0;
+              const auto q     = acquisition_func::FindNextQueryByInformationGainFromStarts(
+                  r, num_options, btl_scale, starts, num_draws, num_local_search_iters, seed, num_frequencies, &value);
+              return std::make_pair(q, value);
+          },
+          "regressor"_a, "num_options"_a, "starts"_a, "btl_scale"_a = 0.010, "num_draws"_a = 256,
+          "num_local_search_iters"_a = 50, "seed"_a = 0ULL, "num_frequencies"_a = 2048);
 
     // a batch of points chosen jointly by noisy expected improvement on posterior draws (acquisition-function.hpp): (points, value)
     m.def("find_next_points_by_noisy_expected_improvement",
@@ -578,6 +618,8 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
              "seed"_a, "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0)
         .def("determine_next_query_by_expected_utility_of_draws", &PreferentialBayesianOptimizer::DetermineNextQueryByExpectedUtilityOfDraws,
              "seed"_a, "num_draws"_a = 256, "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0)
+        .def("determine_next_query_by_information_gain", &PreferentialBayesianOptimizer::DetermineNextQueryByInformationGain, "seed"_a,
+             "num_draws"_a = 256, "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0, "btl_scale"_a = 0.0)
         .def("determine_next_query_by_noisy_expected_improvement",
              &PreferentialBayesianOptimizer::DetermineNextQueryByNoisyExpectedImprovement, "seed"_a, "num_draws"_a = 256,
              "num_global_search_iters"_a = 0, "num_local_search_iters"_a = 0)

@@ -107,7 +107,7 @@ EXPORTS = [
     "sls_eubo_eval", "sls_eubo_maximize", "sls_qeubo_eval", "sls_qeubo_maximize",
     "sls_path_max_over_points", "sls_qnei_eval", "sls_qnei_maximize",
     "sls_line_eval", "sls_line_maximize", "sls_patch_eval", "sls_patch_maximize",
-    "sls_qlognei_terms", "sls_qlognei_eval", "sls_qlognei_maximize",
+    "sls_qlognei_terms", "sls_qlognei_eval", "sls_qlognei_maximize", "sls_qbald_eval", "sls_qbald_maximize",
     "sls_acq_eval_sub", "sls_acq_maximize_sub", "sls_mes_eval_sub", "sls_mes_maximize_sub", "sls_path_eval_sub", "sls_path_maximize_sub",
     "sls_nll_loo", "sls_gp_loo_grad", "sls_gp_loo",
 ]
@@ -483,6 +483,7 @@ LINE_MIN_POSITIONS = 2   # SLS_LINE_MIN_POSITIONS
 PATCH_MIN_POSITIONS = 2  # SLS_PATCH_MIN_POSITIONS
 QEUBO_FLOOR = -1.0e300   # SLS_QEUBO_FLOOR
 QLOGNEI_TAU_RELU, QLOGNEI_TAU_MAX = 1e-6, 1e-2   # SLS_QLOGNEI_TAU_RELU, SLS_QLOGNEI_TAU_MAX
+QBALD_SCALE = 0.010      # SLS_QBALD_SCALE: the reference's default btl_scale
 
 
 class PathSamples:
@@ -673,6 +674,38 @@ class PathSamples:
         t = self._baseline("qlognei_maximize", baseline)
         t0, tm = self._temperatures("qlognei_maximize", tau_relu, tau_max)
         return self._set_maximize(lib().sls_qlognei_maximize, q * self.D, starts, n_local, offset, want_all, opts, q, _p(t), t0, tm)
+
+    @staticmethod
+    def _scale(who, scale):
+        t = float(scale)
+        if not (np.isfinite(t) and t >= np.finfo(np.float64).tiny):
+            raise SlsError(f"{who}: scale = {t} (finite, > 0, not subnormal)")
+        return C.c_double(t)
+
+    def qbald_eval(self, sets, q, scale=QBALD_SCALE, want_grad=True, want_prob=False, want_wins=False):
+        """Information gain of a q-option choice query under the BTL likelihood of the given scale, on the draws (sls_qbald_eval), at
+        the columns of sets (qD x M: rows iD..iD+D-1 = option i): values (M,), then with want_grad the gradient (qD, M), then with
+        want_prob the predicted choice probabilities (q, M), then with want_wins the hard win counts of qeubo_eval (q, M) int32."""
+        sets = _f(sets)
+        q = self._set_block("qbald_eval", q, sets, "sets")
+        tau = self._scale("qbald_eval", scale)
+        M = sets.shape[1]
+        val = np.empty(M)
+        grad = np.empty((q * self.D, M), order="F") if want_grad else None
+        prob = np.zeros((q, M), order="F") if want_prob else None
+        wins = np.zeros((q, M), dtype=np.int32, order="F") if want_wins else None
+        _ck(lib().sls_qbald_eval(self.h, q, tau, _p(sets), M, _p(val), _p(grad) if want_grad else None, _p(prob) if want_prob else None,
+                                 wins.ctypes.data_as(C.POINTER(C.c_int)) if want_wins else None))
+        out = (val,) + ((grad,) if want_grad else ()) + ((prob,) if want_prob else ()) + ((wins,) if want_wins else ())
+        return out if len(out) > 1 else val
+
+    def qbald_maximize(self, starts, q, n_local, scale=QBALD_SCALE, offset=0, want_all=True, opts=None):
+        """acq_maximize over [0,1]^(qD) with the set objective of qbald_eval (sls_qbald_maximize): starts qD x S, x and x_stars have
+        qD rows.  GP.last_stats() of the path's handle reports the run."""
+        starts = _f(starts)
+        q = self._set_block("qbald_maximize", q, starts, "starts")
+        tau = self._scale("qbald_maximize", scale)
+        return self._set_maximize(lib().sls_qbald_maximize, q * self.D, starts, n_local, offset, want_all, opts, q, tau)
 
     def _line_args(self, who, q, anchor, baseline, block, what):
         q = self._set_block(who, q, None, what, LINE_MIN_POSITIONS)

@@ -1,4 +1,4 @@
-// C-ABI of the pathwise posterior function draws (include/sls_hip.h: sls_path_*, and sls_qeubo_* / sls_qnei_* / sls_qlognei_* /
+// C-ABI of the pathwise posterior function draws (include/sls_hip.h: sls_path_*, and sls_qeubo_* / sls_qnei_* / sls_qlognei_* / sls_qbald_* /
 // sls_line_* / sls_patch_* on them): host orchestration of kernels_path.hip and kernels_qeubo.hip, the cross Gram / gradient products of
 // kernels_gram.hip / kernels_acq.hip, the tile GEMM and block solve of kernels_tri.hip and the lock-step L-BFGS rounds of
 // lbfgs_driver.hpp.  No CPU fallback.
@@ -10,7 +10,7 @@
 //   gathered_route          one weight column per point: value, data term and gradient (tiled, or direct beyond the guard)
 //   path_eval_gathered      host body of sls_path_eval (gathered form) and sls_path_eval_sub
 //   path_maximize           host body of sls_path_maximize and sls_path_maximize_sub
-//   set_eval / set_maximize host bodies of sls_qeubo_*, sls_qnei_*, sls_qlognei_*, sls_line_* and sls_patch_* (SetCall tells them apart)
+//   set_eval / set_maximize host bodies of sls_qeubo_*, sls_qnei_*, sls_qlognei_*, sls_qbald_*, sls_line_* and sls_patch_* (SetCall tells them apart)
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -445,18 +445,32 @@ int qeubo_sets_per_pass(const sls_ctx* c, int q, int Np, int Fp, int Rp) {
 }
 
 // What the selection of a pass computes: qEUBO (base == nullptr), qNEI (base: n_draws device doubles, the per-draw baseline) or
-// qLogNEI (log_form, with base and the two temperatures).
+// qLogNEI (log_form, with base and the two temperatures), or qBALD (bald: the BTL scale, no base; prob[n + i*ldp], device, receives
+// the predicted choice probabilities of the call's columns, nullptr: not asked for).
 struct SetMode {
     const double* base = nullptr;
     bool log_form = false;
     double tau_relu = 0.0, tau_max = 0.0;
+    bool bald = false;
+    double scale = 0.0;
+    double* prob = nullptr;
+    long ldp = 0;
 };
 
 // What a pass of sets adds to the blocks of its q Sp points
 struct SetWs : PassWs {
     DBuf VM, Wbar, Vbar, sum, fbar, gpt, badb, identb;
     DBuf lmq, lzq, lpmx, lpsm, lpbadb, lpwinb;   // the scratch of the log-form selection (launch_qlognei_select)
+    DBuf bpp, bkl, bpbar;                        // the scratch of the BTL selection (launch_qbald_select), with lpbadb and lpwinb
     int *lpbad = nullptr, *lpwin = nullptr;
+    void ensure_bald(const sls_path* p, int q, int Sp) {
+        const size_t nsl = (size_t)qbald_slices(p->n_draws);
+        bpp.ensure((size_t)Sp * nsl * q);
+        bkl.ensure((size_t)Sp * nsl);
+        bpbar.ensure((size_t)Sp * q);
+        lpbad = ints(lpbadb, (size_t)Sp * nsl);
+        lpwin = ints(lpwinb, (size_t)Sp * nsl * q);
+    }
     void ensure_log(const sls_path* p, int q, int Sp) {
         const size_t nsl = (size_t)qlognei_slices(p->n_draws);
         lmq.ensure((size_t)Sp * p->Rp);
@@ -504,16 +518,19 @@ void draw_values_device(sls_path* p, const GpView& g, SetWs& w, const PassPoints
 // base != nullptr (device, n_draws doubles): qNEI -- the selection competes against the per-draw baseline, the guard value is 0 and
 // the two kernels count under "qnei".  mode.log_form: qLogNEI -- the selection is launch_qlognei_select (real weights in place of the
 // mask), the finish divides nothing, the guard value is SLS_QEUBO_FLOOR and the launches count under "qlognei".
+// mode.bald: qBALD -- the selection is launch_qbald_select (real weights again), the finish is launch_qbald_finish (it adds the
+// slices' sums of KL_s, divides once and writes mode.prob), the guard value is SLS_QEUBO_FLOOR and the launches count under "qbald".
 void qeubo_eval_device(sls_path* p, const GpView& g, SetWs& w, int q, const SetMode& mode, const double* xr, long ldr, int M,
                        double* val, double* grad, long ldo, int* wins, long ldw) {
     sls_ctx* c = g.ctx;
     const double* base = mode.base;
-    const char* scope = mode.log_form ? "qlognei" : base ? "qnei" : "qeubo";
+    const char* scope = mode.bald ? "qbald" : mode.log_form ? "qlognei" : base ? "qnei" : "qeubo";
     const double floor = base && !mode.log_form ? 0.0 : SLS_QEUBO_FLOOR;
     const int D = g.D, Np = g.Np, Fp = p->Fp, Rp = p->Rp, S = p->n_draws;
     const int pass_max = std::min(round_up(M, 128), qeubo_sets_per_pass(c, q, Np, Fp, Rp));
     w.ensure_sets(c, p, g, q * pass_max, pass_max);
     if (mode.log_form) w.ensure_log(p, q, pass_max);
+    if (mode.bald) w.ensure_bald(p, q, pass_max);
     if (!g.gram_direct) w.ensure_b2(p, g);
     for (int s0 = 0; s0 < M; s0 += pass_max) {
         const int sc = std::min(pass_max, M - s0), Sp = round_up(sc, 128), Pp = q * Sp;
@@ -521,7 +538,10 @@ void qeubo_eval_device(sls_path* p, const GpView& g, SetWs& w, int q, const SetM
         draw_values_device(p, g, w, pt);
         {
             ProfScope ps(c, scope);
-            if (mode.log_form)
+            if (mode.bald)
+                launch_qbald_select(c->stream, sc, Sp, q, S, Rp, w.VM.p, Pp, mode.scale, w.bpp.p, w.bkl.p, w.lpbad, w.lpwin, w.bpbar.p,
+                                    wins ? wins + s0 : nullptr, ldw, w.bad);
+            else if (mode.log_form)
                 launch_qlognei_select(c->stream, sc, Sp, q, S, Rp, w.VM.p, Pp, base, mode.tau_relu, mode.tau_max, w.lmq.p, w.lzq.p, w.lpmx.p,
                                       w.lpsm.p, w.lpbad, w.lpwin, w.sum.p, wins ? wins + s0 : nullptr, ldw, w.bad);
             else
@@ -538,8 +558,12 @@ void qeubo_eval_device(sls_path* p, const GpView& g, SetWs& w, int q, const SetM
         gathered_route(p, g, w, pt, w.Wbar.p, 2L * Fp, w.Vbar.p, Np, w.ident, Pp, true, w.fbar.p, w.gpt.p, Pp);
         {
             ProfScope ps(c, scope);
-            launch_qeubo_finish(c->stream, sc, Sp, q, D, S, w.sum.p, w.bad, w.gpt.p, Pp, floor, val ? val + s0 : nullptr,
-                                grad ? grad + s0 : nullptr, ldo, mode.log_form);
+            if (mode.bald)
+                launch_qbald_finish(c->stream, sc, Sp, q, D, S, w.bkl.p, w.bad, w.gpt.p, Pp, w.bpbar.p, floor, val ? val + s0 : nullptr,
+                                    grad ? grad + s0 : nullptr, ldo, mode.prob ? mode.prob + s0 : nullptr, mode.ldp);
+            else
+                launch_qeubo_finish(c->stream, sc, Sp, q, D, S, w.sum.p, w.bad, w.gpt.p, Pp, floor, val ? val + s0 : nullptr,
+                                    grad ? grad + s0 : nullptr, ldo, mode.log_form);
         }
     }
 }
@@ -550,6 +574,11 @@ void qeubo_eval_device(sls_path* p, const GpView& g, SetWs& w, int q, const SetM
 static void require_temperatures(const char* who, const double* taus) {
     SLS_REQUIRE(std::isfinite(taus[0]) && taus[0] > 0.0, "%s: tau_relu = %g (finite, > 0)", who, taus[0]);
     SLS_REQUIRE(std::isfinite(taus[1]) && taus[1] > 0.0, "%s: tau_max = %g (finite, > 0)", who, taus[1]);
+}
+
+// The BTL scale of the choice likelihood, checked once per call before anything is uploaded
+static void require_scale(const char* who, double scale) {
+    SLS_REQUIRE(std::isnormal(scale) && scale > 0.0, "%s: scale = %g (finite, > 0, not subnormal)", who, scale);
 }
 
 static void require_finite_baseline(const char* who, const sls_path* p, const double* baseline) {
@@ -680,7 +709,8 @@ void require_patch_args(const char* who, const sls_path* p, int qs, int qt, cons
 // against; sls_qlognei_*: need_base and taus = (tau_relu, tau_max); sls_line_*: line, with the optional baseline and the optional
 // anchor -- one start is then one line, 2D variables (D with the anchor) whatever q is; sls_patch_*: the grid (qs, qt) with q = its
 // cells (patch_cells: 0 for a grid outside the contract), the optional baseline and anchor -- one start is one patch, 4D variables
-// (3D with the anchor) whatever the grid.
+// (3D with the anchor) whatever the grid; sls_qbald_*: scale, the BTL scale of the choice likelihood, and prob, the optional q x M
+// output of the predicted choice probabilities (an evaluation's; a maximisation has none).
 struct SetCall {
     const char* who;
     int q;
@@ -691,6 +721,8 @@ struct SetCall {
     const double* anchor = nullptr;
     bool patch = false;
     int qs = 0, qt = 0;
+    const double* scale = nullptr;
+    double* prob = nullptr;
     int nvar(int D) const { return patch ? (anchor ? 3 : 4) * D : !line ? q * D : anchor ? D : 2 * D; }
     const char* block_name() const { return patch ? "patches" : line ? "lines" : "sets"; }
 };
@@ -713,6 +745,7 @@ void require_set_args(const SetCall& s, const sls_path* p, const int* M, const d
         SLS_REQUIRE(block != nullptr, "%s: %s is NULL", who, s.block_name());
     }
     if (s.taus) require_temperatures(who, s.taus);
+    if (s.scale) require_scale(who, *s.scale);
     if (s.need_base) require_finite_baseline(who, p, s.baseline);
 }
 
@@ -731,9 +764,10 @@ struct SetInputs {
     }
 };
 
-// The objective of a call at n columns of candidate-major variables trial[j + r*ld]: val[j], grad[j + r*ldo], wins[j + i*ldw]
+// The objective of a call at n columns of candidate-major variables trial[j + r*ld]: val[j], grad[j + r*ldo], wins[j + i*ldw] and,
+// of sls_qbald_eval alone, prob[j + i*ldp]
 void set_objective(sls_path* p, const GpView& g, LineWs& w, const SetCall& s, const SetInputs& in, const double* trial, long ld, int n,
-                   double* val, double* grad, long ldo, int* wins, long ldw) {
+                   double* val, double* grad, long ldo, int* wins, long ldw, double* prob = nullptr, long ldp = 0) {
     if (s.patch) {
         patch_eval_device(p, g, w, s.qs, s.qt, in.base.p, in.anchor.p, trial, ld, n, val, grad, ldo, wins, ldw);
         return;
@@ -742,11 +776,12 @@ void set_objective(sls_path* p, const GpView& g, LineWs& w, const SetCall& s, co
         line_eval_device(p, g, w, s.q, in.base.p, in.anchor.p, trial, ld, n, val, grad, ldo, wins, ldw);
         return;
     }
-    const SetMode mode{in.base.p, s.taus != nullptr, s.taus ? s.taus[0] : 0.0, s.taus ? s.taus[1] : 0.0};
+    const SetMode mode{in.base.p,          s.taus != nullptr,        s.taus ? s.taus[0] : 0.0, s.taus ? s.taus[1] : 0.0,
+                       s.scale != nullptr, s.scale ? *s.scale : 0.0, prob,                     ldp};
     qeubo_eval_device(p, g, w.q, s.q, mode, trial, ld, n, val, grad, ldo, wins, ldw);
 }
 
-// sls_qeubo_eval / sls_qnei_eval / sls_qlognei_eval / sls_line_eval / sls_patch_eval
+// sls_qeubo_eval / sls_qnei_eval / sls_qlognei_eval / sls_qbald_eval / sls_line_eval / sls_patch_eval
 int set_eval(const SetCall& s, sls_path* p, const double* block, int M, double* val, double* grad, int* wins) {
     SLS_TRY
     require_set_args(s, p, &M, block);
@@ -756,27 +791,31 @@ int set_eval(const SetCall& s, sls_path* p, const double* block, int M, double* 
     sls_ctx* c = g.ctx;
     const int q = s.q, nvar = s.nvar(g.D), Mp = round_up(M, 128);
     const std::vector<double> t = host_to_cm(block, nvar, M, Mp);   // alive until the synchronisation below
-    DBuf raw, out, wb;
+    DBuf raw, out, wb, pb;
     SetInputs in;
     raw.ensure(t.size());
     h2d(c, raw.p, t.data(), t.size());
     in.upload(c, p, s);
     out.ensure((size_t)Mp * (1 + nvar));
     int* d_wins = wins ? ints(wb, (size_t)Mp * q) : nullptr;
+    if (s.prob) pb.ensure((size_t)Mp * q);
     LineWs ws;
-    set_objective(p, g, ws, s, in, raw.p, Mp, M, out.p, grad ? out.p + Mp : nullptr, Mp, d_wins, Mp);
+    set_objective(p, g, ws, s, in, raw.p, Mp, M, out.p, grad ? out.p + Mp : nullptr, Mp, d_wins, Mp, s.prob ? pb.p : nullptr, Mp);
     std::vector<double> oh((size_t)Mp * (grad ? 1 + nvar : 1));
     std::vector<int> wh(wins ? (size_t)Mp * q : 0);
+    std::vector<double> ph(s.prob ? (size_t)Mp * q : 0);
     d2h(c, oh.data(), out.p, oh.size());
+    if (s.prob) d2h(c, ph.data(), pb.p, ph.size());
     if (wins) SLS_HIP(hipMemcpyAsync(wh.data(), d_wins, wh.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     SLS_HIP(hipStreamSynchronize(c->stream));
     cm_to_host(oh.data(), Mp, 1, M, val);
     cm_to_host(oh.data() + Mp, Mp, nvar, M, grad);
     cm_to_host(wh.data(), Mp, q, M, wins);
+    cm_to_host(ph.data(), Mp, q, M, s.prob);
     SLS_CATCH
 }
 
-// sls_qeubo_maximize / sls_qnei_maximize / sls_qlognei_maximize / sls_line_maximize / sls_patch_maximize: the maximiser of
+// sls_qeubo_maximize / sls_qnei_maximize / sls_qlognei_maximize / sls_qbald_maximize / sls_line_maximize / sls_patch_maximize: the maximiser of
 // sls_acq_maximize over the box of the call's variables, one start = one set of q options (one line, one patch).  Workspaces are per
 // call; the best start and every fetch come back through pageable memory.
 int set_maximize(const SetCall& s, sls_path* p, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts,
@@ -850,6 +889,22 @@ extern "C" int sls_qlognei_maximize(sls_path* p, int q, const double* baseline, 
     const double taus[2] = {tau_relu, tau_max};
     return set_maximize({"sls_qlognei_maximize", q, baseline, true, taus}, p, starts, S_starts, n_local, opts, start_index_offset, x_out,
                         val_out, idx_out, x_stars, y_stars);
+}
+
+extern "C" int sls_qbald_eval(sls_path* p, int q, double scale, const double* sets, int M, double* val, double* grad, double* prob,
+                              int* wins) {
+    SetCall s{"sls_qbald_eval", q};
+    s.scale = &scale;
+    s.prob = prob;
+    return set_eval(s, p, sets, M, val, grad, wins);
+}
+
+extern "C" int sls_qbald_maximize(sls_path* p, int q, double scale, const double* starts, int S_starts, int n_local,
+                                  const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
+                                  double* x_stars, double* y_stars) {
+    SetCall s{"sls_qbald_maximize", q};
+    s.scale = &scale;
+    return set_maximize(s, p, starts, S_starts, n_local, opts, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars);
 }
 
 extern "C" int sls_line_eval(sls_path* p, int q, const double* baseline, const double* anchor, const double* lines, int M, double* val,

@@ -551,6 +551,23 @@ void launch_qlognei_select(hipStream_t s, int nsets, int Sp, int q, int S, int R
                            double taum, double* mq, double* zq, double* pmx, double* psm, int* pbad, int* pwin, double* sum, int* wins,
                            long ldw, int* bad);
 
+// ---- kernels_qbald.hip: information gain of a choice query on posterior draws (sls_qbald_*) -------------------------------
+// The slices the S draws are cut into (a fixed slice length, whatever S and the pass are)
+int qbald_slices(int S);
+// The selection of the qEUBO pass under the BTL likelihood of scale tau, two launches.  V[i*Sp + n + s*ldv] = f_s(x_i) on entry,
+// c_{i,s} = d value / d v_{i,s} on exit (rows S <= s < Rp, the lanes n >= nsets and sets with a NaN: exactly 0).
+// pkl[n + k*Sp] = the sum of KL_s over slice k (launch_qbald_finish adds the slices), pbar[n + i*Sp] = the predicted choice
+// probability of option i, wins[n + i*ldw] = the hard wins of launch_qeubo_select without a baseline (wins may be NULL), bad[n] = a
+// NaN among the q S values.
+// Scratch: pp (Sp x q qbald_slices(S) doubles), pbad (Sp x qbald_slices(S) ints), pwin (q times as many ints).
+void launch_qbald_select(hipStream_t s, int nsets, int Sp, int q, int S, int Rp, double* V, long ldv, double tau, double* pp, double* pkl,
+                         int* pbad, int* pwin, double* pbar, int* wins, long ldw, int* bad);
+// val[n] = (sum over the slices k, increasing, of pkl[n + k*Sp]) / S, grad[n + (i*D + d)*ldo] = gpt[i*Sp + n + d*ldg] as it stands,
+// prob[n + i*ldp] = pbar[n + i*Sp] for n < nsets; bad[n] or a NaN among value and gradient: `floor`, the zero gradient and a zero
+// prob column.  val / grad / prob may be NULL.
+void launch_qbald_finish(hipStream_t s, int nsets, int Sp, int q, int D, int S, const double* pkl, const int* bad, const double* gpt,
+                         long ldg, const double* pbar, double floor, double* val, double* grad, long ldo, double* prob, long ldp);
+
 // ---- kernels_line.hip: expected utility of the best slider position (sls_line_*) ------------------------------------------
 // A line is its ends (a, b); position i of q is x_i = u_i a + t_i b with u_i = (q-1-i)/(q-1), t_i = i/(q-1) computed on the device (one
 // division each; two products and one sum per coordinate, never fused).  trial[n + r*ld] is the candidate-major line block: rows

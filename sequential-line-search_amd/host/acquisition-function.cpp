@@ -524,6 +524,36 @@ namespace sequential_line_search
             num_draws, num_local_search_iters, seed, num_frequencies, value);
     }
 
+    // ---- information gain of a choice query on posterior draws (include/sls_hip.h sls_qbald_*; Houlsby et al. 2011) ----
+    std::vector<VectorXd> acquisition_func::FindNextQueryByInformationGainFromStarts(const Regressor& regressor, const int num_options,
+                                                                                     const double btl_scale, const MatrixXd& starts,
+                                                                                     const unsigned           num_draws,
+                                                                                     const unsigned           num_local_search_iters,
+                                                                                     const unsigned long long seed,
+                                                                                     const int num_frequencies, double* value)
+    {
+        RequireDeviceHandleForExpectedUtility(regressor);
+        const PosteriorFunctionSamples draws =
+            regressor.SamplePosteriorFunctions(static_cast<int>(std::max(1u, num_draws)), seed, num_frequencies);
+        return draws.MaximizeChoiceInformationGain(num_options, btl_scale, starts, num_local_search_iters, value);
+    }
+
+    std::vector<VectorXd> acquisition_func::FindNextQueryByInformationGain(const Regressor& regressor, const int num_options,
+                                                                           const double btl_scale, const unsigned num_draws,
+                                                                           const unsigned num_global_search_iters,
+                                                                           const unsigned num_local_search_iters,
+                                                                           const unsigned long long seed, const int num_frequencies,
+                                                                           double* value)
+    {
+        RequireDeviceHandleForExpectedUtility(regressor);
+        if (num_options < 1 || num_options > SLS_QEUBO_MAX_OPTIONS)
+            throw std::invalid_argument("FindNextQueryByInformationGain: 1 .. 16 options");
+        return FindNextQueryByInformationGainFromStarts(
+            regressor, num_options, btl_scale,
+            SeededStarts(num_options * regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed), num_draws,
+            num_local_search_iters, seed, num_frequencies, value);
+    }
+
     // ---- noisy expected improvement of a batch on posterior draws (include/sls_hip.h sls_qnei_*; Letham et al. 2019) ----
     std::vector<VectorXd> acquisition_func::FindNextPointsByNoisyExpectedImprovementFromStarts(
         const Regressor& regressor, const int num_points, const MatrixXd& starts, const unsigned num_draws,

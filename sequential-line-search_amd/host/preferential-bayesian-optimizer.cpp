@@ -155,6 +155,32 @@ namespace sequential_line_search
         for (int i = 0; i < m_num_options; ++i) m_current_options[i] = q[i];
     }
 
+    void PreferentialBayesianOptimizer::DetermineNextQueryByInformationGain(const unsigned long long seed, const int num_draws,
+                                                                            const int num_global_search_iters,
+                                                                            const int num_local_search_iters, const double btl_scale)
+    {
+        if (!m_regressor)
+            throw std::logic_error("PreferentialBayesianOptimizer::DetermineNextQueryByInformationGain called before any feedback");
+        const int num_dims = static_cast<int>(GetMaximizer().size());
+        const int n_global = num_global_search_iters > 0 ? num_global_search_iters : 500 * num_dims;
+        const int n_local  = num_local_search_iters > 0 ? num_local_search_iters : 10 * num_dims;
+        std::vector<VectorXd> q = acquisition_func::FindNextQueryByInformationGain(
+            *m_regressor, m_num_options, btl_scale > 0.0 ? btl_scale : m_btl_scale, std::max(1, num_draws), n_global, n_local, seed);
+        int    best    = 0;
+        double mu_best = m_regressor->PredictMu(q[0]);
+        for (int i = 1; i < m_num_options; ++i)
+        {
+            const double mu = m_regressor->PredictMu(q[i]);
+            if (mu > mu_best)
+            {
+                mu_best = mu;
+                best    = i;
+            }
+        }
+        std::rotate(q.begin(), q.begin() + best, q.begin() + best + 1);   // the best one to the front, the others keep their order
+        for (int i = 0; i < m_num_options; ++i) m_current_options[i] = q[i];
+    }
+
     void PreferentialBayesianOptimizer::DetermineNextQueryByNoisyExpectedImprovement(const unsigned long long seed, const int num_draws,
                                                                                      const int num_global_search_iters,
                                                                                      const int num_local_search_iters)

@@ -233,7 +233,7 @@ namespace sequential_line_search
 
     VectorXd PosteriorFunctionSamples::CalcSetCriterion(const char* who, const std::vector<MatrixXd>& options, const VectorXd* baseline,
                                                         std::vector<MatrixXd>* grads, Eigen::MatrixXi* win_counts,
-                                                        const double* taus) const
+                                                        const double* taus, const double* scale, MatrixXd* probabilities) const
     {
         const std::string name = std::string("PosteriorFunctionSamples::") + who;
         const long        q    = static_cast<long>(options.size());
@@ -251,7 +251,12 @@ namespace sequential_line_search
         if (win_counts) *win_counts = Eigen::MatrixXi::Zero(q, M);
         double* gp = grads ? g.data() : nullptr;
         int*    wp = win_counts ? win_counts->data() : nullptr;
-        if (baseline && taus)
+        if (probabilities) *probabilities = MatrixXd::Zero(q, M);
+        if (scale)
+            device::Check(sls_qbald_eval(m_path, static_cast<int>(q), *scale, sets.data(), static_cast<int>(M), v.data(), gp,
+                                         probabilities ? probabilities->data() : nullptr, wp),
+                          "sls_qbald_eval");
+        else if (baseline && taus)
             device::Check(sls_qlognei_eval(m_path, static_cast<int>(q), baseline->data(), taus[0], taus[1], sets.data(),
                                            static_cast<int>(M), v.data(), gp, wp),
                           "sls_qlognei_eval");
@@ -272,7 +277,8 @@ namespace sequential_line_search
 
     std::vector<VectorXd> PosteriorFunctionSamples::MaximizeSetCriterion(const char* who, int num_options, const VectorXd* baseline,
                                                                          const MatrixXd& starts, unsigned num_local_search_iters,
-                                                                         double* value, const double* taus) const
+                                                                         double* value, const double* taus,
+                                                                         const double* scale) const
     {
         const std::string name = std::string("PosteriorFunctionSamples::") + who;
         if (num_options < 1 || num_options > SLS_QEUBO_MAX_OPTIONS) throw std::invalid_argument(name + ": 1 .. 16 options");
@@ -287,7 +293,11 @@ namespace sequential_line_search
         double    v   = 0.0;
         long      idx = 0;
         const int S = static_cast<int>(starts.cols()), n_local = std::max(1, static_cast<int>(num_local_search_iters));
-        if (baseline && taus)
+        if (scale)
+            device::Check(sls_qbald_maximize(m_path, num_options, *scale, starts.data(), S, n_local, &o, 0, x.data(), &v, &idx, nullptr,
+                                             nullptr),
+                          "sls_qbald_maximize");
+        else if (baseline && taus)
             device::Check(sls_qlognei_maximize(m_path, num_options, baseline->data(), taus[0], taus[1], starts.data(), S, n_local, &o, 0,
                                                x.data(), &v, &idx, nullptr, nullptr),
                           "sls_qlognei_maximize");
@@ -356,6 +366,20 @@ namespace sequential_line_search
         const double taus[2] = {tau_relu, tau_max};
         return MaximizeSetCriterion("MaximizeLogNoisyExpectedImprovement", num_points, &baseline, starts, num_local_search_iters, value,
                                     taus);
+    }
+
+    VectorXd PosteriorFunctionSamples::CalcChoiceInformationGains(const std::vector<MatrixXd>& options, double scale,
+                                                                  std::vector<MatrixXd>* grads, MatrixXd* probabilities,
+                                                                  Eigen::MatrixXi* win_counts) const
+    {
+        return CalcSetCriterion("CalcChoiceInformationGains", options, nullptr, grads, win_counts, nullptr, &scale, probabilities);
+    }
+
+    std::vector<VectorXd> PosteriorFunctionSamples::MaximizeChoiceInformationGain(int num_options, double scale, const MatrixXd& starts,
+                                                                                  unsigned num_local_search_iters, double* value) const
+    {
+        return MaximizeSetCriterion("MaximizeChoiceInformationGain", num_options, nullptr, starts, num_local_search_iters, value, nullptr,
+                                    &scale);
     }
 
     VectorXd PosteriorFunctionSamples::CalcExpectedUtilitiesOfBestSliderPosition(const MatrixXd& ends_a, const MatrixXd& ends_b,
