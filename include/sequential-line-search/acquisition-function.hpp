@@ -159,6 +159,36 @@ namespace sequential_line_search
                                                                        const Eigen::MatrixXd& starts,
                                                                        const unsigned num_local_search_iters, double* value = nullptr);
 
+        /// Joint entropy search (not in the reference; Hvarfner et al. 2022, Tu et al. 2022, include/sls_hip.h sls_jes_*).
+        /// A Monte-Carlo sample of the OPTIMA of the latent function: locations (D x K) and values (K) of the maxima of num_samples
+        /// pathwise posterior draws, found exactly as SampleMaxValues finds its values (same draws, same starts, same clamp: the
+        /// values equal SampleMaxValues with the same arguments) with the locations kept.  num_samples <= 1024 for the calls below.
+        /// A value that the clamp raised to the mean at the best data point keeps the location where the local search ended: such a
+        /// pair (x*, f*) is not a point of its draw (the draw is lower there); JES conditions on it as on any other sampled pair.
+        std::pair<Eigen::MatrixXd, Eigen::VectorXd> SampleOptima(const Regressor& regressor, const unsigned num_samples = 64,
+                                                                 const unsigned num_global_search_iters = 100,
+                                                                 const unsigned num_local_search_iters  = 50,
+                                                                 const unsigned long long seed = 0, const int num_frequencies = 2048);
+        /// alpha(x) of joint entropy search for the columns of Xs on the optima (optima_x D x K, optima_f K) (and its gradient, D x
+        /// M, if grad != nullptr): one device pass.  The future observation's noise variance is max(b, 1e-12) of the regressor;
+        /// star_noise is the variance with which an optimum value counts as observed (negative: the default 1e-8 a).
+        Eigen::VectorXd CalcJointEntropies(const Regressor& regressor, const Eigen::MatrixXd& Xs, const Eigen::MatrixXd& optima_x,
+                                           const Eigen::VectorXd& optima_f, Eigen::MatrixXd* grad = nullptr,
+                                           const double star_noise = -1.0);
+        /// Maximiser of alpha over [0,1]^D: SampleOptima, then one L-BFGS of num_local_search_iters evaluations (the tolerances of
+        /// GetLocalSearchTolerances) from each of num_global_search_iters uniform starts, seeded exactly as
+        /// FindNextPointByMaxValueEntropySearch is.  The same seed gives the same point.  value (may be nullptr) receives alpha there.
+        Eigen::VectorXd FindNextPointByJointEntropySearch(const Regressor& regressor, const unsigned num_optima = 64,
+                                                          const unsigned num_global_search_iters = 100,
+                                                          const unsigned num_local_search_iters  = 50,
+                                                          const unsigned long long seed = 0, const int num_frequencies = 2048,
+                                                          double* value = nullptr);
+        /// The same from an explicit sample of optima and an explicit start set (D x S).
+        Eigen::VectorXd FindNextPointByJointEntropySearchFromStarts(const Regressor& regressor, const Eigen::MatrixXd& optima_x,
+                                                                    const Eigen::VectorXd& optima_f, const Eigen::MatrixXd& starts,
+                                                                    const unsigned num_local_search_iters, double* value = nullptr,
+                                                                    const double star_noise = -1.0);
+
         /// Expected utility of the best option of a query pair (not in the reference; the q = 2 case of qEUBO, Astudillo et al.
         /// 2023, include/sls_hip.h sls_eubo_*): EUBO(x, x') = E[max(f(x), f(x'))] under the joint posterior of the two options,
         /// for the pairs (Xa.col(m), Xb.col(m)) (both D x M), and its gradients in x (grad_a, D x M) and x' (grad_b, D x M) where

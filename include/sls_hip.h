@@ -301,6 +301,73 @@ int sls_mes_maximize(sls_gp* gp, const double* y_star, int K, const double* star
                      const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
                      double* x_stars, double* y_stars);
 
+/* ---- joint entropy search (not in the reference) ----------------------------------------------------------------------
+ * JES (Hvarfner et al., NeurIPS 2022; Tu et al., NeurIPS 2022): the expected reduction of the entropy of the optimum PAIR (x*, f*),
+ * estimated on K sampled optima (x*_k, f*_k) -- x_out / val_out of sls_path_maximize are such a sample.  MES uses the values f*_k alone;
+ * JES conditions the posterior on each pair and asks how much an observation at x shrinks what is left.
+ * mu(x), sigma(x): the tiled evaluation's mean and deviation in the handle's sigma mode (the quantities of max-value entropy search
+ * above).  star_noise >= 0: the variance with which an optimum value counts as observed.  noise_var > 0: the observation-noise variance
+ * of a future measurement (the host layer passes the handle's b).
+ * Per optimum, fixed when the object is created (x*_k clamped into [0,1]^D first, as starts are):
+ *   mu*_k = mu(x*_k)     v_k = max(sigma^2(x*_k), 0) + star_noise     d_k = f*_k - mu*_k     w_k = K_y^-1 k(X, x*_k)
+ * (mu(x*_k), sigma(x*_k) >= 0 are what sls_gp_predict's tiled route returns at x*_k, bit for bit; v_k is formed from that clamped
+ * deviation as sigma sigma + star_noise, the square rounded on its own).
+ * k(X, x*_k) and k(x, x*_k) are formed from the differences of the raw coordinates on EVERY handle (relative error (D + O(1)) eps in the
+ * scaled distance at any length scale), also where the handle's own Gram routes use the norm expansion: on such a handle the
+ * right-hand side of w_k is not the Gram the factor of K_y was built from, entry for entry, but agrees with it within the guard's
+ * bound (1e-11 absolute in the scaled squared distance), which is below what cond(K_y) eps leaves of w_k.
+ * Per candidate and optimum:
+ *   c_k(x) = k(x, x*_k) - k*(x)^T w_k            posterior covariance of f(x) and f(x*_k)
+ *   m_k    = mu + (c_k / v_k) d_k                 s_k^2 = sigma^2 - c_k (c_k / v_k)          (c_k / v_k formed as c_k (1 / v_k))
+ *   gamma_k = (f*_k - m_k) / s_k
+ *   tau(t) = 1 - r(t) (t + r(t)),  r = phi / Phi  variance factor of a unit normal truncated above at t
+ *   q_k    = noise_var + s_k^2 tau(gamma_k)
+ *   alpha(x) = 1/2 log(sigma^2 + noise_var) - (1 / 2K) sum_k log q_k                         (every sum over k in increasing k)
+ * Gradient, with tau'(t) = r [(t + r)(t + 2 r) - 1]:
+ *   grad alpha = A_mu grad mu + A_sigma grad sigma + sum_k h_k grad c_k(x)
+ *   grad c_k(x) = grad_x k(x, x*_k) - sum_i W_ik grad_x k(x, X_i)
+ *   dq_k/dmu = -s_k tau'     dq_k/dsigma = 2 sigma tau - gamma_k sigma tau'
+ *   dq_k/dc  = -(2 c_k / v_k) tau + tau' (gamma_k c_k / v_k - s_k d_k / v_k)
+ *   A_mu = -(1 / 2K) sum_k (dq_k/dmu) / q_k     A_sigma = sigma / (sigma^2 + noise_var) - (1 / 2K) sum_k (dq_k/dsigma) / q_k
+ *   h_k  = -(1 / 2K) (dq_k/dc) / q_k
+ * Rules that make the value a function:
+ *   uninformative optimum: v_k < 1e-20 takes c_k / v_k as 0 (m_k = mu, s_k = sigma, dq_k/dc = 0);
+ *   collapsed conditional: s_k^2 < 1e-20 makes the term log noise_var and adds nothing to A_mu, A_sigma or h_k;
+ *   the guard of expected improvement: sigma < 1e-10, or a NaN in the value or any gradient component: value 0, gradient 0.
+ * Numerics of tau: Phi never appears alone.  t < 0: r = sqrt(2/pi) / erfcx(-t / sqrt 2), w = r + t (LogEI's), c = 1 + t w (MES's),
+ * tau = c - w^2, tau' = r (w^2 - tau); for t < -30 c comes from MES's series in u = 1 / t^2 and w = (c - 1) / t (the direct forms
+ * cancel to ~1 / t^2).  t >= 0: Phi = erfc(-t / sqrt 2) / 2, w = r + t, tau = 1 - r w, tau' = r (w^2 - tau).  tau' is the difference of two
+ * O(1 / t^2) terms that leaves O(1 / t^4): its relative error grows to ~t^6 eps / 2 just above t = -30 (DESIGN.md has the measured figures).
+ * The object is a snapshot, as sls_path is: it keeps W (N x K, padded), the clamped optima, mu*, v, d, f* on the device and records
+ * sls_gp_generation: a call after the handle was refitted, grown (sls_gp_append_point) or switched in sigma mode returns SLS_ERR_INVALID
+ * and uses no stale state.  It must not outlive its handle.  Every call holds the context's lock for its whole length, as the handle's
+ * other large calls do, always takes the tiled evaluation (never the single-launch path of small problems or the evaluation slots) and
+ * forms mu, sigma as the gradient evaluations do, whether or not grad is asked for.
+ * Stages per candidate chunk: the tiled evaluation (mu, sigma, grad mu, grad sigma); k(x, x*_k) from the raw coordinate differences and
+ * c = k(x, x*) - K* W on the tile GEMM (fixed k order); the combiner, one lane per candidate; for the gradient U = -H W^T on the tile
+ * GEMM, P = C* o U, the P-pass of grad_gemm (or the raw-difference contraction beyond the Gram guard), the optima term and the finish.
+ * A point's bits depend on neither its column, the other points of the call, the candidate chunk nor active-set compaction.
+ * sls_prof_get names: "jes_setup" (create: k(X, X*), the solve, mu*, v), "jes_cov" (the candidate-optima stage and K* W), "jes" (the
+ * combiner and the finish: two entries per chunk), "jes_agg" (U = -H W^T), "jes_grad" (P = C* o U and the optima term),
+ * "jes_grad_gemm" (the second gradient contraction, P X~ or its raw-difference form); the tiled evaluation counts under its own names. */
+typedef struct sls_jes sls_jes;
+#define SLS_JES_MAX_OPTIMA 1024
+/* x_star D x K, f_star K, 1 <= K <= SLS_JES_MAX_OPTIMA, all finite; star_noise >= 0 and finite: else SLS_ERR_INVALID. */
+int sls_jes_create(sls_gp* gp, const double* x_star, const double* f_star, int K, double star_noise, sls_jes** out);
+int sls_jes_destroy(sls_jes* j);
+/* mu_star[k] = mu*_k, var_star[k] = v_k; either may be NULL. */
+int sls_jes_optima(sls_jes* j, double* mu_star, double* var_star);
+/* tau[i] = tau(t[i]), dtau[i] = tau'(t[i]); either out pointer may be NULL; n >= 0 (n < 0: SLS_ERR_INVALID).  A test hook, as
+ * sls_mes_terms is. */
+int sls_jes_terms(sls_ctx* ctx, const double* t, long n, double* tau, double* dtau);
+/* alpha at the M points Xs (D x M): val (M), grad (D x M, may be NULL), cov (M x K column-major, cov[m + k*M] = c_k(x_m), may be NULL).
+ * noise_var > 0 and finite, val != NULL when M > 0: else SLS_ERR_INVALID; M = 0 is a no-op. */
+int sls_jes_eval(sls_jes* j, double noise_var, const double* Xs, int M, double* val, double* grad, double* cov);
+/* sls_acq_maximize with alpha as the objective: same outputs, same semantics of idx_out / x_stars / y_stars; the statistics go to
+ * sls_acq_last_stats of the handle. */
+int sls_jes_maximize(sls_jes* j, double noise_var, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts,
+                     long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars, double* y_stars);
+
 /* ---- log expected improvement (not in the reference) -------------------------------------------------------------------
  * acq_type SLS_ACQ_LOG_EXPECTED_IMPROVEMENT, accepted wherever an acq_type is taken (sls_acq_eval, sls_acq_maximize,
  * sls_acq_maximize_dev, sls_acq_eval_pair, sls_acq_maximize_pair, sls_multi_acq_maximize); every returned value (val, val_out,

@@ -199,6 +199,26 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
           "regressor"_a, "num_max_value_samples"_a = 64, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50,
           "seed"_a = 0ULL, "num_frequencies"_a = 2048);
 
+    // joint entropy search (acquisition-function.hpp): the sampled optima (locations D x K, values K), alpha on them at the columns
+    // of points, and the maximiser with its value
+    m.def("sample_optima", &acquisition_func::SampleOptima, "regressor"_a, "num_samples"_a = 64, "num_global_search_iters"_a = 100,
+          "num_local_search_iters"_a = 50, "seed"_a = 0ULL, "num_frequencies"_a = 2048);
+    m.def("calc_joint_entropies",
+          [](const Regressor& r, const MatrixXd& Xs, const MatrixXd& optima_x, const VectorXd& optima_f, double star_noise) {
+              return acquisition_func::CalcJointEntropies(r, Xs, optima_x, optima_f, nullptr, star_noise);
+          },
+          "regressor"_a, "points"_a, "optima_x"_a, "optima_f"_a, "star_noise"_a = -1.0);
+    m.def("find_next_point_by_joint_entropy_search",
+          [](const Regressor& r, unsigned num_optima, unsigned num_global_search_iters, unsigned num_local_search_iters,
+             unsigned long long seed, int num_frequencies) {
+              double         value = 0.0;
+              const VectorXd x     = acquisition_func::FindNextPointByJointEntropySearch(r, num_optima, num_global_search_iters,
+                                                                                     num_local_search_iters, seed, num_frequencies, &value);
+              return std::make_pair(x, value);
+          },
+          "regressor"_a, "num_optima"_a = 64, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50, "seed"_a = 0ULL,
+          "num_frequencies"_a = 2048);
+
     // expected utility of the best option of a query pair (acquisition-function.hpp): values for the pairs (points_a.col(m),
     // points_b.col(m)), and the maximising pair with its value: (x, x', value)
     m.def("calc_expected_utilities_of_best_option",

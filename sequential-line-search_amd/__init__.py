@@ -110,6 +110,7 @@ EXPORTS = [
     "sls_qlognei_terms", "sls_qlognei_eval", "sls_qlognei_maximize", "sls_qbald_eval", "sls_qbald_maximize",
     "sls_acq_eval_sub", "sls_acq_maximize_sub", "sls_mes_eval_sub", "sls_mes_maximize_sub", "sls_path_eval_sub", "sls_path_maximize_sub",
     "sls_nll_loo", "sls_gp_loo_grad", "sls_gp_loo",
+    "sls_jes_create", "sls_jes_destroy", "sls_jes_optima", "sls_jes_terms", "sls_jes_eval", "sls_jes_maximize",
 ]
 
 
@@ -194,6 +195,14 @@ class Context:
         g, dg = np.empty(t.size), np.empty(t.size)
         _ck(lib().sls_mes_terms(self.h, _p(t), C.c_long(t.size), _p(g), _p(dg)))
         return g, dg
+
+    def jes_terms(self, t):
+        """(tau(t), tau'(t)) of joint entropy search, the variance factor of a unit normal truncated above at t and its derivative, for
+        an array of t (sls_jes_terms)."""
+        t = np.ascontiguousarray(np.asarray(t, dtype=np.float64).ravel())
+        tau, dtau = np.empty(t.size), np.empty(t.size)
+        _ck(lib().sls_jes_terms(self.h, _p(t), C.c_long(t.size), _p(tau), _p(dtau)))
+        return tau, dtau
 
     def logei_terms(self, u):
         """(log h(u), Phi/h, phi/h) of log expected improvement, h = phi + u Phi, for an array of u (sls_logei_terms)."""
@@ -395,6 +404,10 @@ class GP:
                                    C.byref(idx), _p(xs) if want_all else None, _p(ys) if want_all else None))
         return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
 
+    def jes_create(self, x_star, f_star, star_noise=0.0):
+        """The snapshot of K sampled optima (x_star (D, K), f_star (K,)) joint entropy search conditions on (sls_jes_create)."""
+        return JesOptima(self, x_star, f_star, star_noise)
+
     def eubo_eval(self, pairs, want_grad=True):
         """Expected utility of the best option E[max(f(x), f(x'))] at the columns of pairs (2D x M: rows 0..D-1 = x, D..2D-1 = x'),
         sls_eubo_eval; the gradient is 2D x M in the same row order."""
@@ -476,6 +489,64 @@ class GP:
 
     def refit_dev(self, X_dev_ptr, y_dev_ptr):
         _ck(lib().sls_gp_refit_dev(self.h, C.c_void_p(X_dev_ptr), C.c_void_p(y_dev_ptr)))
+
+
+JES_MAX_OPTIMA = 1024     # SLS_JES_MAX_OPTIMA
+
+
+class JesOptima:
+    """K sampled optima (x*_k, f*_k) of a fitted GP handle, conditioned on for joint entropy search (sls_jes_*).  A snapshot: after
+    the handle is refitted, grown or switched in sigma mode every call is refused; it must be closed before its handle."""
+
+    def __init__(self, gp, x_star, f_star, star_noise=0.0):
+        x_star, f_star = _f(x_star), _f(f_star).ravel()
+        if x_star.ndim != 2 or x_star.shape != (gp.D, f_star.size):
+            raise SlsError(f"JesOptima: x_star must be D x K = {gp.D} x {f_star.size}, got {x_star.shape}")
+        self.gp, self.D, self.K = gp, gp.D, f_star.size
+        self.h = C.c_void_p()
+        _ck(lib().sls_jes_create(gp.h, _p(x_star), _p(f_star), self.K, C.c_double(star_noise), C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().sls_jes_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def optima(self):
+        """(mu*_k, v_k): the posterior mean at the optima and the variance they are conditioned with."""
+        mu, v = np.empty(self.K), np.empty(self.K)
+        _ck(lib().sls_jes_optima(self.h, _p(mu), _p(v)))
+        return mu, v
+
+    def eval(self, Xs, noise_var, want_grad=True, want_cov=False):
+        """alpha at the columns of Xs: values (M,), then with want_grad the gradient (D, M), then with want_cov the posterior
+        covariances c_k(x_m) (M, K)."""
+        Xs = _f(Xs)
+        M = Xs.shape[1]
+        val = np.empty(M)
+        grad = np.empty((self.D, M), order="F") if want_grad else None
+        cov = np.empty((M, self.K), order="F") if want_cov else None
+        _ck(lib().sls_jes_eval(self.h, C.c_double(noise_var), _p(Xs), M, _p(val), _p(grad) if want_grad else None,
+                               _p(cov) if want_cov else None))
+        out = (val,) + ((grad,) if want_grad else ()) + ((cov,) if want_cov else ())
+        return out if len(out) > 1 else val
+
+    def maximize(self, starts, n_local, noise_var, offset=0, want_all=True, opts=None):
+        """acq_maximize with joint entropy search as the objective (sls_jes_maximize)."""
+        starts = _f(starts)
+        S = starts.shape[1]
+        x, val, idx = np.empty(self.D), C.c_double(), C.c_long()
+        xs = np.empty((self.D, S), order="F") if want_all else None
+        ys = np.empty(S) if want_all else None
+        _ck(lib().sls_jes_maximize(self.h, C.c_double(noise_var), _p(starts), S, int(n_local),
+                                   C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val), C.byref(idx),
+                                   _p(xs) if want_all else None, _p(ys) if want_all else None))
+        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
 
 
 QEUBO_MAX_OPTIONS = 16   # SLS_QEUBO_MAX_OPTIONS

@@ -1400,6 +1400,234 @@ extern "C" int sls_mes_maximize(sls_gp* g, const double* y_star, int K, const do
     SLS_CATCH
 }
 
+// ---- joint entropy search (include/sls_hip.h) ------------------------------------------------------------------------------
+// The snapshot of the conditioned optima and the blocks of a candidate chunk (grown on demand, kept with the object so that the rounds
+// of a maximisation allocate nothing).
+struct sls_jes {
+    sls_gp* gp = nullptr;
+    sls_ctx* ctx = nullptr;
+    long generation = 0;
+    int D = 0, K = 0, Kp = 0, Np = 0;
+    // W [i + k*Np] (Np x Kp, 0 for k >= K and i >= N), xs [d + k*D] (raw, clamped), K doubles each of mu*, sigma*, v, d, 1 / v, f*
+    DBuf W, xs, mu_star, sg_star, v, dd, inv_v, f_star;
+    // per chunk, candidate-major with the chunk's leading dimension: cov / cx / H (Sp x Kp), A_mu, A_sigma, csum (Sp), Go (Sp x D)
+    DBuf cov, cx, H, a_mu, a_sg, csum, Go;
+};
+
+// alpha (+ gradient, + the covariances) at S candidate-major points xr[n + d*ldr]; val[n], grad[n + d*ldo] (may be nullptr),
+// cov_out[n + k*ldc] (may be nullptr).  eval_candidates reuses K*, C* and P per chunk, and this pass needs the chunk's K* and C* after
+// it: it drives the tiled evaluation ONE chunk at a time.  A candidate's bits do not depend on the chunk it falls into.
+static void jes_eval_device(sls_jes* j, double noise_var, const double* xr, long ldr, int S, double* val, double* grad, long ldo,
+                            double* cov_out, long ldc) {
+    sls_gp* g = j->gp;
+    sls_ctx* c = g->ctx;
+    const int D = g->D, Np = g->Np, N = g->N, K = j->K, Kp = j->Kp;
+    const KernelSpec ks{g->kernel, g->a};
+    // mu, sigma and their gradients always (sigma as the gradient evaluations form it, whether or not grad is asked for)
+    g->pair_mu.ensure(ldo); g->pair_sg.ensure(ldo);
+    g->pair_dmu.ensure((size_t)ldo * D); g->pair_dsg.ensure((size_t)ldo * D);
+    const int chunk_max = std::min(round_up(S, 128), c->cand_chunk);
+    const size_t blk = (size_t)chunk_max * Kp;
+    j->cov.ensure(blk);
+    if (grad) {
+        j->cx.ensure(blk); j->H.ensure(blk);
+        j->a_mu.ensure(chunk_max); j->a_sg.ensure(chunk_max); j->csum.ensure(chunk_max);
+        j->Go.ensure((size_t)chunk_max * D);
+    }
+    for (int s0 = 0; s0 < S; s0 += chunk_max) {
+        const int sc = std::min(chunk_max, S - s0), Sp = round_up(sc, 128);
+        const long ldk = Sp;
+        EvalOut eo;
+        eo.ldo = ldo;
+        eo.mu = g->pair_mu.p + s0; eo.sigma = g->pair_sg.p + s0; eo.dmu = g->pair_dmu.p + s0; eo.dsigma = g->pair_dsg.p + s0;
+        eval_candidates(g, xr + s0, ldr, sc, eo);   // one chunk: K* (g->Ks), C*, X~* (g->XsT) of these sc candidates stay behind it
+        const double* Cs = (g->kernel == SLS_KERNEL_ARD_MATERN52) ? g->Cs.p : g->Ks.p;
+        {
+            ProfScope ps(c, "jes_cov");
+            launch_jes_cross(c->stream, xr + s0, 1, ldr, sc, Sp, j->xs.p, D, K, Kp, g->inv_ell.p, ks, j->cov.p, grad ? j->cx.p : nullptr, ldk);
+            // c = k(x, x*) - K* W: accumulated onto the prior term on the tile GEMM, k = the training points in increasing order
+            launch_gemm_plain(c->stream, g->Ks.p, ldk, false, j->W.p, Np, true, j->cov.p, ldk, Sp / 128, Kp / 128, Np, -1.0, 1.0);
+        }
+        if (cov_out)
+            SLS_HIP(hipMemcpy2DAsync(cov_out + s0, (size_t)ldc * 8, j->cov.p, (size_t)ldk * 8, (size_t)sc * 8, K, hipMemcpyDeviceToDevice,
+                                     c->stream));
+        {
+            ProfScope ps(c, "jes");
+            if (grad && Kp > K) SLS_HIP(hipMemsetAsync(j->H.p + (size_t)K * ldk, 0, (size_t)(Kp - K) * ldk * 8, c->stream));
+            launch_jes_combine(c->stream, sc, Sp, ldk, eo.mu, eo.sigma, j->cov.p, j->f_star.p, j->dd.p, j->inv_v.p, K, noise_var, val + s0,
+                               grad ? j->a_mu.p : nullptr, grad ? j->a_sg.p : nullptr, grad ? j->H.p : nullptr);
+        }
+        if (grad) {
+            {
+                // U[m + i*ldk] = -sum_k H[m + k*ldk] W[i + k*Np] into P's block: one weight vector W h(x) per candidate
+                ProfScope ps(c, "jes_agg");
+                launch_gemm_plain(c->stream, j->H.p, ldk, false, j->W.p, Np, false, g->P.p, ldk, Sp / 128, Np / 128, Kp, -1.0, 0.0);
+            }
+            {
+                ProfScope ps(c, "jes_grad");
+                launch_jes_weight(c->stream, Sp, Np, ldk, Cs, g->P.p, j->csum.p);
+                launch_jes_optima_grad(c->stream, xr + s0, 1, ldr, sc, j->xs.p, D, K, g->inv_ell.p, j->H.p, j->cx.p, ldk, j->Go.p);
+            }
+            {
+                ProfScope ps(c, "jes_grad_gemm");
+                if (g->gram_direct)
+                    launch_grad_direct(c->stream, g->P.p, nullptr, ldk, Sp, xr + s0, 1, ldr, sc, g->X.p, D, g->inv_ell.p, N, nullptr, g->Gs.p,
+                                       nullptr);
+                else
+                    launch_grad_gemm(c->stream, g->P.p, nullptr, ldk, Sp, g->XT.p, nullptr, Np, Np, D <= 64 ? -g->Dcols : g->Dcols, g->Gs.p,
+                                     nullptr, grad_split_scratch(g->Gpart, D, Sp), 1);
+            }
+        }
+        ProfScope ps(c, "jes");
+        launch_jes_finish(c->stream, sc, D, ldo, ldk, eo.sigma, eo.dmu, eo.dsigma, j->a_mu.p, j->a_sg.p, g->Gs.p, j->Go.p,
+                          g->gram_direct ? nullptr : g->XsT.p, j->csum.p, g->inv_ell.p, val + s0, grad ? grad + s0 : nullptr);
+    }
+}
+
+// the object is what its handle still stands for
+static void jes_check(const char* who, sls_jes* j) {
+    SLS_REQUIRE(j->gp->generation == j->generation,
+                "%s: the GP handle was refitted, grown or switched in sigma mode since sls_jes_create (generation %ld, now %ld): create a new object", who,
+                j->generation, j->gp->generation);
+}
+static void jes_check_noise(const char* who, double noise_var) {
+    SLS_REQUIRE(std::isfinite(noise_var) && noise_var > 0.0, "%s: noise_var = %g (finite, > 0)", who, noise_var);
+}
+
+extern "C" int sls_jes_create(sls_gp* g, const double* x_star, const double* f_star, int K, double star_noise, sls_jes** out) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g != nullptr, "sls_jes_create: gp is NULL");
+    SLS_REQUIRE(out != nullptr, "sls_jes_create: out is NULL");
+    *out = nullptr;
+    SLS_REQUIRE(K >= 1 && K <= SLS_JES_MAX_OPTIMA, "sls_jes_create: K = %d (1 .. %d)", K, SLS_JES_MAX_OPTIMA);
+    SLS_REQUIRE(x_star != nullptr, "sls_jes_create: x_star is NULL");
+    SLS_REQUIRE(f_star != nullptr, "sls_jes_create: f_star is NULL");
+    SLS_REQUIRE(std::isfinite(star_noise) && star_noise >= 0.0, "sls_jes_create: star_noise = %g (finite, >= 0)", star_noise);
+    const int D = g->D, N = g->N, Np = g->Np, Kp = round_up(K, 128);
+    for (int k = 0; k < K; ++k) SLS_REQUIRE(std::isfinite(f_star[k]), "sls_jes_create: f_star[%d] is not finite", k);
+    std::vector<double> xh((size_t)D * K);
+    for (size_t i = 0; i < xh.size(); ++i) {
+        SLS_REQUIRE(std::isfinite(x_star[i]), "sls_jes_create: x_star[%d] of optimum %d is not finite", (int)(i % D), (int)(i / D));
+        xh[i] = std::min(1.0, std::max(0.0, x_star[i]));
+    }
+    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
+    sls_ctx* c = g->ctx;
+    std::unique_ptr<sls_jes> j(new sls_jes);
+    j->gp = g; j->ctx = c; j->generation = g->generation;
+    j->D = D; j->K = K; j->Kp = Kp; j->Np = Np;
+    j->W.ensure((size_t)Np * Kp);
+    j->xs.ensure((size_t)D * K);
+    j->mu_star.ensure(Kp); j->sg_star.ensure(Kp); j->v.ensure(K); j->dd.ensure(K); j->inv_v.ensure(K); j->f_star.ensure(K);
+    h2d(c, j->xs.p, xh.data(), xh.size());
+    h2d(c, j->f_star.p, f_star, (size_t)K);
+    {
+        ProfScope ps(c, "jes_setup");
+        // K(X, X*) [i + k*Np] from the raw differences (rows i >= N and columns k >= K exactly 0), then W = K_y^-1 K(X, X*) on the factor
+        launch_jes_cross(c->stream, g->X.p, D, 1, N, Np, j->xs.p, D, K, Kp, g->inv_ell.p, KernelSpec{g->kernel, g->a}, j->W.p, nullptr, Np);
+        launch_potrs(c->stream, g->L.p, g->Linv.p, Np, j->W.p, Kp);
+    }
+    // mu*, sigma* through the tiled evaluation, exactly as sls_gp_predict's tiled route forms them (mean and deviation, no gradient)
+    {
+        EvalOut eo;
+        eo.ldo = Kp;
+        eo.mu = j->mu_star.p; eo.sigma = j->sg_star.p;
+        eval_candidates(g, j->xs.p, 0, K, eo, true);
+    }
+    {
+        ProfScope ps(c, "jes_setup");
+        launch_jes_optima(c->stream, K, j->mu_star.p, j->sg_star.p, j->f_star.p, star_noise, j->v.p, j->dd.p, j->inv_v.p);
+    }
+    sync(c);   // the staging vectors go out of scope; nothing but the error state comes back
+    slsk::ctx_retain(c);
+    *out = j.release();
+    SLS_CATCH
+}
+
+extern "C" int sls_jes_destroy(sls_jes* j) {
+    if (!j) return SLS_OK;
+    slsk::note_entry();
+    destroy_handle(j);
+    return SLS_OK;
+}
+
+extern "C" int sls_jes_optima(sls_jes* j, double* mu_star, double* var_star) {
+    SLS_TRY
+    SLS_REQUIRE(j != nullptr, "sls_jes_optima: j is NULL");
+    CtxCall call_(j);
+    jes_check("sls_jes_optima", j);
+    if (mu_star) d2h(j->ctx, mu_star, j->mu_star.p, (size_t)j->K);
+    if (var_star) d2h(j->ctx, var_star, j->v.p, (size_t)j->K);
+    sync(j->ctx);
+    SLS_CATCH
+}
+
+extern "C" int sls_jes_terms(sls_ctx* ctx, const double* t, long n, double* tau, double* dtau) {
+    double* const host[2] = {tau, dtau};
+    return scalar_terms("sls_jes_terms", ctx, t, n, 2, host,
+                        [&](const double* in, long m, double* const* out) { launch_jes_terms(ctx->stream, in, m, out[0], out[1]); });
+}
+
+extern "C" int sls_jes_eval(sls_jes* j, double noise_var, const double* Xs, int M, double* val, double* grad, double* cov) {
+    SLS_TRY
+    SLS_REQUIRE(j != nullptr, "sls_jes_eval: j is NULL");
+    CtxCall call_(j);
+    SLS_REQUIRE(M >= 0, "sls_jes_eval: M = %d", M);
+    jes_check_noise("sls_jes_eval", noise_var);
+    jes_check("sls_jes_eval", j);
+    if (M == 0) return SLS_OK;
+    SLS_REQUIRE(Xs != nullptr, "sls_jes_eval: Xs is NULL");
+    SLS_REQUIRE(val != nullptr, "sls_jes_eval: val is NULL");
+    sls_gp* g = j->gp;
+    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
+    const int Mp = round_up(M, 128), D = g->D, K = j->K;
+    upload_candidates(g, Xs, D, M, Mp);
+    EvalOut want;
+    want.val = val; want.grad = grad;
+    g->outv.ensure(eval_block_doubles(want, D, Mp));
+    const EvalOut o = eval_block(want, g->outv.p, D, Mp);
+    DBuf covd;
+    if (cov) covd.ensure((size_t)Mp * K);
+    jes_eval_device(j, noise_var, g->raw.p, Mp, M, o.val, o.grad, Mp, cov ? covd.p : nullptr, Mp);
+    std::vector<double> covh;
+    if (cov) {
+        covh.resize((size_t)Mp * K);
+        d2h(g->ctx, covh.data(), covd.p, covh.size());
+    }
+    download_block(g, want, g->outv.p, D, M, Mp);   // the call's one synchronisation
+    if (cov)
+        for (int k = 0; k < K; ++k) std::copy(covh.begin() + (size_t)k * Mp, covh.begin() + (size_t)k * Mp + M, cov + (size_t)k * M);
+    SLS_CATCH
+}
+
+extern "C" int sls_jes_maximize(sls_jes* j, double noise_var, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts,
+                                long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars,
+                                double* y_stars) {
+    SLS_TRY
+    SLS_REQUIRE(j != nullptr, "sls_jes_maximize: j is NULL");
+    CtxCall call_(j);
+    SLS_REQUIRE(starts != nullptr, "sls_jes_maximize: starts is NULL");
+    jes_check_noise("sls_jes_maximize", noise_var);
+    jes_check("sls_jes_maximize", j);
+    sls_gp* g = j->gp;
+    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
+    sls_ctx* c = g->ctx;
+    MultistartRun r = maximize_begin("sls_jes_maximize", g, g->lb, opts, S, n_local, g->D);
+    DBuf sd;
+    sd.ensure((size_t)g->D * S);
+    h2d(c, sd.p, starts, (size_t)g->D * S);
+    LockstepStats ls;
+    lockstep_rounds(c, r.st, g->lb, sd.p, S, n_local,
+                    [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
+                        jes_eval_device(j, noise_var, trial, ld, nlive, val, grad, ld, nullptr, 0);
+                    },
+                    &ls);
+    std::vector<double> pageable;
+    maximize_finish(c, r, ls, BestBlock{g->sum.dev + 8, g->sum.host + 8, false}, staged_fetch(g, pageable), start_index_offset, x_out,
+                    val_out, idx_out, x_stars, y_stars);
+    SLS_CATCH
+}
+
 // ---- maximisation over affine subspaces (include/sls_hip.h) --------------------------------------------------------------
 // eval_acq at x = c + A z: expand the candidate-major variables z[n + j*ld] (n < count; column n is start live[n], nullptr: identity)
 // into the handle's block of points, the unchanged evaluation there, then the fold of its gradient onto z.  Always the tiled evaluation.

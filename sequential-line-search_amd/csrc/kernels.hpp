@@ -282,6 +282,34 @@ void launch_logei_combine(hipStream_t s, int S, int D, long ld, const double* mu
 // log_h[i], b1[i], b2[i] of u[i], i < n; any output may be NULL
 void launch_logei_terms(hipStream_t s, const double* u, long n, double* log_h, double* b1, double* b2);
 
+// ---- kernels_jes.hip: joint entropy search on the optima of posterior draws (sls_jes_*) ----------------------------------
+// tau[i] = 1 - r (t + r), dtau[i] = r ((t + r)(t + 2 r) - 1), r = phi / Phi, of t[i], i < n; either output may be NULL
+void launch_jes_terms(hipStream_t s, const double* t, long n, double* tau, double* dtau);
+// v[k] = sg_star[k]^2 + star_noise, dd[k] = f_star[k] - mu_star[k], inv_v[k] = 1 / v[k] (0 where v[k] < 1e-20), k < K
+void launch_jes_optima(hipStream_t s, int K, const double* mu_star, const double* sg_star, const double* f_star, double star_noise,
+                       double* v, double* dd, double* inv_v);
+// kx[m + k*ld] = k(x_m, x*_k), cx[m + k*ld] = its derivative weight (cx may be NULL) from the raw coordinate differences, for m < M,
+// k < K; 0 for m in [M, Mp), k in [K, Kp).  x[m*sn + d*sd] (device), xs[d + k*D] (device), Kp a multiple of 4.
+void launch_jes_cross(hipStream_t s, const double* x, long sn, long sd, int M, int Mp, const double* xs, int D, int K, int Kp,
+                      const double* inv_ell, KernelSpec ks, double* kx, double* cx, long ld);
+// The combiner (include/sls_hip.h "joint entropy search"): one lane per candidate, every sum over k in increasing k.  cov / H are
+// candidate-major [m + k*ld]; val[n], a_mu[n], a_sg[n] for n < S (unguarded: launch_jes_finish applies the guard); H[n + k*ld] for
+// n < Sp, k < K (0 for n >= S).  a_mu, a_sg and H may be NULL together (value only).
+void launch_jes_combine(hipStream_t s, int S, int Sp, long ld, const double* mu, const double* sigma, const double* cov,
+                        const double* f_star, const double* dd, const double* inv_v, int K, double noise_var, double* val, double* a_mu,
+                        double* a_sg, double* H);
+// U[m + i*ld] <- Cs[m + i*ld] U[m + i*ld] and csum[m] = their sum over i < Np as four fixed quarters of i (((q0 + q1) + q2) + q3),
+// each from zero in increasing i (path_data_kernel's order), m < Sp; Np a multiple of 128
+void launch_jes_weight(hipStream_t s, int Sp, int Np, long ld, const double* Cs, double* U, double* csum);
+// Go[m + d*ld] = (1 / l_d) sum_k H[m + k*ld] cx[m + k*ld] (x*_kd - x_md) in increasing k < K, m < M, d < D
+void launch_jes_optima_grad(hipStream_t s, const double* x, long sn, long sd, int M, const double* xs, int D, int K,
+                            const double* inv_ell, const double* H, const double* cx, long ld, double* Go);
+// grad[n + d*ldo] = a_mu dmu + a_sg dsigma + (Gd[n + d*ldk] - XsT[n + d*ldk] csum[n] + Go[n + d*ldk]) / l_d (XsT == nullptr: no csum
+// term) and the guard (sigma < 1e-10 or a NaN in val or the gradient: val 0, gradient 0), n < S.  grad == nullptr: the guard on val.
+void launch_jes_finish(hipStream_t s, int S, int D, long ldo, long ldk, const double* sigma, const double* dmu, const double* dsigma,
+                       const double* a_mu, const double* a_sg, const double* Gd, const double* Go, const double* XsT, const double* csum,
+                       const double* inv_ell, double* val, double* grad);
+
 // ---- kernels_eubo.hip: expected utility of the best option of a query pair (sls_eubo_*) ----------------------------------
 // Kd[n + i*ldk] = Ka[n + i*ldk] - Kb[n + i*ldk] over the whole padded block (ldk x Np doubles, both multiples of 128)
 void launch_pair_diff(hipStream_t s, const double* Ka, const double* Kb, long ldk, int Np, double* Kd);

@@ -368,17 +368,8 @@ namespace sequential_line_search
                                                const unsigned num_global_search_iters, const unsigned num_local_search_iters,
                                                const unsigned long long seed, const int num_frequencies)
     {
-        if (num_samples == 0) return VectorXd();
-        sls_gp*        h = RequireHandle(regressor);
-        const unsigned S = std::max(1u, num_global_search_iters);
-        const PosteriorFunctionSamples draws = regressor.SamplePosteriorFunctions(static_cast<int>(num_samples), seed, num_frequencies);
-        VectorXd                       values;
-        draws.Maximize(SeededStarts(regressor.GetNumDims(), static_cast<long>(num_samples) * S, seed), num_local_search_iters, &values);
-        // the maximum of a function is at least its value at the best data point (a local search may have ended below it)
-        double mu_best = 0.0;
-        device::Check(sls_gp_get_summary(h, nullptr, &mu_best, nullptr), "sls_gp_get_summary");
-        for (long k = 0; k < values.size(); ++k) values(k) = std::max(values(k), mu_best);
-        return values;
+        // the values of the sampled optima (draws, starts and the clamp at the mean at the best data point are SampleOptima's)
+        return SampleOptima(regressor, num_samples, num_global_search_iters, num_local_search_iters, seed, num_frequencies).second;
     }
 
     VectorXd acquisition_func::CalcMaxValueEntropies(const Regressor& regressor, const MatrixXd& Xs, const VectorXd& max_values,
@@ -419,6 +410,99 @@ namespace sequential_line_search
             SampleMaxValues(regressor, num_max_value_samples, num_global_search_iters, num_local_search_iters, seed, num_frequencies);
         return FindNextPointByMaxValueEntropySearchFromStarts(
             regressor, max_values, SeededStarts(regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed),
+            num_local_search_iters, value);
+    }
+
+    // ---- joint entropy search (include/sls_hip.h sls_jes_*; Hvarfner et al. 2022, Tu et al. 2022) ----
+    namespace
+    {
+        // the snapshot of the conditioned optima for the length of one call
+        struct JesObject
+        {
+            sls_jes* h = nullptr;
+            JesObject(const Regressor& r, const MatrixXd& optima_x, const VectorXd& optima_f, double star_noise)
+            {
+                if (optima_x.rows() != static_cast<long>(r.GetNumDims()) || optima_x.cols() != optima_f.size())
+                    throw std::invalid_argument("acquisition_func: optima_x must be D x K and optima_f K long");
+                device::Check(sls_jes_create(RequireHandle(r), optima_x.data(), optima_f.data(), static_cast<int>(optima_f.size()),
+                                             star_noise, &h),
+                              "sls_jes_create");
+            }
+            ~JesObject() { sls_jes_destroy(h); }
+            JesObject(const JesObject&)            = delete;
+            JesObject& operator=(const JesObject&) = delete;
+        };
+        // a < 0 as the argument: the default 1e-8 a
+        double StarNoise(const Regressor& r, double star_noise) { return star_noise < 0.0 ? 1e-8 * r.GetKernelHyperparams()(0) : star_noise; }
+        double FutureNoise(const Regressor& r) { return std::max(r.GetNoiseHyperparam(), 1e-12); }
+    }   // namespace
+
+    std::pair<MatrixXd, VectorXd> acquisition_func::SampleOptima(const Regressor& regressor, const unsigned num_samples,
+                                                                 const unsigned num_global_search_iters,
+                                                                 const unsigned num_local_search_iters, const unsigned long long seed,
+                                                                 const int num_frequencies)
+    {
+        const unsigned D = regressor.GetNumDims();
+        if (num_samples == 0) return {MatrixXd(D, 0), VectorXd()};
+        sls_gp*        h = RequireHandle(regressor);
+        const unsigned S = std::max(1u, num_global_search_iters);
+        const PosteriorFunctionSamples draws = regressor.SamplePosteriorFunctions(static_cast<int>(num_samples), seed, num_frequencies);
+        VectorXd                       values;
+        const std::vector<VectorXd>    xs =
+            draws.Maximize(SeededStarts(D, static_cast<long>(num_samples) * S, seed), num_local_search_iters, &values);
+        // the maximum of a function is at least its value at the best data point (a local search may have ended below it)
+        double mu_best = 0.0;
+        device::Check(sls_gp_get_summary(h, nullptr, &mu_best, nullptr), "sls_gp_get_summary");
+        MatrixXd X(D, static_cast<long>(xs.size()));
+        for (long k = 0; k < values.size(); ++k)
+        {
+            X.col(k)  = xs[static_cast<size_t>(k)];
+            values(k) = std::max(values(k), mu_best);
+        }
+        return {X, values};
+    }
+
+    VectorXd acquisition_func::CalcJointEntropies(const Regressor& regressor, const MatrixXd& Xs, const MatrixXd& optima_x,
+                                                  const VectorXd& optima_f, MatrixXd* grad, const double star_noise)
+    {
+        const long M = Xs.cols();
+        VectorXd   v = VectorXd::Zero(M);
+        if (grad) *grad = MatrixXd::Zero(Xs.rows(), M);
+        if (regressor.GetSmallY().rows() == 0 || M == 0) return v;
+        const JesObject j(regressor, optima_x, optima_f, StarNoise(regressor, star_noise));
+        device::Check(sls_jes_eval(j.h, FutureNoise(regressor), Xs.data(), static_cast<int>(M), v.data(), grad ? grad->data() : nullptr,
+                                   nullptr),
+                      "sls_jes_eval");
+        return v;
+    }
+
+    VectorXd acquisition_func::FindNextPointByJointEntropySearchFromStarts(const Regressor& regressor, const MatrixXd& optima_x,
+                                                                           const VectorXd& optima_f, const MatrixXd& starts,
+                                                                           const unsigned num_local_search_iters, double* value,
+                                                                           const double star_noise)
+    {
+        VectorXd             x(starts.rows());
+        double               v     = 0.0;
+        long                 idx   = 0;
+        const sls_lbfgs_opts lopts = LocalSearchOpts();   // GetLocalSearchTolerances
+        const JesObject      j(regressor, optima_x, optima_f, StarNoise(regressor, star_noise));
+        device::Check(sls_jes_maximize(j.h, FutureNoise(regressor), starts.data(), static_cast<int>(starts.cols()),
+                                       std::max(1, static_cast<int>(num_local_search_iters)), &lopts, 0, x.data(), &v, &idx, nullptr,
+                                       nullptr),
+                      "sls_jes_maximize");
+        if (value) *value = v;
+        return x;
+    }
+
+    VectorXd acquisition_func::FindNextPointByJointEntropySearch(const Regressor& regressor, const unsigned num_optima,
+                                                                 const unsigned num_global_search_iters,
+                                                                 const unsigned num_local_search_iters, const unsigned long long seed,
+                                                                 const int num_frequencies, double* value)
+    {
+        const std::pair<MatrixXd, VectorXd> optima =
+            SampleOptima(regressor, num_optima, num_global_search_iters, num_local_search_iters, seed, num_frequencies);
+        return FindNextPointByJointEntropySearchFromStarts(
+            regressor, optima.first, optima.second, SeededStarts(regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed),
             num_local_search_iters, value);
     }
 
