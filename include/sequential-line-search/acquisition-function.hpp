@@ -189,6 +189,29 @@ namespace sequential_line_search
                                                                     const unsigned num_local_search_iters, double* value = nullptr,
                                                                     const double star_noise = -1.0);
 
+        /// Knowledge gradient on a discrete set (not in the reference; Frazier, Powell & Dayanik 2009; with the candidate itself in the
+        /// set KGCP, Scott, Frazier & Powell 2011; include/sls_hip.h sls_kg_*): the expected gain of the highest posterior mean over
+        /// ref_points (D x K, K <= 1024) -- plus the candidate when include_candidate -- from one noisy measurement at x, for the
+        /// columns of Xs (and its gradient, D x M, if grad != nullptr): one device pass.  The baseline is the highest mean over
+        /// ref_points alone, so the value is smooth in x.  The measurement's noise variance is max(b, 1e-12) of the regressor, as
+        /// CalcJointEntropies passes it.
+        Eigen::VectorXd CalcKnowledgeGradients(const Regressor& regressor, const Eigen::MatrixXd& Xs, const Eigen::MatrixXd& ref_points,
+                                               Eigen::MatrixXd* grad = nullptr, const bool include_candidate = true);
+        /// The default reference set: the regressor's data points; above 1024 of them the 1024 with the highest posterior mean
+        /// (ties to the lower index), kept in increasing index order.
+        Eigen::MatrixXd KnowledgeGradientReferencePoints(const Regressor& regressor);
+        /// Maximiser of the knowledge gradient over [0,1]^D on the default reference set with the candidate included: one L-BFGS of
+        /// num_local_search_iters evaluations (the tolerances of GetLocalSearchTolerances) from each of num_global_search_iters
+        /// uniform starts, seeded exactly as FindNextPointByMaxValueEntropySearch seeds them.  The same seed gives the same point.
+        /// value (may be nullptr) receives the knowledge gradient there.
+        Eigen::VectorXd FindNextPointByKnowledgeGradient(const Regressor& regressor, const unsigned num_global_search_iters = 100,
+                                                         const unsigned num_local_search_iters = 50, const unsigned long long seed = 0,
+                                                         double* value = nullptr);
+        /// The same from an explicit reference set and an explicit start set (D x S).
+        Eigen::VectorXd FindNextPointByKnowledgeGradientFromStarts(const Regressor& regressor, const Eigen::MatrixXd& ref_points,
+                                                                   const Eigen::MatrixXd& starts, const unsigned num_local_search_iters,
+                                                                   double* value = nullptr, const bool include_candidate = true);
+
         /// Expected utility of the best option of a query pair (not in the reference; the q = 2 case of qEUBO, Astudillo et al.
         /// 2023, include/sls_hip.h sls_eubo_*): EUBO(x, x') = E[max(f(x), f(x'))] under the joint posterior of the two options,
         /// for the pairs (Xa.col(m), Xb.col(m)) (both D x M), and its gradients in x (grad_a, D x M) and x' (grad_b, D x M) where

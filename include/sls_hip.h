@@ -368,6 +368,66 @@ int sls_jes_eval(sls_jes* j, double noise_var, const double* Xs, int M, double* 
 int sls_jes_maximize(sls_jes* j, double noise_var, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts,
                      long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars, double* y_stars);
 
+/* ---- knowledge gradient on a discrete set (not in the reference) ----------------------------------------------------------
+ * The library recommends the point of highest posterior mean; the knowledge gradient (Frazier, Powell & Dayanik 2009) values a
+ * measurement at x by what it does to that recommendation, KG(x) = E_y[max_x' mu_{n+1}(x')] - max_x' mu_n(x'), with the inner maximum
+ * over a finite set: K fixed points x_k, optionally plus the candidate itself (KGCP, Scott, Frazier & Powell 2011).
+ * The object: K fixed points x_k, 1 <= K <= SLS_KG_MAX_POINTS, clamped into [0,1]^D at creation (as joint entropy search clamps its
+ * optima); a_k = mu(x_k) is what sls_gp_predict's tiled route returns there, bit for bit; a_max = max_k a_k (the lowest k wins ties);
+ * w_k = K_y^-1 k(X, x_k) from raw coordinate differences, as in sls_jes_create.
+ * Per candidate x: mu, sigma from the tiled evaluation in the handle's sigma mode, formed as the gradient evaluations form them whether
+ * or not grad is asked for; noise_var >= 0 and finite; c_k(x) = k(x, x_k) - k*(x)^T w_k as joint entropy search forms it.
+ *   s      = sqrt(sigma sigma + noise_var)
+ *   b_k    = c_k(x) / s                slope of the future mean at x_k per unit z:  mu_{n+1}(x_k) = a_k + b_k z,  z ~ N(0,1)
+ *   include_self != 0 adds line K:   a_K = mu(x),   b_K = sigma sigma / s
+ *   KG(x)  = E_z max_j (a_j + b_j z)  -  a_max
+ * The baseline is the constant a_max of the fixed set, not max(a_max, mu(x)): the value is smooth in x, >= 0, and differs from KGCP by
+ * max(0, mu(x) - a_max) only.
+ * Evaluation (Frazier's algorithm): the lines ordered by (b ascending, a descending, index ascending); among equal slopes the first
+ * stays; a stack scan leaves the envelope lines e_0 .. e_{E-1} with breakpoints t_1 < .. < t_{E-1},
+ * t_i = (a_{e_{i-1}} - a_{e_i}) / (b_{e_i} - b_{e_{i-1}}), t_0 = -inf, t_E = +inf; a line whose breakpoint with the new line is <= its own
+ * breakpoint is popped.
+ *   E max - max_j a_j = sum_{i=1..E-1} (b_{e_i} - b_{e_{i-1}}) f(-|t_i|),   f(-t) = phi(t) - t Phi(-t), 0 at t = inf    (envelope order)
+ *   KG                = that + (include_self ? max(0, mu - a_max) : 0)
+ *   beta_j = dKG/db_j = phi(t_i) - phi(t_{i+1})   for j = e_i, 0 off the envelope
+ *   pi_j   = dKG/da_j = Phi(t_{i+1}) - Phi(t_i)   for j = e_i, 0 off the envelope      (sum_j pi_j = 1)
+ * Phi(-t) = erfc(t / sqrt 2) / 2; pi is a difference of the smaller tails: Phi(t_{i+1}) - Phi(t_i) for t_{i+1} <= 0, Phi(-t_i) -
+ * Phi(-t_{i+1}) for t_i >= 0, (1 - Phi(t_i)) - Phi(-t_{i+1}) across 0.  E = 1 gives exactly 0, beta = 0, pi = 1.  Every product is rounded
+ * on its own (no fused multiply-add in the combiner).
+ * Gradient, of the shape of joint entropy search's (everything after the combiner is shared with it):
+ *   grad KG = A_mu grad mu + A_sigma grad sigma + sum_k h_k grad c_k(x)
+ *   h_k     = beta_k / s                   A_mu = pi_K  (0 without the self line)
+ *   A_sigma = (beta_K (sigma sigma + 2 noise_var) - sum_k beta_k c_k) (sigma / s^3)          (the sum over k < K in increasing k)
+ * Guard (expected improvement's, as joint entropy search applies it): sigma < 1e-10, or a NaN in the value or any gradient component:
+ * value 0, gradient 0.  A NaN among a candidate's lines makes its value NaN before the guard.
+ * The combiner works per candidate cooperatively (one workgroup per candidate: the lines sorted in LDS, the scan by one lane, the
+ * weights by all lanes); the comparison is the total order above and both sums have one fixed order that depends on the candidate's
+ * lines alone, so a point's bits depend on neither its column, the other points of the call, the candidate chunk nor active-set
+ * compaction.  The object is a snapshot, as sls_jes is (W, the clamped points, a_k, a_max, sls_gp_generation): a call after the handle
+ * was refitted, grown or switched in sigma mode returns SLS_ERR_INVALID.  It must not outlive its handle.  Every call holds the
+ * context's lock for its whole length and always takes the tiled evaluation.
+ * sls_prof_get names: "kg_setup" (create), "kg" (the combiner and the finish: two entries per chunk); the stages shared with joint
+ * entropy search keep its names "jes_cov", "jes_agg", "jes_grad" and "jes_grad_gemm". */
+typedef struct sls_kg sls_kg;
+#define SLS_KG_MAX_POINTS 1024
+/* x_ref D x K, 1 <= K <= SLS_KG_MAX_POINTS, all finite: else SLS_ERR_INVALID. */
+int sls_kg_create(sls_gp* gp, const double* x_ref, int K, sls_kg** out);
+int sls_kg_destroy(sls_kg* k);
+/* mu_ref[k] = a_k, *mu_max = a_max, *arg_max = its (lowest) index; any may be NULL. */
+int sls_kg_points(sls_kg* k, double* mu_ref, double* mu_max, int* arg_max);
+/* KG at the M points Xs (D x M): val (M), grad (D x M, may be NULL), slope (M x K column-major, slope[m + k*M] = b_k(x_m), may be NULL).
+ * noise_var >= 0 and finite, val != NULL when M > 0: else SLS_ERR_INVALID; M = 0 is a no-op. */
+int sls_kg_eval(sls_kg* k, double noise_var, int include_self, const double* Xs, int M, double* val, double* grad, double* slope);
+/* sls_acq_maximize with KG as the objective: same outputs, same semantics of idx_out / x_stars / y_stars; the statistics go to
+ * sls_acq_last_stats of the handle. */
+int sls_kg_maximize(sls_kg* k, double noise_var, int include_self, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts,
+                    long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars, double* y_stars);
+/* A test hook, as sls_jes_terms is: the combiner alone on caller-supplied lines.  a (K), B (M x K, [m + k*M]); a_self, b_self (M each,
+ * both NULL or both given); val (M) = E max - max_k a_k (+ max(0, a_self - max_k a_k) with a self line); beta, prob (M x K), self_out
+ * (M x 2: beta_K at [m], pi_K at [m + M]) may be NULL.  Every input finite, 1 <= K <= SLS_KG_MAX_POINTS: else SLS_ERR_INVALID. */
+int sls_kg_lines(sls_ctx* ctx, const double* a, const double* B, const double* a_self, const double* b_self, int K, int M,
+                 double* val, double* beta, double* prob, double* self_out);
+
 /* ---- log expected improvement (not in the reference) -------------------------------------------------------------------
  * acq_type SLS_ACQ_LOG_EXPECTED_IMPROVEMENT, accepted wherever an acq_type is taken (sls_acq_eval, sls_acq_maximize,
  * sls_acq_maximize_dev, sls_acq_eval_pair, sls_acq_maximize_pair, sls_multi_acq_maximize); every returned value (val, val_out,

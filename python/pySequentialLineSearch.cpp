@@ -219,6 +219,23 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
           "regressor"_a, "num_optima"_a = 64, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50, "seed"_a = 0ULL,
           "num_frequencies"_a = 2048);
 
+    // knowledge gradient on a discrete set (acquisition-function.hpp): values at the columns of points for the reference set
+    // ref_points (D x K), the default reference set, and the maximiser on it with its value
+    m.def("calc_knowledge_gradients",
+          [](const Regressor& r, const MatrixXd& Xs, const MatrixXd& ref_points, bool include_candidate) {
+              return acquisition_func::CalcKnowledgeGradients(r, Xs, ref_points, nullptr, include_candidate);
+          },
+          "regressor"_a, "points"_a, "ref_points"_a, "include_candidate"_a = true);
+    m.def("knowledge_gradient_reference_points", &acquisition_func::KnowledgeGradientReferencePoints, "regressor"_a);
+    m.def("find_next_point_by_knowledge_gradient",
+          [](const Regressor& r, unsigned num_global_search_iters, unsigned num_local_search_iters, unsigned long long seed) {
+              double         value = 0.0;
+              const VectorXd x =
+                  acquisition_func::FindNextPointByKnowledgeGradient(r, num_global_search_iters, num_local_search_iters, seed, &value);
+              return std::make_pair(x, value);
+          },
+          "regressor"_a, "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50, "seed"_a = 0ULL);
+
     // expected utility of the best option of a query pair (acquisition-function.hpp): values for the pairs (points_a.col(m),
     // points_b.col(m)), and the maximising pair with its value: (x, x', value)
     m.def("calc_expected_utilities_of_best_option",

@@ -111,6 +111,7 @@ EXPORTS = [
     "sls_acq_eval_sub", "sls_acq_maximize_sub", "sls_mes_eval_sub", "sls_mes_maximize_sub", "sls_path_eval_sub", "sls_path_maximize_sub",
     "sls_nll_loo", "sls_gp_loo_grad", "sls_gp_loo",
     "sls_jes_create", "sls_jes_destroy", "sls_jes_optima", "sls_jes_terms", "sls_jes_eval", "sls_jes_maximize",
+    "sls_kg_create", "sls_kg_destroy", "sls_kg_points", "sls_kg_eval", "sls_kg_maximize", "sls_kg_lines",
 ]
 
 
@@ -203,6 +204,27 @@ class Context:
         tau, dtau = np.empty(t.size), np.empty(t.size)
         _ck(lib().sls_jes_terms(self.h, _p(t), C.c_long(t.size), _p(tau), _p(dtau)))
         return tau, dtau
+
+    def kg_lines(self, a, B, a_self=None, b_self=None, want_beta=True, want_prob=True):
+        """The knowledge-gradient combiner alone on caller-supplied lines (sls_kg_lines): intercepts a (K,), slopes B (M, K), optionally
+        one own line per candidate (a_self, b_self (M,)).  Returns val (M,), then with want_beta beta (M, K), then with want_prob pi
+        (M, K), then with a self line (beta_K, pi_K) as an (M, 2) array."""
+        a, B = _f(a).ravel(), _f(B)
+        if B.ndim != 2 or B.shape[1] != a.size:
+            raise SlsError(f"kg_lines: B must be M x K = M x {a.size}, got {B.shape}")
+        M, K = B.shape
+        own = a_self is not None
+        if own:
+            a_self, b_self = _f(a_self).ravel(), _f(b_self).ravel()
+            if a_self.size != M or b_self.size != M:
+                raise SlsError(f"kg_lines: a_self and b_self must have M = {M} entries")
+        val = np.empty(M)
+        beta = np.empty((M, K), order="F") if want_beta else None
+        prob = np.empty((M, K), order="F") if want_prob else None
+        so = np.empty((M, 2), order="F") if own else None
+        _ck(lib().sls_kg_lines(self.h, _p(a), _p(B), _p(a_self) if own else None, _p(b_self) if own else None, K, M, _p(val),
+                               _p(beta) if want_beta else None, _p(prob) if want_prob else None, _p(so) if own else None))
+        return (val,) + ((beta,) if want_beta else ()) + ((prob,) if want_prob else ()) + ((so,) if own else ())
 
     def logei_terms(self, u):
         """(log h(u), Phi/h, phi/h) of log expected improvement, h = phi + u Phi, for an array of u (sls_logei_terms)."""
@@ -408,6 +430,10 @@ class GP:
         """The snapshot of K sampled optima (x_star (D, K), f_star (K,)) joint entropy search conditions on (sls_jes_create)."""
         return JesOptima(self, x_star, f_star, star_noise)
 
+    def kg_create(self, x_ref):
+        """The snapshot of K fixed points (x_ref (D, K)) the knowledge gradient maximises the future mean over (sls_kg_create)."""
+        return KnowledgeGradient(self, x_ref)
+
     def eubo_eval(self, pairs, want_grad=True):
         """Expected utility of the best option E[max(f(x), f(x'))] at the columns of pairs (2D x M: rows 0..D-1 = x, D..2D-1 = x'),
         sls_eubo_eval; the gradient is 2D x M in the same row order."""
@@ -546,6 +572,64 @@ class JesOptima:
         _ck(lib().sls_jes_maximize(self.h, C.c_double(noise_var), _p(starts), S, int(n_local),
                                    C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val), C.byref(idx),
                                    _p(xs) if want_all else None, _p(ys) if want_all else None))
+        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+
+
+KG_MAX_POINTS = 1024      # SLS_KG_MAX_POINTS
+
+
+class KnowledgeGradient:
+    """K fixed points x_k of a fitted GP handle for the knowledge gradient on a discrete set (sls_kg_*).  A snapshot: after the handle
+    is refitted, grown or switched in sigma mode every call is refused; it must be closed before its handle."""
+
+    def __init__(self, gp, x_ref):
+        x_ref = _f(x_ref)
+        if x_ref.ndim != 2 or x_ref.shape[0] != gp.D:
+            raise SlsError(f"KnowledgeGradient: x_ref must be D x K = {gp.D} x K, got {x_ref.shape}")
+        self.gp, self.D, self.K = gp, gp.D, x_ref.shape[1]
+        self.h = C.c_void_p()
+        _ck(lib().sls_kg_create(gp.h, _p(x_ref), self.K, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().sls_kg_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def points(self):
+        """(a_k, a_max, arg max): the posterior mean at the points, its maximum and the (lowest) index of the maximum."""
+        mu, mx, am = np.empty(self.K), C.c_double(), C.c_int()
+        _ck(lib().sls_kg_points(self.h, _p(mu), C.byref(mx), C.byref(am)))
+        return mu, mx.value, am.value
+
+    def eval(self, Xs, noise_var, include_self=True, want_grad=False, want_slopes=False):
+        """KG at the columns of Xs: values (M,), then with want_grad the gradient (D, M), then with want_slopes the slopes b_k(x_m)
+        (M, K)."""
+        Xs = _f(Xs)
+        M = Xs.shape[1]
+        val = np.empty(M)
+        grad = np.empty((self.D, M), order="F") if want_grad else None
+        slope = np.empty((M, self.K), order="F") if want_slopes else None
+        _ck(lib().sls_kg_eval(self.h, C.c_double(noise_var), int(bool(include_self)), _p(Xs), M, _p(val),
+                              _p(grad) if want_grad else None, _p(slope) if want_slopes else None))
+        out = (val,) + ((grad,) if want_grad else ()) + ((slope,) if want_slopes else ())
+        return out if len(out) > 1 else val
+
+    def maximize(self, starts, n_local, noise_var, include_self=True, offset=0, want_all=True, opts=None):
+        """acq_maximize with the knowledge gradient as the objective (sls_kg_maximize)."""
+        starts = _f(starts)
+        S = starts.shape[1]
+        x, val, idx = np.empty(self.D), C.c_double(), C.c_long()
+        xs = np.empty((self.D, S), order="F") if want_all else None
+        ys = np.empty(S) if want_all else None
+        _ck(lib().sls_kg_maximize(self.h, C.c_double(noise_var), int(bool(include_self)), _p(starts), S, int(n_local),
+                                  C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val), C.byref(idx),
+                                  _p(xs) if want_all else None, _p(ys) if want_all else None))
         return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
 
 

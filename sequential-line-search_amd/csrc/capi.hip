@@ -1403,22 +1403,30 @@ extern "C" int sls_mes_maximize(sls_gp* g, const double* y_star, int K, const do
 // ---- joint entropy search (include/sls_hip.h) ------------------------------------------------------------------------------
 // The snapshot of the conditioned optima and the blocks of a candidate chunk (grown on demand, kept with the object so that the rounds
 // of a maximisation allocate nothing).
-struct sls_jes {
+// The part every criterion on K fixed points shares (joint entropy search, the knowledge gradient): the snapshot of the points and
+// the chunk pass around a criterion's combiner.
+struct PointSet {
     sls_gp* gp = nullptr;
     sls_ctx* ctx = nullptr;
     long generation = 0;
     int D = 0, K = 0, Kp = 0, Np = 0;
-    // W [i + k*Np] (Np x Kp, 0 for k >= K and i >= N), xs [d + k*D] (raw, clamped), K doubles each of mu*, sigma*, v, d, 1 / v, f*
-    DBuf W, xs, mu_star, sg_star, v, dd, inv_v, f_star;
+    // W [i + k*Np] (Np x Kp, 0 for k >= K and i >= N), xs [d + k*D] (raw, clamped), mu*, sigma* (K each)
+    DBuf W, xs, mu_star, sg_star;
     // per chunk, candidate-major with the chunk's leading dimension: cov / cx / H (Sp x Kp), A_mu, A_sigma, csum (Sp), Go (Sp x D)
     DBuf cov, cx, H, a_mu, a_sg, csum, Go;
+};
+struct sls_jes : PointSet {
+    DBuf v, dd, inv_v, f_star;   // K doubles each
 };
 
 // alpha (+ gradient, + the covariances) at S candidate-major points xr[n + d*ldr]; val[n], grad[n + d*ldo] (may be nullptr),
 // cov_out[n + k*ldc] (may be nullptr).  eval_candidates reuses K*, C* and P per chunk, and this pass needs the chunk's K* and C* after
 // it: it drives the tiled evaluation ONE chunk at a time.  A candidate's bits do not depend on the chunk it falls into.
-static void jes_eval_device(sls_jes* j, double noise_var, const double* xr, long ldr, int S, double* val, double* grad, long ldo,
-                            double* cov_out, long ldc) {
+// combine(sc, Sp, ldk, mu, sigma, s0, val, a_mu, a_sg, H) is the criterion's combiner on the chunk that starts at candidate s0 (a_mu,
+// a_sg, H nullptr without grad); `scope` is the profiling name of the combiner and the finish.
+template <class Combine>
+static void pointset_eval_device(PointSet* j, const char* scope, Combine&& combine, const double* xr, long ldr, int S, double* val,
+                                 double* grad, long ldo, double* cov_out, long ldc) {
     sls_gp* g = j->gp;
     sls_ctx* c = g->ctx;
     const int D = g->D, Np = g->Np, N = g->N, K = j->K, Kp = j->Kp;
@@ -1452,10 +1460,10 @@ static void jes_eval_device(sls_jes* j, double noise_var, const double* xr, long
             SLS_HIP(hipMemcpy2DAsync(cov_out + s0, (size_t)ldc * 8, j->cov.p, (size_t)ldk * 8, (size_t)sc * 8, K, hipMemcpyDeviceToDevice,
                                      c->stream));
         {
-            ProfScope ps(c, "jes");
+            ProfScope ps(c, scope);
             if (grad && Kp > K) SLS_HIP(hipMemsetAsync(j->H.p + (size_t)K * ldk, 0, (size_t)(Kp - K) * ldk * 8, c->stream));
-            launch_jes_combine(c->stream, sc, Sp, ldk, eo.mu, eo.sigma, j->cov.p, j->f_star.p, j->dd.p, j->inv_v.p, K, noise_var, val + s0,
-                               grad ? j->a_mu.p : nullptr, grad ? j->a_sg.p : nullptr, grad ? j->H.p : nullptr);
+            combine(sc, Sp, ldk, eo.mu, eo.sigma, s0, val + s0, grad ? j->a_mu.p : nullptr, grad ? j->a_sg.p : nullptr,
+                    grad ? j->H.p : nullptr);
         }
         if (grad) {
             {
@@ -1478,20 +1486,65 @@ static void jes_eval_device(sls_jes* j, double noise_var, const double* xr, long
                                      nullptr, grad_split_scratch(g->Gpart, D, Sp), 1);
             }
         }
-        ProfScope ps(c, "jes");
+        ProfScope ps(c, scope);
         launch_jes_finish(c->stream, sc, D, ldo, ldk, eo.sigma, eo.dmu, eo.dsigma, j->a_mu.p, j->a_sg.p, g->Gs.p, j->Go.p,
                           g->gram_direct ? nullptr : g->XsT.p, j->csum.p, g->inv_ell.p, val + s0, grad ? grad + s0 : nullptr);
     }
 }
 
-// the object is what its handle still stands for
-static void jes_check(const char* who, sls_jes* j) {
-    SLS_REQUIRE(j->gp->generation == j->generation,
-                "%s: the GP handle was refitted, grown or switched in sigma mode since sls_jes_create (generation %ld, now %ld): create a new object", who,
-                j->generation, j->gp->generation);
+static void jes_eval_device(sls_jes* j, double noise_var, const double* xr, long ldr, int S, double* val, double* grad, long ldo,
+                            double* cov_out, long ldc) {
+    pointset_eval_device(
+        j, "jes",
+        [&](int sc, int Sp, long ldk, const double* mu, const double* sigma, int, double* v, double* a_mu, double* a_sg, double* H) {
+            launch_jes_combine(j->ctx->stream, sc, Sp, ldk, mu, sigma, j->cov.p, j->f_star.p, j->dd.p, j->inv_v.p, j->K, noise_var, v, a_mu,
+                               a_sg, H);
+        },
+        xr, ldr, S, val, grad, ldo, cov_out, ldc);
 }
+
+// the object is what its handle still stands for
+static void pointset_check(const char* who, const char* made_by, PointSet* j) {
+    SLS_REQUIRE(j->gp->generation == j->generation,
+                "%s: the GP handle was refitted, grown or switched in sigma mode since %s (generation %ld, now %ld): create a new object", who,
+                made_by, j->generation, j->gp->generation);
+}
+static void jes_check(const char* who, sls_jes* j) { pointset_check(who, "sls_jes_create", j); }
 static void jes_check_noise(const char* who, double noise_var) {
     SLS_REQUIRE(std::isfinite(noise_var) && noise_var > 0.0, "%s: noise_var = %g (finite, > 0)", who, noise_var);
+}
+
+// x (D x K on the host) checked finite and clamped into [0,1]^D, as starts are
+static std::vector<double> pointset_clamped(const char* who, const char* name, const char* noun, const double* x, int D, int K) {
+    std::vector<double> xh((size_t)D * K);
+    for (size_t i = 0; i < xh.size(); ++i) {
+        SLS_REQUIRE(std::isfinite(x[i]), "%s: %s[%d] of %s %d is not finite", who, name, (int)(i % D), noun, (int)(i / D));
+        xh[i] = std::min(1.0, std::max(0.0, x[i]));
+    }
+    return xh;
+}
+// The snapshot of K points of a fitted handle (its state lock held): W = K_y^-1 k(X, x_k), mu(x_k), sigma(x_k).  xh stays alive until the
+// caller's sync.
+static void pointset_snapshot(PointSet* j, sls_gp* g, const std::vector<double>& xh, int K, const char* scope) {
+    sls_ctx* c = g->ctx;
+    const int D = g->D, N = g->N, Np = g->Np, Kp = round_up(K, 128);
+    j->gp = g; j->ctx = c; j->generation = g->generation;
+    j->D = D; j->K = K; j->Kp = Kp; j->Np = Np;
+    j->W.ensure((size_t)Np * Kp);
+    j->xs.ensure((size_t)D * K);
+    j->mu_star.ensure(Kp); j->sg_star.ensure(Kp);
+    h2d(c, j->xs.p, xh.data(), xh.size());
+    {
+        ProfScope ps(c, scope);
+        // K(X, X*) [i + k*Np] from the raw differences (rows i >= N and columns k >= K exactly 0), then W = K_y^-1 K(X, X*) on the factor
+        launch_jes_cross(c->stream, g->X.p, D, 1, N, Np, j->xs.p, D, K, Kp, g->inv_ell.p, KernelSpec{g->kernel, g->a}, j->W.p, nullptr, Np);
+        launch_potrs(c->stream, g->L.p, g->Linv.p, Np, j->W.p, Kp);
+    }
+    // mu, sigma through the tiled evaluation, exactly as sls_gp_predict's tiled route forms them (mean and deviation, no gradient)
+    EvalOut eo;
+    eo.ldo = Kp;
+    eo.mu = j->mu_star.p; eo.sigma = j->sg_star.p;
+    eval_candidates(g, j->xs.p, 0, K, eo, true);
 }
 
 extern "C" int sls_jes_create(sls_gp* g, const double* x_star, const double* f_star, int K, double star_noise, sls_jes** out) {
@@ -1504,36 +1557,14 @@ extern "C" int sls_jes_create(sls_gp* g, const double* x_star, const double* f_s
     SLS_REQUIRE(x_star != nullptr, "sls_jes_create: x_star is NULL");
     SLS_REQUIRE(f_star != nullptr, "sls_jes_create: f_star is NULL");
     SLS_REQUIRE(std::isfinite(star_noise) && star_noise >= 0.0, "sls_jes_create: star_noise = %g (finite, >= 0)", star_noise);
-    const int D = g->D, N = g->N, Np = g->Np, Kp = round_up(K, 128);
     for (int k = 0; k < K; ++k) SLS_REQUIRE(std::isfinite(f_star[k]), "sls_jes_create: f_star[%d] is not finite", k);
-    std::vector<double> xh((size_t)D * K);
-    for (size_t i = 0; i < xh.size(); ++i) {
-        SLS_REQUIRE(std::isfinite(x_star[i]), "sls_jes_create: x_star[%d] of optimum %d is not finite", (int)(i % D), (int)(i / D));
-        xh[i] = std::min(1.0, std::max(0.0, x_star[i]));
-    }
+    const std::vector<double> xh = pointset_clamped("sls_jes_create", "x_star", "optimum", x_star, g->D, K);
     std::shared_lock<std::shared_mutex> state_(g->state_mtx);
     sls_ctx* c = g->ctx;
     std::unique_ptr<sls_jes> j(new sls_jes);
-    j->gp = g; j->ctx = c; j->generation = g->generation;
-    j->D = D; j->K = K; j->Kp = Kp; j->Np = Np;
-    j->W.ensure((size_t)Np * Kp);
-    j->xs.ensure((size_t)D * K);
-    j->mu_star.ensure(Kp); j->sg_star.ensure(Kp); j->v.ensure(K); j->dd.ensure(K); j->inv_v.ensure(K); j->f_star.ensure(K);
-    h2d(c, j->xs.p, xh.data(), xh.size());
+    j->v.ensure(K); j->dd.ensure(K); j->inv_v.ensure(K); j->f_star.ensure(K);
     h2d(c, j->f_star.p, f_star, (size_t)K);
-    {
-        ProfScope ps(c, "jes_setup");
-        // K(X, X*) [i + k*Np] from the raw differences (rows i >= N and columns k >= K exactly 0), then W = K_y^-1 K(X, X*) on the factor
-        launch_jes_cross(c->stream, g->X.p, D, 1, N, Np, j->xs.p, D, K, Kp, g->inv_ell.p, KernelSpec{g->kernel, g->a}, j->W.p, nullptr, Np);
-        launch_potrs(c->stream, g->L.p, g->Linv.p, Np, j->W.p, Kp);
-    }
-    // mu*, sigma* through the tiled evaluation, exactly as sls_gp_predict's tiled route forms them (mean and deviation, no gradient)
-    {
-        EvalOut eo;
-        eo.ldo = Kp;
-        eo.mu = j->mu_star.p; eo.sigma = j->sg_star.p;
-        eval_candidates(g, j->xs.p, 0, K, eo, true);
-    }
+    pointset_snapshot(j.get(), g, xh, K, "jes_setup");
     {
         ProfScope ps(c, "jes_setup");
         launch_jes_optima(c->stream, K, j->mu_star.p, j->sg_star.p, j->f_star.p, star_noise, j->v.p, j->dd.p, j->inv_v.p);
@@ -1568,6 +1599,53 @@ extern "C" int sls_jes_terms(sls_ctx* ctx, const double* t, long n, double* tau,
                         [&](const double* in, long m, double* const* out) { launch_jes_terms(ctx->stream, in, m, out[0], out[1]); });
 }
 
+// The bodies of the eval / maximize entry points of a point-set criterion (the argument checks are the caller's).
+// eval(xr, ldr, S, val, grad, ldo, extra, ldc): the criterion's chunk pass; extra: an M x K block the pass fills per candidate and
+// point (candidate-major on the device, [m + k*M] for the caller), may be NULL.
+template <class Eval>
+static void pointset_eval_points(PointSet* j, const double* Xs, int M, double* val, double* grad, double* extra, Eval&& eval) {
+    sls_gp* g = j->gp;
+    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
+    const int Mp = round_up(M, 128), D = g->D, K = j->K;
+    upload_candidates(g, Xs, D, M, Mp);
+    EvalOut want;
+    want.val = val; want.grad = grad;
+    g->outv.ensure(eval_block_doubles(want, D, Mp));
+    const EvalOut o = eval_block(want, g->outv.p, D, Mp);
+    DBuf covd;
+    if (extra) covd.ensure((size_t)Mp * K);
+    eval(g->raw.p, (long)Mp, M, o.val, o.grad, (long)Mp, extra ? covd.p : nullptr, (long)Mp);
+    std::vector<double> covh;
+    if (extra) {
+        covh.resize((size_t)Mp * K);
+        d2h(g->ctx, covh.data(), covd.p, covh.size());
+    }
+    download_block(g, want, g->outv.p, D, M, Mp);   // the call's one synchronisation
+    if (extra)
+        for (int k = 0; k < K; ++k) std::copy(covh.begin() + (size_t)k * Mp, covh.begin() + (size_t)k * Mp + M, extra + (size_t)k * M);
+}
+template <class Eval>
+static void pointset_maximize(const char* who, PointSet* j, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts,
+                              long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars, double* y_stars,
+                              Eval&& eval) {
+    sls_gp* g = j->gp;
+    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
+    sls_ctx* c = g->ctx;
+    MultistartRun r = maximize_begin(who, g, g->lb, opts, S, n_local, g->D);
+    DBuf sd;
+    sd.ensure((size_t)g->D * S);
+    h2d(c, sd.p, starts, (size_t)g->D * S);
+    LockstepStats ls;
+    lockstep_rounds(c, r.st, g->lb, sd.p, S, n_local,
+                    [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
+                        eval(trial, ld, nlive, val, grad, ld, nullptr, 0L);
+                    },
+                    &ls);
+    std::vector<double> pageable;
+    maximize_finish(c, r, ls, BestBlock{g->sum.dev + 8, g->sum.host + 8, false}, staged_fetch(g, pageable), start_index_offset, x_out,
+                    val_out, idx_out, x_stars, y_stars);
+}
+
 extern "C" int sls_jes_eval(sls_jes* j, double noise_var, const double* Xs, int M, double* val, double* grad, double* cov) {
     SLS_TRY
     SLS_REQUIRE(j != nullptr, "sls_jes_eval: j is NULL");
@@ -1578,25 +1656,9 @@ extern "C" int sls_jes_eval(sls_jes* j, double noise_var, const double* Xs, int 
     if (M == 0) return SLS_OK;
     SLS_REQUIRE(Xs != nullptr, "sls_jes_eval: Xs is NULL");
     SLS_REQUIRE(val != nullptr, "sls_jes_eval: val is NULL");
-    sls_gp* g = j->gp;
-    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
-    const int Mp = round_up(M, 128), D = g->D, K = j->K;
-    upload_candidates(g, Xs, D, M, Mp);
-    EvalOut want;
-    want.val = val; want.grad = grad;
-    g->outv.ensure(eval_block_doubles(want, D, Mp));
-    const EvalOut o = eval_block(want, g->outv.p, D, Mp);
-    DBuf covd;
-    if (cov) covd.ensure((size_t)Mp * K);
-    jes_eval_device(j, noise_var, g->raw.p, Mp, M, o.val, o.grad, Mp, cov ? covd.p : nullptr, Mp);
-    std::vector<double> covh;
-    if (cov) {
-        covh.resize((size_t)Mp * K);
-        d2h(g->ctx, covh.data(), covd.p, covh.size());
-    }
-    download_block(g, want, g->outv.p, D, M, Mp);   // the call's one synchronisation
-    if (cov)
-        for (int k = 0; k < K; ++k) std::copy(covh.begin() + (size_t)k * Mp, covh.begin() + (size_t)k * Mp + M, cov + (size_t)k * M);
+    pointset_eval_points(j, Xs, M, val, grad, cov, [&](const double* xr, long ldr, int S, double* v, double* gr, long ldo, double* cv, long ldc) {
+        jes_eval_device(j, noise_var, xr, ldr, S, v, gr, ldo, cv, ldc);
+    });
     SLS_CATCH
 }
 
@@ -1609,22 +1671,154 @@ extern "C" int sls_jes_maximize(sls_jes* j, double noise_var, const double* star
     SLS_REQUIRE(starts != nullptr, "sls_jes_maximize: starts is NULL");
     jes_check_noise("sls_jes_maximize", noise_var);
     jes_check("sls_jes_maximize", j);
-    sls_gp* g = j->gp;
+    pointset_maximize("sls_jes_maximize", j, starts, S, n_local, opts, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars,
+                      [&](const double* xr, long ldr, int n, double* v, double* gr, long ldo, double* cv, long ldc) {
+                          jes_eval_device(j, noise_var, xr, ldr, n, v, gr, ldo, cv, ldc);
+                      });
+    SLS_CATCH
+}
+
+// ---- knowledge gradient on a discrete set (include/sls_hip.h) ---------------------------------------------------------------------
+// The snapshot of the K fixed points: the point set (W, x_k, a_k = mu(x_k)) plus a_max and its index.
+struct sls_kg : PointSet {
+    double a_max = 0.0;
+    int arg_max = 0;
+};
+
+// KG (+ gradient, + the slopes b_k) at S candidate-major points: joint entropy search's chunk pass around launch_kg_combine.
+static void kg_eval_device(sls_kg* k, double noise_var, int include_self, const double* xr, long ldr, int S, double* val, double* grad,
+                           long ldo, double* slope_out, long lds) {
+    pointset_eval_device(
+        k, "kg",
+        [&](int sc, int Sp, long ldk, const double* mu, const double* sigma, int s0, double* v, double* a_mu, double* a_sg, double* H) {
+            launch_kg_combine(k->ctx->stream, sc, Sp, ldk, mu, sigma, k->cov.p, k->mu_star.p, k->a_max, k->K, noise_var, include_self, v,
+                              a_mu, a_sg, H, slope_out ? slope_out + s0 : nullptr, lds);
+        },
+        xr, ldr, S, val, grad, ldo, nullptr, 0);
+}
+static void kg_check_noise(const char* who, double noise_var) {
+    SLS_REQUIRE(std::isfinite(noise_var) && noise_var >= 0.0, "%s: noise_var = %g (finite, >= 0)", who, noise_var);
+}
+
+extern "C" int sls_kg_create(sls_gp* g, const double* x_ref, int K, sls_kg** out) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g != nullptr, "sls_kg_create: gp is NULL");
+    SLS_REQUIRE(out != nullptr, "sls_kg_create: out is NULL");
+    *out = nullptr;
+    SLS_REQUIRE(K >= 1 && K <= SLS_KG_MAX_POINTS, "sls_kg_create: K = %d (1 .. %d)", K, SLS_KG_MAX_POINTS);
+    SLS_REQUIRE(x_ref != nullptr, "sls_kg_create: x_ref is NULL");
+    const std::vector<double> xh = pointset_clamped("sls_kg_create", "x_ref", "point", x_ref, g->D, K);
     std::shared_lock<std::shared_mutex> state_(g->state_mtx);
     sls_ctx* c = g->ctx;
-    MultistartRun r = maximize_begin("sls_jes_maximize", g, g->lb, opts, S, n_local, g->D);
-    DBuf sd;
-    sd.ensure((size_t)g->D * S);
-    h2d(c, sd.p, starts, (size_t)g->D * S);
-    LockstepStats ls;
-    lockstep_rounds(c, r.st, g->lb, sd.p, S, n_local,
-                    [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
-                        jes_eval_device(j, noise_var, trial, ld, nlive, val, grad, ld, nullptr, 0);
-                    },
-                    &ls);
-    std::vector<double> pageable;
-    maximize_finish(c, r, ls, BestBlock{g->sum.dev + 8, g->sum.host + 8, false}, staged_fetch(g, pageable), start_index_offset, x_out,
-                    val_out, idx_out, x_stars, y_stars);
+    std::unique_ptr<sls_kg> k(new sls_kg);
+    pointset_snapshot(k.get(), g, xh, K, "kg_setup");
+    std::vector<double> a(K);
+    d2h(c, a.data(), k->mu_star.p, (size_t)K);
+    sync(c);
+    k->a_max = a[0];
+    for (int i = 1; i < K; ++i)
+        if (a[i] > k->a_max) { k->a_max = a[i]; k->arg_max = i; }   // the lowest index wins ties
+    slsk::ctx_retain(c);
+    *out = k.release();
+    SLS_CATCH
+}
+
+extern "C" int sls_kg_destroy(sls_kg* k) {
+    if (!k) return SLS_OK;
+    slsk::note_entry();
+    destroy_handle(k);
+    return SLS_OK;
+}
+
+extern "C" int sls_kg_points(sls_kg* k, double* mu_ref, double* mu_max, int* arg_max) {
+    SLS_TRY
+    SLS_REQUIRE(k != nullptr, "sls_kg_points: k is NULL");
+    CtxCall call_(k);
+    pointset_check("sls_kg_points", "sls_kg_create", k);
+    if (mu_ref) d2h(k->ctx, mu_ref, k->mu_star.p, (size_t)k->K);
+    if (mu_max) *mu_max = k->a_max;
+    if (arg_max) *arg_max = k->arg_max;
+    sync(k->ctx);
+    SLS_CATCH
+}
+
+extern "C" int sls_kg_eval(sls_kg* k, double noise_var, int include_self, const double* Xs, int M, double* val, double* grad,
+                           double* slope) {
+    SLS_TRY
+    SLS_REQUIRE(k != nullptr, "sls_kg_eval: k is NULL");
+    CtxCall call_(k);
+    SLS_REQUIRE(M >= 0, "sls_kg_eval: M = %d", M);
+    kg_check_noise("sls_kg_eval", noise_var);
+    pointset_check("sls_kg_eval", "sls_kg_create", k);
+    if (M == 0) return SLS_OK;
+    SLS_REQUIRE(Xs != nullptr, "sls_kg_eval: Xs is NULL");
+    SLS_REQUIRE(val != nullptr, "sls_kg_eval: val is NULL");
+    pointset_eval_points(k, Xs, M, val, grad, slope, [&](const double* xr, long ldr, int S, double* v, double* gr, long ldo, double* sl, long lds) {
+        kg_eval_device(k, noise_var, include_self != 0, xr, ldr, S, v, gr, ldo, sl, lds);
+    });
+    SLS_CATCH
+}
+
+extern "C" int sls_kg_maximize(sls_kg* k, double noise_var, int include_self, const double* starts, int S, int n_local,
+                               const sls_lbfgs_opts* opts, long start_index_offset, double* x_out, double* val_out, long* idx_out,
+                               double* x_stars, double* y_stars) {
+    SLS_TRY
+    SLS_REQUIRE(k != nullptr, "sls_kg_maximize: k is NULL");
+    CtxCall call_(k);
+    SLS_REQUIRE(starts != nullptr, "sls_kg_maximize: starts is NULL");
+    kg_check_noise("sls_kg_maximize", noise_var);
+    pointset_check("sls_kg_maximize", "sls_kg_create", k);
+    pointset_maximize("sls_kg_maximize", k, starts, S, n_local, opts, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars,
+                      [&](const double* xr, long ldr, int n, double* v, double* gr, long ldo, double* sl, long lds) {
+                          kg_eval_device(k, noise_var, include_self != 0, xr, ldr, n, v, gr, ldo, sl, lds);
+                      });
+    SLS_CATCH
+}
+
+// The combiner alone on caller-supplied lines (a test hook): M candidates at a time in blocks of at most 4096.
+extern "C" int sls_kg_lines(sls_ctx* ctx, const double* a, const double* B, const double* a_self, const double* b_self, int K, int M,
+                            double* val, double* beta, double* prob, double* self_out) {
+    SLS_TRY
+    CtxCall call_(ctx);
+    SLS_REQUIRE(ctx != nullptr, "sls_kg_lines: ctx is NULL");
+    SLS_REQUIRE(K >= 1 && K <= SLS_KG_MAX_POINTS, "sls_kg_lines: K = %d (1 .. %d)", K, SLS_KG_MAX_POINTS);
+    SLS_REQUIRE(M >= 0, "sls_kg_lines: M = %d", M);
+    SLS_REQUIRE((a_self == nullptr) == (b_self == nullptr), "sls_kg_lines: a_self and b_self go together");
+    if (M == 0) return SLS_OK;
+    SLS_REQUIRE(a != nullptr && B != nullptr, "sls_kg_lines: a or B is NULL");
+    SLS_REQUIRE(val != nullptr, "sls_kg_lines: val is NULL");
+    SLS_REQUIRE(self_out == nullptr || a_self != nullptr, "sls_kg_lines: self_out without a self line");
+    for (int k = 0; k < K; ++k) SLS_REQUIRE(std::isfinite(a[k]), "sls_kg_lines: a[%d] is not finite", k);
+    for (size_t i = 0; i < (size_t)M * K; ++i) SLS_REQUIRE(std::isfinite(B[i]), "sls_kg_lines: B[%zu] is not finite", i);
+    for (int m = 0; a_self && m < M; ++m)
+        SLS_REQUIRE(std::isfinite(a_self[m]) && std::isfinite(b_self[m]), "sls_kg_lines: the self line of candidate %d is not finite", m);
+    SLS_HIP(hipSetDevice(ctx->device));
+    const double a_max = *std::max_element(a, a + K);
+    const size_t MK = (size_t)M * K;
+    DBuf buf;
+    buf.ensure((size_t)K + 3 * MK + 5 * (size_t)M);
+    double *ad = buf.p, *Bd = ad + K, *betad = Bd + MK, *probd = betad + MK, *asd = probd + MK, *bsd = asd + M, *vald = bsd + M,
+           *spi = vald + M, *sbeta = spi + M;
+    h2d(ctx, ad, a, (size_t)K);
+    h2d(ctx, Bd, B, MK);
+    if (a_self) {
+        h2d(ctx, asd, a_self, (size_t)M);
+        h2d(ctx, bsd, b_self, (size_t)M);
+    }
+    {
+        ProfScope ps(ctx, "kg");
+        launch_kg_lines(ctx->stream, M, M, ad, a_max, Bd, K, a_self ? asd : nullptr, a_self ? bsd : nullptr, vald, beta ? betad : nullptr,
+                        prob ? probd : nullptr, self_out ? spi : nullptr, self_out ? sbeta : nullptr);
+    }
+    d2h(ctx, val, vald, (size_t)M);
+    if (beta) d2h(ctx, beta, betad, MK);
+    if (prob) d2h(ctx, prob, probd, MK);
+    if (self_out) {
+        d2h(ctx, self_out, sbeta, (size_t)M);
+        d2h(ctx, self_out + M, spi, (size_t)M);
+    }
+    sync(ctx);
     SLS_CATCH
 }
 

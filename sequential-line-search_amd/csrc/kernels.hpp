@@ -310,6 +310,20 @@ void launch_jes_finish(hipStream_t s, int S, int D, long ldo, long ldk, const do
                        const double* a_mu, const double* a_sg, const double* Gd, const double* Go, const double* XsT, const double* csum,
                        const double* inv_ell, double* val, double* grad);
 
+// ---- kernels_kg.hip: knowledge gradient on a discrete set (sls_kg_*) ------------------------------------------------------------
+// The combiner (include/sls_hip.h "knowledge gradient"): one workgroup per candidate, the lines sorted in LDS under a total order, the
+// envelope by one lane, KG summed in envelope order and sum_k beta_k c_k in increasing k.  The inputs of launch_jes_combine plus the
+// fixed means a[K], a_max and include_self; val[n], a_mu[n], a_sg[n] for n < S (unguarded: launch_jes_finish applies the guard);
+// H[n + k*ld] for n < Sp, k < K (0 off the envelope and for n >= S).  a_mu, a_sg and H may be NULL together (value only, same bits).
+// slope[n + k*ld_slope] = b_k(x_n) for n < S, k < K (may be NULL).
+void launch_kg_combine(hipStream_t s, int S, int Sp, long ld, const double* mu, const double* sigma, const double* cov, const double* a,
+                       double a_max, int K, double noise_var, int include_self, double* val, double* a_mu, double* a_sg, double* H,
+                       double* slope, long ld_slope);
+// The same kernel on caller-supplied lines (sls_kg_lines): slopes B[m + k*ld], own line (a_self[m], b_self[m]) when a_self != NULL;
+// val[m] = E max - a_max + (own line: max(0, a_self - a_max)), beta / prob [m + k*ld], self_pi / self_beta [m]; each may be NULL.
+void launch_kg_lines(hipStream_t s, int M, long ld, const double* a, double a_max, const double* B, int K, const double* a_self,
+                     const double* b_self, double* val, double* beta, double* prob, double* self_pi, double* self_beta);
+
 // ---- kernels_eubo.hip: expected utility of the best option of a query pair (sls_eubo_*) ----------------------------------
 // Kd[n + i*ldk] = Ka[n + i*ldk] - Kb[n + i*ldk] over the whole padded block (ldk x Np doubles, both multiples of 128)
 void launch_pair_diff(hipStream_t s, const double* Ka, const double* Kb, long ldk, int Np, double* Kd);

@@ -506,6 +506,84 @@ namespace sequential_line_search
             num_local_search_iters, value);
     }
 
+    // ---- knowledge gradient on a discrete set (include/sls_hip.h sls_kg_*; Frazier et al. 2009, Scott et al. 2011) ----
+    namespace
+    {
+        // the snapshot of the fixed points for the length of one call
+        struct KgObject
+        {
+            sls_kg* h = nullptr;
+            KgObject(const Regressor& r, const MatrixXd& ref_points)
+            {
+                if (ref_points.rows() != static_cast<long>(r.GetNumDims()) || ref_points.cols() < 1)
+                    throw std::invalid_argument("acquisition_func: ref_points must be D x K, K >= 1");
+                device::Check(sls_kg_create(RequireHandle(r), ref_points.data(), static_cast<int>(ref_points.cols()), &h), "sls_kg_create");
+            }
+            ~KgObject() { sls_kg_destroy(h); }
+            KgObject(const KgObject&)            = delete;
+            KgObject& operator=(const KgObject&) = delete;
+        };
+    }   // namespace
+
+    MatrixXd acquisition_func::KnowledgeGradientReferencePoints(const Regressor& regressor)
+    {
+        const MatrixXd& X = regressor.GetLargeX();
+        const long      N = X.cols();
+        if (N <= SLS_KG_MAX_POINTS) return X;
+        VectorXd mu(N);
+        device::Check(sls_gp_predict(RequireHandle(regressor), X.data(), static_cast<int>(N), mu.data(), nullptr), "sls_gp_predict");
+        std::vector<long> order(static_cast<size_t>(N));
+        for (long i = 0; i < N; ++i) order[static_cast<size_t>(i)] = i;
+        // the SLS_KG_MAX_POINTS highest means, ties to the lower index, kept in increasing index order
+        std::stable_sort(order.begin(), order.end(), [&](long p, long q) { return mu(p) > mu(q); });
+        order.resize(SLS_KG_MAX_POINTS);
+        std::sort(order.begin(), order.end());
+        MatrixXd R(X.rows(), SLS_KG_MAX_POINTS);
+        for (long k = 0; k < SLS_KG_MAX_POINTS; ++k)
+            for (long d = 0; d < X.rows(); ++d) R(d, k) = X(d, order[static_cast<size_t>(k)]);
+        return R;
+    }
+
+    VectorXd acquisition_func::CalcKnowledgeGradients(const Regressor& regressor, const MatrixXd& Xs, const MatrixXd& ref_points,
+                                                      MatrixXd* grad, const bool include_candidate)
+    {
+        const long M = Xs.cols();
+        VectorXd   v = VectorXd::Zero(M);
+        if (grad) *grad = MatrixXd::Zero(Xs.rows(), M);
+        if (regressor.GetSmallY().rows() == 0 || M == 0) return v;
+        const KgObject k(regressor, ref_points);
+        device::Check(sls_kg_eval(k.h, FutureNoise(regressor), include_candidate ? 1 : 0, Xs.data(), static_cast<int>(M), v.data(),
+                                  grad ? grad->data() : nullptr, nullptr),
+                      "sls_kg_eval");
+        return v;
+    }
+
+    VectorXd acquisition_func::FindNextPointByKnowledgeGradientFromStarts(const Regressor& regressor, const MatrixXd& ref_points,
+                                                                          const MatrixXd& starts, const unsigned num_local_search_iters,
+                                                                          double* value, const bool include_candidate)
+    {
+        VectorXd             x(starts.rows());
+        double               v     = 0.0;
+        long                 idx   = 0;
+        const sls_lbfgs_opts lopts = LocalSearchOpts();   // GetLocalSearchTolerances
+        const KgObject       k(regressor, ref_points);
+        device::Check(sls_kg_maximize(k.h, FutureNoise(regressor), include_candidate ? 1 : 0, starts.data(), static_cast<int>(starts.cols()),
+                                      std::max(1, static_cast<int>(num_local_search_iters)), &lopts, 0, x.data(), &v, &idx, nullptr,
+                                      nullptr),
+                      "sls_kg_maximize");
+        if (value) *value = v;
+        return x;
+    }
+
+    VectorXd acquisition_func::FindNextPointByKnowledgeGradient(const Regressor& regressor, const unsigned num_global_search_iters,
+                                                                const unsigned num_local_search_iters, const unsigned long long seed,
+                                                                double* value)
+    {
+        return FindNextPointByKnowledgeGradientFromStarts(
+            regressor, KnowledgeGradientReferencePoints(regressor),
+            SeededStarts(regressor.GetNumDims(), std::max(1u, num_global_search_iters), seed), num_local_search_iters, value);
+    }
+
     // ---- expected utility of the best option of a query pair (include/sls_hip.h sls_eubo_*; Astudillo et al. 2023) ----
     namespace
     {
