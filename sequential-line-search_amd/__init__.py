@@ -141,6 +141,29 @@ def _p(a):
     return a.ctypes.data_as(_dp)
 
 
+def _eval_call(call, block, rows, want_grad, *extras):
+    """call(block, M, val, grad, *extras) at the M columns of block: values (M,), then with want_grad the gradient (rows, M), then
+    those of `extras` (further output arrays of the call; None: not asked for) that were asked for.  The values alone are not a tuple."""
+    M = block.shape[1]
+    val = np.empty(M)
+    grad = np.empty((rows, M), order="F") if want_grad else None
+    _ck(call(_p(block), M, _p(val), _p(grad) if want_grad else None,
+             *(None if e is None else e.ctypes.data_as(C.c_void_p) for e in extras)))
+    out = (val,) + tuple(a for a in (grad,) + extras if a is not None)
+    return out if len(out) > 1 else val
+
+
+def _maximize_call(call, block, rows, n_local, offset, want_all, opts):
+    """call(starts, S, n_local, opts, offset, x, value, index, x_stars, y_stars) from the S columns of block (rows x S)."""
+    S = block.shape[1]
+    x, val, idx = np.empty(rows), C.c_double(), C.c_long()
+    xs = np.empty((rows, S), order="F") if want_all else None
+    ys = np.empty(S) if want_all else None
+    _ck(call(_p(block), S, int(n_local), C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val),
+             C.byref(idx), _p(xs) if want_all else None, _p(ys) if want_all else None))
+    return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+
+
 class Context:
     def __init__(self, device=0):
         self.h = C.c_void_p()
@@ -363,33 +386,16 @@ class GP:
         return dm, ds
 
     def acq_eval(self, Xs, acq=ACQ_EI, ucb_h=1.0, want_grad=True):
-        Xs = _f(Xs)
-        M = Xs.shape[1]
-        val = np.empty(M)
-        grad = np.empty((self.D, M), order="F") if want_grad else None
-        _ck(lib().sls_acq_eval(self.h, int(acq), C.c_double(ucb_h), _p(Xs), M, _p(val), _p(grad) if want_grad else None))
-        return (val, grad) if want_grad else val
+        return _eval_call(lambda *a: lib().sls_acq_eval(self.h, int(acq), C.c_double(ucb_h), *a), _f(Xs), self.D, want_grad)
 
     def acq_maximize(self, starts, n_local, acq=ACQ_EI, ucb_h=1.0, offset=0, want_all=True, opts=None):
-        starts = _f(starts)
-        S = starts.shape[1]
-        x, val, idx = np.empty(self.D), C.c_double(), C.c_long()
-        xs = np.empty((self.D, S), order="F") if want_all else None
-        ys = np.empty(S) if want_all else None
-        _ck(lib().sls_acq_maximize(self.h, int(acq), C.c_double(ucb_h), _p(starts), S, int(n_local),
-                                   C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val),
-                                   C.byref(idx), _p(xs) if want_all else None, _p(ys) if want_all else None))
-        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+        return _maximize_call(lambda *a: lib().sls_acq_maximize(self.h, int(acq), C.c_double(ucb_h), *a), _f(starts), self.D, n_local,
+                              offset, want_all, opts)
 
     def acq_eval_pair(self, sigma_gp, Xs, acq=ACQ_EI, ucb_h=1.0, want_grad=True):
         """objective_for_multiple_points: mean (and mu+) from this handle, deviation from `sigma_gp`."""
-        Xs = _f(Xs)
-        M = Xs.shape[1]
-        val = np.empty(M)
-        grad = np.empty((self.D, M), order="F") if want_grad else None
-        _ck(lib().sls_acq_eval_pair(self.h, sigma_gp.h, int(acq), C.c_double(ucb_h), _p(Xs), M, _p(val),
-                                    _p(grad) if want_grad else None))
-        return (val, grad) if want_grad else val
+        return _eval_call(lambda *a: lib().sls_acq_eval_pair(self.h, sigma_gp.h, int(acq), C.c_double(ucb_h), *a), _f(Xs), self.D,
+                          want_grad)
 
     def acq_maximize_pair(self, sigma_gp, starts, n_local, acq=ACQ_EI, ucb_h=1.0):
         starts = _f(starts)
@@ -407,24 +413,14 @@ class GP:
 
     def mes_eval(self, y_star, Xs, want_grad=True):
         """Max-value entropy search at the columns of Xs on the samples y_star of the maximum value (sls_mes_eval)."""
-        y_star, Xs = _f(y_star).ravel(), _f(Xs)
-        M = Xs.shape[1]
-        val = np.empty(M)
-        grad = np.empty((self.D, M), order="F") if want_grad else None
-        _ck(lib().sls_mes_eval(self.h, _p(y_star), y_star.size, _p(Xs), M, _p(val), _p(grad) if want_grad else None))
-        return (val, grad) if want_grad else val
+        y_star = _f(y_star).ravel()
+        return _eval_call(lambda *a: lib().sls_mes_eval(self.h, _p(y_star), y_star.size, *a), _f(Xs), self.D, want_grad)
 
     def mes_maximize(self, y_star, starts, n_local, offset=0, want_all=True, opts=None):
         """acq_maximize with max-value entropy search on the samples y_star as the objective (sls_mes_maximize)."""
-        y_star, starts = _f(y_star).ravel(), _f(starts)
-        S = starts.shape[1]
-        x, val, idx = np.empty(self.D), C.c_double(), C.c_long()
-        xs = np.empty((self.D, S), order="F") if want_all else None
-        ys = np.empty(S) if want_all else None
-        _ck(lib().sls_mes_maximize(self.h, _p(y_star), y_star.size, _p(starts), S, int(n_local),
-                                   C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val),
-                                   C.byref(idx), _p(xs) if want_all else None, _p(ys) if want_all else None))
-        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+        y_star = _f(y_star).ravel()
+        return _maximize_call(lambda *a: lib().sls_mes_maximize(self.h, _p(y_star), y_star.size, *a), _f(starts), self.D, n_local, offset,
+                              want_all, opts)
 
     def jes_create(self, x_star, f_star, star_noise=0.0):
         """The snapshot of K sampled optima (x_star (D, K), f_star (K,)) joint entropy search conditions on (sls_jes_create)."""
@@ -440,11 +436,7 @@ class GP:
         pairs = _f(pairs)
         if pairs.ndim != 2 or pairs.shape[0] != 2 * self.D:
             raise SlsError(f"eubo_eval: pairs must be 2D x M = {2 * self.D} x M, got {pairs.shape}")
-        M = pairs.shape[1]
-        val = np.empty(M)
-        grad = np.empty((2 * self.D, M), order="F") if want_grad else None
-        _ck(lib().sls_eubo_eval(self.h, _p(pairs), M, _p(val), _p(grad) if want_grad else None))
-        return (val, grad) if want_grad else val
+        return _eval_call(lambda *a: lib().sls_eubo_eval(self.h, *a), pairs, 2 * self.D, want_grad)
 
     def eubo_maximize(self, starts, n_local, offset=0, want_all=True, opts=None):
         """acq_maximize over [0,1]^(2D) with the pair objective of eubo_eval (sls_eubo_maximize): starts 2D x S, x and x_stars have
@@ -452,26 +444,14 @@ class GP:
         starts = _f(starts)
         if starts.ndim != 2 or starts.shape[0] != 2 * self.D:
             raise SlsError(f"eubo_maximize: starts must be 2D x S = {2 * self.D} x S, got {starts.shape}")
-        S = starts.shape[1]
-        x, val, idx = np.empty(2 * self.D), C.c_double(), C.c_long()
-        xs = np.empty((2 * self.D, S), order="F") if want_all else None
-        ys = np.empty(S) if want_all else None
-        _ck(lib().sls_eubo_maximize(self.h, _p(starts), S, int(n_local), C.byref(opts) if opts is not None else None,
-                                    C.c_long(offset), _p(x), C.byref(val), C.byref(idx), _p(xs) if want_all else None,
-                                    _p(ys) if want_all else None))
-        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+        return _maximize_call(lambda *a: lib().sls_eubo_maximize(self.h, *a), starts, 2 * self.D, n_local, offset, want_all, opts)
 
     # ---- maximisation over affine subspaces (sls_*_sub): maps is a SubMaps (or its C struct), Z / starts_z are d x M / d x S
     def _eval_sub(self, call, maps, Z, want_grad, want_x):
         s = _sub_struct(maps)
         Z = _f(Z)
-        rows, M = max(1, s.d), Z.shape[1]
-        val = np.empty(M)
-        grad = np.empty((rows, M), order="F") if want_grad else None
-        X = np.empty((self.D, M), order="F") if want_x else None
-        _ck(call(C.byref(s), _p(Z), M, _p(val), _p(grad) if want_grad else None, _p(X) if want_x else None))
-        out = (val,) + ((grad,) if want_grad else ()) + ((X,) if want_x else ())
-        return out if len(out) > 1 else val
+        X = np.empty((self.D, Z.shape[1]), order="F") if want_x else None
+        return _eval_call(lambda *a: call(C.byref(s), *a), Z, max(1, s.d), want_grad, X)
 
     def _maximize_sub(self, call, maps, starts_z, n_local, offset, want_all, opts):
         s = _sub_struct(maps)
@@ -553,26 +533,13 @@ class JesOptima:
         """alpha at the columns of Xs: values (M,), then with want_grad the gradient (D, M), then with want_cov the posterior
         covariances c_k(x_m) (M, K)."""
         Xs = _f(Xs)
-        M = Xs.shape[1]
-        val = np.empty(M)
-        grad = np.empty((self.D, M), order="F") if want_grad else None
-        cov = np.empty((M, self.K), order="F") if want_cov else None
-        _ck(lib().sls_jes_eval(self.h, C.c_double(noise_var), _p(Xs), M, _p(val), _p(grad) if want_grad else None,
-                               _p(cov) if want_cov else None))
-        out = (val,) + ((grad,) if want_grad else ()) + ((cov,) if want_cov else ())
-        return out if len(out) > 1 else val
+        cov = np.empty((Xs.shape[1], self.K), order="F") if want_cov else None
+        return _eval_call(lambda *a: lib().sls_jes_eval(self.h, C.c_double(noise_var), *a), Xs, self.D, want_grad, cov)
 
     def maximize(self, starts, n_local, noise_var, offset=0, want_all=True, opts=None):
         """acq_maximize with joint entropy search as the objective (sls_jes_maximize)."""
-        starts = _f(starts)
-        S = starts.shape[1]
-        x, val, idx = np.empty(self.D), C.c_double(), C.c_long()
-        xs = np.empty((self.D, S), order="F") if want_all else None
-        ys = np.empty(S) if want_all else None
-        _ck(lib().sls_jes_maximize(self.h, C.c_double(noise_var), _p(starts), S, int(n_local),
-                                   C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val), C.byref(idx),
-                                   _p(xs) if want_all else None, _p(ys) if want_all else None))
-        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+        return _maximize_call(lambda *a: lib().sls_jes_maximize(self.h, C.c_double(noise_var), *a), _f(starts), self.D, n_local, offset,
+                              want_all, opts)
 
 
 KG_MAX_POINTS = 1024      # SLS_KG_MAX_POINTS
@@ -611,26 +578,14 @@ class KnowledgeGradient:
         """KG at the columns of Xs: values (M,), then with want_grad the gradient (D, M), then with want_slopes the slopes b_k(x_m)
         (M, K)."""
         Xs = _f(Xs)
-        M = Xs.shape[1]
-        val = np.empty(M)
-        grad = np.empty((self.D, M), order="F") if want_grad else None
-        slope = np.empty((M, self.K), order="F") if want_slopes else None
-        _ck(lib().sls_kg_eval(self.h, C.c_double(noise_var), int(bool(include_self)), _p(Xs), M, _p(val),
-                              _p(grad) if want_grad else None, _p(slope) if want_slopes else None))
-        out = (val,) + ((grad,) if want_grad else ()) + ((slope,) if want_slopes else ())
-        return out if len(out) > 1 else val
+        slope = np.empty((Xs.shape[1], self.K), order="F") if want_slopes else None
+        return _eval_call(lambda *a: lib().sls_kg_eval(self.h, C.c_double(noise_var), int(bool(include_self)), *a), Xs, self.D, want_grad,
+                          slope)
 
     def maximize(self, starts, n_local, noise_var, include_self=True, offset=0, want_all=True, opts=None):
         """acq_maximize with the knowledge gradient as the objective (sls_kg_maximize)."""
-        starts = _f(starts)
-        S = starts.shape[1]
-        x, val, idx = np.empty(self.D), C.c_double(), C.c_long()
-        xs = np.empty((self.D, S), order="F") if want_all else None
-        ys = np.empty(S) if want_all else None
-        _ck(lib().sls_kg_maximize(self.h, C.c_double(noise_var), int(bool(include_self)), _p(starts), S, int(n_local),
-                                  C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x), C.byref(val), C.byref(idx),
-                                  _p(xs) if want_all else None, _p(ys) if want_all else None))
-        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+        return _maximize_call(lambda *a: lib().sls_kg_maximize(self.h, C.c_double(noise_var), int(bool(include_self)), *a), _f(starts),
+                              self.D, n_local, offset, want_all, opts)
 
 
 QEUBO_MAX_OPTIONS = 16   # SLS_QEUBO_MAX_OPTIONS
@@ -734,24 +689,12 @@ class PathSamples:
     def _set_eval(self, call, rows, q, block, want_grad, want_wins, *lead_args, grid=None):
         """call(h, q, *lead_args, block, M, val, grad, wins) at the M columns of block (with grid = (qs, qt) in the place of q = qs qt):
         values (M,), then with want_grad the gradient (rows, M), then with want_wins the win counts (q, M) int32."""
-        M = block.shape[1]
-        val = np.empty(M)
-        grad = np.empty((rows, M), order="F") if want_grad else None
-        wins = np.zeros((q, M), dtype=np.int32, order="F") if want_wins else None
-        _ck(call(self.h, *(grid or (q,)), *lead_args, _p(block), M, _p(val), _p(grad) if want_grad else None,
-                 wins.ctypes.data_as(C.POINTER(C.c_int)) if want_wins else None))
-        out = (val,) + ((grad,) if want_grad else ()) + ((wins,) if want_wins else ())
-        return out if len(out) > 1 else val
+        wins = np.zeros((q, block.shape[1]), dtype=np.int32, order="F") if want_wins else None
+        return _eval_call(lambda *a: call(self.h, *(grid or (q,)), *lead_args, *a), block, rows, want_grad, wins)
 
     def _set_maximize(self, call, rows, block, n_local, offset, want_all, opts, *lead_args):
         """call(h, *lead_args, starts, S, n_local, opts, offset, x, value, index, x_stars, y_stars) from the S columns of block."""
-        S = block.shape[1]
-        x, val, idx = np.empty(rows), C.c_double(), C.c_long()
-        xs = np.empty((rows, S), order="F") if want_all else None
-        ys = np.empty(S) if want_all else None
-        _ck(call(self.h, *lead_args, _p(block), S, int(n_local), C.byref(opts) if opts is not None else None, C.c_long(offset), _p(x),
-                 C.byref(val), C.byref(idx), _p(xs) if want_all else None, _p(ys) if want_all else None))
-        return dict(index=idx.value, x=x, value=val.value, x_stars=xs, y_stars=ys)
+        return _maximize_call(lambda *a: call(self.h, *lead_args, *a), block, rows, n_local, offset, want_all, opts)
 
     def qeubo_eval(self, sets, q, want_grad=True, want_wins=False):
         """Expected utility of the best of q options on the draws (sls_qeubo_eval) at the columns of sets (qD x M: rows iD..iD+D-1 =
@@ -845,14 +788,9 @@ class PathSamples:
         q = self._set_block("qbald_eval", q, sets, "sets")
         tau = self._scale("qbald_eval", scale)
         M = sets.shape[1]
-        val = np.empty(M)
-        grad = np.empty((q * self.D, M), order="F") if want_grad else None
         prob = np.zeros((q, M), order="F") if want_prob else None
         wins = np.zeros((q, M), dtype=np.int32, order="F") if want_wins else None
-        _ck(lib().sls_qbald_eval(self.h, q, tau, _p(sets), M, _p(val), _p(grad) if want_grad else None, _p(prob) if want_prob else None,
-                                 wins.ctypes.data_as(C.POINTER(C.c_int)) if want_wins else None))
-        out = (val,) + ((grad,) if want_grad else ()) + ((prob,) if want_prob else ()) + ((wins,) if want_wins else ())
-        return out if len(out) > 1 else val
+        return _eval_call(lambda *a: lib().sls_qbald_eval(self.h, q, tau, *a), sets, q * self.D, want_grad, prob, wins)
 
     def qbald_maximize(self, starts, q, n_local, scale=QBALD_SCALE, offset=0, want_all=True, opts=None):
         """acq_maximize over [0,1]^(qD) with the set objective of qbald_eval (sls_qbald_maximize): starts qD x S, x and x_stars have

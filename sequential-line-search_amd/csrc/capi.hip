@@ -947,15 +947,15 @@ static void eval_block_to_host(const EvalOut& want, const EvalOut& at, int D, in
     cm_to_host(at.mu, at.ldo, 1, M, want.mu); cm_to_host(at.sigma, at.ldo, 1, M, want.sigma); cm_to_host(at.val, at.ldo, 1, M, want.val);
     cm_to_host(at.dmu, at.ldo, D, M, want.dmu); cm_to_host(at.dsigma, at.ldo, D, M, want.dsigma); cm_to_host(at.grad, at.ldo, D, M, want.grad);
 }
-// n doubles of device memory where the host can read them on return: the handle's page-locked staging block when they fit,
-// `pageable` otherwise; ONE synchronisation
+// where a call's downloads land: the handle's page-locked staging block when n doubles fit, `pageable` otherwise
+static double* host_stage(sls_gp* g, size_t n, std::vector<double>& pageable) {
+    if (n <= IO_STAGE_MAX) return g->io_stage(n);
+    pageable.resize(n);
+    return pageable.data();
+}
+// n doubles of device memory where the host can read them on return; ONE synchronisation
 static double* fetch(sls_gp* g, const double* dev, size_t n, std::vector<double>& pageable) {
-    double* t;
-    if (n <= IO_STAGE_MAX) t = g->io_stage(n);
-    else {
-        pageable.resize(n);
-        t = pageable.data();
-    }
+    double* t = host_stage(g, n, pageable);
     d2h(g->ctx, t, dev, n);
     sync(g->ctx);
     return t;
@@ -1040,16 +1040,6 @@ static bool eval_in_slot(sls_gp* g, const double* Xs, int M, const EvalOut& want
     return true;
 }
 
-// value (+ gradient) of the acquisition at candidate-major points xr; gs != nullptr: sigma / dsigma come from gs
-// (objective_for_multiple_points, src/acquisition-function.cpp:63-110)
-// mes != nullptr: max-value entropy search instead (acq_type, ucb_h and gs are not used): mu, sigma and their gradients of g in the
-// handle's pair blocks, then the MES combiner on the y* samples
-// acq_type SLS_ACQ_LOG_EXPECTED_IMPROVEMENT: mu / dmu of g and sigma / dsigma of gs (of g if there is none) in g's pair blocks, then the
-// LogEI combiner with g's mu_best
-struct MesSamples {
-    const double* y_star;   // device, K doubles
-    int K;
-};
 // mu / dmu of g and sigma / dsigma of gs (of g when there is no gs) at the S points into g's pair blocks, leading dimension ldo
 static void eval_pair_blocks(sls_gp* g, sls_gp* gs, const double* xr, long ldr, int S, bool want_grad, long ldo) {
     const size_t D = g->D;
@@ -1063,21 +1053,22 @@ static void eval_pair_blocks(sls_gp* g, sls_gp* gs, const double* xr, long ldr, 
     eval_candidates(g, xr, ldr, S, a);
     if (gs) eval_candidates(gs, xr, ldr, S, b);
 }
+// value (+ gradient) of the acquisition at candidate-major points xr; gs != nullptr: sigma / dsigma come from gs
+// (objective_for_multiple_points, src/acquisition-function.cpp:63-110)
+// acq_type SLS_ACQ_LOG_EXPECTED_IMPROVEMENT: mu / dmu of g and sigma / dsigma of gs (of g if there is none) in g's pair blocks, then the
+// LogEI combiner with g's mu_best
 static void eval_acq(sls_gp* g, sls_gp* gs, const double* xr, long ldr, int S, int acq_type, double ucb_h, double* val,
-                     double* grad, long ldo, const MesSamples* mes = nullptr) {
+                     double* grad, long ldo) {
     sls_ctx* c = g->ctx;
-    if (!mes && !gs && acq_type != SLS_ACQ_LOG_EXPECTED_IMPROVEMENT) {   // EI / UCB of one handle: finalize forms them itself
+    if (!gs && acq_type != SLS_ACQ_LOG_EXPECTED_IMPROVEMENT) {   // EI / UCB of one handle: finalize forms them itself
         EvalOut eo;
         eo.ldo = ldo; eo.val = val; eo.grad = grad; eo.acq = acq_type; eo.ucb_h = ucb_h;
         eval_candidates(g, xr, ldr, S, eo);
         return;
     }
-    eval_pair_blocks(g, mes ? nullptr : gs, xr, ldr, S, grad != nullptr, ldo);
+    eval_pair_blocks(g, gs, xr, ldr, S, grad != nullptr, ldo);
     const double *mu = g->pair_mu.p, *sg = g->pair_sg.p, *dmu = g->pair_dmu.p, *dsg = g->pair_dsg.p;
-    if (mes) {
-        ProfScope ps(c, "mes");
-        launch_mes_combine(c->stream, S, g->D, ldo, mu, sg, dmu, dsg, mes->y_star, mes->K, val, grad);
-    } else if (acq_type == SLS_ACQ_LOG_EXPECTED_IMPROVEMENT) {
+    if (acq_type == SLS_ACQ_LOG_EXPECTED_IMPROVEMENT) {
         ProfScope ps(c, "logei");
         launch_logei_combine(c->stream, S, g->D, ldo, mu, sg, dmu, dsg, g->mu_best, val, grad);
     } else {
@@ -1085,24 +1076,84 @@ static void eval_acq(sls_gp* g, sls_gp* gs, const double* xr, long ldr, int S, i
     }
 }
 
-// eval_acq at M >= 1 host-supplied points (D x M column-major) through the transposing upload, results to the caller's arrays
-static void eval_acq_points(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, const double* Xs, int M, double* val, double* grad,
-                            const MesSamples* mes = nullptr) {
-    const int Mp = round_up(M, 128), D = g->D;
-    upload_candidates(g, Xs, D, M, Mp);
-    std::vector<double> unused;   // the combiners always write the values
-    if (!val) unused.resize(M);
-    EvalOut want;
-    want.val = val ? val : unused.data(); want.grad = grad;
-    g->outv.ensure(eval_block_doubles(want, D, Mp));
-    const EvalOut o = eval_block(want, g->outv.p, D, Mp);
-    eval_acq(g, gs, g->raw.p, Mp, M, acq_type, ucb_h, o.val, o.grad, Mp, mes);
-    download_block(g, want, g->outv.p, D, M, Mp);
+// ---- objectives on a handle and their front ends ---------------------------------------------------------------------------------
+// What the two front ends (eval_points, maximize_starts) need to know of an acquisition.  A new acquisition constructs one of these
+// and has its eval / maximize entry points, and through sub_objective its *_sub ones.
+template <class Eval>
+struct Objective {
+    sls_gp* g;        // the handle whose workspace (raw, outv, lb, io), statistics and locks the call uses
+    int nvar;         // rows of the caller's points / starts: D; 2D for query pairs; d for a subspace
+    BestBlock best;   // the winner's block of a maximisation, 8 + nvar doubles
+    // eval(xr, ldr, count, live, val, grad, ldo): value and gradient (may be nullptr) at the candidate-major points xr[n + r*ldr],
+    // n < count, on the context's stream; live: as lockstep_rounds hands it over (only sub_objective reads it)
+    Eval eval;
+    int wave_acq;     // plain EI / UCB of the handle: the acq_type of the one-launch search (maximize_wave); -1 for everything else
+    double ucb_h;
+};
+template <class Eval>
+static Objective<Eval> objective(sls_gp* g, int nvar, BestBlock best, Eval eval, int wave_acq = -1, double ucb_h = 0.0) {
+    return Objective<Eval>{g, nvar, best, eval, wave_acq, ucb_h};
 }
+static BestBlock sum_best(sls_gp* g) { return BestBlock{g->sum.dev + 8, g->sum.host + 8, false}; }   // nvar <= D
 
 static bool known_acq(int acq_type) {
     return acq_type == SLS_ACQ_EXPECTED_IMPROVEMENT || acq_type == SLS_ACQ_GP_UCB || acq_type == SLS_ACQ_LOG_EXPECTED_IMPROVEMENT;
 }
+// EI / UCB / LogEI of g, with sigma from gs when there is one (the *_pair entry points)
+static auto acq_objective(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h) {
+    SLS_REQUIRE(known_acq(acq_type), "unknown acquisition type %d", acq_type);
+    // (the wave kernel has neither the pair nor the LogEI objective)
+    const bool plain = !gs && acq_type != SLS_ACQ_LOG_EXPECTED_IMPROVEMENT;
+    return objective(
+        g, g->D, sum_best(g),
+        [=](const double* xr, long ldr, int n, const int*, double* val, double* grad, long ldo) {
+            eval_acq(g, gs, xr, ldr, n, acq_type, ucb_h, val, grad, ldo);
+        },
+        plain ? acq_type : -1, ucb_h);
+}
+
+// One more block of a point call: rows x Mp candidate-major doubles at dev->p once the evaluation has run (it may grow the block), back
+// to the caller as rows x M column-major (transposed) or as they are, [m + r*M]
+struct ExtraBlock {
+    const DBuf* dev = nullptr;
+    int rows = 0;
+    double* host = nullptr;   // NULL: not asked for
+    bool transposed = false;
+};
+
+// THE LOCKING RULE of every route through the two front ends: the context's lock and the handle's device first (the entry point's
+// CtxCall), then the handle's state_mtx shared (here).  Mutators take the same two in the same order, state_mtx exclusively; only the
+// slot path (eval_in_slot) has an order of its own, written down there.  Objects derived from a handle (sls_jes, sls_kg) check its
+// generation under the context's lock, which every mutator holds.
+//
+// The objective at M >= 1 host points (nvar x M column-major) through the transposing upload; value (val == NULL: computed into
+// scratch, the combiners always write it), gradient (nvar x M, may be NULL) and `extra` to the caller's arrays.  Two synchronisations:
+// behind the upload, and ONE behind every download.
+template <class Obj>
+static void eval_points(const Obj& f, const double* pts, int M, double* val, double* grad, const ExtraBlock& extra = ExtraBlock()) {
+    sls_gp* g = f.g;
+    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
+    const int Mp = round_up(M, 128), nvar = f.nvar;
+    upload_candidates(g, pts, nvar, M, Mp);
+    std::vector<double> unused;
+    if (!val) unused.resize(M);
+    EvalOut want;
+    want.val = val ? val : unused.data(); want.grad = grad;
+    const size_t n = eval_block_doubles(want, nvar, Mp), ne = extra.host ? (size_t)extra.rows * Mp : 0;
+    g->outv.ensure(n);
+    const EvalOut o = eval_block(want, g->outv.p, nvar, Mp);
+    f.eval(g->raw.p, (long)Mp, M, nullptr, o.val, o.grad, (long)Mp);
+    std::vector<double> pageable;
+    double* t = host_stage(g, n + ne, pageable);
+    d2h(g->ctx, t, g->outv.p, n);
+    if (ne) d2h(g->ctx, t + n, extra.dev->p, ne);
+    sync(g->ctx);
+    eval_block_to_host(want, eval_block(want, t, nvar, Mp), nvar, M);
+    if (ne && extra.transposed) cm_to_host(t + n, Mp, extra.rows, M, extra.host);
+    else
+        for (int r = 0; ne && r < extra.rows; ++r) std::copy(t + n + (size_t)r * Mp, t + n + (size_t)r * Mp + M, extra.host + (size_t)r * M);
+}
+
 // The body of sls_gp_predict, sls_gp_predict_grad and sls_acq_eval: `want` names the caller's arrays (any may be NULL).
 static int eval_entry(const char* who, sls_gp* g, const double* Xs, int M, const EvalOut& want) {
     SLS_TRY
@@ -1115,7 +1166,7 @@ static int eval_entry(const char* who, sls_gp* g, const double* Xs, int M, const
     SLS_REQUIRE(known_acq(want.acq), "unknown acquisition type %d", want.acq);
     if (M == 0) return SLS_OK;
     if (logei) {
-        eval_acq_points(g, nullptr, want.acq, want.ucb_h, Xs, M, want.val, want.grad);
+        eval_points(acq_objective(g, nullptr, want.acq, want.ucb_h), Xs, M, want.val, want.grad);
         return SLS_OK;
     }
     sls_ctx* c = g->ctx;
@@ -1221,37 +1272,38 @@ static auto staged_fetch(sls_gp* g, std::vector<double>& pageable) {
     return [g, &pageable](const double* dev, size_t n) { return fetch(g, dev, n, pageable); };
 }
 
-// The body of sls_acq_maximize, _pair, _dev and sls_mes_maximize (`who`): the shared maximiser (lbfgs_driver.hpp) with one of two
-// searches, and the handle's mapped block for the best start -- one launch, one synchronisation, no copies.
-// starts: D x S column-major, on the host (uploaded here) or already on the device.
-static void maximize_impl(const char* who, sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, const double* starts, bool starts_on_host,
-                          int S, int n_local, const sls_lbfgs_opts* opts_in, long off, double* x_out, double* val_out, long* idx_out,
-                          double* x_stars, double* y_stars, const MesSamples* mes = nullptr) {
+// The body of every *_maximize entry point on an sls_gp handle (`who`), under the locking rule of eval_points: the shared maximiser
+// (lbfgs_driver.hpp) with one of two searches, and a mapped block for the best start -- one synchronisation, no copies.
+// starts: nvar x S column-major, on the host (uploaded here) or already on the device.  The outputs and the return value are
+// maximize_finish's; the starts' end variables stay in f.g->lb.x (leading dimension round_up(S, 128)).
+template <class Obj>
+static long maximize_starts(const char* who, const Obj& f, const double* starts, bool starts_on_host, int S, int n_local,
+                            const sls_lbfgs_opts* opts_in, long off, double* x_out, double* val_out, long* idx_out, double* x_stars,
+                            double* y_stars) {
+    sls_gp* g = f.g;
     sls_ctx* c = g->ctx;
-    SLS_REQUIRE(mes || known_acq(acq_type), "unknown acquisition type %d", acq_type);
-    MultistartRun r = maximize_begin(who, g, g->lb, opts_in, S, n_local, g->D);
+    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
+    MultistartRun r = maximize_begin(who, g, g->lb, opts_in, S, n_local, f.nvar);
     DBuf sd;
     if (starts_on_host) {
-        sd.ensure((size_t)g->D * S);
-        h2d(c, sd.p, starts, (size_t)g->D * S);
+        sd.ensure((size_t)f.nvar * S);
+        h2d(c, sd.p, starts, (size_t)f.nvar * S);
     }
     const double* starts_dev = starts_on_host ? sd.p : starts;
     LockstepStats ls;
-    // (the wave kernel has neither the MES nor the LogEI objective: those always take the general path)
-    if (!gs && !mes && acq_type != SLS_ACQ_LOG_EXPECTED_IMPROVEMENT && wave_path_applies(g, S)) {
+    if (f.wave_acq >= 0 && wave_path_applies(g, S)) {
         // Small problems: one wavefront per start runs the whole search in a single launch (kernels_wave.hip)
-        ls.issued_dev = maximize_wave(g, acq_type, ucb_h, starts_dev, r);
+        ls.issued_dev = maximize_wave(g, f.wave_acq, f.ucb_h, starts_dev, r);
         ls.rounds = n_local;
     } else {
         lockstep_rounds(c, r.st, g->lb, starts_dev, S, n_local,
-                        [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
-                            eval_acq(g, gs, trial, ld, nlive, acq_type, ucb_h, val, grad, ld, mes);
+                        [&](const double* trial, long ld, int nlive, const int* live, double* val, double* grad) {
+                            f.eval(trial, ld, nlive, live, val, grad, ld);
                         },
                         &ls);
     }
     std::vector<double> pageable;
-    maximize_finish(c, r, ls, BestBlock{g->sum.dev + 8, g->sum.host + 8, false}, staged_fetch(g, pageable), off, x_out, val_out,
-                    idx_out, x_stars, y_stars);
+    return maximize_finish(c, r, ls, f.best, staged_fetch(g, pageable), off, x_out, val_out, idx_out, x_stars, y_stars);
 }
 
 extern "C" int sls_acq_last_stats(sls_gp* g, long* evals_issued, long* evals_cap, int* rounds, int* live_at_end) {
@@ -1270,8 +1322,8 @@ extern "C" int sls_acq_maximize(sls_gp* g, int acq_type, double ucb_h, const dou
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g && starts, "sls_acq_maximize: NULL argument");
-    maximize_impl("sls_acq_maximize", g, nullptr, acq_type, ucb_h, starts, true, S, n_local, opts, start_index_offset, x_out, val_out,
-                  idx_out, x_stars, y_stars);
+    maximize_starts("sls_acq_maximize", acq_objective(g, nullptr, acq_type, ucb_h), starts, true, S, n_local, opts, start_index_offset,
+                    x_out, val_out, idx_out, x_stars, y_stars);
     SLS_CATCH
 }
 
@@ -1286,8 +1338,8 @@ extern "C" int sls_acq_maximize_pair(sls_gp* g, sls_gp* gs, int acq_type, double
     CtxCall call_(g);
     check_pair(g, gs);
     SLS_REQUIRE(starts, "sls_acq_maximize_pair: starts is NULL");
-    maximize_impl("sls_acq_maximize_pair", g, gs, acq_type, ucb_h, starts, true, S, n_local, opts, 0, x_out, val_out, idx_out, nullptr,
-                  nullptr);
+    maximize_starts("sls_acq_maximize_pair", acq_objective(g, gs, acq_type, ucb_h), starts, true, S, n_local, opts, 0, x_out, val_out,
+                    idx_out, nullptr, nullptr);
     SLS_CATCH
 }
 
@@ -1297,9 +1349,9 @@ extern "C" int sls_acq_eval_pair(sls_gp* g, sls_gp* gs, int acq_type, double ucb
     CtxCall call_(g);
     check_pair(g, gs);
     SLS_REQUIRE(Xs && M >= 0, "sls_acq_eval_pair: bad argument");
-    SLS_REQUIRE(known_acq(acq_type), "unknown acquisition type %d", acq_type);
+    const auto f = acq_objective(g, gs, acq_type, ucb_h);
     if (M == 0) return SLS_OK;
-    eval_acq_points(g, gs, acq_type, ucb_h, Xs, M, val, grad);
+    eval_points(f, Xs, M, val, grad);
     SLS_CATCH
 }
 
@@ -1309,19 +1361,26 @@ extern "C" int sls_acq_maximize_dev(sls_gp* g, int acq_type, double ucb_h, const
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g && starts_dev, "sls_acq_maximize_dev: NULL argument");
-    maximize_impl("sls_acq_maximize_dev", g, nullptr, acq_type, ucb_h, starts_dev, false, S, n_local, opts, start_index_offset, x_out,
-                  val_out, idx_out, nullptr, nullptr);
+    maximize_starts("sls_acq_maximize_dev", acq_objective(g, nullptr, acq_type, ucb_h), starts_dev, false, S, n_local, opts,
+                    start_index_offset, x_out, val_out, idx_out, nullptr, nullptr);
     SLS_CATCH
 }
 
 // ---- max-value entropy search (include/sls_hip.h) ------------------------------------------------------------------
-// the y* samples of a call, validated and uploaded once
-static void upload_max_values(const char* who, sls_gp* g, const double* y_star, int K, DBuf& ys) {
+// The MES objective of a call: the y* samples validated and uploaded once into ys (the caller's, alive for the call); mu, sigma and
+// their gradients of g in the handle's pair blocks, then the MES combiner on the samples
+static auto mes_objective(const char* who, sls_gp* g, const double* y_star, int K, DBuf& ys) {
     SLS_REQUIRE(y_star != nullptr, "%s: y_star is NULL", who);
     SLS_REQUIRE(K >= 1 && K <= SLS_MES_MAX_SAMPLES, "%s: K = %d (1 .. %d)", who, K, SLS_MES_MAX_SAMPLES);
     for (int k = 0; k < K; ++k) SLS_REQUIRE(std::isfinite(y_star[k]), "%s: y_star[%d] is not finite", who, k);
     ys.ensure((size_t)K);
     h2d(g->ctx, ys.p, y_star, (size_t)K);
+    const double* ysd = ys.p;
+    return objective(g, g->D, sum_best(g), [=](const double* xr, long ldr, int n, const int*, double* val, double* grad, long ldo) {
+        eval_pair_blocks(g, nullptr, xr, ldr, n, grad != nullptr, ldo);
+        ProfScope ps(g->ctx, "mes");
+        launch_mes_combine(g->ctx->stream, n, g->D, ldo, g->pair_mu.p, g->pair_sg.p, g->pair_dmu.p, g->pair_dsg.p, ysd, K, val, grad);
+    });
 }
 
 // The scalar terms on their own (test hooks): n inputs through `launch(in, m, out)` in chunks, out[k] (device) for the outputs
@@ -1373,15 +1432,14 @@ extern "C" int sls_mes_eval(sls_gp* g, const double* y_star, int K, const double
     SLS_REQUIRE(g != nullptr, "sls_mes_eval: gp is NULL");
     SLS_REQUIRE(M >= 0, "sls_mes_eval: M = %d", M);
     DBuf ys;
-    upload_max_values("sls_mes_eval", g, y_star, K, ys);
+    const auto f = mes_objective("sls_mes_eval", g, y_star, K, ys);
     if (M == 0) {
         sync(g->ctx);
         return SLS_OK;
     }
     SLS_REQUIRE(Xs != nullptr, "sls_mes_eval: Xs is NULL");
     SLS_REQUIRE(val != nullptr, "sls_mes_eval: val is NULL");
-    const MesSamples mes{ys.p, K};
-    eval_acq_points(g, nullptr, 0, 0.0, Xs, M, val, grad, &mes);
+    eval_points(f, Xs, M, val, grad);
     SLS_CATCH
 }
 
@@ -1393,10 +1451,8 @@ extern "C" int sls_mes_maximize(sls_gp* g, const double* y_star, int K, const do
     SLS_REQUIRE(g != nullptr, "sls_mes_maximize: gp is NULL");
     SLS_REQUIRE(starts != nullptr, "sls_mes_maximize: starts is NULL");
     DBuf ys;
-    upload_max_values("sls_mes_maximize", g, y_star, K, ys);
-    const MesSamples mes{ys.p, K};
-    maximize_impl("sls_mes_maximize", g, nullptr, 0, 0.0, starts, true, S, n_local, opts, start_index_offset, x_out, val_out, idx_out,
-                  x_stars, y_stars, &mes);
+    maximize_starts("sls_mes_maximize", mes_objective("sls_mes_maximize", g, y_star, K, ys), starts, true, S, n_local, opts,
+                    start_index_offset, x_out, val_out, idx_out, x_stars, y_stars);
     SLS_CATCH
 }
 
@@ -1492,15 +1548,17 @@ static void pointset_eval_device(PointSet* j, const char* scope, Combine&& combi
     }
 }
 
-static void jes_eval_device(sls_jes* j, double noise_var, const double* xr, long ldr, int S, double* val, double* grad, long ldo,
-                            double* cov_out, long ldc) {
-    pointset_eval_device(
-        j, "jes",
-        [&](int sc, int Sp, long ldk, const double* mu, const double* sigma, int, double* v, double* a_mu, double* a_sg, double* H) {
-            launch_jes_combine(j->ctx->stream, sc, Sp, ldk, mu, sigma, j->cov.p, j->f_star.p, j->dd.p, j->inv_v.p, j->K, noise_var, v, a_mu,
-                               a_sg, H);
-        },
-        xr, ldr, S, val, grad, ldo, cov_out, ldc);
+// The JES objective; cov_out (device, may be nullptr): the covariances of every candidate with the optima, [n + k*ldc]
+static auto jes_objective(sls_jes* j, double noise_var, double* cov_out, long ldc) {
+    return objective(j->gp, j->D, sum_best(j->gp), [=](const double* xr, long ldr, int S, const int*, double* val, double* grad, long ldo) {
+        pointset_eval_device(
+            j, "jes",
+            [&](int sc, int Sp, long ldk, const double* mu, const double* sigma, int, double* v, double* a_mu, double* a_sg, double* H) {
+                launch_jes_combine(j->ctx->stream, sc, Sp, ldk, mu, sigma, j->cov.p, j->f_star.p, j->dd.p, j->inv_v.p, j->K, noise_var, v,
+                                   a_mu, a_sg, H);
+            },
+            xr, ldr, S, val, grad, ldo, cov_out, ldc);
+    });
 }
 
 // the object is what its handle still stands for
@@ -1599,53 +1657,6 @@ extern "C" int sls_jes_terms(sls_ctx* ctx, const double* t, long n, double* tau,
                         [&](const double* in, long m, double* const* out) { launch_jes_terms(ctx->stream, in, m, out[0], out[1]); });
 }
 
-// The bodies of the eval / maximize entry points of a point-set criterion (the argument checks are the caller's).
-// eval(xr, ldr, S, val, grad, ldo, extra, ldc): the criterion's chunk pass; extra: an M x K block the pass fills per candidate and
-// point (candidate-major on the device, [m + k*M] for the caller), may be NULL.
-template <class Eval>
-static void pointset_eval_points(PointSet* j, const double* Xs, int M, double* val, double* grad, double* extra, Eval&& eval) {
-    sls_gp* g = j->gp;
-    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
-    const int Mp = round_up(M, 128), D = g->D, K = j->K;
-    upload_candidates(g, Xs, D, M, Mp);
-    EvalOut want;
-    want.val = val; want.grad = grad;
-    g->outv.ensure(eval_block_doubles(want, D, Mp));
-    const EvalOut o = eval_block(want, g->outv.p, D, Mp);
-    DBuf covd;
-    if (extra) covd.ensure((size_t)Mp * K);
-    eval(g->raw.p, (long)Mp, M, o.val, o.grad, (long)Mp, extra ? covd.p : nullptr, (long)Mp);
-    std::vector<double> covh;
-    if (extra) {
-        covh.resize((size_t)Mp * K);
-        d2h(g->ctx, covh.data(), covd.p, covh.size());
-    }
-    download_block(g, want, g->outv.p, D, M, Mp);   // the call's one synchronisation
-    if (extra)
-        for (int k = 0; k < K; ++k) std::copy(covh.begin() + (size_t)k * Mp, covh.begin() + (size_t)k * Mp + M, extra + (size_t)k * M);
-}
-template <class Eval>
-static void pointset_maximize(const char* who, PointSet* j, const double* starts, int S, int n_local, const sls_lbfgs_opts* opts,
-                              long start_index_offset, double* x_out, double* val_out, long* idx_out, double* x_stars, double* y_stars,
-                              Eval&& eval) {
-    sls_gp* g = j->gp;
-    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
-    sls_ctx* c = g->ctx;
-    MultistartRun r = maximize_begin(who, g, g->lb, opts, S, n_local, g->D);
-    DBuf sd;
-    sd.ensure((size_t)g->D * S);
-    h2d(c, sd.p, starts, (size_t)g->D * S);
-    LockstepStats ls;
-    lockstep_rounds(c, r.st, g->lb, sd.p, S, n_local,
-                    [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
-                        eval(trial, ld, nlive, val, grad, ld, nullptr, 0L);
-                    },
-                    &ls);
-    std::vector<double> pageable;
-    maximize_finish(c, r, ls, BestBlock{g->sum.dev + 8, g->sum.host + 8, false}, staged_fetch(g, pageable), start_index_offset, x_out,
-                    val_out, idx_out, x_stars, y_stars);
-}
-
 extern "C" int sls_jes_eval(sls_jes* j, double noise_var, const double* Xs, int M, double* val, double* grad, double* cov) {
     SLS_TRY
     SLS_REQUIRE(j != nullptr, "sls_jes_eval: j is NULL");
@@ -1656,9 +1667,10 @@ extern "C" int sls_jes_eval(sls_jes* j, double noise_var, const double* Xs, int 
     if (M == 0) return SLS_OK;
     SLS_REQUIRE(Xs != nullptr, "sls_jes_eval: Xs is NULL");
     SLS_REQUIRE(val != nullptr, "sls_jes_eval: val is NULL");
-    pointset_eval_points(j, Xs, M, val, grad, cov, [&](const double* xr, long ldr, int S, double* v, double* gr, long ldo, double* cv, long ldc) {
-        jes_eval_device(j, noise_var, xr, ldr, S, v, gr, ldo, cv, ldc);
-    });
+    const int Mp = round_up(M, 128);
+    DBuf covd;
+    if (cov) covd.ensure((size_t)Mp * j->K);
+    eval_points(jes_objective(j, noise_var, covd.p, Mp), Xs, M, val, grad, ExtraBlock{&covd, j->K, cov});
     SLS_CATCH
 }
 
@@ -1671,10 +1683,8 @@ extern "C" int sls_jes_maximize(sls_jes* j, double noise_var, const double* star
     SLS_REQUIRE(starts != nullptr, "sls_jes_maximize: starts is NULL");
     jes_check_noise("sls_jes_maximize", noise_var);
     jes_check("sls_jes_maximize", j);
-    pointset_maximize("sls_jes_maximize", j, starts, S, n_local, opts, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars,
-                      [&](const double* xr, long ldr, int n, double* v, double* gr, long ldo, double* cv, long ldc) {
-                          jes_eval_device(j, noise_var, xr, ldr, n, v, gr, ldo, cv, ldc);
-                      });
+    maximize_starts("sls_jes_maximize", jes_objective(j, noise_var, nullptr, 0), starts, true, S, n_local, opts, start_index_offset, x_out,
+                    val_out, idx_out, x_stars, y_stars);
     SLS_CATCH
 }
 
@@ -1685,16 +1695,18 @@ struct sls_kg : PointSet {
     int arg_max = 0;
 };
 
-// KG (+ gradient, + the slopes b_k) at S candidate-major points: joint entropy search's chunk pass around launch_kg_combine.
-static void kg_eval_device(sls_kg* k, double noise_var, int include_self, const double* xr, long ldr, int S, double* val, double* grad,
-                           long ldo, double* slope_out, long lds) {
-    pointset_eval_device(
-        k, "kg",
-        [&](int sc, int Sp, long ldk, const double* mu, const double* sigma, int s0, double* v, double* a_mu, double* a_sg, double* H) {
-            launch_kg_combine(k->ctx->stream, sc, Sp, ldk, mu, sigma, k->cov.p, k->mu_star.p, k->a_max, k->K, noise_var, include_self, v,
-                              a_mu, a_sg, H, slope_out ? slope_out + s0 : nullptr, lds);
-        },
-        xr, ldr, S, val, grad, ldo, nullptr, 0);
+// The KG objective: joint entropy search's chunk pass around launch_kg_combine; slope_out (device, may be nullptr): the slopes b_k of
+// every candidate, [n + k*lds]
+static auto kg_objective(sls_kg* k, double noise_var, int include_self, double* slope_out, long lds) {
+    return objective(k->gp, k->D, sum_best(k->gp), [=](const double* xr, long ldr, int S, const int*, double* val, double* grad, long ldo) {
+        pointset_eval_device(
+            k, "kg",
+            [&](int sc, int Sp, long ldk, const double* mu, const double* sigma, int s0, double* v, double* a_mu, double* a_sg, double* H) {
+                launch_kg_combine(k->ctx->stream, sc, Sp, ldk, mu, sigma, k->cov.p, k->mu_star.p, k->a_max, k->K, noise_var, include_self, v,
+                                  a_mu, a_sg, H, slope_out ? slope_out + s0 : nullptr, lds);
+            },
+            xr, ldr, S, val, grad, ldo, nullptr, 0);
+    });
 }
 static void kg_check_noise(const char* who, double noise_var) {
     SLS_REQUIRE(std::isfinite(noise_var) && noise_var >= 0.0, "%s: noise_var = %g (finite, >= 0)", who, noise_var);
@@ -1754,9 +1766,10 @@ extern "C" int sls_kg_eval(sls_kg* k, double noise_var, int include_self, const 
     if (M == 0) return SLS_OK;
     SLS_REQUIRE(Xs != nullptr, "sls_kg_eval: Xs is NULL");
     SLS_REQUIRE(val != nullptr, "sls_kg_eval: val is NULL");
-    pointset_eval_points(k, Xs, M, val, grad, slope, [&](const double* xr, long ldr, int S, double* v, double* gr, long ldo, double* sl, long lds) {
-        kg_eval_device(k, noise_var, include_self != 0, xr, ldr, S, v, gr, ldo, sl, lds);
-    });
+    const int Mp = round_up(M, 128);
+    DBuf sld;
+    if (slope) sld.ensure((size_t)Mp * k->K);
+    eval_points(kg_objective(k, noise_var, include_self != 0, sld.p, Mp), Xs, M, val, grad, ExtraBlock{&sld, k->K, slope});
     SLS_CATCH
 }
 
@@ -1769,10 +1782,8 @@ extern "C" int sls_kg_maximize(sls_kg* k, double noise_var, int include_self, co
     SLS_REQUIRE(starts != nullptr, "sls_kg_maximize: starts is NULL");
     kg_check_noise("sls_kg_maximize", noise_var);
     pointset_check("sls_kg_maximize", "sls_kg_create", k);
-    pointset_maximize("sls_kg_maximize", k, starts, S, n_local, opts, start_index_offset, x_out, val_out, idx_out, x_stars, y_stars,
-                      [&](const double* xr, long ldr, int n, double* v, double* gr, long ldo, double* sl, long lds) {
-                          kg_eval_device(k, noise_var, include_self != 0, xr, ldr, n, v, gr, ldo, sl, lds);
-                      });
+    maximize_starts("sls_kg_maximize", kg_objective(k, noise_var, include_self != 0, nullptr, 0), starts, true, S, n_local, opts,
+                    start_index_offset, x_out, val_out, idx_out, x_stars, y_stars);
     SLS_CATCH
 }
 
@@ -1823,69 +1834,47 @@ extern "C" int sls_kg_lines(sls_ctx* ctx, const double* a, const double* B, cons
 }
 
 // ---- maximisation over affine subspaces (include/sls_hip.h) --------------------------------------------------------------
-// eval_acq at x = c + A z: expand the candidate-major variables z[n + j*ld] (n < count; column n is start live[n], nullptr: identity)
-// into the handle's block of points, the unchanged evaluation there, then the fold of its gradient onto z.  Always the tiled evaluation.
-// The expand pads the last 128-wide tile of the points with 0.5; the gradient block is written by the evaluation for n < count and
-// read by the fold for n < count only.
-static void sub_eval_device(sls_gp* g, const SubMaps& m, const double* z, long ld, int count, const int* live, int acq_type, double ucb_h,
-                            double* val, double* grad_z, const MesSamples* mes) {
-    sls_ctx* c = g->ctx;
-    g->sub_x.ensure((size_t)g->D * ld);
-    if (grad_z) g->sub_gx.ensure((size_t)g->D * ld);
-    sub_expand(c, m, count, live, z, ld, g->sub_x.p, ld);
-    eval_acq(g, nullptr, g->sub_x.p, ld, count, acq_type, ucb_h, val, grad_z ? g->sub_gx.p : nullptr, ld, mes);
-    if (grad_z) sub_fold(c, m, count, live, g->sub_gx.p, ld, grad_z, ld);
+// Any objective in the D variables of a handle as one in the d variables z of x = c + A z (sub_eval, sub_maps.hpp, over the handle's
+// blocks sub_x / sub_gx).  Never the one-launch search: its kernel knows no maps.
+template <class Obj>
+static auto sub_objective(const Obj& f, const SubMaps& m) {
+    sls_gp* g = f.g;
+    return objective(g, m.d, f.best, [=](const double* z, long ld, int n, const int* live, double* val, double* grad_z, long) {
+        sub_eval(g->ctx, m, g->sub_x, g->sub_gx, z, ld, n, live, grad_z,
+                 [&](const double* x, double* gx) { f.eval(x, ld, n, nullptr, val, gx, ld); });
+    });
 }
 
-// The body of sls_acq_eval_sub and sls_mes_eval_sub (M >= 1): Z is d x M on the host; results to the caller's arrays.
-static void eval_sub_points(const char* who, sls_gp* g, int acq_type, double ucb_h, const sls_submaps* maps, const double* Z, int M,
-                            double* val, double* grad_z, double* X_out, const MesSamples* mes) {
+// The body of sls_acq_eval_sub and sls_mes_eval_sub (M >= 1): Z is d x M on the host; results to the caller's arrays, X_out from the
+// expanded points.
+template <class Obj>
+static void eval_sub_points(const char* who, const Obj& f, const sls_submaps* maps, const double* Z, int M, double* val, double* grad_z,
+                            double* X_out) {
+    sls_gp* g = f.g;
     SubMapsDev up;
     upload_sub_maps(who, g->ctx, maps, g->D, M, up);
-    const int Mp = round_up(M, 128), d = up.m.d;
-    upload_candidates(g, Z, d, M, Mp);
-    std::vector<double> unused;   // the combiners always write the values
-    if (!val) unused.resize(M);
-    EvalOut want;
-    want.val = val ? val : unused.data(); want.grad = grad_z;
-    g->outv.ensure(eval_block_doubles(want, d, Mp));
-    const EvalOut o = eval_block(want, g->outv.p, d, Mp);
-    sub_eval_device(g, up.m, g->raw.p, Mp, M, nullptr, acq_type, ucb_h, o.val, o.grad, mes);
-    download_block(g, want, g->outv.p, d, M, Mp);
-    if (X_out) {
-        std::vector<double> pageable;
-        cm_to_host(fetch(g, g->sub_x.p, (size_t)g->D * Mp, pageable), Mp, g->D, M, X_out);
-    }
+    eval_points(sub_objective(f, up.m), Z, M, val, grad_z, ExtraBlock{&g->sub_x, g->D, X_out, true});
 }
 
-// The body of sls_acq_maximize_sub and sls_mes_maximize_sub: the shared maximiser in the d variables with sub_eval_device as its
-// objective -- the step kernels see z in [0,1]^d and nothing else --, then one more expand launch for the points of the end variables.
-static void maximize_sub_impl(const char* who, sls_gp* g, int acq_type, double ucb_h, const sls_submaps* maps, const double* starts_z, int S,
-                              int n_local, const sls_lbfgs_opts* opts_in, long off, double* z_out, double* x_out, double* val_out,
-                              long* idx_out, double* z_stars, double* x_stars, double* y_stars, const MesSamples* mes = nullptr) {
+// The body of sls_acq_maximize_sub and sls_mes_maximize_sub: the shared maximiser in the d variables -- the step kernels see z in
+// [0,1]^d and nothing else --, then one more expand launch for the points of the end variables.
+template <class Obj>
+static void maximize_sub(const char* who, const Obj& f, const sls_submaps* maps, const double* starts_z, int S, int n_local,
+                         const sls_lbfgs_opts* opts_in, long off, double* z_out, double* x_out, double* val_out, long* idx_out,
+                         double* z_stars, double* x_stars, double* y_stars) {
+    sls_gp* g = f.g;
     sls_ctx* c = g->ctx;
-    SLS_REQUIRE(mes || known_acq(acq_type), "unknown acquisition type %d", acq_type);
     SLS_REQUIRE(S >= 1, "%s: need S >= 1 (S = %d)", who, S);
     SubMapsDev up;
     upload_sub_maps(who, c, maps, g->D, S, up);
-    const int D = g->D, d = up.m.d;
-    MultistartRun r = maximize_begin(who, g, g->lb, opts_in, S, n_local, d);
-    DBuf sd;
-    sd.ensure((size_t)d * S);
-    h2d(c, sd.p, starts_z, (size_t)d * S);
-    LockstepStats ls;
-    lockstep_rounds(c, r.st, g->lb, sd.p, S, n_local,
-                    [&](const double* trial, long ld, int nlive, const int* live, double* val, double* grad) {
-                        sub_eval_device(g, up.m, trial, ld, nlive, live, acq_type, ucb_h, val, grad, mes);
-                    },
-                    &ls);
-    std::vector<double> pageable;
-    const long winner = maximize_finish(c, r, ls, BestBlock{g->sum.dev + 8, g->sum.host + 8, false}, staged_fetch(g, pageable), off, z_out,
-                                        val_out, idx_out, z_stars, y_stars);
+    const long winner = maximize_starts(who, sub_objective(f, up.m), starts_z, true, S, n_local, opts_in, off, z_out, val_out, idx_out,
+                                        z_stars, y_stars);
     if (!x_out && !x_stars) return;
-    const long ld = r.st.ld;
+    const int D = g->D;
+    const long ld = round_up(S, 128);
     g->sub_x.ensure((size_t)D * ld);
-    sub_expand(c, up.m, S, nullptr, r.st.x, ld, g->sub_x.p, ld);
+    sub_expand(c, up.m, S, nullptr, g->lb.x.p, ld, g->sub_x.p, ld);
+    std::vector<double> pageable;
     const double* xs = fetch(g, g->sub_x.p, (size_t)D * ld, pageable);
     if (x_out)
         for (int rr = 0; rr < D; ++rr) x_out[rr] = xs[(size_t)winner + (size_t)rr * ld];
@@ -1897,10 +1886,10 @@ extern "C" int sls_acq_eval_sub(sls_gp* g, int acq_type, double ucb_h, const sls
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g && M >= 0, "sls_acq_eval_sub: bad argument");
-    SLS_REQUIRE(known_acq(acq_type), "unknown acquisition type %d", acq_type);
+    const auto f = acq_objective(g, nullptr, acq_type, ucb_h);
     if (M == 0) return SLS_OK;
     SLS_REQUIRE(Z != nullptr, "sls_acq_eval_sub: Z is NULL");
-    eval_sub_points("sls_acq_eval_sub", g, acq_type, ucb_h, maps, Z, M, val, grad_z, X_out, nullptr);
+    eval_sub_points("sls_acq_eval_sub", f, maps, Z, M, val, grad_z, X_out);
     SLS_CATCH
 }
 
@@ -1910,8 +1899,8 @@ extern "C" int sls_acq_maximize_sub(sls_gp* g, int acq_type, double ucb_h, const
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g && starts_z, "sls_acq_maximize_sub: NULL argument");
-    maximize_sub_impl("sls_acq_maximize_sub", g, acq_type, ucb_h, maps, starts_z, S, n_local, opts, start_index_offset, z_out, x_out,
-                      val_out, idx_out, z_stars, x_stars, y_stars);
+    maximize_sub("sls_acq_maximize_sub", acq_objective(g, nullptr, acq_type, ucb_h), maps, starts_z, S, n_local, opts, start_index_offset,
+                 z_out, x_out, val_out, idx_out, z_stars, x_stars, y_stars);
     SLS_CATCH
 }
 
@@ -1922,15 +1911,14 @@ extern "C" int sls_mes_eval_sub(sls_gp* g, const double* y_star, int K, const sl
     SLS_REQUIRE(g != nullptr, "sls_mes_eval_sub: gp is NULL");
     SLS_REQUIRE(M >= 0, "sls_mes_eval_sub: M = %d", M);
     DBuf ys;
-    upload_max_values("sls_mes_eval_sub", g, y_star, K, ys);
+    const auto f = mes_objective("sls_mes_eval_sub", g, y_star, K, ys);
     if (M == 0) {
         sync(g->ctx);
         return SLS_OK;
     }
     SLS_REQUIRE(Z != nullptr, "sls_mes_eval_sub: Z is NULL");
     SLS_REQUIRE(val != nullptr, "sls_mes_eval_sub: val is NULL");
-    const MesSamples mes{ys.p, K};
-    eval_sub_points("sls_mes_eval_sub", g, 0, 0.0, maps, Z, M, val, grad_z, X_out, &mes);
+    eval_sub_points("sls_mes_eval_sub", f, maps, Z, M, val, grad_z, X_out);
     SLS_CATCH
 }
 
@@ -1942,10 +1930,8 @@ extern "C" int sls_mes_maximize_sub(sls_gp* g, const double* y_star, int K, cons
     SLS_REQUIRE(g != nullptr, "sls_mes_maximize_sub: gp is NULL");
     SLS_REQUIRE(starts_z != nullptr, "sls_mes_maximize_sub: starts_z is NULL");
     DBuf ys;
-    upload_max_values("sls_mes_maximize_sub", g, y_star, K, ys);
-    const MesSamples mes{ys.p, K};
-    maximize_sub_impl("sls_mes_maximize_sub", g, 0, 0.0, maps, starts_z, S, n_local, opts, start_index_offset, z_out, x_out, val_out,
-                      idx_out, z_stars, x_stars, y_stars, &mes);
+    maximize_sub("sls_mes_maximize_sub", mes_objective("sls_mes_maximize_sub", g, y_star, K, ys), maps, starts_z, S, n_local, opts,
+                 start_index_offset, z_out, x_out, val_out, idx_out, z_stars, x_stars, y_stars);
     SLS_CATCH
 }
 
@@ -2066,6 +2052,15 @@ static void eval_pairs(sls_gp* g, const double* xr, long ldr, int S, double* val
     }
 }
 
+// The pair objective over [0,1]^(2D): every block sized by the number of variables is sized for 2D (the optimiser's workspace, the
+// downloads, and the mapped block of the best start, which sls_eubo_maximize ensures); the handle's own sizes stay as they are
+static auto eubo_objective(sls_gp* g) {
+    return objective(g, 2 * g->D, BestBlock{g->eubo_best.dev, g->eubo_best.host, false},
+                     [=](const double* xr, long ldr, int n, const int*, double* val, double* grad, long ldo) {
+                         eval_pairs(g, xr, ldr, n, val, grad, ldo);   // the block of x' is xr + D ldr
+                     });
+}
+
 extern "C" int sls_eubo_eval(sls_gp* g, const double* pairs, int M, double* val, double* grad) {
     SLS_TRY
     CtxCall call_(g);
@@ -2073,17 +2068,7 @@ extern "C" int sls_eubo_eval(sls_gp* g, const double* pairs, int M, double* val,
     SLS_REQUIRE(pairs != nullptr, "sls_eubo_eval: pairs is NULL");
     SLS_REQUIRE(M >= 0, "sls_eubo_eval: M = %d", M);
     if (M == 0) return SLS_OK;
-    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
-    const int Mp = round_up(M, 128), D2 = 2 * g->D;
-    upload_candidates(g, pairs, D2, M, Mp);
-    std::vector<double> unused;   // the kernel always writes the values
-    if (!val) unused.resize(M);
-    EvalOut want;
-    want.val = val ? val : unused.data(); want.grad = grad;
-    g->outv.ensure(eval_block_doubles(want, D2, Mp));
-    const EvalOut o = eval_block(want, g->outv.p, D2, Mp);
-    eval_pairs(g, g->raw.p, Mp, M, o.val, o.grad, Mp);
-    download_block(g, want, g->outv.p, D2, M, Mp);
+    eval_points(eubo_objective(g), pairs, M, val, grad);
     SLS_CATCH
 }
 
@@ -2094,25 +2079,9 @@ extern "C" int sls_eubo_maximize(sls_gp* g, const double* starts, int S, int n_l
     CtxCall call_(g);
     SLS_REQUIRE(g != nullptr, "sls_eubo_maximize: gp is NULL");
     SLS_REQUIRE(starts != nullptr, "sls_eubo_maximize: starts is NULL");
-    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
-    sls_ctx* c = g->ctx;
-    // the maximiser of sls_acq_maximize over [0,1]^(2D): every block sized by the number of variables is sized for 2D here (the
-    // optimiser's workspace, the mapped block of the best start, the downloads); the handle's own sizes stay as they are
-    const int D2 = 2 * g->D;
-    MultistartRun r = maximize_begin("sls_eubo_maximize", g, g->lb, opts, S, n_local, D2);
-    DBuf sd;
-    sd.ensure((size_t)D2 * S);
-    h2d(c, sd.p, starts, (size_t)D2 * S);
-    g->eubo_best.ensure(c, (size_t)(8 + D2) * sizeof(double), true);
-    LockstepStats ls;
-    lockstep_rounds(c, r.st, g->lb, sd.p, S, n_local,
-                    [&](const double* trial, long ld, int nlive, const int*, double* val, double* grad) {
-                        eval_pairs(g, trial, ld, nlive, val, grad, ld);   // the trial block of x' is trial + D ld
-                    },
-                    &ls);
-    std::vector<double> pageable;
-    maximize_finish(c, r, ls, BestBlock{g->eubo_best.dev, g->eubo_best.host, false}, staged_fetch(g, pageable), start_index_offset,
-                    x_out, val_out, idx_out, x_stars, y_stars);
+    g->eubo_best.ensure(g->ctx, (size_t)(8 + 2 * g->D) * sizeof(double), true);
+    maximize_starts("sls_eubo_maximize", eubo_objective(g), starts, true, S, n_local, opts, start_index_offset, x_out, val_out, idx_out,
+                    x_stars, y_stars);
     SLS_CATCH
 }
 

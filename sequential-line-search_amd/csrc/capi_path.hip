@@ -270,18 +270,6 @@ struct SubWs {
     DBuf x, gx;
 };
 
-// path_eval_device (gathered form) at x = c + A z: z[n + j*ld] candidate-major, n < count, column n is start live[n] (nullptr:
-// identity) under draw[n]; the fold of the gradient onto z goes to grad_z[n + j*ld] (may be nullptr).
-void path_sub_eval_device(sls_path* p, const GpView& g, PassWs& ws, SubWs& sw, const SubMaps& m, const double* z, long ld, int count,
-                          const int* live, const int* draw, double* val, double* grad_z) {
-    sls_ctx* c = g.ctx;
-    sw.x.ensure((size_t)g.D * ld);
-    if (grad_z) sw.gx.ensure((size_t)g.D * ld);
-    sub_expand(c, m, count, live, z, ld, sw.x.p, ld);
-    path_eval_device(p, g, ws, sw.x.p, ld, false, count, draw, val, 0, grad_z ? sw.gx.p : nullptr, ld);
-    if (grad_z) sub_fold(c, m, count, live, sw.gx.p, ld, grad_z, ld);
-}
-
 }  // namespace
 
 // The gathered evaluation behind sls_path_eval (pts = Xs, point-major as the caller holds them) and, with sub, sls_path_eval_sub (pts =
@@ -309,7 +297,9 @@ static void path_eval_gathered(const char* who, sls_path* p, bool sub, const sls
     if (grad) gout.ensure((size_t)Mp * rows);
     PassWs ws;
     SubWs sw;
-    if (sub) path_sub_eval_device(p, g, ws, sw, up.m, in.p, Mp, M, nullptr, d_draw, vout.p, grad ? gout.p : nullptr);
+    if (sub)   // path_eval_device (gathered form) at x = c + A z, point m under d_draw[m]
+        sub_eval(c, up.m, sw.x, sw.gx, in.p, Mp, M, nullptr, grad ? gout.p : nullptr,
+                 [&](const double* x, double* gx) { path_eval_device(p, g, ws, x, Mp, false, M, d_draw, vout.p, 0, gx, Mp); });
     else path_eval_device(p, g, ws, in.p, 0, true, M, d_draw, vout.p, 0, grad ? gout.p : nullptr, Mp);
     d2h(c, val, vout.p, (size_t)M);
     std::vector<double> gh(grad ? (size_t)Mp * rows : 0), xh(X_out ? (size_t)Mp * D : 0);
@@ -386,7 +376,10 @@ static void path_maximize(const char* who, sls_path* p, bool sub, const sls_subm
     lockstep_rounds(c, r.st, lb, sd.p, T, n_local,
                     [&](const double* trial, long ld, int nlive, const int* live, double* val, double* grad) {
                         launch_path_draw_of_live(c->stream, live, nlive, S, d_draw);
-                        if (sub) path_sub_eval_device(p, g, ws, sw, up.m, trial, ld, nlive, live, d_draw, val, grad);
+                        if (sub)
+                            sub_eval(c, up.m, sw.x, sw.gx, trial, ld, nlive, live, grad, [&](const double* x, double* gx) {
+                                path_eval_device(p, g, ws, x, ld, false, nlive, d_draw, val, 0, gx, ld);
+                            });
                         else path_eval_device(p, g, ws, trial, ld, false, nlive, d_draw, val, 0, grad, ld);
                     },
                     nullptr);

@@ -1,5 +1,5 @@
 // Search over affine subspaces (include/sls_hip.h "maximisation over affine subspaces"): the two kernels the *_sub entry points add
-// around an evaluation that stays what it is (capi.hip: sub_eval_device; capi_path.hip).  A column's variables z in R^d are expanded
+// around an evaluation that stays what it is (sub_maps.hpp: sub_eval).  A column's variables z in R^d are expanded
 // into the point x = c_k + A_k z in R^D the evaluation reads, and the gradient in x is folded back onto z by the chain rule.
 #include "common.hpp"
 #include "kernels.hpp"

@@ -49,4 +49,18 @@ inline void sub_fold(sls_ctx* c, const SubMaps& m, int ncols, const int* live, c
     launch_sub_fold(c->stream, m, ncols, live, gx, ldx, gz, ldo);
 }
 
+// An objective at x = c + A z: expand the candidate-major variables z[n + j*ld] (n < count; column n is start live[n], nullptr:
+// identity) into x (D x ld, grown here), inner(x, gx) -- the unchanged evaluation at the count points x[n + r*ld], its gradient into
+// gx[n + r*ld] (nullptr: not asked for) --, then the fold of gx onto grad_z[n + j*ld] (may be nullptr).
+// The expand pads the last 128-wide tile of the points with 0.5; gx is written by inner and read by the fold for n < count only.
+template <class Inner>
+void sub_eval(sls_ctx* c, const SubMaps& m, DBuf& x, DBuf& gx, const double* z, long ld, int count, const int* live, double* grad_z,
+              Inner&& inner) {
+    x.ensure((size_t)m.D * ld);
+    if (grad_z) gx.ensure((size_t)m.D * ld);
+    sub_expand(c, m, count, live, z, ld, x.p, ld);
+    inner(x.p, grad_z ? gx.p : nullptr);
+    if (grad_z) sub_fold(c, m, count, live, gx.p, ld, grad_z, ld);
+}
+
 }  // namespace slsk
