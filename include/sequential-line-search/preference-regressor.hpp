@@ -86,9 +86,22 @@ namespace sequential_line_search
         /// Value of the MAP objective at the solution (diagnostics / tests).
         double GetMapObjectiveValue() const { return m_map_objective; }
 
+        /// Laplace approximation at the MAP goodness values (Chu & Ghahramani 2005; include/sls_hip.h sls_gp_set_laplace): the
+        /// handle was fitted as if the goodness values had been observed with noise b; with this on, every predictive deviation --
+        /// PredictSigma, its derivative, the acquisition functions, the joint covariance and the posterior function draws -- is that
+        /// of a model that has only seen the choices.  The mean does not change.  Off by default; a regressor without data ignores
+        /// the call.  Not to be switched while other threads evaluate the regressor.
+        void UseLaplacePosterior(bool on = true);
+        bool UsesLaplacePosterior() const override { return m_laplace; }
+        /// log Z = sum_t log p_t0 - 1/2 y^T K^-1 y - 1/2 log|I + L^T W L| (std::logic_error unless the Laplace posterior is on).
+        double GetLaplaceLogEvidence() const;
+        /// Sigma_g = (K^-1 + W)^-1, the posterior covariance of the goodness values (std::logic_error unless it is on).
+        Eigen::MatrixXd GetGoodnessCovariance() const;
+
     private:
         Eigen::VectorXd m_y;
         double          m_map_objective = 0.0;
+        bool            m_laplace       = false;
 
         void PerformMapEstimation(const unsigned num_iters);
 

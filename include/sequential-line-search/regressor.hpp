@@ -46,6 +46,9 @@ namespace sequential_line_search
 
         /// Device-resident state (K_y^-1, alpha, ...) or nullptr; used by acquisition_func for batched evaluation.
         virtual sls_gp* GetDeviceHandle() const { return nullptr; }
+        /// true when the device handle carries the Laplace posterior of a preference model (PreferenceRegressor::UseLaplacePosterior):
+        /// every sigma above is then the Laplace variance, and the routes that cannot honour it refuse the regressor.
+        virtual bool UsesLaplacePosterior() const { return false; }
 
         // Batched forms (not in the reference; D x M input, one query point per column).
         void PredictBatch(const Eigen::MatrixXd& Xs, Eigen::VectorXd& mu, Eigen::VectorXd& sigma) const;

@@ -81,12 +81,18 @@ namespace sequential_line_search
             m_gaussian_process_upper_confidence_bound_hyperparam = hyperparam;
         }
 
+        /// Laplace posterior of the goodness values (PreferenceRegressor::UseLaplacePosterior) for every regressor the
+        /// SubmitFeedbackData* calls build from now on, and for the current one.  Off by default: today's behaviour, bit for bit.
+        void SetUseLaplacePosterior(const bool use_laplace_posterior);
+        bool GetUseLaplacePosterior() const { return m_use_laplace_posterior; }
+
     private:
         const bool m_use_map_hyperparams;
 
         const CurrentBestSelectionStrategy m_current_best_selection_strategy;
 
         std::shared_ptr<PreferenceRegressor>   m_regressor;
+        bool                                   m_use_laplace_posterior = false;
         std::shared_ptr<PreferenceDataManager> m_data;
         GalleryCorners                         m_corners;
 

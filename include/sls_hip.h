@@ -232,6 +232,64 @@ int sls_acq_maximize_pair(sls_gp* gp_mean, sls_gp* gp_sigma, int acq_type, doubl
  * everything. */
 int sls_gp_refit_dev(sls_gp* gp, const double* X_dev, const double* y_dev);
 
+/* ---- Laplace posterior for preference data (not in the reference) -------------------------------------------------------------
+ * A handle that stands for a PreferenceRegressor was fitted to the MAP goodness values y as if they had been OBSERVED with noise b: its
+ * variance a - k*^T K_y^-1 k* is that of a GP that has seen y, not of a model that has only seen choices.  The Laplace approximation at
+ * y (Chu & Ghahramani 2005; Rasmussen & Williams 3.4) replaces it.  With K_y = K_f + b I = L L^T, alpha = K_y^-1 y, the tuples in the
+ * CSR form of sls_pref_objective (first index of a tuple = the chosen point) and s = btl_scale:
+ *   per tuple (i_0 .. i_{m-1}):  p = softmax(y_i / s), the maximum subtracted (no overflow at any y, s);  H = (diag(p) - p p^T) / s^2
+ *   W        N x N, the scatter-sum of every H at (i_j, i_k); an index repeated inside a tuple adds.  Symmetric PSD, singular.
+ *   B        = I + L^T W L                      eigenvalues >= 1;  B = L_B L_B^T
+ *   Sigma_g  = (K_y^-1 + W)^-1 = L B^-1 L^T     posterior covariance of the goodness values
+ *   T        = I - B^-1 = B^-1 (L^T W L)        formed as that PRODUCT, eigenvalues in [0, 1)
+ *   M        = L^-T T L^-1 = L^-T B^-1 (L^T W)  the effective inverse (= K_y^-1 - K_y^-1 Sigma_g K_y^-1, never formed as a difference)
+ *   mean     k*^T alpha (unchanged)             sigma^2 = max(0, a - k*^T M k*)          grad sigma = -(1 / sigma) J M k*
+ *   cov      = K(Xs, Xs) - V T V^T, V = K* L^-T (sls_gp_predict_cov's V)
+ *   path     r_s = (y + L L_B^-T z_s) - sqrt(b) eps_s - f_prior,s(X),  v_s = K_y^-1 r_s:  Matheron's rule with a sampled goodness vector
+ *   evidence log_lik = sum_t log p_{t,0};  log Z = log_lik - 1/2 y^T alpha - 1/2 log|B|
+ * M, T, L^T W L and Sigma_g are symmetric products: their lower 128 x 128 tiles are computed and the upper triangle is the exact mirror.
+ * W is assembled without floating-point atomics (one lane per row, tuples in increasing order), log_lik and log|B| are reduced in one
+ * fixed order: equal inputs give equal bits in every matrix and in the summary.  All device work runs on the context's stream.
+ *
+ * sls_gp_set_laplace: n_prefs >= 1, every tuple of length >= 2 (pref_offsets[0] = 0, increasing), every index < N, btl_scale > 0 and
+ * finite: else SLS_ERR_INVALID before any launch, the handle unchanged.  It works at any y (the handle's y need not be a mode) and in
+ * either sigma mode: the Laplace variance takes the place of both.  Setting twice replaces the state.  Set and clear change
+ * sls_gp_generation, so objects derived from the handle before (sls_path, sls_jes, sls_kg) are refused afterwards.  After
+ * sls_gp_clear_laplace every call returns the bits it returned before the set.  Memory: five N x N matrices while set.
+ * While the state is set the fit is frozen: sls_gp_set_sigma_mode, sls_gp_append_point and sls_gp_refit_dev return SLS_ERR_UNSUPPORTED
+ * and change nothing.
+ *
+ * What a Laplace handle does, per entry point ("tiled": the explicit-inverse route of the tiled evaluation with M in the place of K_y^-1;
+ * the one-wavefront path, the evaluation slots, the zero-copy path and the triangular value-only form are switched off for it, so mu
+ * is bit-equal to the plain handle's mu ON THE TILED ROUTE):
+ *   sls_gp_predict, sls_gp_predict_grad, sls_acq_eval                    honour (tiled)
+ *   sls_acq_maximize, sls_acq_maximize_dev                               honour (tiled, lock-step L-BFGS)
+ *   sls_acq_eval_sub, sls_acq_maximize_sub                               honour
+ *   sls_mes_eval, sls_mes_maximize, sls_mes_eval_sub, sls_mes_maximize_sub   honour
+ *   sls_gp_predict_cov, sls_gp_sample_posterior                          honour (cov = K - V T V^T)
+ *   sls_path_create                                                      honour; draw s takes 2F + 2N normal numbers from B0 + s (2F + 2N)
+ *                                                                        in the order w, w', eps, z (plain handles keep 2F + N); the first
+ *                                                                        k draws of an n-draw object stay a k-draw object bit for bit
+ *   sls_path_*, sls_qeubo_*, sls_qnei_*, sls_qlognei_*, sls_qbald_*, sls_line_*, sls_patch_*   unchanged: they consume the object's (W, V)
+ *   sls_multi_acq_maximize, sls_multi_gp_predict                         refuse when any shard carries the state (the borrowed primary of
+ *                                                                        sls_multi_gp_create_from after a later sls_gp_set_laplace, or a
+ *                                                                        shard of sls_multi_gp_shard): the other shards are plain fits
+ *   sls_eubo_eval, sls_eubo_maximize                                     refuse (SLS_ERR_UNSUPPORTED)
+ *   sls_acq_eval_pair, sls_acq_maximize_pair (either handle)             refuse
+ *   sls_jes_create, sls_kg_create                                        refuse
+ *   sls_gp_loo                                                           refuse
+ *   sls_multi_gp_create_from                                             refuse (sls_multi_gp_create builds plain replicas: no state)
+ *   sls_gp_get_matrix, sls_gp_get_summary                                the plain fit's K_y, K_y^-1, L, alpha, mu_best, log|K_y| (no variance)
+ * No entry point uses the plain variance on a Laplace handle. */
+int sls_gp_set_laplace(sls_gp* gp, const unsigned* prefs_flat, const int* pref_offsets, int n_prefs, double btl_scale);
+int sls_gp_clear_laplace(sls_gp* gp);                 /* back to the plain handle: bit-equal to before the set; no state: a no-op */
+#define SLS_LAPLACE_W 0      /* N x N */
+#define SLS_LAPLACE_COV 1    /* N x N  Sigma_g (formed on demand: two N^3 products per call) */
+#define SLS_LAPLACE_M 2      /* N x N  effective inverse */
+/* SLS_ERR_INVALID on a handle without the state */
+int sls_gp_laplace_get(sls_gp* gp, int what, double* out);
+int sls_gp_laplace_summary(sls_gp* gp, double* log_lik, double* logdet_B, double* log_evidence);   /* any may be NULL */
+
 /* ---- pathwise posterior function draws (not in the reference) ---------------------------------------------------------
  * Thompson sampling needs a draw of the latent function that can be evaluated -- and maximised -- anywhere in [0,1]^D.  Pathwise
  * conditioning (Wilson et al. 2020) gives each draw s in closed form:
@@ -1000,6 +1058,8 @@ int sls_gp_map_fit(sls_nll* h, const double* y, const double* z0, const double* 
  * "sub_expand" for x_out / x_stars; the evaluation between them counts as in the plain call);
  * "loo_terms" (the per-point terms and L: one launch per sls_nll_loo / sls_gp_loo_grad / sls_gp_loo call, two in the Cholesky-solve
  * sigma mode), "loo_syrk" (the scaled copy R and M = R R^T) and "loo_weight" (the LOO weights), one entry each per gradient call;
+ * "laplace_w" (the BTL Hessian W of sls_gp_set_laplace), "laplace_b" (W L and B = I + L^T W L), "laplace_potri" (chol(B) and B^-1),
+ * "laplace_m" (B^-1 L^T W, M and T), one entry each per sls_gp_set_laplace;
  * "potrf_fallbacks": launches = how often a single-launch factorisation gave up and was recomputed. */
 int sls_prof_enable(sls_ctx* ctx, int on);
 int sls_prof_reset(sls_ctx* ctx);

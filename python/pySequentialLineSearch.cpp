@@ -181,6 +181,38 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
             r.CalcLeaveOneOutPredictions(mu, var, logp);
             return std::make_tuple(mu, var, logp);
         });
+    // preference regressor with fixed or MAP hyper-parameters: the model behind the three optimisers, reachable on its own for the
+    // Laplace posterior of its goodness values (preference-regressor.hpp)
+    py::class_<PreferenceRegressor, Regressor>(m, "PreferenceRegressor")
+        .def(py::init([](const MatrixXd& X, const std::vector<std::vector<unsigned>>& preferences, bool use_map_hyperparams,
+                         double default_kernel_signal_var, double default_kernel_length_scale, double default_noise_level,
+                         double kernel_hyperparams_prior_var, double btl_scale, unsigned num_map_estimation_iters,
+                         KernelType kernel_type) {
+                 std::vector<Preference> D;
+                 for (const auto& p : preferences) D.emplace_back(p);
+                 return new PreferenceRegressor(X, D, use_map_hyperparams, default_kernel_signal_var, default_kernel_length_scale,
+                                                default_noise_level, kernel_hyperparams_prior_var, btl_scale, num_map_estimation_iters,
+                                                kernel_type);
+             }),
+             "X"_a, "preferences"_a, "use_map_hyperparams"_a = false, "default_kernel_signal_var"_a = 0.500,
+             "default_kernel_length_scale"_a = 0.500, "default_noise_level"_a = 0.005, "kernel_hyperparams_prior_var"_a = 0.250,
+             "btl_scale"_a = 0.010, "num_map_estimation_iters"_a = 100, "kernel_type"_a = KernelType::ArdMatern52Kernel)
+        .def("goodness_values", [](const PreferenceRegressor& r) { return r.GetSmallY(); })
+        .def("kernel_hyperparams", [](const PreferenceRegressor& r) { return r.GetKernelHyperparams(); })
+        .def("noise_hyperparam", &PreferenceRegressor::GetNoiseHyperparam)
+        // (mean, standard deviation) at the columns of points (D, M)
+        .def("predict", [](const PreferenceRegressor& r, const MatrixXd& points) {
+            VectorXd mu, sigma;
+            r.PredictBatch(points, mu, sigma);
+            return std::make_pair(mu, sigma);
+        }, "points"_a)
+        .def("use_laplace_posterior", &PreferenceRegressor::UseLaplacePosterior, "on"_a = true)
+        .def("uses_laplace_posterior", &PreferenceRegressor::UsesLaplacePosterior)
+        .def("laplace_log_evidence", &PreferenceRegressor::GetLaplaceLogEvidence)
+        .def("goodness_covariance", &PreferenceRegressor::GetGoodnessCovariance);
+    m.def("find_next_points", &acquisition_func::FindNextPoints, "regressor"_a, "num_points"_a, "num_global_search_iters"_a = 100,
+          "num_local_search_iters"_a = 50, "func_type"_a = AcquisitionFuncType::ExpectedImprovement,
+          "gaussian_process_upper_confidence_bound_hyperparam"_a = 1.0);
     m.def("sample_max_values", &acquisition_func::SampleMaxValues, "regressor"_a, "num_samples"_a = 64,
           "num_global_search_iters"_a = 100, "num_local_search_iters"_a = 50, "seed"_a = 0ULL, "num_frequencies"_a = 2048);
     m.def("calc_max_value_entropies",
@@ -601,6 +633,8 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
         .def("get_acquisition_func_values", &SequentialLineSearchOptimizer::GetAcquisitionFuncValues, "points"_a)
         .def("get_raw_data_points", &SequentialLineSearchOptimizer::GetRawDataPoints)
         .def("damp_data", &SequentialLineSearchOptimizer::DampData, "directory_path"_a)
+        .def("set_use_laplace_posterior", &SequentialLineSearchOptimizer::SetUseLaplacePosterior, "use_laplace_posterior"_a)
+        .def("get_use_laplace_posterior", &SequentialLineSearchOptimizer::GetUseLaplacePosterior)
         .def("set_gaussian_process_upper_confidence_bound_hyperparam",
              &SequentialLineSearchOptimizer::SetGaussianProcessUpperConfidenceBoundHyperparam, "hyperparam"_a);
 
@@ -632,6 +666,8 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
         .def("get_acquisition_func_values", &SequentialGallerySearchOptimizer::GetAcquisitionFuncValues, "points"_a)
         .def("get_raw_data_points", &SequentialGallerySearchOptimizer::GetRawDataPoints)
         .def("damp_data", &SequentialGallerySearchOptimizer::DampData, "directory_path"_a)
+        .def("set_use_laplace_posterior", &SequentialGallerySearchOptimizer::SetUseLaplacePosterior, "use_laplace_posterior"_a)
+        .def("get_use_laplace_posterior", &SequentialGallerySearchOptimizer::GetUseLaplacePosterior)
         .def("set_gaussian_process_upper_confidence_bound_hyperparam",
              &SequentialGallerySearchOptimizer::SetGaussianProcessUpperConfidenceBoundHyperparam, "hyperparam"_a);
 
@@ -675,6 +711,8 @@ PYBIND11_MODULE(pySequentialLineSearch, m)
         .def("get_acquisition_func_values", &PreferentialBayesianOptimizer::GetAcquisitionFuncValues, "points"_a)
         .def("get_raw_data_points", &PreferentialBayesianOptimizer::GetRawDataPoints)
         .def("damp_data", &PreferentialBayesianOptimizer::DampData, "directory_path"_a)
+        .def("set_use_laplace_posterior", &PreferentialBayesianOptimizer::SetUseLaplacePosterior, "use_laplace_posterior"_a)
+        .def("get_use_laplace_posterior", &PreferentialBayesianOptimizer::GetUseLaplacePosterior)
         .def("set_gaussian_process_upper_confidence_bound_hyperparam",
              &PreferentialBayesianOptimizer::SetGaussianProcessUpperConfidenceBoundHyperparam, "hyperparam"_a);
 }

@@ -112,6 +112,7 @@ EXPORTS = [
     "sls_nll_loo", "sls_gp_loo_grad", "sls_gp_loo",
     "sls_jes_create", "sls_jes_destroy", "sls_jes_optima", "sls_jes_terms", "sls_jes_eval", "sls_jes_maximize",
     "sls_kg_create", "sls_kg_destroy", "sls_kg_points", "sls_kg_eval", "sls_kg_maximize", "sls_kg_lines",
+    "sls_gp_set_laplace", "sls_gp_clear_laplace", "sls_gp_laplace_get", "sls_gp_laplace_summary",
 ]
 
 
@@ -120,7 +121,10 @@ def tuning_reload():
     lib().sls_tuning_reload()
 
 
+ERR_INVALID = -1
 ERR_UNSUPPORTED = -5
+# selectors of GP.laplace_matrix (SLS_LAPLACE_*)
+LAPLACE_W, LAPLACE_COV, LAPLACE_M = 0, 1, 2
 SIGMA_EXPLICIT_INVERSE, SIGMA_CHOLESKY_SOLVE = 0, 1
 
 
@@ -130,7 +134,10 @@ class Unsupported(SlsError):
 
 def _ck(rc):
     if rc != 0:
-        raise SlsError(f"libsls_hip error {rc}: {lib().sls_last_error().decode()}")
+        # SLS_ERR_UNSUPPORTED has a class of its own (a subclass: callers that catch SlsError see no difference)
+        err = (Unsupported if rc == ERR_UNSUPPORTED else SlsError)(f"libsls_hip error {rc}: {lib().sls_last_error().decode()}")
+        err.code = rc
+        raise err
 
 
 def _f(a):
@@ -331,6 +338,33 @@ class GP:
         g = C.c_long(0)
         _ck(lib().sls_gp_generation(self.h, C.byref(g)))
         return int(g.value)
+
+    def set_laplace(self, prefs, btl_scale=0.01):
+        """Laplace posterior of the goodness values at the handle's y (sls_gp_set_laplace): prefs is a sequence of index tuples, the
+        first index of a tuple the chosen point.  From here on every sigma route of the handle returns the Laplace variance and the
+        fit is frozen (set_sigma_mode, append_point, refit_dev raise Unsupported) until clear_laplace()."""
+        flat = np.array([i for p in prefs for i in p], dtype=np.uint32)
+        offs = np.zeros(len(prefs) + 1, dtype=np.int32)
+        offs[1:] = np.cumsum([len(p) for p in prefs])
+        _ck(lib().sls_gp_set_laplace(self.h, flat.ctypes.data_as(C.POINTER(C.c_uint)), offs.ctypes.data_as(C.POINTER(C.c_int)),
+                                     len(prefs), C.c_double(btl_scale)))
+
+    def clear_laplace(self):
+        """Back to the plain handle: every call returns the bits it returned before set_laplace."""
+        _ck(lib().sls_gp_clear_laplace(self.h))
+
+    def laplace_matrix(self, what):
+        """LAPLACE_W (the BTL Hessian), LAPLACE_COV (Sigma_g, the posterior covariance of the goodness values) or LAPLACE_M (the
+        effective inverse that stands in the place of K_y^-1): N x N each."""
+        out = np.empty((self.N, self.N), order="F")
+        _ck(lib().sls_gp_laplace_get(self.h, int(what), _p(out)))
+        return out
+
+    def laplace_summary(self):
+        """dict(log_lik, logdet_B, log_evidence): sum_t log p_t0, log|I + L^T W L| and log Z = log_lik - y.alpha / 2 - log|B| / 2."""
+        ll, ld, ev = C.c_double(), C.c_double(), C.c_double()
+        _ck(lib().sls_gp_laplace_summary(self.h, C.byref(ll), C.byref(ld), C.byref(ev)))
+        return dict(log_lik=ll.value, logdet_B=ld.value, log_evidence=ev.value)
 
     def append_point(self, x, y):
         x = _f(x)

@@ -446,7 +446,26 @@ struct sls_gp {
     // SHARED lock on the fitted state; everything that changes the state (refit, appended point, sigma mode) holds it exclusively.
     // The slots belong to the CONTEXT (sls_ctx::slots): a stream costs ~1 ms to create and the facade builds a new handle per submit.
     std::shared_mutex state_mtx;
+    // Laplace posterior of the goodness values (sls_gp_set_laplace): while set, every sigma route of the handle reads M in the place
+    // of K_y^-1 on the tiled evaluation, and the fit is frozen.  laplace_on mirrors `lap != nullptr` for readers that have not taken
+    // a lock yet (the slot path asks before it takes the state lock, and again under it).
+    struct LaplaceState {
+        double btl_scale = 0.0;
+        DBuf W, M, T, LBinv, Binv;   // Np x Np each: the BTL Hessian, the effective inverse, T = I - B^-1, chol(B)^-1 (path draws), B^-1 (Sigma_g)
+        double log_lik = 0.0, logdet_B = 0.0, quad = 0.0;   // sum_t log p_t0, log|B|, y . alpha
+    };
+    std::unique_ptr<LaplaceState> lap;
+    std::atomic<bool> laplace_on{false};
 };
+
+// An entry point that neither honours the Laplace state nor may silently use the plain variance refuses the handle.
+static void refuse_laplace(const sls_gp* g, const char* who) {
+    if (g && g->lap) {
+        set_error("%s: the handle carries a Laplace posterior (sls_gp_set_laplace); this entry point does not support it -- "
+                  "sls_gp_clear_laplace first", who);
+        throw HipFail{SLS_ERR_UNSUPPORTED};
+    }
+}
 
 // N <= 128: the whole fit is one single-workgroup launch (kernels_small.hip); SLS_FIT_SMALL=0 forces the tiled pipeline (A/B, tests)
 static bool gp_fit_small_ok(const sls_gp* g) {
@@ -591,6 +610,7 @@ extern "C" int sls_gp_refit_dev(sls_gp* g, const double* X_dev, const double* y_
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g && X_dev && y_dev, "sls_gp_refit_dev: NULL argument");
+    refuse_laplace(g, "sls_gp_refit_dev");
     std::unique_lock<std::shared_mutex> state_(g->state_mtx);
     sls_ctx* c = g->ctx;
     SLS_HIP(hipMemcpyAsync(g->X.p, X_dev, (size_t)g->D * g->N * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -620,8 +640,15 @@ GpView gp_view(sls_gp* g) {
     v.y = g->y.p; v.L = g->L.p;
     v.X = g->X.p; v.gram_direct = g->gram_direct;
     v.generation = g->generation;
+    v.laplace = g->lap != nullptr;
+    v.lap_T = g->lap ? g->lap->T.p : nullptr;
+    v.lap_LBinv = g->lap ? g->lap->LBinv.p : nullptr;
     v.state = &g->state_mtx;
     return v;
+}
+bool gp_has_laplace(sls_gp* g) {
+    CtxCall call_(g);
+    return g->lap != nullptr;
 }
 void gp_set_acq_stats(sls_gp* g, long issued, long cap, int rounds, int live_end) {
     g->stat_issued = issued; g->stat_cap = cap; g->stat_rounds = rounds; g->stat_live_end = live_end;
@@ -649,6 +676,7 @@ int gp_export_inputs(sls_gp* g, int* D, int* N, int* kernel, int* sigma_mode, in
                      std::vector<double>* y, std::vector<double>* theta) {
     SLS_TRY
     CtxCall call_(g);
+    refuse_laplace(g, "sls_multi_gp_create_from");
     *D = g->D; *N = g->N; *kernel = g->kernel; *sigma_mode = g->sigma_mode; *device = g->ctx->device; *b = g->b;
     *theta = g->theta;
     X->resize((size_t)g->D * g->N);
@@ -664,12 +692,185 @@ extern "C" int sls_gp_set_sigma_mode(sls_gp* g, int mode) {
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g && (mode == SLS_SIGMA_EXPLICIT_INVERSE || mode == SLS_SIGMA_CHOLESKY_SOLVE), "sls_gp_set_sigma_mode: bad argument");
+    refuse_laplace(g, "sls_gp_set_sigma_mode");
     std::unique_lock<std::shared_mutex> state_(g->state_mtx);
     if (mode == SLS_SIGMA_CHOLESKY_SOLVE && g->sigma_mode != mode)
         launch_transpose_full(g->ctx->stream, g->Linv.p, g->U.p, g->Np);   // every block of U = (L^-1)^T (trtri writes the upper ones only)
     if (g->sigma_mode != mode) g->generation = ++g_gp_generation;
     g->sigma_mode = mode;
     sync(g->ctx);   // slot streams are not ordered behind the context's stream: the state is complete before the lock goes
+    SLS_CATCH
+}
+
+// ---- Laplace posterior of the goodness values (include/sls_hip.h "Laplace posterior") ---------------------------------------------
+// Everything on the context's stream; nothing N^2-sized passes through the host.  With L = chol(K_y) (a copy with its upper triangle
+// cleared), W the BTL Hessian at the handle's y:
+//   "laplace_w"      W: probabilities per tuple, one lane per row in a fixed order, the upper triangle mirrored from the lower
+//   "laplace_b"      T1 = W L,  A = L^T T1 (lower tiles, mirrored),  B = A + I
+//   "laplace_potri"  B = L_B L_B^T and B^-1 (launch_potri at the handle's padding)
+//   "laplace_m"      G = B^-1 T1^T (= T L^-1),  M = L^-T G and T = G L (lower tiles, mirrored)
+// M = L^-T B^-1 (L^T W L) L^-1 is a product throughout: no two K_y^-1-sized quantities are ever differenced.
+static void laplace_clean_factor(sls_gp* g, DBuf& Lc) {
+    const size_t n2 = (size_t)g->Np * g->Np;
+    Lc.ensure(n2);
+    SLS_HIP(hipMemcpyAsync(Lc.p, g->L.p, n2 * sizeof(double), hipMemcpyDeviceToDevice, g->ctx->stream));
+    launch_zero_upper(g->ctx->stream, Lc.p, g->Np);
+}
+static void laplace_build(sls_gp* g, sls_gp::LaplaceState& st, const std::vector<int>& off, const std::vector<int>& flat) {
+    sls_ctx* c = g->ctx;
+    const int N = g->N, Np = g->Np, nt = Np / 128, n_prefs = (int)off.size() - 1, E = (int)flat.size();
+    const size_t n2 = (size_t)Np * Np;
+    // the transposed CSR (point -> flat positions, increasing) and the tuple of every flat position
+    std::vector<int> ints;
+    ints.reserve((size_t)n_prefs + 1 + 3 * (size_t)E + N + 1);
+    ints.insert(ints.end(), off.begin(), off.end());
+    ints.insert(ints.end(), flat.begin(), flat.end());
+    std::vector<int> csc_off(N + 1, 0), csc_ent(E), tuple_of(E);
+    for (int e = 0; e < E; ++e) ++csc_off[flat[e] + 1];
+    for (int i = 0; i < N; ++i) csc_off[i + 1] += csc_off[i];
+    {
+        std::vector<int> at(csc_off.begin(), csc_off.end() - 1);
+        for (int e = 0; e < E; ++e) csc_ent[at[flat[e]]++] = e;
+    }
+    for (int t = 0; t < n_prefs; ++t)
+        for (int e = off[t]; e < off[t + 1]; ++e) tuple_of[e] = t;
+    ints.insert(ints.end(), csc_off.begin(), csc_off.end());
+    ints.insert(ints.end(), csc_ent.begin(), csc_ent.end());
+    ints.insert(ints.end(), tuple_of.begin(), tuple_of.end());
+    DBuf ibuf, P, logp0, Lc, T1, A, U, G, scal, LB;   // LB: B, then its factor (read by the summary only)
+    ibuf.ensure((ints.size() + 1) / 2);
+    SLS_HIP(hipMemcpyAsync(ibuf.p, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    const int* d_off = reinterpret_cast<const int*>(ibuf.p);
+    const int* d_flat = d_off + n_prefs + 1;
+    const int* d_csc_off = d_flat + E;
+    const int* d_csc_ent = d_csc_off + N + 1;
+    const int* d_tuple_of = d_csc_ent + E;
+    P.ensure(E); logp0.ensure(n_prefs); T1.ensure(n2); A.ensure(n2); U.ensure(n2); G.ensure(n2); scal.ensure(4);
+    st.W.ensure(n2); st.M.ensure(n2); st.T.ensure(n2); LB.ensure(n2); st.LBinv.ensure(n2); st.Binv.ensure(n2);
+    {
+        ProfScope ps(c, "laplace_w");
+        launch_laplace_w(c->stream, d_off, d_flat, d_csc_off, d_csc_ent, d_tuple_of, n_prefs, g->y.p, st.btl_scale, N, Np, P.p, logp0.p,
+                         st.W.p);
+        launch_mirror_lower(c->stream, st.W.p, Np);
+    }
+    {
+        ProfScope ps(c, "laplace_b");
+        laplace_clean_factor(g, Lc);
+        launch_gemm_plain(c->stream, st.W.p, Np, false, Lc.p, Np, true, T1.p, Np, nt, nt, Np, 1.0, 0.0);          // T1 = W L
+        launch_gemm_lower_tiles(c->stream, Lc.p, Np, true, T1.p, Np, true, A.p, Np, nt, Np, 1.0, 0.0);           // A = L^T T1
+        launch_mirror_lower(c->stream, A.p, Np);
+    }
+    for (int attempt = 0;; ++attempt) {
+        SLS_HIP(hipMemcpyAsync(LB.p, A.p, n2 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        launch_add_diag(c->stream, LB.p, Np, Np, 1.0);   // B = I + L^T W L (the padding of A is zero: identity there)
+        SLS_HIP(hipMemsetAsync(c->d_info, 0, 64, c->stream));
+        c->potrf_tick_rearm();
+        int* df_sync = c->potrf_df_sync(Np);
+        {
+            ProfScope ps(c, "laplace_potri");
+            launch_fill(c->stream, st.LBinv.p, (long)n2, 0.0);   // L_B^-1 is kept and read as a full matrix: zero above the diagonal
+            launch_potri(c->stream, LB.p, Np, st.LBinv.p, U.p, st.Binv.p, c->d_info, df_sync);
+        }
+        int info[2] = {0, 0};
+        SLS_HIP(hipMemcpyAsync(info, c->d_info, sizeof(info), hipMemcpyDeviceToHost, c->stream));
+        sync(c);
+        if (potrf_gave_up(c, info[1], attempt)) continue;   // once more, on the multi-launch schedule
+        if (info[0] != 0) {
+            set_error("sls_gp_set_laplace: I + L^T W L is not positive definite (pivot %d): y or the fit is not finite", info[0] - 1);
+            throw HipFail{SLS_ERR_NOT_SPD};
+        }
+        break;
+    }
+    {
+        ProfScope ps(c, "laplace_m");
+        launch_gemm_plain(c->stream, st.Binv.p, Np, false, T1.p, Np, false, G.p, Np, nt, nt, Np, 1.0, 0.0);      // G = B^-1 T1^T
+        launch_gemm_lower_tiles(c->stream, g->Linv.p, Np, true, G.p, Np, true, st.M.p, Np, nt, Np, 1.0, 0.0);    // M = L^-T G
+        launch_mirror_lower(c->stream, st.M.p, Np);
+        launch_gemm_lower_tiles(c->stream, G.p, Np, false, Lc.p, Np, true, st.T.p, Np, nt, Np, 1.0, 0.0);        // T = G L
+        launch_mirror_lower(c->stream, st.T.p, Np);
+    }
+    launch_laplace_summary(c->stream, logp0.p, n_prefs, LB.p, Np, N, g->y.p, g->alpha.p, scal.p);
+    double sm[3] = {0, 0, 0};
+    d2h(c, sm, scal.p, 3);
+    sync(c);   // also: the temporaries of this call are idle before they go back to the pool
+    st.log_lik = sm[0]; st.logdet_B = sm[1]; st.quad = sm[2];
+}
+
+extern "C" int sls_gp_set_laplace(sls_gp* g, const unsigned* prefs_flat, const int* pref_offsets, int n_prefs, double btl_scale) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g && prefs_flat && pref_offsets, "sls_gp_set_laplace: NULL argument");
+    SLS_REQUIRE(n_prefs >= 1, "sls_gp_set_laplace: n_prefs = %d (need at least one tuple)", n_prefs);
+    SLS_REQUIRE(std::isfinite(btl_scale) && btl_scale > 0.0, "sls_gp_set_laplace: btl_scale = %g (must be > 0)", btl_scale);
+    SLS_REQUIRE(pref_offsets[0] == 0, "sls_gp_set_laplace: pref_offsets[0] = %d (must be 0)", pref_offsets[0]);
+    for (int t = 0; t < n_prefs; ++t)
+        SLS_REQUIRE(pref_offsets[t + 1] - pref_offsets[t] >= 2 && pref_offsets[t + 1] - pref_offsets[t] <= (1 << 20),
+                    "sls_gp_set_laplace: tuple %d has %d members (need at least 2)", t, pref_offsets[t + 1] - pref_offsets[t]);
+    const int E = pref_offsets[n_prefs];
+    for (int e = 0; e < E; ++e)
+        SLS_REQUIRE(prefs_flat[e] < (unsigned)g->N, "sls_gp_set_laplace: index %u at flat position %d (N = %d)", prefs_flat[e], e, g->N);
+    std::unique_lock<std::shared_mutex> state_(g->state_mtx);
+    std::vector<int> off(pref_offsets, pref_offsets + n_prefs + 1), flat(prefs_flat, prefs_flat + E);
+    std::unique_ptr<sls_gp::LaplaceState> st(new sls_gp::LaplaceState());
+    st->btl_scale = btl_scale;
+    laplace_build(g, *st, off, flat);   // a failure leaves the handle as it was
+    g->lap = std::move(st);
+    g->laplace_on.store(true);
+    g->generation = ++g_gp_generation;
+    SLS_CATCH
+}
+
+extern "C" int sls_gp_clear_laplace(sls_gp* g) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g, "sls_gp_clear_laplace: NULL handle");
+    std::unique_lock<std::shared_mutex> state_(g->state_mtx);
+    if (!g->lap) return SLS_OK;
+    sync(g->ctx);
+    g->lap.reset();
+    g->laplace_on.store(false);
+    g->generation = ++g_gp_generation;
+    SLS_CATCH
+}
+
+extern "C" int sls_gp_laplace_get(sls_gp* g, int what, double* out) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g && out, "sls_gp_laplace_get: NULL argument");
+    std::shared_lock<std::shared_mutex> state_(g->state_mtx);
+    SLS_REQUIRE(g->lap != nullptr, "sls_gp_laplace_get: the handle has no Laplace posterior (sls_gp_set_laplace)");
+    sls_ctx* c = g->ctx;
+    const int N = g->N, Np = g->Np, nt = Np / 128;
+    switch (what) {
+        case SLS_LAPLACE_W: d2h_matrix(c, out, g->lap->W.p, N, Np); break;
+        case SLS_LAPLACE_M: d2h_matrix(c, out, g->lap->M.p, N, Np); break;
+        case SLS_LAPLACE_COV: {
+            // Sigma_g = L B^-1 L^T, formed on demand: S1 = B^-1 L^T, Sigma = L S1 (lower tiles, mirrored)
+            DBuf Lc, S1, Sg;
+            laplace_clean_factor(g, Lc);
+            S1.ensure((size_t)Np * Np); Sg.ensure((size_t)Np * Np);
+            launch_gemm_plain(c->stream, g->lap->Binv.p, Np, false, Lc.p, Np, false, S1.p, Np, nt, nt, Np, 1.0, 0.0);
+            launch_gemm_lower_tiles(c->stream, Lc.p, Np, false, S1.p, Np, true, Sg.p, Np, nt, Np, 1.0, 0.0);
+            launch_mirror_lower(c->stream, Sg.p, Np);
+            d2h_matrix(c, out, Sg.p, N, Np);
+            sync(c);
+            break;
+        }
+        default: SLS_REQUIRE(false, "sls_gp_laplace_get: unknown selector %d", what);
+    }
+    sync(c);
+    SLS_CATCH
+}
+
+extern "C" int sls_gp_laplace_summary(sls_gp* g, double* log_lik, double* logdet_B, double* log_evidence) {
+    SLS_TRY
+    CtxCall call_(g);
+    SLS_REQUIRE(g, "sls_gp_laplace_summary: NULL handle");
+    SLS_REQUIRE(g->lap != nullptr, "sls_gp_laplace_summary: the handle has no Laplace posterior (sls_gp_set_laplace)");
+    const sls_gp::LaplaceState& st = *g->lap;
+    if (log_lik) *log_lik = st.log_lik;
+    if (logdet_B) *logdet_B = st.logdet_B;
+    if (log_evidence) *log_evidence = st.log_lik - 0.5 * st.quad - 0.5 * st.logdet_B;
     SLS_CATCH
 }
 
@@ -800,7 +1001,10 @@ static void eval_candidates(sls_gp* g, const double* xr, long ldr, int S, const 
                                   ldk, mu_part, ca_part);
         }
         int split_first = 0x7fffffff;
-        const bool solve_grad = g->sigma_mode == 1 && (want_grad || !tri_predict());
+        // a Laplace handle: the explicit-inverse route with M = L^-T T L^-1 in the place of K_y^-1, in either sigma mode
+        const bool lap = g->lap != nullptr;
+        const double* Kinv = lap ? g->lap->M.p : g->Kinv.p;
+        const bool solve_grad = !lap && g->sigma_mode == 1 && (want_grad || !tri_predict());
         {
             ProfScope ps(c, want_grad ? "acq_gemm" : "var_gemm");
             if (solve_grad) {
@@ -810,8 +1014,8 @@ static void eval_candidates(sls_gp* g, const double* xr, long ldr, int S, const 
                 g->Vs.ensure((size_t)chunk_max * Np);
                 launch_gemm_plain(c->stream, g->Ks.p, ldk, false, g->Linv.p, Np, false, g->Vs.p, ldk, Sp / 128, Np / 128, Np, 1.0, 0.0);
                 split_first = launch_acq_gemm(c->stream, g->Vs.p, Cs, ldk, Sp, g->U.p, Np, g->P.p, kw_part, cw_part, c->d_info + 32);
-            } else if (want_grad || !tri_predict())
-                split_first = launch_acq_gemm(c->stream, g->Ks.p, Cs, ldk, Sp, g->Kinv.p, Np, g->P.p, kw_part, cw_part, c->d_info + 32);
+            } else if (lap || want_grad || !tri_predict())
+                split_first = launch_acq_gemm(c->stream, g->Ks.p, Cs, ldk, Sp, Kinv, Np, g->P.p, kw_part, cw_part, c->d_info + 32);
             else
                 launch_var_gemm(c->stream, g->Ks.p, ldk, Sp, g->Linv.p, Np, kw_part, cw_part);
         }
@@ -859,7 +1063,10 @@ static void eval_candidates(sls_gp* g, const double* xr, long ldr, int S, const 
 // (wave_path_dims); Np grows with appended points, so whoever works without the context's lock asks under the state lock.
 constexpr int WAVE_PATH_MAX_POINTS = 4096;   // query points / starts per launch
 // A handle beyond the guard of the norm expansion (gram_direct) takes the tiled pipeline: the wavefront kernels difference scaled coordinates.
-static bool wave_path_dims(const sls_gp* g) { return tune_on(TUNE_WAVE_PATH) && g->D <= WAVE_PATH_MAX_D && !g->gram_direct; }
+// So does a Laplace handle: the wavefront kernels read K_y^-1 / L^-1.
+static bool wave_path_dims(const sls_gp* g) {
+    return tune_on(TUNE_WAVE_PATH) && g->D <= WAVE_PATH_MAX_D && !g->gram_direct && !g->laplace_on.load();
+}
 static bool wave_path_applies(const sls_gp* g, int count) {
     return wave_path_dims(g) && g->Np <= WAVE_PATH_MAX_NP && count <= WAVE_PATH_MAX_POINTS;
 }
@@ -1330,6 +1537,8 @@ extern "C" int sls_acq_maximize(sls_gp* g, int acq_type, double ucb_h, const dou
 static void check_pair(sls_gp* g, sls_gp* gs) {
     SLS_REQUIRE(g && gs, "NULL handle");
     SLS_REQUIRE(g->ctx == gs->ctx && g->D == gs->D, "the two regressors must share the context and the dimensionality");
+    refuse_laplace(g, "sls_acq_*_pair");
+    refuse_laplace(gs, "sls_acq_*_pair");
 }
 
 extern "C" int sls_acq_maximize_pair(sls_gp* g, sls_gp* gs, int acq_type, double ucb_h, const double* starts, int S, int n_local,
@@ -1609,6 +1818,7 @@ extern "C" int sls_jes_create(sls_gp* g, const double* x_star, const double* f_s
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g != nullptr, "sls_jes_create: gp is NULL");
+    refuse_laplace(g, "sls_jes_create");
     SLS_REQUIRE(out != nullptr, "sls_jes_create: out is NULL");
     *out = nullptr;
     SLS_REQUIRE(K >= 1 && K <= SLS_JES_MAX_OPTIMA, "sls_jes_create: K = %d (1 .. %d)", K, SLS_JES_MAX_OPTIMA);
@@ -1716,6 +1926,7 @@ extern "C" int sls_kg_create(sls_gp* g, const double* x_ref, int K, sls_kg** out
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g != nullptr, "sls_kg_create: gp is NULL");
+    refuse_laplace(g, "sls_kg_create");
     SLS_REQUIRE(out != nullptr, "sls_kg_create: out is NULL");
     *out = nullptr;
     SLS_REQUIRE(K >= 1 && K <= SLS_KG_MAX_POINTS, "sls_kg_create: K = %d (1 .. %d)", K, SLS_KG_MAX_POINTS);
@@ -2065,6 +2276,7 @@ extern "C" int sls_eubo_eval(sls_gp* g, const double* pairs, int M, double* val,
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g != nullptr, "sls_eubo_eval: gp is NULL");
+    refuse_laplace(g, "sls_eubo_eval");
     SLS_REQUIRE(pairs != nullptr, "sls_eubo_eval: pairs is NULL");
     SLS_REQUIRE(M >= 0, "sls_eubo_eval: M = %d", M);
     if (M == 0) return SLS_OK;
@@ -2078,6 +2290,7 @@ extern "C" int sls_eubo_maximize(sls_gp* g, const double* starts, int S, int n_l
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g != nullptr, "sls_eubo_maximize: gp is NULL");
+    refuse_laplace(g, "sls_eubo_maximize");
     SLS_REQUIRE(starts != nullptr, "sls_eubo_maximize: starts is NULL");
     g->eubo_best.ensure(g->ctx, (size_t)(8 + 2 * g->D) * sizeof(double), true);
     maximize_starts("sls_eubo_maximize", eubo_objective(g), starts, true, S, n_local, opts, start_index_offset, x_out, val_out, idx_out,
@@ -2234,6 +2447,7 @@ extern "C" int sls_gp_loo(sls_gp* g, double* loo_mu, double* loo_var, double* lo
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g, "sls_gp_loo: NULL handle");
+    refuse_laplace(g, "sls_gp_loo");
     std::shared_lock<std::shared_mutex> state_(g->state_mtx);
     sls_ctx* c = g->ctx;
     const int N = g->N, Np = g->Np;
@@ -2267,6 +2481,7 @@ extern "C" int sls_gp_append_point(sls_gp* g, const double* x, double y_new) {
     SLS_TRY
     CtxCall call_(g);
     SLS_REQUIRE(g && x, "sls_gp_append_point: NULL argument");
+    refuse_laplace(g, "sls_gp_append_point");
     std::unique_lock<std::shared_mutex> state_(g->state_mtx);   // ends with gp_fetch_summary's synchronisation: the state is complete
     sls_ctx* c = g->ctx;
     const int D = g->D, N = g->N, Np = g->Np;

@@ -358,11 +358,23 @@ extern "C" sls_gp* sls_multi_gp_shard(sls_multi_gp* g, int shard) {
     return (g && shard >= 0 && shard < (int)g->gps.size()) ? g->gps[shard] : nullptr;
 }
 
+// The shards of a replicated handle are plain fits of one (X, y); a shard that was given a Laplace posterior afterwards (the borrowed
+// primary of sls_multi_gp_create_from, or a shard reached through sls_multi_gp_shard) would mix the two variances in one search.
+static void refuse_laplace_shards(sls_multi_gp* g, const char* who) {
+    for (sls_gp* h : g->gps)
+        if (h && slsk::gp_has_laplace(h)) {
+            set_error("%s: a shard carries a Laplace posterior (sls_gp_set_laplace) and the others do not; sls_gp_clear_laplace first, "
+                      "or run on the handle itself", who);
+            throw HipFail{SLS_ERR_UNSUPPORTED};
+        }
+}
+
 extern "C" int sls_multi_acq_maximize(sls_multi_gp* g, int acq_type, double ucb_h, const double* starts, int S, int n_local,
                                       const sls_lbfgs_opts* opts, double* x_out, double* val_out, long* idx_out,
                                       long* evals_issued) {
     try {
         SLS_REQUIRE(g && starts && S >= 1, "sls_multi_acq_maximize: bad argument");
+        refuse_laplace_shards(g, "sls_multi_acq_maximize");
         sls_multi* m = g->m;
         const int n = (int)m->devices.size(), D = g->D;
         const size_t rec = 2 + (size_t)D;
@@ -427,6 +439,7 @@ extern "C" int sls_multi_acq_maximize(sls_multi_gp* g, int acq_type, double ucb_
 extern "C" int sls_multi_gp_predict(sls_multi_gp* g, const double* Xs, int M, double* mu, double* sigma) {
     try {
         SLS_REQUIRE(g && Xs && M >= 0, "sls_multi_gp_predict: bad argument");
+        refuse_laplace_shards(g, "sls_multi_gp_predict");
         const int n = (int)g->m->devices.size(), D = g->D;
         return for_each_shard(n, [&](int r) {
             int lo, hi;

@@ -223,8 +223,10 @@ extern "C" int sls_path_create(sls_gp* gp, int n_draws, int n_freq, unsigned lon
     const int F = n_freq, Fp = p->Fp, D = g.D, N = g.N, Np = g.Np, Rp = p->Rp;
     const bool matern = g.kernel == SLS_KERNEL_ARD_MATERN52;
     const long B0 = (long)F * D + (matern ? 5L * F : 0L);
-    const long nE = (long)n_draws * (2L * F + N);
-    DBuf Z, E, Phi;
+    // a Laplace handle (sls_gp_set_laplace): every draw takes N more numbers, z, after eps -- the sampled goodness vector
+    const int Ndraw = g.laplace ? 2 * N : N;
+    const long nE = (long)n_draws * (2L * F + Ndraw);
+    DBuf Z, E, Phi, Lc, Zm, Xm, Q;   // alive until the synchronisation at the end
     Z.ensure((size_t)B0);
     E.ensure((size_t)nE);
     p->Om.ensure((size_t)Fp * g.Dcols);
@@ -235,7 +237,7 @@ extern "C" int sls_path_create(sls_gp* gp, int n_draws, int n_freq, unsigned lon
         launch_random_normal(c->stream, seed, 0, B0, Z.p);
         launch_random_normal(c->stream, seed, B0, nE, E.p);
         launch_path_omega(c->stream, Z.p, F, Fp, D, g.Dcols, matern ? 1 : 0, p->Om.p);
-        launch_path_weights(c->stream, E.p, F, Fp, N, n_draws, Rp, std::sqrt(g.a / F), p->W.p);
+        launch_path_weights(c->stream, E.p, F, Fp, Ndraw, n_draws, Rp, std::sqrt(g.a / F), p->W.p);
         // f_prior,s(x_i) for every draw into V's block (Phi_X^T W, row blocks of the training points), then r = y - sqrt(b) eps - f_prior
         const int rows = std::max(128, std::min(Np, ((1 << 26) / (2 * Fp)) / 128 * 128));
         Phi.ensure((size_t)rows * 2 * Fp);
@@ -244,7 +246,18 @@ extern "C" int sls_path_create(sls_gp* gp, int n_draws, int n_freq, unsigned lon
             launch_path_feat(c->stream, g.XT + i0, Np, g.Dp, rc, p->Om.p, Fp, p->W.p, 2L * Fp, nullptr, rc, Phi.p, rc, nullptr, 0);
             launch_gemm_plain(c->stream, Phi.p, rc, false, p->W.p, 2L * Fp, true, p->V.p + i0, Np, rc / 128, Rp / 128, 2 * Fp, 1.0, 0.0);
         }
-        launch_path_rhs(c->stream, g.y, E.p, F, N, Np, n_draws, Rp, std::sqrt(g.b), p->V.p);
+        if (g.laplace) {
+            // Q = L (L_B^-T Z): one product with the explicit L_B^-1 for all draws at once, then one with a copy of L whose upper
+            // triangle is cleared (the factor's own buffer keeps K_y's entries there)
+            const size_t n2 = (size_t)Np * Np, nr = (size_t)Np * Rp;
+            Lc.ensure(n2); Zm.ensure(nr); Xm.ensure(nr); Q.ensure(nr);
+            SLS_HIP(hipMemcpyAsync(Lc.p, g.L, n2 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            launch_zero_upper(c->stream, Lc.p, Np);
+            launch_path_laplace_z(c->stream, E.p, F, N, Np, n_draws, Rp, Zm.p);
+            launch_gemm_plain(c->stream, g.lap_LBinv, Np, true, Zm.p, Np, true, Xm.p, Np, Np / 128, Rp / 128, Np, 1.0, 0.0);
+            launch_gemm_plain(c->stream, Lc.p, Np, false, Xm.p, Np, true, Q.p, Np, Np / 128, Rp / 128, Np, 1.0, 0.0);
+        }
+        launch_path_rhs(c->stream, g.y, E.p, F, N, Np, n_draws, Rp, std::sqrt(g.b), p->V.p, g.laplace ? Q.p : nullptr);
     }
     {
         ProfScope ps(c, "path_solve");

@@ -74,8 +74,14 @@ void post_cov_device(const GpView& g, const double* Xs, int M, PostWs& w) {
     }
     {
         ProfScope ps(c, "post_cov");
-        if (g.gram_direct) launch_post_cov_direct(c->stream, w.raw.p, g.D, g.inv_ell, w.V.p, Mp, Np, Mp, M, ks, w.cov.p);
-        else launch_post_cov(c->stream, w.XsT.p, Mp, g.Dp, w.ns.p, w.V.p, Mp, Np, Mp, M, ks, w.cov.p);
+        // a Laplace handle: cov = K - V T V^T, the second factor Y = V T one plain product (K* is no longer needed: its block)
+        const double* V2 = nullptr;
+        if (g.laplace) {
+            launch_gemm_plain(c->stream, w.V.p, Mp, false, g.lap_T, Np, false, w.Ks.p, Mp, Mp / 128, nbt, Np, 1.0, 0.0);
+            V2 = w.Ks.p;
+        }
+        if (g.gram_direct) launch_post_cov_direct(c->stream, w.raw.p, g.D, g.inv_ell, w.V.p, Mp, Np, Mp, M, ks, w.cov.p, V2);
+        else launch_post_cov(c->stream, w.XsT.p, Mp, g.Dp, w.ns.p, w.V.p, Mp, Np, Mp, M, ks, w.cov.p, V2);
     }
 }
 

@@ -38,9 +38,13 @@ struct GpView {
     const double* X;       // the raw design matrix (D x N): what the direct-difference Gram forms read
     bool gram_direct;      // the fit is beyond the guard of the norm expansion (gram_direct_form, kernels.hpp)
     long generation;       // sls_gp_generation
+    bool laplace;          // the handle carries a Laplace posterior (sls_gp_set_laplace); then, Np x Np each:
+    const double *lap_T, *lap_LBinv;   // T = I - B^-1 (symmetric, product form) and L_B^-1 (zero above the diagonal)
     std::shared_mutex* state;
 };
 GpView gp_view(sls_gp* g);
+// does the handle carry a Laplace posterior (sls_gp_set_laplace)?  Takes the context's lock.
+bool gp_has_laplace(sls_gp* g);
 // what sls_acq_last_stats reports for the handle: the one place every maximiser stores it (lbfgs_driver.hpp)
 void gp_set_acq_stats(sls_gp* g, long issued, long cap, int rounds, int live_end);
 // sls_lbfgs_opts as the caller's struct_size declares it, over the library's defaults (capi.hip)

@@ -508,11 +508,13 @@ void launch_gemm_lhs_lower(hipStream_t s, const double* L, long ldl, const doubl
 // the full Mp x Mp matrix: one workgroup per LOWER 128 x 128 tile, the tile and its mirror written from the same registers, so C
 // is exactly symmetric.  XsT [n + d*ldx] / ns: the query points' scaled coordinates and norms (launch_prep_points); Dp, Kv
 // multiples of 16.
+// V2 != nullptr (same layout as V): the second factor of the product, C = k - V V2^T -- a Laplace handle passes V2 = V T, T symmetric;
+// only the lower half of every tile is computed and the mirror is written from the same registers, so C stays exactly symmetric.
 void launch_post_cov(hipStream_t s, const double* XsT, long ldx, int Dp, const double* ns, const double* V, long ldv, int Kv, int Mp,
-                     int M, KernelSpec ks, double* C);
+                     int M, KernelSpec ks, double* C, const double* V2 = nullptr);
 // the same with the prior term k(Xs, Xs) from the raw query points Xs[d + i*D] (gram_direct_form)
 void launch_post_cov_direct(hipStream_t s, const double* Xs, int D, const double* inv_ell, const double* V, long ldv, int Kv, int Mp,
-                            int M, KernelSpec ks, double* C);
+                            int M, KernelSpec ks, double* C, const double* V2 = nullptr);
 // Standard normal number t of stream `seed`: Philox4x64-10 with key (seed, 0) on block counter (t / 4, 0, 0, 0); each 64-bit
 // output x becomes u = ((x >> 11) + 0.5) 2^-53; Box-Muller on the output pairs (0, 1) and (2, 3) gives r01 cos, r01 sin, r23 cos,
 // r23 sin for t mod 4 = 0 .. 3.
@@ -533,10 +535,15 @@ void launch_bcast_cols(hipStream_t s, const double* mu, int Mp, double* C, long 
 // Om[l + d*Fp] = frequency l (l < F, d < D; 0 in the padding up to Fp x Dc) from the B0 normals Z of the draw-independent block
 void launch_path_omega(hipStream_t s, const double* Z, int F, int Fp, int D, int Dc, int matern, double* Om);
 // W (2Fp x Rp, ld 2Fp): cos weights in rows [0, F), sin weights in rows [Fp, Fp + F), times `scale`, from the draw block E; 0 elsewhere
+// (N enters through the draw stride 2F + N alone: a Laplace handle, whose draws take 2F + 2N numbers, passes 2N)
 void launch_path_weights(hipStream_t s, const double* E, int F, int Fp, int N, int n_draws, int Rp, double scale, double* W);
 // R[i + s*Np] <- y_i - sqrt_b eps_{s,i} - R[i + s*Np] (i < N, s < n_draws), 0 in the padding (Np x Rp)
+// Q != nullptr (a Laplace handle; Np x Rp): draws take 2F + 2N numbers (w, w', eps, z) and
+// R[i + s*Np] <- (y_i + Q[i + s*Np]) - sqrt_b eps_{s,i} - R[i + s*Np], Q = L L_B^-T z the sampled deviation of the goodness values
 void launch_path_rhs(hipStream_t s, const double* y, const double* E, int F, int N, int Np, int n_draws, int Rp, double sqrt_b,
-                     double* R);
+                     double* R, const double* Q = nullptr);
+// Z[i + s*Np] = E[s (2F + 2N) + 2F + N + i] for i < N, s < n_draws; 0 elsewhere (Np x Rp): the z block of a Laplace handle's draws
+void launch_path_laplace_z(hipStream_t s, const double* E, int F, int N, int Np, int n_draws, int Rp, double* Z);
 // Random-feature contraction of Mp points (XsT [m + d*ldx], Dp columns) with the frequencies (Om [l + d*Fp], Fp a multiple of 128) on
 // the matrix cores, sincos epilogue.  draw != nullptr (gathered form, rows m < nvalid under draw[m]): G[m + l*ldg] = W_s cos - W_c
 // sin and the value partials vpart[chunk*ldv + m] of the 128-frequency chunks; draw == nullptr: G[m + l*ldg] = cos, G[m + (Fp+l)*ldg]
@@ -700,5 +707,22 @@ void launch_loo_weight_direct(hipStream_t s, const double* X, int D, const doubl
 // out[0] = sum_t part[t], out[1] = dL/db = sum_{i < N} (u_i alpha_i - M_ii), both in launch_nll_scalars' orders
 void launch_loo_scalars(hipStream_t s, const double* part, int nparts, const double* alpha, const double* u, const double* M, int Np,
                         int N, double* out);
+
+// ---- kernels_laplace.hip: Laplace posterior of the goodness values (sls_gp_set_laplace) ----------------------------------------
+// W (Np x Np, zero in the padding) = the Hessian of the Bradley-Terry-Luce terms at y: per tuple (diag(p) - p p^T) / s^2, p = softmax
+// (y / s) with the maximum subtracted, scattered at the tuple's indices.  off / flat: the CSR of the tuples; csc_off / csc_ent: the
+// flat positions that name point i, increasing; tuple_of[e]: the tuple of flat position e (all device ints).  P (flat length) and
+// logp0 (n_prefs) receive the probabilities and log p of each tuple's first member.  No atomics: one lane owns one row, fixed order.
+void launch_laplace_w(hipStream_t s, const int* off, const int* flat, const int* csc_off, const int* csc_ent, const int* tuple_of,
+                      int n_prefs, const double* y, double btl_scale, int N, int Np, double* P, double* logp0, double* W);
+// A[r + c*Np] <- A[c + r*Np] for r < c: exactly symmetric from the lower triangle
+void launch_mirror_lower(hipStream_t s, double* A, int Np);
+// out[0] = sum_t logp0[t], out[1] = 2 sum_{i<N} log LB_ii, out[2] = y . alpha: one workgroup, one fixed order
+void launch_laplace_summary(hipStream_t s, const double* logp0, int n_prefs, const double* LB, int Np, int N, const double* y,
+                            const double* alpha, double* out);
+// launch_gemm_plain on the tiles with tm >= tn only (square nt x nt outputs): the lower tiles of a symmetric product; the tiles above
+// the diagonal keep what they held (launch_mirror_lower fills them)
+void launch_gemm_lower_tiles(hipStream_t s, const double* A, long lda, bool a_kc, const double* B, long ldb, bool b_kc, double* C,
+                             long ldc, int nt, int K, double alpha, double beta);
 
 }  // namespace slsk

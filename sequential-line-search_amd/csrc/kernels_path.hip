@@ -53,18 +53,34 @@ void launch_path_weights(hipStream_t s, const double* E, int F, int Fp, int N, i
 
 // R[i + s*Np] <- y_i - sqrt(b) E[s (2F + N) + 2F + i] - R[i + s*Np] for i < N, s < n_draws; 0 elsewhere (i < Np, s < Rp)
 __global__ __launch_bounds__(256) void path_rhs_kernel(const double* __restrict__ y, const double* __restrict__ E, int F, int N, int Np,
-                                                       int n_draws, int Rp, double sqrt_b, double* __restrict__ R) {
+                                                       int n_draws, int Rp, double sqrt_b, double* __restrict__ R,
+                                                       const double* __restrict__ Q) {
     const long idx = blockIdx.x * 256L + threadIdx.x;
     if (idx >= (long)Np * Rp) return;
     const int i = (int)(idx % Np), s = (int)(idx / Np);
     double v = 0.0;
-    if (i < N && s < n_draws) v = (y[i] - sqrt_b * E[(long)s * (2L * F + N) + 2L * F + i]) - R[idx];
+    if (i < N && s < n_draws) {
+        if (Q) v = ((y[i] + Q[idx]) - sqrt_b * E[(long)s * (2L * F + 2L * N) + 2L * F + i]) - R[idx];   // a Laplace handle's draw layout
+        else v = (y[i] - sqrt_b * E[(long)s * (2L * F + N) + 2L * F + i]) - R[idx];
+    }
     R[idx] = v;
 }
 void launch_path_rhs(hipStream_t s, const double* y, const double* E, int F, int N, int Np, int n_draws, int Rp, double sqrt_b,
-                     double* R) {
+                     double* R, const double* Q) {
     const long n = (long)Np * Rp;
-    hipLaunchKernelGGL(path_rhs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, E, F, N, Np, n_draws, Rp, sqrt_b, R);
+    hipLaunchKernelGGL(path_rhs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, E, F, N, Np, n_draws, Rp, sqrt_b, R, Q);
+}
+
+__global__ __launch_bounds__(256) void path_laplace_z_kernel(const double* __restrict__ E, int F, int N, int Np, int n_draws, int Rp,
+                                                             double* __restrict__ Z) {
+    const long idx = blockIdx.x * 256L + threadIdx.x;
+    if (idx >= (long)Np * Rp) return;
+    const int i = (int)(idx % Np), s = (int)(idx / Np);
+    Z[idx] = (i < N && s < n_draws) ? E[(long)s * (2L * F + 2L * N) + 2L * F + N + i] : 0.0;
+}
+void launch_path_laplace_z(hipStream_t s, const double* E, int F, int N, int Np, int n_draws, int Rp, double* Z) {
+    const long n = (long)Np * Rp;
+    hipLaunchKernelGGL(path_laplace_z_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, E, F, N, Np, n_draws, Rp, Z);
 }
 
 // (point, draw) of pair p: the gathered form (draw != nullptr) evaluates point p under draw[p]; the every-draw form point p % npts

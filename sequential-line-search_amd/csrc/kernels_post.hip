@@ -14,8 +14,8 @@ namespace slsk {
 // and no HBM pass over K(Xs, Xs).  Diagonal tiles write their lower half and mirror it: C is exactly symmetric.
 template <bool MATERN>
 __global__ __launch_bounds__(256, 2) void post_cov_kernel(const double* __restrict__ XsT, long ldx, int Dp, const double* __restrict__ ns,
-                                                          const double* __restrict__ V, long ldv, int Kv, int Mp, int M, double a,
-                                                          double* __restrict__ C) {
+                                                          const double* __restrict__ V, const double* __restrict__ V2, long ldv,
+                                                          int Kv, int Mp, int M, double a, double* __restrict__ C) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* lds = reinterpret_cast<double*>(smem);
     const int nt = Mp / GEMM_BM;
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256, 2) void post_cov_kernel(const double* __restri
                 acc.v[i][j][r] = -k;
             }
         }
-    gemm_tile_mc(acc, V + m0, ldv, V + n0, ldv, 0, Kv, lds);
+    gemm_tile_mc(acc, V + m0, ldv, V2 + n0, ldv, 0, Kv, lds);   // V2 == V: V V^T; a Laplace handle: V (V T)^T
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -64,22 +64,23 @@ __global__ __launch_bounds__(256, 2) void post_cov_kernel(const double* __restri
 }
 
 void launch_post_cov(hipStream_t s, const double* XsT, long ldx, int Dp, const double* ns, const double* V, long ldv, int Kv, int Mp,
-                     int M, KernelSpec ks, double* C) {
+                     int M, KernelSpec ks, double* C, const double* V2) {
+    if (!V2) V2 = V;
     ensure_dyn_lds((const void*)post_cov_kernel<false>, GEMM_LDS_BYTES);
     ensure_dyn_lds((const void*)post_cov_kernel<true>, GEMM_LDS_BYTES);
     const int nt = Mp / GEMM_BM;
     const dim3 grid(nt * (nt + 1) / 2);
     if (ks.kernel == SLS_KERNEL_ARD_MATERN52)
-        hipLaunchKernelGGL(post_cov_kernel<true>, grid, dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, XsT, ldx, Dp, ns, V, ldv, Kv, Mp, M, ks.a, C);
+        hipLaunchKernelGGL(post_cov_kernel<true>, grid, dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, XsT, ldx, Dp, ns, V, V2, ldv, Kv, Mp, M, ks.a, C);
     else
-        hipLaunchKernelGGL(post_cov_kernel<false>, grid, dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, XsT, ldx, Dp, ns, V, ldv, Kv, Mp, M, ks.a, C);
+        hipLaunchKernelGGL(post_cov_kernel<false>, grid, dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, XsT, ldx, Dp, ns, V, V2, ldv, Kv, Mp, M, ks.a, C);
 }
 
 // The same Sigma with the prior term from the raw coordinate differences (gram_direct_form, kernels.hpp): thread = entry (i, j) of the
 // lower triangle, written with its mirror.  Xs[d + i*D]: the M raw query points.
 __global__ __launch_bounds__(256) void post_cov_direct_kernel(const double* __restrict__ Xs, int D, const double* __restrict__ inv_ell,
-                                                              const double* __restrict__ V, long ldv, int Kv, int Mp, int M, int kernel,
-                                                              double a, double* __restrict__ C) {
+                                                              const double* __restrict__ V, const double* __restrict__ V2, long ldv,
+                                                              int Kv, int Mp, int M, int kernel, double a, double* __restrict__ C) {
     const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
     if (i >= Mp || i < j) return;
     double v;
@@ -95,15 +96,16 @@ __global__ __launch_bounds__(256) void post_cov_direct_kernel(const double* __re
         double k, c;
         kernel_kc(kernel, a, q, k, c);
         double vv = 0.0;
-        for (int kk = 0; kk < Kv; ++kk) vv = fma(V[i + (long)kk * ldv], V[j + (long)kk * ldv], vv);
+        for (int kk = 0; kk < Kv; ++kk) vv = fma(V[i + (long)kk * ldv], V2[j + (long)kk * ldv], vv);
         v = k - vv;
     }
     C[(long)i + (long)j * Mp] = v;
     if (i != j) C[(long)j + (long)i * Mp] = v;
 }
 void launch_post_cov_direct(hipStream_t s, const double* Xs, int D, const double* inv_ell, const double* V, long ldv, int Kv, int Mp,
-                            int M, KernelSpec ks, double* C) {
-    hipLaunchKernelGGL(post_cov_direct_kernel, dim3((Mp + 255) / 256, Mp), dim3(256), 0, s, Xs, D, inv_ell, V, ldv, Kv, Mp, M, ks.kernel,
+                            int M, KernelSpec ks, double* C, const double* V2) {
+    if (!V2) V2 = V;
+    hipLaunchKernelGGL(post_cov_direct_kernel, dim3((Mp + 255) / 256, Mp), dim3(256), 0, s, Xs, D, inv_ell, V, V2, ldv, Kv, Mp, M, ks.kernel,
                        ks.a, C);
 }
 

@@ -139,6 +139,16 @@ void launch_gemm_plain(hipStream_t s, const double* A, long lda, bool a_kc, cons
     else if (a_kc && b_kc) launch_tri_gemm<true, true>(s, g, 1);
     else launch_tri_gemm<true, false>(s, g, 1);
 }
+// the same product on the tiles with tm >= tn only (symmetric results: the Laplace state's L^T W L, M, T, Sigma_g)
+void launch_gemm_lower_tiles(hipStream_t s, const double* A, long lda, bool a_kc, const double* B, long ldb, bool b_kc, double* C,
+                             long ldc, int nt, int K, double alpha, double beta) {
+    GemmDesc g = mkdesc(A, lda, B, ldb, C, ldc, nt, nt, K, alpha, beta);
+    g.tri = 1;
+    if (!a_kc && !b_kc) launch_tri_gemm<false, false>(s, g, 1);
+    else if (!a_kc && b_kc) launch_tri_gemm<false, true>(s, g, 1);
+    else if (a_kc && b_kc) launch_tri_gemm<true, true>(s, g, 1);
+    else launch_tri_gemm<true, false>(s, g, 1);
+}
 
 // C = A L^T with L lower triangular (both M-contiguous): output tile column tn contracts k < 128 (tn + 1) only -- the blocks of L
 // above its diagonal are never read (V = K* L^-T of the joint posterior: half the flops of the plain product).  Longest k range first.

@@ -191,7 +191,9 @@ namespace sequential_line_search
         // handle: they are built on the first call (the shard on the primary's device IS the primary: no second fit there) and
         // reused by every later one.
         const sls_lbfgs_opts lopts = LocalSearchOpts();   // nloptutil::solve's relative tolerances
-        if (std::shared_ptr<device::MultiGpHandle> replicas = device::ReplicasFor(RequireHandle(regressor), regressor.GetLargeX().cols()))
+        // (a Laplace regressor runs on the primary device: replicas are plain fits of (X, y) and would carry the plain variance)
+        if (std::shared_ptr<device::MultiGpHandle> replicas =
+                regressor.UsesLaplacePosterior() ? nullptr : device::ReplicasFor(RequireHandle(regressor), regressor.GetLargeX().cols()))
         {
             device::Check(sls_multi_acq_maximize(replicas->h, AcqId(func_type), hyperparam, starts.data(),
                                                  static_cast<int>(starts.cols()), static_cast<int>(num_local_search_iters), &lopts,
@@ -286,6 +288,19 @@ namespace sequential_line_search
     {
         const unsigned        num_dim = regressor.GetNumDims();
         std::vector<VectorXd> points;
+        if (regressor.UsesLaplacePosterior())
+        {
+            // Schonlau's trick conditions the variance on pseudo-observations: on a plain GP that is one appended point, on the Laplace
+            // posterior it is not defined here.  One point needs no pseudo-observation: the single-point search, on the Laplace variance.
+            if (num_points > 1)
+                throw std::runtime_error("acquisition_func::FindNextPoints: more than one point appends pseudo-observations (Schonlau's trick), "
+                                         "which a regressor with the Laplace posterior does not support; use a draw-based batch criterion: "
+                                         "FindNextQueryByExpectedUtility, FindNextQueryByInformationGain, "
+                                         "FindNextPointsByNoisyExpectedImprovement or FindNextPointsByThompsonSampling");
+            if (num_points == 1)
+                points.push_back(FindNextPoint(regressor, num_global_search_iters, num_local_search_iters, func_type, hyperparam));
+            return points;
+        }
         sls_gp*               mean_handle = RequireHandle(regressor);
         const VectorXd        theta       = regressor.GetKernelHyperparams();
 

@@ -2,6 +2,7 @@
 #include <chrono>
 #include <cmath>
 #include <fstream>
+#include <stdexcept>
 #include <sequential-line-search/preference-regressor.hpp>
 #include <sequential-line-search/utils.hpp>
 
@@ -74,6 +75,45 @@ namespace sequential_line_search
     }
 
     sls_gp* PreferenceRegressor::GetDeviceHandle() const { return m_handle ? m_handle->h : nullptr; }
+
+    void PreferenceRegressor::UseLaplacePosterior(const bool on)
+    {
+        if (!m_handle || on == m_laplace) return;   // no data: nothing to approximate
+        if (on)
+        {
+            std::vector<unsigned> flat;
+            std::vector<int>      offs{0};
+            for (const Preference& p : m_D)
+            {
+                flat.insert(flat.end(), p.begin(), p.end());
+                offs.push_back(static_cast<int>(flat.size()));
+            }
+            device::Check(sls_gp_set_laplace(m_handle->h, flat.data(), offs.data(), static_cast<int>(m_D.size()), m_btl_scale),
+                          "sls_gp_set_laplace");
+        }
+        else
+        {
+            device::Check(sls_gp_clear_laplace(m_handle->h), "sls_gp_clear_laplace");
+        }
+        m_laplace = on;
+    }
+
+    double PreferenceRegressor::GetLaplaceLogEvidence() const
+    {
+        if (!m_laplace) throw std::logic_error("PreferenceRegressor::GetLaplaceLogEvidence: call UseLaplacePosterior() first");
+        double ev = 0.0;
+        device::Check(sls_gp_laplace_summary(m_handle->h, nullptr, nullptr, &ev), "sls_gp_laplace_summary");
+        return ev;
+    }
+
+    MatrixXd PreferenceRegressor::GetGoodnessCovariance() const
+    {
+        if (!m_laplace) throw std::logic_error("PreferenceRegressor::GetGoodnessCovariance: call UseLaplacePosterior() first");
+        const long M = m_X.cols();
+        MatrixXd   S(M, M);
+        device::Check(sls_gp_laplace_get(m_handle->h, SLS_LAPLACE_COV, S.data()), "sls_gp_laplace_get");
+        return S;
+    }
 
     // reference: src/preference-regressor.cpp:293-330
     double PreferenceRegressor::PredictMu(const VectorXd& x) const

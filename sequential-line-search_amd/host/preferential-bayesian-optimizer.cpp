@@ -267,5 +267,11 @@ namespace sequential_line_search
         m_regressor = std::make_shared<PreferenceRegressor>(m_data->GetX(), m_data->GetD(), m_use_map_hyperparams, m_kernel_signal_var,
                                                             m_kernel_length_scale, m_noise_level, m_kernel_hyperparams_prior_var,
                                                             m_btl_scale, iters, m_kernel_type);
+        if (m_use_laplace_posterior) m_regressor->UseLaplacePosterior();
+    }
+    void PreferentialBayesianOptimizer::SetUseLaplacePosterior(const bool use_laplace_posterior)
+    {
+        m_use_laplace_posterior = use_laplace_posterior;
+        if (m_regressor) m_regressor->UseLaplacePosterior(use_laplace_posterior);
     }
 } // namespace sequential_line_search

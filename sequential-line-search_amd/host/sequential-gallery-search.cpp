@@ -77,6 +77,7 @@ namespace sequential_line_search
         m_regressor = std::make_shared<PreferenceRegressor>(m_data->GetX(), m_data->GetD(), m_use_map_hyperparams, m_kernel_signal_var,
                                                             m_kernel_length_scale, m_noise_level, m_kernel_hyperparams_prior_var,
                                                             m_btl_scale, num_map_estimation_iters, m_kernel_type);
+        if (m_use_laplace_posterior) m_regressor->UseLaplacePosterior();
 
         const VectorXd x_plus = (m_current_best_selection_strategy == CurrentBestSelectionStrategy::LargestExpectValue)
                                     ? m_regressor->FindArgMax()
@@ -147,5 +148,10 @@ namespace sequential_line_search
     void SequentialGallerySearchOptimizer::DampData(const std::string& directory_path) const
     {
         if (m_regressor) m_regressor->DampData(directory_path);
+    }
+    void SequentialGallerySearchOptimizer::SetUseLaplacePosterior(const bool use_laplace_posterior)
+    {
+        m_use_laplace_posterior = use_laplace_posterior;
+        if (m_regressor) m_regressor->UseLaplacePosterior(use_laplace_posterior);
     }
 } // namespace sequential_line_search
